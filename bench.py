@@ -22,9 +22,14 @@ partial groups are exchanged over RCCL and merged by their owner (SURVEY.md §8e
 VNM_BENCH_DRY_RUN=1: no GPU work at all -- the launch, the rendezvous (gloo), the max-over-ranks timing and the JSON line only
 (tests/test_bench_launch.py runs that here).
 
-Extra keys: "roofline" (HIP-event time of the dominant kernel vs 8 TB/s HBM peak) and "cpu_baseline"
-(the reference's CPU path -- NumPy compare + pyarrow filter + the real reference C++ aggregate from
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...); nothing else.
+--full adds what the headline figure does not need, all measured after the timed region or around it:
+"roofline" (HIP-event time of the dominant kernel vs 8 TB/s HBM peak; the kernel timers are on during the timed steps),
+"check" (property check of the last step's result), "device_state", "sustained", "also" (the other configurations)
+and "cpu_baseline" (the reference's CPU path -- NumPy compare + pyarrow filter + the real reference C++ aggregate from
 oracle/_ref when that build is present, else the oracle port -- on a bounded sample, rank 0, N=1 only).
+--dump-outputs DIR: after the timed steps, the arrays the last step handed its caller as DIR/<name>.npy (float64;
+a fixed, seeded sample of at most 2^20 rows of a longer output; group-by results ordered by key), for comparing builds.
 """
 import argparse
 import ctypes
@@ -68,7 +73,14 @@ def parse():
                     help="tell the operator the group count (vnm_agg_set_hint).  The reference's operator boundary has no such "
                          "argument, so the headline is the HINT-LESS run: the operator samples the keys itself")
     ap.add_argument("--no-hint", action="store_true", help=argparse.SUPPRESS)  # r01 spelling of what is now the default
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: kernel roofline, result check, device state, sustained leg, "
+                         "the other configurations and the CPU baseline (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64, at most 2^20 rows each)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.workload is None:
         args.workload = "stream" if args.gpus > 1 else "groupby"
     if args.groups is None:
@@ -314,6 +326,41 @@ class CudaArrayView:
 
     def __init__(self, ptr, n, typestr="<i8"):
         self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+
+DUMP_ROWS = 1 << 20     # --dump-outputs: rows per array at most (8 MB of float64); a longer output is sampled
+
+
+def _column_f64(torch, col, device):
+    """A result DeviceColumn as a float64 tensor on the device, NaN where its validity bitmap says NULL."""
+    n = col.length
+    if n == 0:
+        return torch.zeros(0, dtype=torch.float64, device=device)
+    typestr = np.dtype(col.arrow_type.to_pandas_dtype()).str
+    t = torch.as_tensor(CudaArrayView(col.values_ptr, n, typestr), device=device).to(torch.float64)
+    if col.validity_ptr:
+        bits = torch.as_tensor(CudaArrayView(col.validity_ptr, (n + 7) // 8, "|u1"), device=device)
+        i = torch.arange(n, device=device)
+        valid = ((bits[i >> 3] >> (i & 7)) & 1).bool()
+        t = torch.where(valid, t, torch.full_like(t, float("nan")))
+    return t
+
+
+def dump_outputs(torch, directory, arrays, device):
+    """Write {name: float64 device tensor} as directory/<name>.npy.  An array longer than DUMP_ROWS is reduced to the rows at
+    a fixed, seeded set of positions (the same for every array of one length, so rows stay aligned across the arrays);
+    result_rows.npy holds the full length."""
+    os.makedirs(directory, exist_ok=True)
+    lengths = {int(t.numel()) for t in arrays.values()}
+    assert len(lengths) == 1, f"--dump-outputs: arrays of different lengths {sorted(lengths)}"
+    n = lengths.pop()
+    pos = None
+    if n > DUMP_ROWS:
+        pos = torch.as_tensor(np.unique(np.random.default_rng(0).integers(0, n, DUMP_ROWS)), device=device)
+    for name, t in arrays.items():
+        t = t if pos is None else t[pos]
+        np.save(os.path.join(directory, name + ".npy"), t.to(torch.float64).cpu().numpy())
+    np.save(os.path.join(directory, "result_rows.npy"), np.array([n], dtype=np.float64))
 
 
 def _spans(lib, ctypes, names, steps):
@@ -1001,7 +1048,8 @@ def main():
             step()
         sync_all()
         state.pop("phases", None)
-        lib.vnm_set_profiling(1)
+        if args.full:
+            lib.vnm_set_profiling(1)     # HIP events around every kernel: the per-kernel figures of "roofline"
         t0 = time.perf_counter()
         for _ in range(steps):
             step()
@@ -1013,15 +1061,36 @@ def main():
             el = float(t.item())
         return el
 
+    def step_outputs():
+        """What the last timed step handed its caller, as float64 tensors on the device (group-by results ordered by key)."""
+        if world > 1 or force_exchange:
+            raise SystemExit("--dump-outputs: only a single-rank run without VNM_BENCH_FORCE_EXCHANGE")
+        if args.workload == "filter":
+            return {"v": out_buf[:state["out_rows"]]}
+        if args.workload == "topk":
+            ids = torch.as_tensor(CudaArrayView(state["idx"].ptr, min(args.limit, n) if args.limit > 0 else n), device=device)
+            return {"row_id": ids.to(torch.float64), "v": v[ids]}
+        if args.workload == "project":
+            return {f"expr{i}": _column_f64(torch, c, device) for i, c in enumerate(state["outs"])}
+        names = ["k", "sum_v", "avg_v"]
+        if args.workload == "groupby" and args.shape != "hot":
+            names = ["k", "count"] if args.shape == "count_star" else ["k", "min_v", "max_v"]
+        cols = [_column_f64(torch, c, device) for c in state["cols"]]
+        order = torch.argsort(cols[0], stable=True)
+        return {nm: c[order] for nm, c in zip(names, cols)}
+
     elapsed = timed(args.steps, args.warmup)
     headline_phases = dict(state["phases"]) if "phases" in state else None     # (the `also` cases of a multi-rank run reuse `state`)
     headline_exchange = state.get("exchange_kind")
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, step_outputs(), device)
 
     check = None
     # The property check of the LAST step's result (after the timed region, on the device, reduced over all ranks) is part of every
-    # hot-shape line: survivors and totals conserved, (one GPU) the result columns equal to the operator's partial state.
-    # --check: a failed property aborts the run; otherwise it is reported in the line ("ok": false).  --no-check skips it.
-    if not args.no_check and args.workload in ("groupby", "stream") and args.shape == "hot":
+    # hot-shape line of a --full run: survivors and totals conserved, (one GPU) the result columns equal to the operator's partial state.
+    # --check: the check runs in any run, and a failed property aborts it; otherwise it is reported in the line ("ok": false).
+    # --no-check skips it.
+    if not args.no_check and (args.check or args.full) and args.workload in ("groupby", "stream") and args.shape == "hot":
         try:
             check = check_groupby(torch, dist, state, k, v, x_thr, world, rank, device, force_exchange, strict=bool(args.check))
         except AssertionError:
@@ -1035,12 +1104,13 @@ def main():
                                                     b"sort_sample", b"sort_scatter1", b"sort_scatter2", b"sort_local"], "project": [b"project_kernel"]}.get(
         args.workload, AGG_SPANS)
     spans = {}
-    for nm in names:
-        tot_ms, cnt = ctypes.c_double(0), ctypes.c_int64(0)
-        lib.vnm_profile_query(nm, ctypes.byref(tot_ms), ctypes.byref(cnt))
-        if cnt.value:
-            spans[nm.decode()] = (tot_ms.value / max(args.steps, 1), cnt.value / max(args.steps, 1))
-    lib.vnm_set_profiling(0)
+    if args.full:
+        for nm in names:
+            tot_ms, cnt = ctypes.c_double(0), ctypes.c_int64(0)
+            lib.vnm_profile_query(nm, ctypes.byref(tot_ms), ctypes.byref(cnt))
+            if cnt.value:
+                spans[nm.decode()] = (tot_ms.value / max(args.steps, 1), cnt.value / max(args.steps, 1))
+        lib.vnm_set_profiling(0)
     # the dominant kernel = the one with the largest time per step (HIP events on the launch stream)
     dom_name = max(spans, key=lambda k: spans[k][0]) if spans else "none"
     kernel_ms = spans[dom_name][0] if spans else 0.0
@@ -1090,31 +1160,32 @@ def main():
     # newest round first; hinted and hint-less runs take different paths, so they have different entries
     key = (f"{args.workload}_N{n:.0e}_G{groups:.0e}_s{args.selectivity}" + (f"_{args.shape}" if args.shape != "hot" else "")
            + ("_hint" if args.hint else ""))      # (the keys tools/traffic_from_pmc.py writes: other shapes run other kernels)
-    for tf in ("r06_traffic.json", "r05_traffic.json", "r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json"):
-        try:
-            with open(os.path.join(ROOT, "profiles", tf)) as f:
-                tj = json.load(f)
-        except Exception:
-            continue
-        k2 = key if key in tj else (key[:-5] if tf == "r01_traffic.json" and args.hint and key[:-5] in tj else None)
-        if k2:
-            ent = tj[k2]
-            # pass 1 runs in one of two states, decided per process (profiles/tuning_log_r02.md): take the PMC profile whose pass-1 duration matches
-            # the one measured live
-            live = spans.get("agg_part_scatter1", (None,))[0]
-            cands = [ent] + list(ent.get("variants", []))
-            if live is not None and all("kernel_ms" in c for c in cands):
-                ent2 = min(cands, key=lambda c: abs(c["kernel_ms"].get("agg_part_scatter1", 0.0) - live))
-            else:
-                ent2 = ent
-            traffic = ent2["bytes_per_step"]
-            traffic_src = ent2.get("source", "profiles/") + " (" + ent.get("how", "") + ")"
-            break
+    if args.full:
+        for tf in ("r06_traffic.json", "r05_traffic.json", "r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json"):
+            try:
+                with open(os.path.join(ROOT, "profiles", tf)) as f:
+                    tj = json.load(f)
+            except Exception:
+                continue
+            k2 = key if key in tj else (key[:-5] if tf == "r01_traffic.json" and args.hint and key[:-5] in tj else None)
+            if k2:
+                ent = tj[k2]
+                # pass 1 runs in one of two states, decided per process (profiles/tuning_log_r02.md): take the PMC profile whose pass-1 duration matches
+                # the one measured live
+                live = spans.get("agg_part_scatter1", (None,))[0]
+                cands = [ent] + list(ent.get("variants", []))
+                if live is not None and all("kernel_ms" in c for c in cands):
+                    ent2 = min(cands, key=lambda c: abs(c["kernel_ms"].get("agg_part_scatter1", 0.0) - live))
+                else:
+                    ent2 = ent
+                traffic = ent2["bytes_per_step"]
+                traffic_src = ent2.get("source", "profiles/") + " (" + ent.get("how", "") + ")"
+                break
     # ---- a multi-rank run's other configurations (every rank takes part: the exchanges are collectives), a few steps each, same
     # bracketing: configs[3] at G = 7 (all-gather of a handful of partial groups) and the one-batch G = 1e8 shape of configs[2]
     # (dense tables over all_to_all)
     multi_also = None
-    if (world > 1 or force_exchange) and args.workload == "stream" and not args.no_also:
+    if args.full and (world > 1 or force_exchange) and args.workload == "stream" and not args.no_also:
         multi_also = {}
         try:
             def also_entry(tag, what, nrows):
@@ -1153,51 +1224,52 @@ def main():
                        "parallelism": f"batch-sharded x{world}" + (", RCCL all_to_all partial-aggregate exchange" if world > 1 else ""),
                        "scaling_reference": ("the SAME workload on one GPU is also['configs[3] one-GPU leg, G=1e6'] of the --gpus 1 line "
                                              "(its default workload is configs[2], one 1e9-row batch at G = 1e8)") if args.workload == "stream" and world > 1 else None},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "kernel": dom,
-                         "kernel_ms": total_kernel_ms, "dominant_kernel_ms": kernel_ms,
-                         "kernels_ms": {k: round(v[0], 4) for k, v in spans.items()},
-                         "algorithmic_bytes": alg_bytes,
-                         "launches_per_step": cnt.value / max(args.steps, 1)},
             "exchange_ms_per_step": ({k2: round(v2 / max(args.steps, 1), 3) for k2, v2 in headline_phases.items()}
                                      if headline_phases is not None else None),
             "exchange": headline_exchange,
         }
         if check is not None:
             result["check"] = check
-        #  the device's state next to the line, and a SUSTAINED leg: the same step for a few seconds after the timed
-        # region -- the timed K steps are ~0.2 s of GPU work in a minute of data generation, invisible to a 5-s utilisation sampler and
-        # too short to show what the rate settles at; reported beside the headline, never part of `value`
-        result["device_state"] = device_state()
-        if world == 1 and not force_exchange and not args.no_also and args.sustain_seconds > 0:
-            try:
-                n_s, t_s = 0, time.perf_counter()
-                while time.perf_counter() - t_s < args.sustain_seconds:
-                    for _ in range(10):
-                        step()
-                    torch.cuda.synchronize()
-                    n_s += 10
-                el_s = time.perf_counter() - t_s
-                result["sustained"] = {"seconds": round(el_s, 2), "steps": n_s, "ms_per_step": el_s / n_s * 1e3, "device_state_after": device_state()}
-            except Exception as e:  # noqa: BLE001 -- reporting only
-                result["sustained"] = {"error": str(e)}
-        if multi_also is not None:
-            result["also"] = multi_also
-        if world == 1 and not force_exchange and args.workload == "groupby" and args.shape == "hot" and not args.no_also:
-            # the other single-GPU configurations of BASELINE.json on the same resident column, a few steps each
-            # (reported beside the headline; not part of `value`)
-            try:
-                result["also"] = side_workloads(torch, lib, L, ops, pa, ctypes, kcol, vcol, n, x_thr, stream, args)
-            except Exception as e:
-                result["also"] = {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline and args.workload in ("groupby", "filter") and args.shape == "hot":
-            try:
-                result["cpu_baseline"] = cpu_baseline(args, x_thr)
-            except Exception as e:  # the baseline is reporting only; never fail the bench line on it
-                result["cpu_baseline"] = {"value": None, "unit": "rows/s", "cores": 1, "kind": "port",
-                                          "sample": f"failed: {e}"}
+        if args.full:
+            result["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                  "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                                  "traffic_source": traffic_src,
+                                  "kernel": dom,
+                                  "kernel_ms": total_kernel_ms, "dominant_kernel_ms": kernel_ms,
+                                  "kernels_ms": {k: round(v[0], 4) for k, v in spans.items()},
+                                  "algorithmic_bytes": alg_bytes,
+                                  "launches_per_step": cnt.value / max(args.steps, 1)}
+            #  the device's state next to the line, and a SUSTAINED leg: the same step for a few seconds after the timed
+            # region -- the timed K steps are ~0.2 s of GPU work in a minute of data generation, invisible to a 5-s utilisation sampler and
+            # too short to show what the rate settles at; reported beside the headline, never part of `value`
+            result["device_state"] = device_state()
+            if world == 1 and not force_exchange and not args.no_also and args.sustain_seconds > 0:
+                try:
+                    n_s, t_s = 0, time.perf_counter()
+                    while time.perf_counter() - t_s < args.sustain_seconds:
+                        for _ in range(10):
+                            step()
+                        torch.cuda.synchronize()
+                        n_s += 10
+                    el_s = time.perf_counter() - t_s
+                    result["sustained"] = {"seconds": round(el_s, 2), "steps": n_s, "ms_per_step": el_s / n_s * 1e3, "device_state_after": device_state()}
+                except Exception as e:  # noqa: BLE001 -- reporting only
+                    result["sustained"] = {"error": str(e)}
+            if multi_also is not None:
+                result["also"] = multi_also
+            if world == 1 and not force_exchange and args.workload == "groupby" and args.shape == "hot" and not args.no_also:
+                # the other single-GPU configurations of BASELINE.json on the same resident column, a few steps each
+                # (reported beside the headline; not part of `value`)
+                try:
+                    result["also"] = side_workloads(torch, lib, L, ops, pa, ctypes, kcol, vcol, n, x_thr, stream, args)
+                except Exception as e:
+                    result["also"] = {"error": str(e)}
+            if world == 1 and not args.no_cpu_baseline and args.workload in ("groupby", "filter") and args.shape == "hot":
+                try:
+                    result["cpu_baseline"] = cpu_baseline(args, x_thr)
+                except Exception as e:  # the baseline is reporting only; never fail the bench line on it
+                    result["cpu_baseline"] = {"value": None, "unit": "rows/s", "cores": 1, "kind": "port",
+                                              "sample": f"failed: {e}"}
     else:
         result = None
     if world > 1 or force_exchange:
@@ -1207,9 +1279,8 @@ def main():
     if result is not None:
         os.write(real_stdout, (json.dumps(result) + "\n").encode())
     os.close(real_stdout)
-    if any(k.startswith(("ROCP", "ROCPROF")) for k in os.environ):
-        return   # under rocprofv3: its tool library writes the trace from an atexit handler
-    os._exit(0)   # skip native atexit chatter; everything is flushed and the process group is destroyed
+    # a normal exit: the native libraries' destructors and atexit handlers run (the operator library joins its helper threads
+    # there, rocprofv3's tool library writes its trace); what they print goes to stderr, fd 1 still points there
 
 
 if __name__ == "__main__":

@@ -17,8 +17,8 @@ def _bench(extra_env, *args):
     env = dict(os.environ)
     env.update(extra_env)
     env.setdefault("MASTER_PORT", str(29600 + os.getpid() % 300))
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-also", "--no-cpu-baseline",
-                        "--check", *args], env=env, capture_output=True, text=True, timeout=600)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-also",
+                        "--no-cpu-baseline", "--check", *args], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     return json.loads(p.stdout.strip().splitlines()[-1])
 
@@ -51,8 +51,8 @@ def test_bench_check_stream_workload_with_exchange(groups, route):
     exchanged -- here by ONE rank with itself, `also` cases included (they are collectives on every rank)."""
     env = dict(os.environ)
     env.update({"VNM_BENCH_FORCE_EXCHANGE": "1", "MASTER_PORT": str(29900 + os.getpid() % 90)})
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "stream", "--batches", "4", "--groups", groups, "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--check"], env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "stream", "--batches", "4", "--groups", groups,
+                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--check"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     j = json.loads(p.stdout.strip().splitlines()[-1])
     assert j["check"]["exchange"] == route, j["check"]
@@ -79,8 +79,8 @@ def test_bench_self_launch_ranks_sharing_the_gpu(ranks, groups, route):
     over all ranks (survivors and totals conserved, no group on two ranks)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["VNM_BENCH_SHARED_GPU"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--batches", "3", "--groups", groups, "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-also", "--check"], env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(ranks), "--batches", "3", "--groups", groups,
+                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-also", "--check"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -101,3 +101,30 @@ def test_bench_side_workloads_run(args, metric):
     j = _bench({}, "--rows", "2e7", *args)
     assert j["value"] > 0 and j["ms_per_step"] > 0, j
     assert j["roofline"]["achieved"] > 0, j["roofline"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) prints the headline line without the side measurements; --dump-outputs writes the result columns
+    of the last timed step ordered by key, and they equal a torch evaluation of the query over the same seeded inputs."""
+    import numpy as np
+    import torch
+    import bench
+    rows, groups = 20_000_000, 100_000
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--rows", str(rows),
+                        "--groups", str(groups), "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    j = json.loads(p.stdout.strip().splitlines()[-1])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] == pytest.approx(rows / (j["ms_per_step"] * 1e-3))
+    assert not {"roofline", "check", "device_state", "sustained", "also", "cpu_baseline"} & set(j), sorted(j)
+    k, s, a = (np.load(os.path.join(tmp_path, f"{nm}.npy")) for nm in ("k", "sum_v", "avg_v"))
+    assert k.dtype == s.dtype == a.dtype == np.float64
+    assert int(np.load(os.path.join(tmp_path, "result_rows.npy"))[0]) == j["config"]["result_rows"] == len(k) == len(s) == len(a)
+    assert (np.diff(k) > 0).all()
+    kt, vt = bench.gen_data(torch, rows, groups, seed=1, device=torch.device("cuda", 0))
+    keep = vt > bench.threshold_for(0.5)
+    cnt = torch.zeros(groups, dtype=torch.int64, device=kt.device).index_add_(0, kt[keep], torch.ones_like(kt[keep]))
+    sm = torch.zeros(groups, dtype=torch.float64, device=kt.device).index_add_(0, kt[keep], vt[keep])
+    live = (cnt > 0).nonzero().flatten()
+    np.testing.assert_array_equal(k, live.to(torch.float64).cpu().numpy())
+    np.testing.assert_array_equal(s, sm[live].cpu().numpy())         # quantised values: every partial sum is exact
+    np.testing.assert_array_equal(a, (sm[live] / cnt[live].to(torch.float64)).cpu().numpy())

@@ -2,7 +2,8 @@
 
 (1) the reference's own gtest known answers (tests/golden/gtest_fixtures.py),
 (2) outputs of the REAL reference operators on seeded inputs (tests/golden/*.arrow, manifest.json),
-(3) when oracle/_ref is present (build container), live comparison against the real reference.
+(3) outputs of the real reference on seeded tables with NULLs and wide sums (tests/golden/live_ref_*.arrow), compared live
+    as well when oracle/_ref is present (build container).
 All comparisons are bit-exact (the oracle follows the reference's evaluation order).
 """
 import os
@@ -14,7 +15,9 @@ import pytest
 from oracle import oracle as O
 from oracle import ref as R
 from tests import util
+from tests.golden import float_cases as FC
 from tests.golden import gtest_fixtures as G
+from tests.golden import live_cases as LC
 
 MAN = util.manifest()
 OPS = {"eq": O.EQ, "ne": O.NE, "gt": O.GT, "ge": O.GE, "lt": O.LT, "le": O.LE}
@@ -99,26 +102,26 @@ def test_oracle_filter_emit_null_matches_arrow():
     util.assert_batches_equal(O.filter_batch(batch, m, mv), exp, what="emit_null")
 
 
-@pytest.mark.skipif(not R.available(), reason="oracle/_ref not built (needs /root/reference)")
-@pytest.mark.parametrize("seed", [0, 1, 2])
+@pytest.mark.parametrize("seed", LC.SEEDS)
 def test_oracle_matches_live_reference(seed):
-    rng = np.random.default_rng(100 + seed)
-    n = 20000
-    t = pa.table({
-        "k": pa.array(rng.integers(-50, 50, n).astype(np.int64), mask=rng.random(n) < 0.02),
-        "k2": pa.array(rng.integers(0, 5, n).astype(np.int16), mask=rng.random(n) < 0.02),
-        "v": pa.array(rng.lognormal(2, 1, n), mask=rng.random(n) < 0.1),
-        "w": pa.array(rng.integers(-2**62, 2**62, n).astype(np.int64), mask=rng.random(n) < 0.1),
-    })
-    funcs = [(O.COUNT_STAR, "", "n"), (O.COUNT, "v", "cv"), (O.SUM, "v", "sv"), (O.AVG, "v", "av"),
-             (O.MIN, "v", "mnv"), (O.MAX, "v", "mxv"), (O.SUM, "w", "sw"), (O.AVG, "w", "aw")]
-    for kind, gb in [(O.SINGLE, ["k"]), (O.MULTI, ["k", "k2"]), (O.ONE_GROUP, [])]:
-        o = O.OracleAggregate(kind, gb, gb, funcs)
-        r = R.RefAggregate(kind, gb, gb, funcs)
-        for b in util.sliced_batches(t, 3000):
+    """The oracle against the real reference on seeded tables with NULL keys / values and int64 sums past 64 bits: against the
+    reference's outputs stored by tests/golden/gen_golden_live.py always, and live as well where oracle/_ref is built."""
+    import json
+    with open(os.path.join(util.GOLDEN, "live_cases.json")) as f:
+        digests = json.load(f)["sha256"]
+    t = LC.table(seed)
+    assert FC.table_digest(t) == digests[str(seed)]
+    for kind, gb in LC.KINDS:
+        o = O.OracleAggregate(kind, gb, gb, LC.FUNCS)
+        r = R.RefAggregate(kind, gb, gb, LC.FUNCS) if R.available() else None
+        for b in util.sliced_batches(t, LC.CHUNK):
             o.next(b)
-            r.next(b)
-        util.assert_batches_equal(o.result(), r.result(), key_names=gb, what=f"live kind={kind}")
+            if r is not None:
+                r.next(b)
+        got = o.result()
+        util.assert_batches_equal(got, util.read_ipc(LC.golden_name(seed, kind)), key_names=gb, what=f"stored kind={kind}")
+        if r is not None:
+            util.assert_batches_equal(got, r.result(), key_names=gb, what=f"live kind={kind}")
 
 
 def test_oracle_float_sum_order_and_minmax_rule_match_the_reference():

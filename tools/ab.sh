@@ -3,7 +3,7 @@
 # previous commit), alternating processes; prints every run and the medians.  usage: bash tools/ab.sh [pairs] [bench.py args]
 P=${1:-3}; shift
 cp vinum_amd/lib/libvinum_hip.so /tmp/new.so; cp vinum_amd/lib_old/libvinum_hip.so /tmp/old.so
-one() { python bench.py --no-also --no-cpu-baseline --steps 10 --warmup 3 "$@" 2>/dev/null | python -c "import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=j['roofline']['kernels_ms']; print(round(j['ms_per_step'],3), ' '.join(f'{n[4:]}={v:.2f}' for n,v in k.items()))"; }
+one() { python bench.py --full --no-also --no-cpu-baseline --steps 10 --warmup 3 "$@" 2>/dev/null | python -c "import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=j['roofline']['kernels_ms']; print(round(j['ms_per_step'],3), ' '.join(f'{n[4:]}={v:.2f}' for n,v in k.items()))"; }
 for i in $(seq 1 $P); do
   cp /tmp/old.so vinum_amd/lib/libvinum_hip.so; echo -n "old: "; one "$@"
   cp /tmp/new.so vinum_amd/lib/libvinum_hip.so; echo -n "new: "; one "$@"

@@ -4,10 +4,10 @@
 TAG=${1:-r03}; N=${2:-5}
 OUT=gpurun_out/repeat_$TAG; mkdir -p $OUT
 for i in $(seq 1 $N); do
-  timeout 300 python bench.py --steps 10 --warmup 3 --no-also --no-cpu-baseline > $OUT/headline_$i.json 2>/dev/null
+  timeout 300 python bench.py --full --steps 10 --warmup 3 --no-also --no-cpu-baseline > $OUT/headline_$i.json 2>/dev/null
 done
-VNM_BENCH_FORCE_EXCHANGE=1 timeout 300 python bench.py --steps 5 --warmup 2 --no-also --no-cpu-baseline --check > $OUT/exchange_dense_1e8.json 2>/dev/null
-VNM_BENCH_FORCE_EXCHANGE=1 timeout 300 python bench.py --steps 5 --warmup 2 --no-also --no-cpu-baseline --check --groups 1e6 > $OUT/exchange_allgather_1e6.json 2>/dev/null
+VNM_BENCH_FORCE_EXCHANGE=1 timeout 300 python bench.py --full --steps 5 --warmup 2 --no-also --no-cpu-baseline --check > $OUT/exchange_dense_1e8.json 2>/dev/null
+VNM_BENCH_FORCE_EXCHANGE=1 timeout 300 python bench.py --full --steps 5 --warmup 2 --no-also --no-cpu-baseline --check --groups 1e6 > $OUT/exchange_allgather_1e6.json 2>/dev/null
 python - <<PY
 import json, glob
 rows = []

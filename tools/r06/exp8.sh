@@ -2,7 +2,7 @@
 # round 6, GPU session 8: pass-1 knobs with narrow words, then the whole suite
 mkdir -p gpurun_out/r06
 O=gpurun_out/r06
-one() { python bench.py --no-also --no-cpu-baseline --steps 10 --warmup 3 "$@" 2>/dev/null | python -c "import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=j['roofline']['kernels_ms']; print(round(j['ms_per_step'],3), (j.get('check') or {}).get('ok'), ' '.join(f'{n[4:]}={v:.2f}' for n,v in k.items()))"; }
+one() { python bench.py --full --no-also --no-cpu-baseline --steps 10 --warmup 3 "$@" 2>/dev/null | python -c "import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=j['roofline']['kernels_ms']; print(round(j['ms_per_step'],3), (j.get('check') or {}).get('ok'), ' '.join(f'{n[4:]}={v:.2f}' for n,v in k.items()))"; }
 {
 echo -n "default: "; one
 echo -n "grid1=1: "; VNM_DENSE_GRID1_PER_CU=1 one
