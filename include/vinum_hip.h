@@ -82,10 +82,28 @@ enum vnm_expr_op {
     VNM_EX_EQ, VNM_EX_NE, VNM_EX_GT, VNM_EX_GE, VNM_EX_LT, VNM_EX_LE, /* NumPy comparison lambdas :30-36 */
     VNM_EX_AND, VNM_EX_OR, VNM_EX_NOT,                             /* pc.and_ / pc.or_ / pc.invert :27-29 */
     VNM_EX_IS_NULL, VNM_EX_IS_NOT_NULL,                            /* pc.is_null / pc.is_valid :37-38 (arg = column) */
-    VNM_EX_STORE      /* pop the top of the stack into output `arg` (vnm_project_multi: one SELECT list, one pass) */
+    VNM_EX_STORE,     /* pop the top of the stack into output `arg` (vnm_project_multi: one SELECT list, one pass) */
+    /* built-in scalar functions: _default_functions_registry, vinum/core/functions.py:353-387.  NumPy 2 ufunc typing:
+     * sqrt and the transcendentals give float16 for (u)int8, float32 for (u)int16 and float32, float64 otherwise */
+    VNM_EX_ABS,       /* 'abs': np.absolute  functions.py:362 (integers wrap: abs(int8 -128) == -128)          */
+    VNM_EX_SQRT,      /* 'sqrt': np.sqrt     functions.py:363 (correctly rounded)                              */
+    VNM_EX_SIN,       /* 'sin': np.sin       functions.py:365                                                  */
+    VNM_EX_COS,       /* 'cos': np.cos       functions.py:364                                                  */
+    VNM_EX_TAN,       /* 'tan': np.tan       functions.py:366                                                  */
+    VNM_EX_LOG,       /* 'log': np.log       functions.py:368                                                  */
+    VNM_EX_LOG2,      /* 'log2': np.log2     functions.py:369                                                  */
+    VNM_EX_LOG10,     /* 'log10': np.log10   functions.py:370                                                  */
+    VNM_EX_POW,       /* 'power': np.power   functions.py:367 (binary; integer ** negative integer: ValueError) */
+    VNM_EX_TO_F64,    /* 'to_float': FloatCastFunction, np.array(x, dtype='float')  functions.py:172-176,355    */
+    VNM_EX_TO_I64,    /* 'to_int': IntCastFunction, np.array(x, dtype='int')  functions.py:179-183,356 (NaN, inf and
+                       * out-of-range floats give INT64_MIN, as on x86-64)                                           */
+    VNM_EX_TO_BOOL    /* 'to_bool': BoolCastFunction, np.array(x, dtype='bool') = x != 0  functions.py:165-169,354 */
 };
 /* out_type of vnm_project when the expression is a predicate: out_values is a byte mask (1 byte per row) */
 #define VNM_MASK_U8 100
+/* out_type of vnm_project for a float16 result (sqrt / sin / ... of an 8-bit integer): 2 bytes per row.  float16 is a
+ * result type only, never an input column type */
+#define VNM_OUT_F16 101
 /* column flags */
 #define VNM_FLAG_SUM32 1 /* time32: SUM accumulates and wraps in int32 (agg_func_factory.cpp:132-137) */
 
@@ -396,7 +414,9 @@ void vnm_sort_op_destroy(vnm_sort_op* h);
  * unsigned + signed -> the next wider signed type (uint64 + signed -> float64), integer results wrap in the result
  * width, `/` -> float64 (float32 for float32 with narrow integers), `%` = floor-mod (sign of the divisor); a literal
  * (VNM_EX_CONST_*) is "weak" and takes the column's type (arg = 1 makes it a strong int64 / float64 value, what an IN
- * list is); a column with NULLs is evaluated as float64 with NaN (float32 stays float32). */
+ * list is); a column with NULLs is evaluated as float64 with NaN (float32 stays float32).  A program with an integer
+ * power whose exponent is a signed column synchronises the stream and fails with NumPy's ValueError when an exponent is
+ * negative; every other program is launched asynchronously. */
 typedef struct vnm_expr_ins {
     int32_t op;  /* enum vnm_expr_op */
     int32_t arg; /* column index for VNM_EX_COL */

@@ -37,8 +37,10 @@ ASC, DESC = 0, 1
 EQ, NE, GT, GE, LT, LE = range(6)
 (EX_COL, EX_CONST_F, EX_CONST_I, EX_ADD, EX_SUB, EX_MUL, EX_DIV, EX_MOD, EX_NEG, EX_BAND, EX_BOR, EX_BXOR,
  EX_BNOT, EX_EQ, EX_NE, EX_GT, EX_GE, EX_LT, EX_LE, EX_AND, EX_OR, EX_NOT, EX_IS_NULL, EX_IS_NOT_NULL,
- EX_STORE) = range(25)
+ EX_STORE, EX_ABS, EX_SQRT, EX_SIN, EX_COS, EX_TAN, EX_LOG, EX_LOG2, EX_LOG10, EX_POW, EX_TO_F64, EX_TO_I64,
+ EX_TO_BOOL) = range(37)
 MASK_U8 = 100
+OUT_F16 = 101
 OUT_U64, OUT_I64, OUT_F64, OUT_F32, OUT_DEC128, OUT_I32 = range(6)
 FLAG_SUM32 = 1
 # accumulator-word merge kinds (vnm_agg_plan_host)

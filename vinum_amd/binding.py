@@ -138,6 +138,51 @@ class AggregateFunction(VectorizedExpression):
         return self._func.upper()
 
 
+# ---- mirror of the numeric built-in functions (vinum/core/functions.py:148-186, 353-387) ---------------------------
+class AbstractCastFunction(VectorizedExpression):
+    """Shape of functions.py:148-162: a VectorizedExpression subclass built as Cls(arguments) -- `_function` is None, the
+    cast lives in `_expr_kernel` as np.array(x, dtype=type)."""
+    type: Optional[str] = None
+
+    def __init__(self, arguments: Iterable, shared_id: Optional[str] = None):
+        super().__init__(arguments)
+
+
+class BoolCastFunction(AbstractCastFunction):
+    type = "bool"
+
+
+class FloatCastFunction(AbstractCastFunction):
+    type = "float"
+
+
+class IntCastFunction(AbstractCastFunction):
+    type = "int"
+
+
+_CAST_SPEC = {"bool": "to_bool", "float": "to_float", "int": "to_int"}
+
+# the numeric part of _default_functions_registry, with the same callables (math constants: the lambdas themselves)
+FUNCTIONS_REGISTRY = {
+    "to_bool": (BoolCastFunction, FunctionType.CLASS),
+    "to_float": (FloatCastFunction, FunctionType.CLASS),
+    "to_int": (IntCastFunction, FunctionType.CLASS),
+    "abs": (np.absolute, FunctionType.NUMPY),
+    "sqrt": (np.sqrt, FunctionType.NUMPY),
+    "cos": (np.cos, FunctionType.NUMPY),
+    "sin": (np.sin, FunctionType.NUMPY),
+    "tan": (np.tan, FunctionType.NUMPY),
+    "power": (np.power, FunctionType.NUMPY),
+    "log": (np.log, FunctionType.NUMPY),
+    "log2": (np.log2, FunctionType.NUMPY),
+    "log10": (np.log10, FunctionType.NUMPY),
+    "pi": (lambda: np.pi, FunctionType.NUMPY),
+    "e": (lambda: np.e, FunctionType.NUMPY),
+}
+_NUMERIC_FNS = tuple(FUNCTIONS_REGISTRY)
+# ufuncs are recognised by identity, whatever spelling reached them (`np.sin`, `np.abs` is np.absolute)
+_UFUNC_SPEC = {id(fn): name for name, (fn, ft) in FUNCTIONS_REGISTRY.items() if isinstance(fn, np.ufunc)}
+
 _SPEC_TO_SQL = {"add": "ADDITION", "sub": "SUBTRACTION", "mul": "MULTIPLICATION", "div": "DIVISION", "mod": "MODULUS",
                 "neg": "NEGATION", "bnot": "BINARY_NOT", "band": "BINARY_AND", "bor": "BINARY_OR", "bxor": "BINARY_XOR",
                 "eq": "EQUALS", "ne": "NOT_EQUALS", "gt": "GREATER_THAN", "ge": "GREATER_THAN_OR_EQUAL", "lt": "LESS_THAN",
@@ -147,7 +192,17 @@ _SPEC_TO_SQL = {"add": "ADDITION", "sub": "SUBTRACTION", "mul": "MULTIPLICATION"
 _SQL_TO_SPEC = {v: k for k, v in _SPEC_TO_SQL.items()}
 
 
-def vectorize(expr, registry=None, classes=None):
+_AGG_NAMES = ("count_star", "count", "sum", "avg", "min", "max", "np.min", "np.max", "np.sum")
+
+
+def _is_builtin(name, functions=None):
+    """a numeric built-in (or an existing np.<ufunc>) -- any other ("fn", name) stays an AggregateFunction node, as before"""
+    if name.startswith("np."):
+        return isinstance(getattr(np, name[3:], None), np.ufunc)
+    return name in (functions or FUNCTIONS_REGISTRY)
+
+
+def vectorize(expr, registry=None, classes=None, functions=None):
     """Build the VectorizedExpression tree the planner builds for `expr` (QueryPlanner._process_expressions_tree,
     vinum/planner/planner.py:140-222) from the prefix form -- with this module's mirror classes by default, or with the
     reference's own (classes = (Column, Literal, VectorizedExpression, AggregateFunction, SQLExpression, FunctionType,
@@ -162,9 +217,20 @@ def vectorize(expr, registry=None, classes=None):
         if isinstance(e, (int, float)):
             return Lt(e)
         op, args = e[0], e[1:]
-        if op == "fn":
+        if op == "fn" and (args[0].lower() in _AGG_NAMES or not _is_builtin(args[0].lower(), functions)):
             arg = build(args[1]) if len(args) > 1 else None
             return AF(args[0], arg) if arg is not None else AF(args[0])
+        if op == "fn" or op in FUNCTIONS_REGISTRY:
+            name = args[0].lower() if op == "fn" else op
+            fargs = args[1:] if op == "fn" else args
+            if name.startswith("np."):
+                fn, ftype = getattr(np, name[3:]), FT.NUMPY                 # lookup_udf: eval("np.<name>")
+            else:
+                fn, ftype = (functions or FUNCTIONS_REGISTRY)[name]
+            built = [build(a) for a in fargs]
+            if ftype == FT.CLASS:
+                return fn(built)                                            # planner.py:129-131: Cls(arguments)
+            return VE(built, function=fn, is_numpy_func=(ftype == FT.NUMPY), is_binary_func=False)
         member = SQL[_SPEC_TO_SQL[op]]
         fn, ftype = registry[member]
         if op in ("in", "not_in"):
@@ -176,12 +242,17 @@ def vectorize(expr, registry=None, classes=None):
 
 
 # ---- the adapter ---------------------------------------------------------------------------------------------------
-def registry_index(expression_functions) -> Dict[int, str]:
-    """id(callable) -> SQL operator name, for any registry with the reference's layout."""
-    return {id(fn): member.name for member, (fn, _ftype) in expression_functions.items()}
+def registry_index(expression_functions, functions_registry=None) -> Dict[int, str]:
+    """id(callable) -> SQL operator name, for any registry with the reference's layout; with a functions registry
+    (_default_functions_registry's layout, name -> (callable, FunctionType)) its numeric built-ins join as "fn:<name>"."""
+    index = {id(fn): member.name for member, (fn, _ftype) in expression_functions.items()}
+    for name, (fn, _ftype) in (functions_registry or {}).items():
+        if name in _NUMERIC_FNS and not isinstance(fn, type):
+            index[id(fn)] = "fn:" + name
+    return index
 
 
-_DEFAULT_INDEX = registry_index(EXPRESSION_FUNCTIONS)
+_DEFAULT_INDEX = registry_index(EXPRESSION_FUNCTIONS, FUNCTIONS_REGISTRY)
 
 
 def lower(node, index: Optional[Dict[int, str]] = None):
@@ -197,11 +268,22 @@ def lower(node, index: Optional[Dict[int, str]] = None):
         return ("fn", name, col) if col else ("fn", name)
     if hasattr(node, "arguments") and hasattr(node, "_function"):
         fn = node._function
+        cast = getattr(type(node), "type", None)
+        if fn is None and cast in _CAST_SPEC and type(node).__name__ in ("BoolCastFunction", "FloatCastFunction", "IntCastFunction"):
+            args = [lower(a, index) for a in node.arguments]   # AbstractCastFunction (functions.py:148-162)
+            return (_CAST_SPEC[cast],) + tuple(args)
+        if fn is not None and id(fn) not in index and id(fn) in _UFUNC_SPEC:
+            return (_UFUNC_SPEC[id(fn)],) + tuple(lower(a, index) for a in node.arguments)
         if fn is None or id(fn) not in index:
-            raise NotImplementedError(f"no GPU lowering for {fn!r} (UDFs, string and datetime functions stay on the CPU path)")
+            raise NotImplementedError(f"no GPU lowering for {fn if fn is not None else type(node).__name__!r}: the numeric "
+                                      "operators and the built-ins abs, sqrt, sin, cos, tan, log, log2, log10, power, pi, e, "
+                                      "to_int, to_float, to_bool run on the GPU; UDFs, LIKE, string and datetime functions "
+                                      "and other np.* functions do not")
         sql = index[id(fn)]
-        op = _SQL_TO_SPEC[sql]
         args = [lower(a, index) for a in node.arguments]
+        if sql.startswith("fn:"):
+            return (sql[3:],) + tuple(args)
+        op = _SQL_TO_SPEC[sql]
         if op in ("in", "not_in"):
             vals = args[1]
             return (op, args[0], tuple(vals) if isinstance(vals, (list, tuple, np.ndarray)) else (vals,))
@@ -265,7 +347,8 @@ def install(vinum_pkg) -> None:
     vinum_amd.vinum_lib covers the native seam B1, see INTEGRATION.md.)"""
     planner_mod = __import__(vinum_pkg.__name__ + ".planner.planner", fromlist=["x"])
     expr_mod = __import__(vinum_pkg.__name__ + ".core.expressions", fromlist=["x"])
-    index = registry_index(expr_mod.EXPRESSION_FUNCTIONS)
+    fn_mod = __import__(vinum_pkg.__name__ + ".core.functions", fromlist=["x"])
+    index = registry_index(expr_mod.EXPRESSION_FUNCTIONS, fn_mod._default_functions_registry)
 
     class _Filter(GpuFilterOperator):
         def __init__(self, predicate, parent_operator):

@@ -12,6 +12,11 @@ from .algebra import FilterOperator
 _FUNCS = {"COUNT": L.COUNT, "COUNT_STAR": L.COUNT_STAR, "MIN": L.MIN, "MAX": L.MAX, "SUM": L.SUM, "AVG": L.AVG}
 
 
+def _has_cast(e) -> bool:
+    """to_int / to_bool turn float64 columns into a non-float64 value: such an input is projected, not handed to the kernel"""
+    return isinstance(e, tuple) and (e[0] in ("to_int", "to_bool") or any(_has_cast(x) for x in e[1:]))
+
+
 class AggregateFunction:
     """expr (optional): the function's argument is an EXPRESSION over input columns (prefix tuple, see vinum_amd.ops) --
     `sum((1 - total) * (2 + tax))`.  The reference's planner projects it into a temporary column before the aggregate
@@ -63,7 +68,7 @@ class AggregateOperator(Operator):
         for e in exprs:
             cols = ops.columns_of(e)
             f64 = all(batch.column(c).arrow_type == pa.float64() and batch.column(c).dictionary is None for c in cols)
-            if self._kernel_expr is None and cols and f64 and len(cols) <= 16:
+            if self._kernel_expr is None and cols and f64 and len(cols) <= 16 and not _has_cast(e):
                 self._kernel_expr, self._kernel_expr_cols = e, cols
             else:
                 self._projected[e] = f"__expr_{len(self._projected)}"

@@ -20,6 +20,17 @@
 // Values travel through the interpreter as 64-bit words: integers sign / zero extended, floats as float64 bits (a
 // float32 value as the float64 of that float32); after every operation whose result type is narrower the word is
 // brought back into that type's range (wraparound / rounding to float32), which is bit-identical to narrow arithmetic.
+//
+// Built-in scalar functions (_default_functions_registry, vinum/core/functions.py:353-387): abs, sqrt, sin, cos, tan, log,
+// log2, log10, power and the casts to_float / to_int / to_bool.  NumPy 2 ufunc typing: sqrt and the transcendentals of
+// (u)int8 are float16 (NumPy's `e` loops: sqrt in float32, rounded to half), of (u)int16 and float32 float32, of wider
+// integers and float64 float64; abs keeps the type (integers wrap); power promotes like the other binary operators.
+// sqrt is correctly rounded in its width (bit-identical to NumPy); the transcendentals and float power run in float64
+// (OCML) and are rounded to the result type.
+// A float16 value is held as the float64 of that half and brought back into half range after every operation (float32
+// first, then half, like NumPy's float16 loops).  Programs with any of these opcodes run a MATH instantiation of the
+// kernel -- MATH = 1 for the exact ones (abs, sqrt, casts, float16 arithmetic), MATH = 2 when a transcendental or power is
+// in the program, whose OCML code needs far more registers; every other program runs the same code as before (MATH = 0).
 #include "vnm_common.hpp"
 
 namespace vnm {
@@ -57,11 +68,17 @@ struct ProjArgs {
     int64_t length;
     void* out[PJ_MAX_OUT];
     uint8_t out_is_mask[PJ_MAX_OUT];  // predicate outputs are byte masks
-    uint8_t out_type[PJ_MAX_OUT];     // vnm_type of a value output (its width decides the store)
+    uint8_t out_type[PJ_MAX_OUT];     // vnm_type of a value output (its width decides the store), or VNM_OUT_F16
+    int* neg_pow;                     // MATH: set when an integer power meets a negative exponent column (NumPy ValueError)
 };
 
+__device__ __forceinline__ uint64_t pj_dbits(double d) { return (uint64_t)__double_as_longlong(d); }
+__device__ __forceinline__ double pj_bitsd(uint64_t x) { return __longlong_as_double((long long)x); }
+
 // wraparound / rounding of a 64-bit interpreter word into the range of a narrower type
+template <int MATH>
 __device__ __forceinline__ uint64_t pj_narrow(int t, uint64_t x) {
+    if (MATH > 0 && t == VNM_OUT_F16) return pj_dbits((double)(_Float16)(float)pj_bitsd(x));   // float32 first, then half
     switch (t) {
         case VNM_I8: return (uint64_t)(int64_t)(int8_t)x;
         case VNM_I16: return (uint64_t)(int64_t)(int16_t)x;
@@ -93,9 +110,63 @@ __device__ __forceinline__ int64_t np_imod(int64_t a, int64_t b) {
     return m;
 }
 
+// an operand word as a double: 0 float64 bits, 1 signed integer, 2 unsigned integer
+__device__ __forceinline__ double pj_as_f64(int cvt, uint64_t x) {
+    return cvt ? (cvt == 2 ? (double)x : (double)(int64_t)x) : pj_bitsd(x);
+}
+
+// the exact unary built-ins (abs, sqrt, casts) over one word.  cvt: how the operand is held; f32: compute in float32 (float32 / float16 results)
+__device__ __forceinline__ uint64_t pj_math1(int op, int cvt, bool f32, uint64_t x) {
+    switch (op) {
+        case VNM_EX_ABS:   // floats: the sign bit cleared (NaN included); signed integers: wraps in the result width
+            return cvt == 0 ? (x & 0x7FFFFFFFFFFFFFFFULL) : ((int64_t)x < 0 ? (uint64_t)0 - x : x);
+        case VNM_EX_TO_BOOL: return (cvt == 0 ? pj_bitsd(x) != 0.0 : x != 0) ? 1ULL : 0ULL;
+        case VNM_EX_TO_F64: return pj_dbits(pj_as_f64(cvt, x));
+        case VNM_EX_TO_I64: {
+            if (cvt != 0) return x;                               // integers: int64 bits (uint64 wraps)
+            const double d = trunc(pj_bitsd(x));
+            // NaN, +-inf and values outside [-2^63, 2^63): INT64_MIN, what cvttsd2si gives NumPy on x86-64
+            if (!(d >= -9223372036854775808.0 && d < 9223372036854775808.0)) return 0x8000000000000000ULL;
+            return (uint64_t)(int64_t)d;
+        }
+        default:           // VNM_EX_SQRT: correctly rounded in both widths
+            return f32 ? pj_dbits((double)sqrtf((float)pj_as_f64(cvt, x))) : pj_dbits(sqrt(pj_as_f64(cvt, x)));
+    }
+}
+// the transcendentals (OCML), kept apart from the cheap functions so only their own loop carries their registers.  They
+// run in float64 for every result type: float32 / float16 results are the float64 value rounded (float32, then half),
+// which is within 1 ULP where OCML's float32 functions measured up to 2.1 ULP (logf)
+__device__ __forceinline__ uint64_t pj_math_t(int op, int cvt, bool f32, uint64_t x) {
+    const double d = pj_as_f64(cvt, x);
+    double r;
+    switch (op) {
+        case VNM_EX_SIN: r = sin(d); break;
+        case VNM_EX_COS: r = cos(d); break;
+        case VNM_EX_TAN: r = tan(d); break;
+        case VNM_EX_LOG: r = log(d); break;
+        case VNM_EX_LOG2: r = log2(d); break;
+        default: r = log10(d); break;
+    }
+    return pj_dbits(f32 ? (double)(float)r : r);
+}
+
+// npy integer power (loops_autovec / `@TYPE@_power`): exponentiation by squaring, wrapping in 64 bits; the caller narrows
+__device__ __forceinline__ uint64_t pj_ipow(uint64_t base, uint64_t e) {
+    if (e == 0 || base == 1) return 1;
+    uint64_t out = (e & 1) ? base : 1;
+    e >>= 1;
+    while (e > 0) {
+        base *= base;
+        if (e & 1) out *= base;
+        e >>= 1;
+    }
+    return out;
+}
+
 // Postfix interpreter.  The program is uniform, so opcode fetch and dispatch are scalar; the top of the stack
 // lives in registers (tos), deeper values in LDS (sized by the host to the program's real depth), and every
 // decoded opcode is applied to PJ_R rows of the lane.
+template <int MATH>
 __global__ __launch_bounds__(PJ_BLOCK) void project_kernel(ProjArgs a) {
     extern __shared__ uint64_t stk[];  // [depth - 1][PJ_R][PJ_BLOCK]
     const int tid = threadIdx.x;
@@ -173,12 +244,42 @@ __global__ __launch_bounds__(PJ_BLOCK) void project_kernel(ProjArgs a) {
                         x = in.is_f ? (uint64_t)__double_as_longlong(-__longlong_as_double((long long)x)) : (uint64_t)0 - x;
                     else if (op == VNM_EX_BNOT) x = ~x;
                     else x ^= 1ULL;
-                    if (in.nar >= 0) x = pj_narrow(in.nar, x);
+                    if (in.nar >= 0) x = pj_narrow<MATH>(in.nar, x);
                     tos[r] = x;
+                }
+            } else if (MATH > 0 && op >= VNM_EX_ABS && op != VNM_EX_POW) {
+                // ---- unary built-in function ----
+                if (op == VNM_EX_ABS || op == VNM_EX_SQRT || op >= VNM_EX_TO_F64) {
+#pragma unroll
+                    for (int r = 0; r < PJ_R; r++) {
+                        uint64_t x = pj_math1(op, in.cvt_a, in.cmp == 1, tos[r]);
+                        if (in.nar >= 0) x = pj_narrow<MATH>(in.nar, x);
+                        tos[r] = x;
+                    }
+                } else if (MATH == 2) {
+                    // transcendentals: one row at a time through the free LDS level sp - 1, so ONE copy of the OCML code
+                    // holds registers (unrolled over the PJ_R rows, interleaved copies cut the occupancy of every MATH program)
+#pragma unroll
+                    for (int r = 0; r < PJ_R; r++) STK(sp - 1, r) = tos[r];
+#pragma unroll 1
+                    for (int r = 0; r < PJ_R; r++) {
+                        uint64_t x = pj_math_t(op, in.cvt_a, in.cmp == 1, STK(sp - 1, r));
+                        if (in.nar >= 0) x = pj_narrow<MATH>(in.nar, x);
+                        STK(sp - 1, r) = x;
+                    }
+#pragma unroll
+                    for (int r = 0; r < PJ_R; r++) tos[r] = STK(sp - 1, r);
                 }
             } else if (op == VNM_EX_STORE) {
                 // ---- pop into an output column ----
-                if (a.out_is_mask[in.arg]) {
+                if (MATH > 0 && a.out_type[in.arg] == VNM_OUT_F16) {
+                    _Float16* o = (_Float16*)a.out[in.arg];
+#pragma unroll
+                    for (int r = 0; r < PJ_R; r++) {
+                        const int64_t row = base + (r >> 1) * (2 * PJ_BLOCK) + (r & 1);
+                        if (row < a.length) o[row] = (_Float16)pj_bitsd(tos[r]);   // exact: the word holds a half
+                    }
+                } else if (a.out_is_mask[in.arg]) {
                     uint8_t* o = (uint8_t*)a.out[in.arg];
 #pragma unroll
                     for (int r = 0; r < PJ_R; r++) {
@@ -225,6 +326,31 @@ __global__ __launch_bounds__(PJ_BLOCK) void project_kernel(ProjArgs a) {
                 sp--;
                 const bool cmp = op >= VNM_EX_EQ && op <= VNM_EX_LE;
                 const bool as_f = cmp ? (in.cvt_a || in.cvt_b || in.arg) : in.is_f != 0;
+                if (MATH == 2 && op == VNM_EX_POW) {
+                    // np.power, one row at a time like the transcendentals (b goes to the free LDS level sp)
+#pragma unroll
+                    for (int r = 0; r < PJ_R; r++) STK(sp, r) = tos[r];
+#pragma unroll 1
+                    for (int r = 0; r < PJ_R; r++) {
+                        const uint64_t xa = STK(sp - 1, r);
+                        const uint64_t xb = STK(sp, r);
+                        uint64_t res;
+                        if (as_f) {
+                            const double da = pj_as_f64(in.cvt_a, xa), db = pj_as_f64(in.cvt_b, xb);
+                            res = pj_dbits(in.cmp == 1 ? (double)(float)pow(da, db) : pow(da, db));   // float64, rounded as above
+                        } else if (in.arg == 1 && (int64_t)xb < 0) {
+                            *a.neg_pow = 1;   // "Integers to negative integer powers are not allowed." (the host raises)
+                            res = 0;
+                        } else {
+                            res = pj_ipow(xa, xb);
+                        }
+                        if (in.nar >= 0) res = pj_narrow<MATH>(in.nar, res);
+                        STK(sp, r) = res;
+                    }
+#pragma unroll
+                    for (int r = 0; r < PJ_R; r++) tos[r] = STK(sp, r);
+                    continue;
+                }
 #pragma unroll
                 for (int r = 0; r < PJ_R; r++) {
                     const uint64_t xa = STK(sp - 1, r);
@@ -271,7 +397,7 @@ __global__ __launch_bounds__(PJ_BLOCK) void project_kernel(ProjArgs a) {
                             default: res = xa ^ xb; break;
                         }
                     }
-                    if (in.nar >= 0) res = pj_narrow(in.nar, res);
+                    if (in.nar >= 0) res = pj_narrow<MATH>(in.nar, res);
                     tos[r] = res;
                 }
             }
@@ -306,6 +432,16 @@ static int pj_promote(int a, int b) {
         default: return VNM_F64;   // uint64 with a signed type
     }
 }
+constexpr int PJ_T_F16 = 13;   // host-side type id of a float16 value (after the bool mask and the weak literals)
+// the same with float16 values (results of sqrt / sin / ... over 8-bit integers): float16 survives 8-bit integers and
+// float16, float32 16-bit integers and float32, everything else goes to float64
+static int pj_promote_h(int a, int b) {
+    if (a != PJ_T_F16 && b != PJ_T_F16) return pj_promote(a, b);
+    const int o = a == PJ_T_F16 ? b : a;
+    if (o == PJ_T_F16) return PJ_T_F16;
+    if (type_is_float(o)) return o;
+    return type_width(o) == 1 ? PJ_T_F16 : type_width(o) == 2 ? VNM_F32 : VNM_F64;
+}
 static const char* pj_type_name(int t) {
     static const char* n[] = {"int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64", "float32", "float64"};
     return t >= 0 && t < 10 ? n[t] : "?";
@@ -327,7 +463,6 @@ static bool pj_int_fits(int t, int64_t v) {
 // Python literals, bool masks), launch.  `single`: the program is one expression without a STORE; out index 0 is implied.
 static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, const vnm_dcol* cols, int64_t length,
                         int n_out, void** out_values, int* out_types, bool single, void* stream) {
-    VNM_TRY(ensure_init());
     if (n_ins <= 0 || n_ins + (single ? 1 : 0) > PJ_MAX_INS)
         return set_error("vnm_project: program must have 1..%d instructions", PJ_MAX_INS - (single ? 1 : 0));
     if (n_cols < 0 || n_cols > PJ_MAX_COLS) return set_error("vnm_project: at most %d input columns", PJ_MAX_COLS);
@@ -347,7 +482,8 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
     bool stored[PJ_MAX_OUT] = {};
     const int total = n_ins + (single ? 1 : 0);
     auto is_num = [&](int t) { return t != T_B; };
-    auto held_f = [&](int t) { return t == T_WF || (t < 10 && type_is_float(t)); };       // held as float64 bits
+    auto is_float_t = [&](int t) { return t == PJ_T_F16 || (t < 10 && type_is_float(t)); };
+    auto held_f = [&](int t) { return t == T_WF || is_float_t(t); };                        // held as float64 bits
     auto cvt_of = [&](int t) { return held_f(t) ? 0 : (t == VNM_U64 ? 2 : 1); };           // how to turn the held word into a double
     // a weak literal meets a float32 column: NumPy casts the scalar to float32 first
     auto round_lit_f32 = [&](int slot) {
@@ -356,6 +492,20 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
         if (p.op == VNM_EX_CONST_I) { p.op = VNM_EX_CONST_F; p.imm_f = (double)(float)p.imm_i; p.is_f = 1; }
         else p.imm_f = (double)(float)p.imm_f;
     };
+    // ... a float16 value: the scalar is cast to float16 (npy_double_to_half: one rounding, straight from double)
+    auto round_lit_f16 = [&](int slot) {
+        if (lit[slot] < 0) return;
+        PIns& p = a.ins[lit[slot]];
+        if (p.op == VNM_EX_CONST_I) { p.op = VNM_EX_CONST_F; p.imm_f = (double)(_Float16)(double)p.imm_i; p.is_f = 1; }
+        else p.imm_f = (double)(_Float16)p.imm_f;
+    };
+    auto round_lit = [&](int slot, int t) {
+        if (t == VNM_F32) round_lit_f32(slot);
+        else if (t == PJ_T_F16) round_lit_f16(slot);
+    };
+    int cst[PJ_STACK];   // the CONST instruction that pushed the slot's value, weak or strong, still unchanged (-1: none)
+    int math = 0;   // the kernel instantiation: 1 exact built-ins / float16 values, 2 transcendentals or power
+    bool pow_check = false;
     for (int i = 0; i < total; i++) {
         vnm_expr_ins in;
         if (i < n_ins) in = program[i];
@@ -378,6 +528,7 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
                 if (cols[in.arg].validity != nullptr && !type_is_float(ct)) t = VNM_F64;   // NULL -> NaN needs a float (record_batch.py:112-118)
                 o.is_f = type_is_float(t);
                 lit[sp] = -1;
+                cst[sp] = -1;
                 ty[sp++] = t;
                 break;
             }
@@ -387,6 +538,7 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
                 o.is_f = in.op == VNM_EX_CONST_F;
                 // arg = 1: a STRONG constant (an element of the array np.isin builds from an IN list): int64 / float64
                 lit[sp] = in.arg == 1 ? -1 : i;
+                cst[sp] = i;
                 ty[sp++] = in.arg == 1 ? (o.is_f ? VNM_F64 : VNM_I64) : (o.is_f ? T_WF : T_WI);
                 o.arg = 0;
                 break;
@@ -395,6 +547,7 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
                 if (in.arg < 0 || in.arg >= n_cols) return set_error("vnm_project: column index %d out of range", in.arg);
                 if (sp >= PJ_STACK) return set_error("vnm_project: expression too deep");
                 lit[sp] = -1;
+                cst[sp] = -1;
                 ty[sp++] = T_B;
                 break;
             case VNM_EX_NEG:
@@ -416,6 +569,37 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
                 o.is_f = held_f(t);
                 if (t < 10 && !type_is_float(t) && type_width(t) < 8) o.nar = t;
                 lit[sp - 1] = -1;
+                cst[sp - 1] = -1;
+                break;
+            }
+            case VNM_EX_ABS: case VNM_EX_SQRT: case VNM_EX_SIN: case VNM_EX_COS: case VNM_EX_TAN: case VNM_EX_LOG:
+            case VNM_EX_LOG2: case VNM_EX_LOG10: case VNM_EX_TO_F64: case VNM_EX_TO_I64: case VNM_EX_TO_BOOL: {
+                if (sp < 1) return set_error("vnm_project: malformed program (stack underflow)");
+                const bool cast = in.op >= VNM_EX_TO_F64;
+                const bool trans = !cast && in.op != VNM_EX_ABS && in.op != VNM_EX_SQRT;
+                math = std::max(math, trans ? 2 : 1);
+                int t = ty[sp - 1];
+                if (t == T_B && !cast) return set_error("vnm_project: arithmetic on a boolean mask is not supported");
+                if (t == T_WI) t = VNM_I64;    // a NumPy ufunc / np.array over a Python scalar: int64 / float64
+                if (t == T_WF) t = VNM_F64;
+                o.cvt_a = t == T_B ? 1 : cvt_of(t);
+                int rt;
+                if (in.op == VNM_EX_ABS) {
+                    rt = t;
+                    if (type_is_unsigned(t)) o.op = PJ_NOP;                     // the identity
+                    else if (!is_float_t(t) && type_width(t) < 8) o.nar = t;     // abs(int8 -128) == -128
+                } else if (in.op == VNM_EX_TO_F64) rt = VNM_F64;
+                else if (in.op == VNM_EX_TO_I64) rt = VNM_I64;
+                else if (in.op == VNM_EX_TO_BOOL) rt = T_B;
+                else {
+                    rt = is_float_t(t) ? t : type_width(t) == 1 ? PJ_T_F16 : type_width(t) == 2 ? VNM_F32 : VNM_F64;
+                    o.cmp = rt != VNM_F64 ? 1 : 0;                             // float32 arithmetic, NumPy's f / e loops
+                    if (rt == PJ_T_F16) o.nar = VNM_OUT_F16;
+                }
+                o.is_f = held_f(rt);
+                ty[sp - 1] = rt;
+                lit[sp - 1] = -1;
+                cst[sp - 1] = -1;
                 break;
             }
             case VNM_EX_NOT:
@@ -433,8 +617,8 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
                 const int tb = ty[sp - 1], ta = ty[sp - 2];
                 if (!is_num(ta) || !is_num(tb)) return set_error("vnm_project: comparing boolean masks is not supported");
                 // a float32 column against a Python literal compares in float32
-                if (ta == VNM_F32 && (tb == T_WI || tb == T_WF)) round_lit_f32(sp - 1);
-                if (tb == VNM_F32 && (ta == T_WI || ta == T_WF)) round_lit_f32(sp - 2);
+                if ((ta == VNM_F32 || ta == PJ_T_F16) && (tb == T_WI || tb == T_WF)) round_lit(sp - 1, ta);
+                if ((tb == VNM_F32 || tb == PJ_T_F16) && (ta == T_WI || ta == T_WF)) round_lit(sp - 2, tb);
                 const bool anyf = held_f(ta) || held_f(tb);
                 if (anyf) {  // NumPy compares in float64 as soon as one side is float (float32 values are exact float64s)
                     o.cmp = 1;
@@ -452,15 +636,15 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
                 sp--;
                 ty[sp - 1] = T_B;
                 lit[sp - 1] = -1;
+                cst[sp - 1] = -1;
                 break;
             }
             case VNM_EX_ADD: case VNM_EX_SUB: case VNM_EX_MUL: case VNM_EX_DIV: case VNM_EX_MOD:
-            case VNM_EX_BAND: case VNM_EX_BOR: case VNM_EX_BXOR: {
+            case VNM_EX_BAND: case VNM_EX_BOR: case VNM_EX_BXOR: case VNM_EX_POW: {
                 if (sp < 2) return set_error("vnm_project: malformed program (stack underflow)");
                 const int tb = ty[sp - 1], ta = ty[sp - 2];
                 if (!is_num(ta) || !is_num(tb)) return set_error("vnm_project: arithmetic on a boolean mask is not supported");
-                const bool bitop = in.op >= VNM_EX_BAND;
-                const bool wa = ta >= T_WI, wb = tb >= T_WI;
+                const bool wa = ta == T_WI || ta == T_WF, wb = tb == T_WI || tb == T_WF;
                 int rt;
                 if (wa && wb) rt = (ta == T_WF || tb == T_WF) ? VNM_F64 : VNM_I64;       // Python scalars: default int64 / float64
                 else if (wa || wb) {
@@ -468,17 +652,27 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
                     if (w == T_WI) {
                         rt = t;                                                               // the literal takes the column's type
                         // true division runs in float64 whatever the integer width: NumPy converts the literal to double, no range check
-                        if (in.op != VNM_EX_DIV && !type_is_float(t) && lit[wslot] >= 0 && !pj_int_fits(t, a.ins[lit[wslot]].imm_i))
+                        if (in.op != VNM_EX_DIV && !is_float_t(t) && lit[wslot] >= 0 && !pj_int_fits(t, a.ins[lit[wslot]].imm_i))
                             return set_error("OverflowError: Python integer %lld out of bounds for %s", (long long)a.ins[lit[wslot]].imm_i, pj_type_name(t));
-                        if (t == VNM_F32) round_lit_f32(wslot);
+                        round_lit(wslot, t);
                     } else {
-                        rt = t == VNM_F32 ? VNM_F32 : VNM_F64;
-                        if (t == VNM_F32) round_lit_f32(wslot);
+                        rt = (t == VNM_F32 || t == PJ_T_F16) ? t : VNM_F64;
+                        round_lit(wslot, t);
                     }
-                } else rt = pj_promote(ta, tb);
-                if (bitop && (type_is_float(rt) || held_f(ta) || held_f(tb))) return set_error("ufunc 'bitwise' not supported for float inputs");
-                if (in.op == VNM_EX_DIV && !type_is_float(rt)) rt = VNM_F64;
-                const bool rf = type_is_float(rt);
+                } else rt = pj_promote_h(ta, tb);
+                const bool bitop = in.op >= VNM_EX_BAND && in.op <= VNM_EX_BXOR;
+                if (bitop && (is_float_t(rt) || held_f(ta) || held_f(tb))) return set_error("ufunc 'bitwise' not supported for float inputs");
+                if (in.op == VNM_EX_DIV && !is_float_t(rt)) rt = VNM_F64;
+                const bool rf = is_float_t(rt);
+                if (in.op == VNM_EX_POW) {
+                    math = 2;
+                    if (!rf) {
+                        // integer ** negative integer: NumPy's ValueError -- a constant exponent here, a column in the kernel
+                        if (cst[sp - 1] >= 0 && a.ins[cst[sp - 1]].op == VNM_EX_CONST_I && a.ins[cst[sp - 1]].imm_i < 0)
+                            return set_error("ValueError: Integers to negative integer powers are not allowed.");
+                        if (cst[sp - 1] < 0 && !type_is_unsigned(tb)) { o.arg = 1; pow_check = true; }
+                    } else if (rt != VNM_F64) o.cmp = 1;   // float32 arithmetic (float32 and float16 results)
+                }
                 o.is_f = rf;
                 if (rf) {
                     const bool a_f = held_f(ta) || (lit[sp - 2] >= 0 && a.ins[lit[sp - 2]].op == VNM_EX_CONST_F);
@@ -487,10 +681,12 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
                     o.cvt_b = b_f ? 0 : (tb == VNM_U64 ? 2 : 1);
                 }
                 if (rt == VNM_F32 || (!rf && type_width(rt) < 8)) o.nar = rt;
-                if (rt == VNM_U64) o.cmp = 2;   // unsigned modulo
+                if (rt == PJ_T_F16) { o.nar = VNM_OUT_F16; math = std::max(math, 1); }
+                if (rt == VNM_U64 && in.op == VNM_EX_MOD) o.cmp = 2;   // unsigned modulo
                 sp--;
                 ty[sp - 1] = rt;
                 lit[sp - 1] = -1;
+                cst[sp - 1] = -1;
                 break;
             }
             case VNM_EX_STORE: {
@@ -502,6 +698,7 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
                 int t = ty[sp - 1];
                 if (t == T_WI) t = VNM_I64;            // np.repeat(5, n) -> int64, np.repeat(5.0, n) -> float64 (algebra.py:77-87)
                 if (t == T_WF) t = VNM_F64;
+                if (t == PJ_T_F16) t = VNM_OUT_F16;
                 a.out[in.arg] = out_values[in.arg];
                 a.out_is_mask[in.arg] = t == T_B;
                 a.out_type[in.arg] = t == T_B ? VNM_U8 : t;
@@ -517,8 +714,12 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
     for (int k = 0; k < n_out; k++)
         if (!stored[k]) return set_error("vnm_project: output %d is never stored", k);
     a.n_ins = total;
+    // typing needs no device: a zero-length call type-checks a program (result types, NumPy's errors) on any host
     if (length <= 0) return 0;
-    const size_t lds = (size_t)(depth > 1 ? depth - 1 : 1) * PJ_R * PJ_BLOCK * 8;
+    VNM_TRY(ensure_init());
+    if (pow_check && math != 2) return set_error("vnm_project: internal error (power outside the MATH kernel)");
+    // depth - 1 levels below the register top; MATH programs stage the top through one more level
+    const size_t lds = (size_t)(math ? depth : (depth > 1 ? depth - 1 : 1)) * PJ_R * PJ_BLOCK * 8;
     // ONE workgroup per tile: a workgroup loads, computes and stores with nothing of its own to overlap, so it is the
     // dispatcher that keeps the memory system busy (three expressions over 1e9 rows: 8 workgroups per CU looping over tiles
     // 11.15 ms, 32 per CU 10.2, 128 per CU 9.7, one per tile 9.27 = 5.2 TB/s)
@@ -526,13 +727,33 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
     int grid = (int)grid64;
     int64_t need = (length + PJ_TILE - 1) / PJ_TILE;
     if (grid > need) grid = (int)need;
+    const void* kern = math == 2 ? (const void*)project_kernel<2> : math == 1 ? (const void*)project_kernel<1> : (const void*)project_kernel<0>;
     if (lds > 64 * 1024)   // depth >= 10: beyond the default dynamic LDS limit
-        VNM_HIP(hipFuncSetAttribute((const void*)project_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    {
-        KernelTimer timer("project_kernel", as_stream(stream));
-        project_kernel<<<grid, PJ_BLOCK, lds, as_stream(stream)>>>(a);
+        VNM_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipStream_t s = as_stream(stream);
+    PoolScope scope;
+    if (pow_check) {   // an integer power with a signed exponent column: the kernel reports a negative exponent
+        a.neg_pow = (int*)scope.take(sizeof(int));
+        if (!a.neg_pow) return 1;
+        VNM_HIP(hipMemsetAsync(a.neg_pow, 0, sizeof(int), s));
+    }
+    if (math == 2) {
+        KernelTimer timer("project_kernel_math", s);
+        project_kernel<2><<<grid, PJ_BLOCK, lds, s>>>(a);
+    } else if (math == 1) {
+        KernelTimer timer("project_kernel_exact_fn", s);
+        project_kernel<1><<<grid, PJ_BLOCK, lds, s>>>(a);
+    } else {
+        KernelTimer timer("project_kernel", s);
+        project_kernel<0><<<grid, PJ_BLOCK, lds, s>>>(a);
     }
     VNM_HIP(hipGetLastError());
+    if (pow_check) {
+        int neg = 0;
+        VNM_HIP(hipMemcpyAsync(&neg, a.neg_pow, sizeof(int), hipMemcpyDeviceToHost, s));
+        VNM_HIP(hipStreamSynchronize(s));
+        if (neg) return set_error("ValueError: Integers to negative integer powers are not allowed.");
+    }
     return 0;
 }
 

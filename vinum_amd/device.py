@@ -15,6 +15,10 @@ _NP = {L.I8: np.int8, L.I16: np.int16, L.I32: np.int32, L.I64: np.int64, L.U8: n
        L.U32: np.uint32, L.U64: np.uint64, L.F32: np.float32, L.F64: np.float64}
 _WIDTH = {L.I8: 1, L.U8: 1, L.I16: 2, L.U16: 2, L.I32: 4, L.U32: 4, L.F32: 4, L.I64: 8, L.U64: 8, L.F64: 8}
 _FROM_NP = {np.dtype(v): k for k, v in _NP.items()}
+# float16 is a RESULT type only (sqrt / sin / ... of an 8-bit integer column): it can be read back and passed through,
+# but it is not staged from Arrow (physical_type) and is the input of no kernel (DeviceColumn.dcol refuses it)
+_NP[L.OUT_F16] = np.float16
+_WIDTH[L.OUT_F16] = 2
 
 
 def physical_type(t: pa.DataType):
@@ -99,7 +103,8 @@ class DeviceColumn:
         bools, decimals: dictionary-encoded on ingest); to_arrow() then returns the decoded values."""
         self._values, self._validity = values, validity
         self.offset, self.length, self.arrow_type = int(offset), int(length), arrow_type
-        self.vnm_type, self.flags = physical_type(arrow_type)
+        # float16: a projection RESULT (sqrt / sin / ... of 8-bit integers), never staged from Arrow (physical_type refuses it)
+        self.vnm_type, self.flags = (L.OUT_F16, 0) if pa.types.is_float16(arrow_type) else physical_type(arrow_type)
         self._keep = keep  # anything that must outlive the raw pointers (torch tensors)
         self.dictionary = dictionary
 
@@ -171,6 +176,9 @@ class DeviceColumn:
         return self._ptr(self._validity)
 
     def dcol(self) -> L.DCol:
+        if self.vnm_type == L.OUT_F16:
+            raise RuntimeError("float16 columns are not GPU operator inputs (aggregate input, sort key, expression "
+                               "operand): cast with to_float()")
         d = L.DCol()
         d.values = self.values_ptr
         d.validity = self.validity_ptr

@@ -449,11 +449,89 @@ _EX = {"add": L.EX_ADD, "sub": L.EX_SUB, "mul": L.EX_MUL, "div": L.EX_DIV, "mod"
        "+": L.EX_ADD, "-": L.EX_SUB, "*": L.EX_MUL, "/": L.EX_DIV, "%": L.EX_MOD,
        "eq": L.EX_EQ, "ne": L.EX_NE, "gt": L.EX_GT, "ge": L.EX_GE, "lt": L.EX_LT, "le": L.EX_LE,
        "==": L.EX_EQ, "=": L.EX_EQ, "!=": L.EX_NE, "<>": L.EX_NE, ">": L.EX_GT, ">=": L.EX_GE, "<": L.EX_LT, "<=": L.EX_LE,
-       "and": L.EX_AND, "or": L.EX_OR, "not": L.EX_NOT}
+       "and": L.EX_AND, "or": L.EX_OR, "not": L.EX_NOT,
+       "abs": L.EX_ABS, "sqrt": L.EX_SQRT, "sin": L.EX_SIN, "cos": L.EX_COS, "tan": L.EX_TAN, "log": L.EX_LOG,
+       "log2": L.EX_LOG2, "log10": L.EX_LOG10, "power": L.EX_POW,
+       "to_float": L.EX_TO_F64, "to_int": L.EX_TO_I64, "to_bool": L.EX_TO_BOOL}
+_UNARY = (L.EX_NEG, L.EX_BNOT, L.EX_NOT, L.EX_ABS, L.EX_SQRT, L.EX_SIN, L.EX_COS, L.EX_TAN, L.EX_LOG, L.EX_LOG2, L.EX_LOG10,
+          L.EX_TO_F64, L.EX_TO_I64, L.EX_TO_BOOL)
+
+# The numeric built-ins of the reference's _default_functions_registry (vinum/core/functions.py:353-387) with the callables
+# it registers: what a subtree of literals folds to on the host, so folded constants keep NumPy's value AND scalar type
+# (np.sqrt(4) is a strong np.float64, pi() the weak Python float np.pi)
+SCALAR_FUNCS = {
+    "abs": np.absolute, "sqrt": np.sqrt, "cos": np.cos, "sin": np.sin, "tan": np.tan, "power": np.power,
+    "log": np.log, "log2": np.log2, "log10": np.log10,
+    "to_int": lambda x: np.array(x, dtype="int"), "to_float": lambda x: np.array(x, dtype="float"),
+    "to_bool": lambda x: np.array(x, dtype="bool"),
+    "pi": lambda: np.pi, "e": lambda: np.e,
+}
+SCALAR_ARITY = {"power": 2, "pi": 0, "e": 0}
+
+
+def _is_lit(e):
+    return (isinstance(e, (int, float)) and not isinstance(e, bool)) or (isinstance(e, tuple) and len(e) == 2 and e[0] == "strong")
+
+
+def _lit_value(e):
+    """a literal operand as the Python / NumPy scalar the reference's ufunc receives"""
+    if isinstance(e, tuple):
+        return np.float64(e[1]) if isinstance(e[1], float) else np.int64(e[1])
+    return e
+
+
+def _fold(e):
+    """Fold every built-in function whose operands are all literals, with NumPy itself."""
+    if not isinstance(e, tuple) or e[0] in ("strong", "lit", "in", "not_in", "is_null", "is_not_null"):
+        return e
+    args = tuple(_fold(x) for x in e[1:])
+    e = (e[0],) + args
+    if e[0] not in SCALAR_FUNCS or not all(_is_lit(a) for a in args):
+        return e
+    with np.errstate(all="ignore"):
+        v = SCALAR_FUNCS[e[0]](*[_lit_value(a) for a in args])
+    if isinstance(v, float) and not isinstance(v, np.floating):
+        return v                                   # pi() / e(): a weak Python float
+    v = np.asarray(v)
+    if v.dtype == np.bool_:
+        raise TypeError("boolean literals are not arithmetic operands")
+    if v.dtype == np.float64:
+        return ("strong", float(v))
+    if v.dtype == np.int64:
+        return ("strong", int(v))
+    raise TypeError(f"a constant of type {v.dtype} is not supported")
 
 
 _ARROW_OF = {L.I8: pa.int8(), L.I16: pa.int16(), L.I32: pa.int32(), L.I64: pa.int64(), L.U8: pa.uint8(), L.U16: pa.uint16(),
-             L.U32: pa.uint32(), L.U64: pa.uint64(), L.F32: pa.float32(), L.F64: pa.float64()}
+             L.U32: pa.uint32(), L.U64: pa.uint64(), L.F32: pa.float32(), L.F64: pa.float64(), L.OUT_F16: pa.float16()}
+
+
+def _check_project(rc):
+    """L.check, with the NumPy exceptions the kernel's host side reports raised under their own class"""
+    try:
+        L.check(rc)
+    except L.VinumHipError as exc:
+        msg = str(exc)
+        if msg.startswith("ValueError: "):
+            raise ValueError(msg[len("ValueError: "):]) from None
+        raise
+
+
+def result_type(expr, types) -> pa.DataType:
+    """Type-check `expr` the way vnm_project does (NumPy 2 typing, NumPy's errors such as `power(<integer column>,
+    <negative integer literal>)` -> ValueError) without touching a device: a zero-length call.  types: column name ->
+    (pa.DataType, has_nulls).  Returns the Arrow type of the result (pa.uint8() for a predicate mask)."""
+    names = columns_of(expr)
+    prog = compile_expr(expr, {n: i for i, n in enumerate(names)})
+    dummy = ctypes.create_string_buffer(8)
+    cols = (L.DCol * max(len(names), 1))()
+    for i, n in enumerate(names):
+        t, nulls = types[n]
+        cols[i].type = physical_type(t)[0]
+        cols[i].validity = ctypes.addressof(dummy) if nulls else None
+    ot = ctypes.c_int(0)
+    _check_project(L.load().vnm_project(len(prog), prog, len(names), cols, 0, ctypes.addressof(dummy), ctypes.byref(ot), None))
+    return pa.uint8() if ot.value == L.MASK_U8 else _ARROW_OF[ot.value]
 
 
 def _desugar(e):
@@ -500,9 +578,14 @@ def _emit_expr(expr, col_index, out):
         elif e[0] in ("is_null", "is_not_null"):
             out.append((L.EX_IS_NULL if e[0] == "is_null" else L.EX_IS_NOT_NULL, col_index[e[1]], 0.0, 0))
         else:
+            if e[0] in ("pi", "e"):
+                out.append((L.EX_CONST_F, 0, float(SCALAR_FUNCS[e[0]]()), 0))
+                return
             op = _EX[e[0]]
             args = e[1:]
-            if op in (L.EX_NEG, L.EX_BNOT, L.EX_NOT):
+            if e[0] in SCALAR_FUNCS and len(args) != SCALAR_ARITY.get(e[0], 1):
+                raise TypeError(f"{e[0]}() takes {SCALAR_ARITY.get(e[0], 1)} argument(s), {len(args)} given")
+            if op in _UNARY:
                 emit(args[0])
                 out.append((op, 0, 0.0, 0))
             else:
@@ -510,7 +593,7 @@ def _emit_expr(expr, col_index, out):
                 for a in args[1:]:
                     emit(a)
                     out.append((op, 0, 0.0, 0))
-    emit(_desugar(expr))
+    emit(_fold(_desugar(expr)))
 
 
 def _program(ins):
@@ -539,7 +622,7 @@ def project(expr, columns: dict, length=None, stream=None) -> DeviceColumn:
     prog = compile_expr(expr, {n: i for i, n in enumerate(names)})
     out = DeviceBuffer(max(length, 1) * 8)
     ot = ctypes.c_int(0)
-    L.check(L.lib().vnm_project(len(prog), prog, len(cols), dcol_array(cols), length, out.ptr, ctypes.byref(ot),
+    _check_project(L.lib().vnm_project(len(prog), prog, len(cols), dcol_array(cols), length, out.ptr, ctypes.byref(ot),
                                 _stream_ptr(stream)))
     if ot.value == L.MASK_U8:
         return DeviceColumn(out, None, 0, length, pa.uint8())   # byte mask (predicate program)
@@ -581,7 +664,7 @@ def project_many(exprs, columns: dict, length=None, stream=None):
         bufs = [DeviceBuffer(max(length, 1) * 8) for _ in ks]
         ptrs = (ctypes.c_void_p * len(ks))(*[b.ptr for b in bufs])
         types = (ctypes.c_int * len(ks))()
-        L.check(L.lib().vnm_project_multi(len(prog), prog, len(cols), dcol_array(cols), length, len(ks), ptrs, types,
+        _check_project(L.lib().vnm_project_multi(len(prog), prog, len(cols), dcol_array(cols), length, len(ks), ptrs, types,
                                           _stream_ptr(stream)))
         for k, b, t in zip(ks, bufs, types):
             at = pa.uint8() if t == L.MASK_U8 else _ARROW_OF[t]

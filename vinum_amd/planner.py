@@ -10,7 +10,9 @@ A query is a dict (see tests/golden/planner_cases.py):
     where      expr | None       group_by [expr]           having expr | None
     order_by   [expr]            sort_order ["ASC" | "DESC"]   limit int | None   offset int
     expr := column name | int | float | (op, arg...)   with op as in vinum_amd.ops plus ("fn", name, arg...) for the
-            aggregate functions count_star / count / sum / avg / min / max.
+            aggregate functions count_star / count / sum / avg / min / max and the numeric built-in scalar functions
+            (SCALAR_FN_NAMES: abs, sqrt, sin, ..., to_int, pi, e and their np. spellings), which are per-row expressions
+            wherever they appear, like any operator.
 
 What the planner does with the aggregate part mirrors planner.py:380-469:
   * DISTINCT = GROUP BY every select expression (:380-382);
@@ -29,13 +31,22 @@ from .core import (AggregateFunction, AggregateOperator, FileReaderOperator, Fil
 from .ops import columns_of
 
 AGG_FUNCS = ("count_star", "count", "sum", "avg", "min", "max")     # vinum/core/functions.py:389-396
+# numeric part of _default_functions_registry (vinum/core/functions.py:353-387) and the `np.` spellings lookup_udf resolves
+# to the same ufuncs (vinum/core/udf.py:28-64) -> the vinum_amd.ops operator name
+SCALAR_FN_NAMES = {n: n for n in ("abs", "sqrt", "cos", "sin", "tan", "power", "log", "log2", "log10", "to_int", "to_float",
+                                  "to_bool", "pi", "e")}
+SCALAR_FN_NAMES.update({"np." + n: n for n in ("sqrt", "cos", "sin", "tan", "power", "log", "log2", "log10", "abs")})
+SCALAR_FN_NAMES["np.absolute"] = "abs"
 
 
 def _t(e):
-    """JSON lists -> tuples (hashable, and what ops.compile_expr takes); IN value lists stay lists."""
+    """JSON lists -> tuples (hashable, and what ops.compile_expr takes); IN value lists stay lists.  A built-in scalar
+    function ("fn", "sqrt", x) becomes the operator node ("sqrt", x); aggregate and unknown names stay "fn" nodes."""
     if isinstance(e, (list, tuple)) and e and isinstance(e[0], str):
         if e[0] in ("in", "not_in"):
             return (e[0], _t(e[1]), tuple(e[2]))
+        if e[0] == "fn" and len(e) > 1 and isinstance(e[1], str) and e[1].lower() in SCALAR_FN_NAMES:
+            return tuple([SCALAR_FN_NAMES[e[1].lower()]] + [_t(x) for x in e[2:]])
         return tuple([e[0]] + [_t(x) for x in e[1:]])
     return e
 
@@ -184,7 +195,7 @@ def plan_query(query: Dict, source, expected_groups: int = 0) -> Plan:
             op = FilterOperator(pred if pred is not None else having, op)
             steps.append(("having", having))
 
-    names = output_names([_t(e) for e in query["select"]], aliases)
+    names = output_names([_raw(e) for e in query["select"]], aliases)
     if order_by:
         # ORDER BY expressions are evaluated into extra columns, sorted by, and dropped by the final projection
         # (SortOperator.next, algebra.py:159-177)
@@ -206,6 +217,13 @@ def plan_query(query: Dict, source, expected_groups: int = 0) -> Plan:
         op = SliceOperator(limit, offset, op)
         steps.append(("slice", limit, offset))
     return Plan(MaterializeTableOperator(op), steps)
+
+
+def _raw(e):
+    """the select expression as written (a function keeps its "fn" node: the reference names the column after it)"""
+    if isinstance(e, (list, tuple)) and e and e[0] == "fn":
+        return tuple(e)
+    return _t(e)
 
 
 def execute(query: Dict, source, expected_groups: int = 0) -> pa.Table:
