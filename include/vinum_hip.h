@@ -352,7 +352,10 @@ typedef struct vnm_agg_op vnm_agg_op;
 vnm_agg_op* vnm_agg_op_create(int kind, int n_groupby, const char** groupby_cols, int n_aggcols,
                               const char** agg_cols, int n_funcs, const int* func_types,
                               const char** in_cols, const char** out_cols);
-int vnm_agg_op_next(vnm_agg_op* h, struct ArrowArray* batch, struct ArrowSchema* schema); /* consumes both */
+/* Consumes both.  The first batch fixes the layout: the columns the operator reads are found there by name, and every later
+ * batch must hold each of them at the same position, with the same name and format (otherwise: "the batch schema changed").
+ * Columns nobody reads may be of any type. */
+int vnm_agg_op_next(vnm_agg_op* h, struct ArrowArray* batch, struct ArrowSchema* schema);
 /* Every batch of an Arrow C stream, as one vnm_agg_op_next each (consumes and releases the stream).  The reference's pipeline
  * hands over 10 000-row batches (vinum/__init__.py:52, table_batch_reader.cpp:5-16); crossing the language boundary once per
  * few hundred of them instead of once each is what the caller saves -- the operator keeps small batches as they are (no

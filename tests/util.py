@@ -81,7 +81,7 @@ def canon(batch, key_names):
             sort_keys.append(vals.astype(np.uint64))
         order = np.lexsort(sort_keys[::-1])
         return batch.take(pa.array(order.astype(np.int64)))
-    keys = [[(0 if v else 1, int(x)) for v, x in zip(valid, vals)] for valid, vals in cols]
+    keys = [[(0 if v else 1, x if isinstance(x, (str, bytes)) else int(x)) for v, x in zip(valid, vals)] for valid, vals in cols]
     order = sorted(range(batch.num_rows), key=lambda r: tuple(k[r] for k in keys))
     return batch.take(pa.array(order, pa.int64()))
 
@@ -151,10 +151,15 @@ def exact_group_sums(source, key_names, col):
     import math
     t = pa.Table.from_batches(list(source)).combine_chunks() if not isinstance(source, pa.Table) else source.combine_chunks()
     n = t.num_rows
-    keycols = []
+    keycols, decode = [], {}
     for k in key_names:
         valid, vals = _bits(t.column(k))
         keycols.append((~valid).astype(np.uint64))
+        if isinstance(vals, list):          # string / binary / decimal keys: grouped by the rank of the value, reported by the value
+            distinct = sorted(set(vals))
+            rank = {v: i for i, v in enumerate(distinct)}
+            decode[len(keycols)] = distinct
+            vals = [rank[v] for v in vals]
         keycols.append(np.asarray(vals, dtype=np.uint64))
     arr = t.column(col).combine_chunks()
     vvalid = np.ones(n, bool) if arr.null_count == 0 else np.array(arr.is_valid())
@@ -176,7 +181,7 @@ def exact_group_sums(source, key_names, col):
             exact = math.fsum(seg.tolist())
         except (ValueError, OverflowError):     # inf - inf, or an intermediate overflow: not a finite exact value (the caller compares
             exact = float(np.sum(seg))          # the class of the result -- NaN / +-inf -- with the reference's)
-        out[tuple(int(w) for w in uniq[g])] = (exact, int(seg.size))
+        out[tuple(decode[j][int(w)] if j in decode else int(w) for j, w in enumerate(uniq[g]))] = (exact, int(seg.size))
     return out
 
 
@@ -233,7 +238,7 @@ def assert_agg_equal(actual, expected, funcs, key_names, exact_float_inputs=("v_
             kb = [_bits(expected.column(k)) for k in key_names]
             rows = []
             for r in range(expected.num_rows):
-                key = tuple(x for valid, vals in kb for x in (int(not valid[r]), int(vals[r])))
+                key = tuple(x for valid, vals in kb for x in (int(not valid[r]), vals[r] if isinstance(vals, list) else int(vals[r])))
                 rows.append(exact_cache[col][key])
             _assert_float_agg_exact(a, e, f, rows, name, what)
         elif name in loose and pa.types.is_floating(e.type):

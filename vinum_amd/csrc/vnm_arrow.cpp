@@ -430,7 +430,7 @@ struct vnm_agg_op {
     // small batches wait here until they add up to a device-sized one (vnm_agg_op_next)
     std::vector<std::unique_ptr<ImportedBatch>> pending;
     int64_t pending_rows = 0;
-    std::vector<std::string> formats;   // child formats of the first batch: later batches must match on the columns used
+    std::vector<std::string> formats, names;   // children of the first batch: later batches must match on the columns used
     // MIN / MAX over utf8 / binary columns (StringMinMaxFunc, agg_funcs.h:219-261), see strmm_* below
     std::vector<std::unique_ptr<StrCol>> strcols;   // one device dictionary per such column
     std::vector<StrFn> strfns;
@@ -844,13 +844,18 @@ int vnm_agg_op_next(vnm_agg_op* h, struct ArrowArray* batch, struct ArrowSchema*
     if (!h->inited) {
         rc = agg_op_init(h, &ib.sch);
         if (!rc) {
-            h->formats.clear();
-            for (int64_t c = 0; c < ib.sch.n_children; c++) h->formats.push_back(ib.sch.children[c]->format ? ib.sch.children[c]->format : "");
+            h->formats.clear(); h->names.clear();
+            for (int64_t c = 0; c < ib.sch.n_children; c++) {
+                h->formats.push_back(ib.sch.children[c]->format ? ib.sch.children[c]->format : "");
+                h->names.push_back(ib.sch.children[c]->name ? ib.sch.children[c]->name : "");
+            }
         }
     } else {
-        // the columns the operator reads must be where -- and what -- they were in the first batch
+        // the columns the operator reads must be where -- and what, under the same name -- they were in the first batch (a
+        // column of the same type in another layout would otherwise be read in their place)
         auto same = [&](int ci) { return ci < (int)ib.sch.n_children && ci < (int)h->formats.size() && ib.sch.children[ci]->format &&
-                                         h->formats[(size_t)ci] == ib.sch.children[ci]->format; };
+                                         h->formats[(size_t)ci] == ib.sch.children[ci]->format && ib.sch.children[ci]->name &&
+                                         h->names[(size_t)ci] == ib.sch.children[ci]->name; };
         for (size_t j = 0; !rc && j < h->key_idx.size(); j++) if (!same(h->key_idx[j])) rc = set_error("vnm_agg_op_next: the batch schema changed");
         for (size_t i = 0; !rc && i < h->funcs.size(); i++) if (h->in_idx[i] >= 0 && !same(h->in_idx[i])) rc = set_error("vnm_agg_op_next: the batch schema changed");
     }

@@ -352,7 +352,10 @@ class _HashAggregateBase:
                 self._send(b)
             return
         # the waiting batches cross the boundary as ONE Arrow C stream: no concatenation on the host (that copy was most of
-        # the cost: 0.8 GB per 5e7 rows), one call instead of one per batch; the library stages them to the device together
+        # the cost: 0.8 GB per 5e7 rows), one call instead of one per batch; the library stages them to the device together.
+        # They cross in the same view as every other batch: the library found its columns by name in the first one and reads
+        # them by position afterwards
+        pending = [self._numeric_view(b) for b in pending]
         reader = pa.RecordBatchReader.from_batches(pending[0].schema, pending)
         stream = ctypes.create_string_buffer(40)      # struct ArrowArrayStream: five pointers
         reader._export_to_c(ctypes.addressof(stream))
@@ -645,6 +648,9 @@ class GenericHashAggregate:
     COUNT(col) of a non-numeric column counts through an int8 stand-in with the same validity and MIN / MAX of strings
     (agg_funcs.h:219-261) are ranks-on-the-device (_StringMinMax), both in the numeric classes underneath."""
 
+    _SMALL_ROWS = 1 << 20       # (as _HashAggregateBase: smaller batches wait here and are encoded together)
+    _FLUSH_ROWS = 1 << 22
+
     def __init__(self, groupby_cols, agg_cols, agg_funcs):
         self._groupby, self._agg_cols, self._funcs = list(groupby_cols), list(agg_cols), list(agg_funcs)
         self._inner = None
@@ -676,13 +682,13 @@ class GenericHashAggregate:
             self._schema0 = batch.schema
             self._encode_and_send(batch)
             return
-        if batch.num_rows >= (1 << 20) or batch.schema != self._schema0:   # (a schema change raises from this call, as in the reference)
+        if batch.num_rows >= self._SMALL_ROWS or batch.schema != self._schema0:   # (a schema change raises from this call, as in the reference)
             self._flush()
             self._encode_and_send(batch)
             return
         self._pending.append(batch)
         self._pending_rows += batch.num_rows
-        if self._pending_rows >= (1 << 22):
+        if self._pending_rows >= self._FLUSH_ROWS:
             self._flush()
 
     def _flush(self) -> None:
