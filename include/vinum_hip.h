@@ -97,7 +97,12 @@ enum vnm_expr_op {
     VNM_EX_TO_F64,    /* 'to_float': FloatCastFunction, np.array(x, dtype='float')  functions.py:172-176,355    */
     VNM_EX_TO_I64,    /* 'to_int': IntCastFunction, np.array(x, dtype='int')  functions.py:179-183,356 (NaN, inf and
                        * out-of-range floats give INT64_MIN, as on x86-64)                                           */
-    VNM_EX_TO_BOOL    /* 'to_bool': BoolCastFunction, np.array(x, dtype='bool') = x != 0  functions.py:165-169,354 */
+    VNM_EX_TO_BOOL,   /* 'to_bool': BoolCastFunction, np.array(x, dtype='bool') = x != 0  functions.py:165-169,354 */
+    /* LIKE / NOT LIKE over a dictionary-coded string column: LikeFunction, functions.py:301-344.  Pushes table[code] as a
+     * predicate value: arg = the int32 code column, imm_i = the index in `cols` of the table -- a VNM_U8 column of one byte
+     * per dictionary id (vnm_strdict_like) whose length is the id count, not the batch length; it is read by this opcode only.
+     * A NULL code, a negative code and a code past the table push 0 (NOT LIKE = NOT of it: true on NULL rows, as `!=`). */
+    VNM_EX_LOOKUP_U8
 };
 /* out_type of vnm_project when the expression is a predicate: out_values is a byte mask (1 byte per row) */
 #define VNM_MASK_U8 100
@@ -476,6 +481,25 @@ int vnm_strdict_fetch_new(vnm_strdict* h, int32_t* ids_host, int32_t* lens_host,
  * a column of codes (device; -1 = NULL -> rank 0, the row's validity bit says NULL) to its ranks: an ordinary int32 sort key column. */
 int vnm_strdict_ranks_device(vnm_strdict* h, int32_t* out_rank_of_id, void* stream);
 int vnm_strdict_codes_to_ranks(const int32_t* codes, const int32_t* rank_of_id, int64_t n, int32_t* out_ranks, void* stream);
+/* LIKE / NOT LIKE against the dictionary's values (LikeFunction, vinum/core/functions.py:301-344: the pattern becomes the regex
+ * '^' + p.replace('_', '.').replace('%', '.*') + '$', matched per row).  Restated exactly: `_` and `.` match one code point other
+ * than '\n', `%` zero or more such code points, every other byte is literal; a value also matches when it ends in '\n' and
+ * matches without that byte ('$' matches before a final newline).  VNM_LIKE_STRIP_NUL: trailing NUL bytes are dropped first (a
+ * utf8 column reaches the reference as a NumPy 'U' array, which strips them; large_utf8 stays an object array and keeps them).
+ * A pattern with another regex metacharacter (\ ^ $ * + ? { } [ ] | ( )) is refused.
+ * vnm_like_compile: the pattern -> tokens on the host (no device): 3 int32 per token (kind VNM_LIKE_TOK_*, byte start, byte
+ * length in the pattern), consecutive `%` folded; out_tokens holds 3 * max(pattern_len, 1) entries.
+ * vnm_strdict_like: out_match_of_id[id] = 1 / 0 for every id in [id_begin, vnm_strdict_ids(h)) -- 0 for an id never handed
+ * out.  out_match_of_id is a DEVICE buffer of at least vnm_strdict_ids(h) bytes; only that range is written, so a table kept
+ * across batches is extended with id_begin = the id count it covers.  One kernel on `stream`, launched asynchronously (a
+ * pattern's tokens are uploaded once per handle and kept). */
+#define VNM_LIKE_STRIP_NUL 1
+#define VNM_LIKE_TOK_LIT 0
+#define VNM_LIKE_TOK_ANY 1
+#define VNM_LIKE_TOK_STAR 2
+int vnm_like_compile(const uint8_t* pattern, int64_t pattern_len, int32_t* out_tokens, int64_t* n_tokens);
+int vnm_strdict_like(vnm_strdict* h, const uint8_t* pattern, int64_t pattern_len, int flags, int64_t id_begin,
+                     uint8_t* out_match_of_id, void* stream);
 
 /* ---- CSV ingest ---------------------------------------------------------------------------------------
  * replaces, for numeric columns, the pyarrow.csv reader behind stream_csv() / read_csv() (vinum/io/arrow.py:58-61,106;
@@ -543,6 +567,8 @@ int64_t vnm_pool_cached_bytes(void);
 int vnm_memcpy_h2d(void* dst, const void* src, int64_t bytes);
 int vnm_memcpy_d2h(void* dst, const void* src, int64_t bytes);
 int vnm_memset(void* dst, int value, int64_t bytes);
+/* device -> device copy on `stream` (asynchronous) */
+int vnm_memcpy_d2d(void* dst, const void* src, int64_t bytes, void* stream);
 
 #ifdef __cplusplus
 }

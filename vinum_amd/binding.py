@@ -162,6 +162,15 @@ class IntCastFunction(AbstractCastFunction):
 
 _CAST_SPEC = {"bool": "to_bool", "float": "to_float", "int": "to_int"}
 
+
+class LikeFunction(VectorizedExpression):
+    """Shape of functions.py:301-344: LikeFunction((column, Literal(pattern)), invert) -- `_function` is None, the regex match
+    lives in `_expr_kernel`; invert = True is NOT LIKE (planner.py:189-193)."""
+
+    def __init__(self, arguments, invert: bool) -> None:
+        super().__init__(arguments, is_numpy_func=True)
+        self.invert = invert
+
 # the numeric part of _default_functions_registry, with the same callables (math constants: the lambdas themselves)
 FUNCTIONS_REGISTRY = {
     "to_bool": (BoolCastFunction, FunctionType.CLASS),
@@ -202,12 +211,13 @@ def _is_builtin(name, functions=None):
     return name in (functions or FUNCTIONS_REGISTRY)
 
 
-def vectorize(expr, registry=None, classes=None, functions=None):
+def vectorize(expr, registry=None, classes=None, functions=None, like_cls=None):
     """Build the VectorizedExpression tree the planner builds for `expr` (QueryPlanner._process_expressions_tree,
     vinum/planner/planner.py:140-222) from the prefix form -- with this module's mirror classes by default, or with the
     reference's own (classes = (Column, Literal, VectorizedExpression, AggregateFunction, SQLExpression, FunctionType,
-    BINARY_EXPRESSIONS), registry = its EXPRESSION_FUNCTIONS) in the build container."""
+    BINARY_EXPRESSIONS), registry = its EXPRESSION_FUNCTIONS, like_cls = its LikeFunction) in the build container."""
     registry = registry or EXPRESSION_FUNCTIONS
+    like_cls = like_cls or LikeFunction
     C, Lt, VE, AF, SQL, FT, BIN = classes or (Column, Literal, VectorizedExpression, AggregateFunction, SQLExpression,
                                              FunctionType, BINARY_EXPRESSIONS)
 
@@ -217,6 +227,10 @@ def vectorize(expr, registry=None, classes=None, functions=None):
         if isinstance(e, (int, float)):
             return Lt(e)
         op, args = e[0], e[1:]
+        if op == "lit":
+            return Lt(args[0])
+        if op in ("like", "not_like"):                           # planner.py:189-193
+            return like_cls(tuple(build(a) for a in args), op == "not_like")
         if op == "fn" and (args[0].lower() in _AGG_NAMES or not _is_builtin(args[0].lower(), functions)):
             arg = build(args[1]) if len(args) > 1 else None
             return AF(args[0], arg) if arg is not None else AF(args[0])
@@ -268,6 +282,10 @@ def lower(node, index: Optional[Dict[int, str]] = None):
         return ("fn", name, col) if col else ("fn", name)
     if hasattr(node, "arguments") and hasattr(node, "_function"):
         fn = node._function
+        if fn is None and type(node).__name__ == "LikeFunction":
+            like = _lower_like(node, index)
+            if like is not None:
+                return like
         cast = getattr(type(node), "type", None)
         if fn is None and cast in _CAST_SPEC and type(node).__name__ in ("BoolCastFunction", "FloatCastFunction", "IntCastFunction"):
             args = [lower(a, index) for a in node.arguments]   # AbstractCastFunction (functions.py:148-162)
@@ -277,8 +295,8 @@ def lower(node, index: Optional[Dict[int, str]] = None):
         if fn is None or id(fn) not in index:
             raise NotImplementedError(f"no GPU lowering for {fn if fn is not None else type(node).__name__!r}: the numeric "
                                       "operators and the built-ins abs, sqrt, sin, cos, tan, log, log2, log10, power, pi, e, "
-                                      "to_int, to_float, to_bool run on the GPU; UDFs, LIKE, string and datetime functions "
-                                      "and other np.* functions do not")
+                                      "to_int, to_float, to_bool and LIKE / NOT LIKE against a string literal run on the "
+                                      "GPU; UDFs, string and datetime functions and other np.* functions do not")
         sql = index[id(fn)]
         args = [lower(a, index) for a in node.arguments]
         if sql.startswith("fn:"):
@@ -296,6 +314,19 @@ def lower(node, index: Optional[Dict[int, str]] = None):
     if hasattr(node, "get_column_name"):                       # Column (:179-233)
         return node.get_column_name()
     raise TypeError(f"Unsupported OperatorArgument type: {type(node)}")     # base.py:52-54
+
+
+def _lower_like(node, index):
+    """LikeFunction((operand, Literal(str)), invert: bool) -> ("like" | "not_like", operand, ("lit", pattern)); any other shape
+    of a node with that class name -> None (the caller raises "no GPU lowering")."""
+    args = tuple(node.arguments)
+    invert = getattr(node, "invert", None)
+    if len(args) != 2 or not isinstance(invert, bool):
+        return None
+    lit = args[1]
+    if type(lit).__name__ != "Literal" or not hasattr(lit, "value") or not isinstance(lit.value, str):
+        return None
+    return ("not_like" if invert else "like", lower(args[0], index), ("lit", lit.value))
 
 
 def device_filter(batch: DeviceRecordBatch, predicate) -> DeviceRecordBatch:

@@ -7,14 +7,15 @@ import pyarrow as pa
 from .. import _lib as L
 from .. import ops
 from .base import DeviceRecordBatch, Operator
-from .algebra import FilterOperator
+from .algebra import FilterOperator, lower_like
 
 _FUNCS = {"COUNT": L.COUNT, "COUNT_STAR": L.COUNT_STAR, "MIN": L.MIN, "MAX": L.MAX, "SUM": L.SUM, "AVG": L.AVG}
 
 
 def _has_cast(e) -> bool:
-    """to_int / to_bool turn float64 columns into a non-float64 value: such an input is projected, not handed to the kernel"""
-    return isinstance(e, tuple) and (e[0] in ("to_int", "to_bool") or any(_has_cast(x) for x in e[1:]))
+    """to_int / to_bool turn float64 columns into a non-float64 value, LIKE into a mask: such an input is projected, not
+    handed to the kernel"""
+    return isinstance(e, tuple) and (e[0] in ("to_int", "to_bool", "like", "not_like") or any(_has_cast(x) for x in e[1:]))
 
 
 class AggregateFunction:
@@ -96,14 +97,15 @@ class AggregateOperator(Operator):
             self._agg.set_input_expr(first, self._kernel_expr, self._kernel_expr_cols)
 
     def _with_projected(self, batch: DeviceRecordBatch) -> DeviceRecordBatch:
-        exprs = list(self._projected)
-        used = {}
-        for e in exprs:
+        exprs, used, extra = [], {}, {}
+        for e in self._projected:
+            e, _ = lower_like(e, batch.columns, extra)    # sum(to_int(name LIKE 'J%')): a dictionary lookup
+            exprs.append(e)
             for c in ops.columns_of(e):
-                used[c] = batch.columns[c]
+                used[c] = extra[c] if c in extra else batch.columns[c]
         outs = ops.project_many(exprs, used, length=batch.num_rows)
         cols = dict(batch.columns)
-        for e, o in zip(exprs, outs):
+        for e, o in zip(self._projected, outs):
             cols[self._projected[e]] = o
         return DeviceRecordBatch(cols, batch.num_rows)
 

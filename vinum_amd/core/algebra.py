@@ -49,6 +49,40 @@ class FileReaderOperator(Operator):
             yield DeviceRecordBatch.from_arrow(batch.select(list(names)), self._dicts)
 
 
+def lower_like(expr, columns, extra=None):
+    """LIKE / NOT LIKE (LikeFunction, vinum/core/functions.py:301-344) -> a lookup in a per-pattern table of the column's
+    dictionary: ("like", col, ("lit", p)) becomes ("lookup", col, table) and ("not_like", ...) ("not", ("lookup", ...)), where
+    `table` names a uint8 column added to `extra` (KeyDictionary.like_table: one byte per dictionary id, matched on the device
+    once per distinct value).  A NULL row looks up 0: LIKE is false, NOT LIKE true -- the project's rule for `=` / `!=`.
+    Only a utf8 / large_utf8 column and a string literal pattern lower; other column types raise TypeError as in the
+    reference, other shapes NotImplementedError.  Returns (expression, extra)."""
+    extra = {} if extra is None else extra
+
+    def walk(e):
+        if not isinstance(e, tuple) or not e or e[0] == "lit":
+            return e
+        if e[0] in ("like", "not_like"):
+            if len(e) != 3:
+                raise NotImplementedError(f"no GPU lowering for a {e[0].upper()} node with {len(e) - 1} operand(s)")
+            col, pat = e[1], e[2]
+            if not (isinstance(pat, tuple) and len(pat) == 2 and pat[0] == "lit" and isinstance(pat[1], str)):
+                raise NotImplementedError(f"no GPU lowering for {e[0].upper()} with the pattern {pat!r}: a string literal is required")
+            if not isinstance(col, str) or col not in columns:
+                raise NotImplementedError(f"no GPU lowering for {e[0].upper()} over {col!r}: the operand must be a column")
+            c = columns[col]
+            if c.dictionary is None:
+                raise TypeError(f"LIKE needs a string column, {col!r} is {c.arrow_type}")
+            table = c.dictionary.like_table(pat[1])
+            name = f"__like_{len(extra)}_{col}"
+            extra[name] = table
+            node = ("lookup", col, name)
+            return node if e[0] == "like" else ("not", node)
+        if e[0] in ("in", "not_in"):
+            return (e[0], walk(e[1]), e[2])
+        return tuple([e[0]] + [walk(x) for x in e[1:]])
+    return walk(expr), extra
+
+
 class FilterOperator(Operator):
     """algebra.py:108-123: `WHERE column <op> literal`; every column of the batch is compacted (no selection
     vectors in the reference either).  predicate = (column, op, literal)."""
@@ -73,8 +107,9 @@ class FilterOperator(Operator):
         comparisons: = / != / IN on the literal's CODE (a value the dictionary does not hold matches no row), < <= > >= on the
         column's order-preserving RANKS (KeyDictionary.rank_column: byte-wise order, as Arrow / NumPy compare such values) against
         the literal's position among the dictionary's values.  NULL rows behave as in every other predicate (compare False,
-        `!=` True: vinum/arrow/record_batch.py:112-118).  Returns (predicate, extra columns the predicate reads)."""
-        extra = {}
+        `!=` True: vinum/arrow/record_batch.py:112-118).  LIKE / NOT LIKE become lookups in the dictionary's match table
+        (lower_like).  Returns (predicate, extra columns the predicate reads)."""
+        pred, extra = lower_like(pred, batch.columns)
 
         def is_dict(x):
             return isinstance(x, str) and x in batch.columns and batch.columns[x].dictionary is not None
@@ -146,12 +181,14 @@ class ProjectOperator(Operator):
         out = dict(batch.columns) if self._keep else {}
         n = batch.num_rows
         # every computed expression of the SELECT list goes into one fused kernel
-        exprs, used = [], {}
+        exprs, used, extra = [], {}, {}
         for name, arg in zip(self._col_names, self._arguments):
             if not isinstance(arg, str):
+                # LIKE nodes, and only those, become dictionary lookups (a predicate keeps the uint8 mask result type)
+                arg, _ = lower_like(arg, batch.columns, extra)
                 exprs.append((name, arg))
                 for c in _columns_of(arg):
-                    used[c] = batch.columns[c]
+                    used[c] = extra[c] if c in extra else batch.columns[c]
         computed = {}
         if exprs:
             # column-free expressions repeat their scalar once per row (:77-87)

@@ -31,6 +31,13 @@
 // first, then half, like NumPy's float16 loops).  Programs with any of these opcodes run a MATH instantiation of the
 // kernel -- MATH = 1 for the exact ones (abs, sqrt, casts, float16 arithmetic), MATH = 2 when a transcendental or power is
 // in the program, whose OCML code needs far more registers; every other program runs the same code as before (MATH = 0).
+//
+// VNM_EX_LOOKUP_U8 (LIKE / NOT LIKE over a dictionary-coded string column, vinum/core/functions.py:301-344) pushes
+// table[code] as a predicate value: `arg` is the int32 code column, `imm_i` the index in `cols` of the TABLE -- a VNM_U8
+// column of one byte per dictionary id (KeyDictionary.like_table, vnm_strdict_like), whose length is the dictionary's id
+// count, not the batch length.  A table is read by this opcode only; a NULL code, a negative code and a code at or past the
+// table's length push 0.  Programs with a lookup run an LK = 1 instantiation, so the push path of every other program keeps
+// the registers it had.
 #include "vnm_common.hpp"
 
 namespace vnm {
@@ -166,7 +173,7 @@ __device__ __forceinline__ uint64_t pj_ipow(uint64_t base, uint64_t e) {
 // Postfix interpreter.  The program is uniform, so opcode fetch and dispatch are scalar; the top of the stack
 // lives in registers (tos), deeper values in LDS (sized by the host to the program's real depth), and every
 // decoded opcode is applied to PJ_R rows of the lane.
-template <int MATH>
+template <int MATH, int LK>
 __global__ __launch_bounds__(PJ_BLOCK) void project_kernel(ProjArgs a) {
     extern __shared__ uint64_t stk[];  // [depth - 1][PJ_R][PJ_BLOCK]
     const int tid = threadIdx.x;
@@ -186,7 +193,7 @@ __global__ __launch_bounds__(PJ_BLOCK) void project_kernel(ProjArgs a) {
             const int op = in.op;
             if (op == PJ_NOP) continue;
             if (op == VNM_EX_COL || op == VNM_EX_CONST_F || op == VNM_EX_CONST_I || op == VNM_EX_IS_NULL ||
-                op == VNM_EX_IS_NOT_NULL) {
+                op == VNM_EX_IS_NOT_NULL || (LK && op == VNM_EX_LOOKUP_U8)) {
                 // ---- push ----
                 if (sp > 0) {
 #pragma unroll
@@ -216,6 +223,22 @@ __global__ __launch_bounds__(PJ_BLOCK) void project_kernel(ProjArgs a) {
                             } else {
                                 v = (uint64_t)col_i64(c, row);   // sign / zero extended
                             }
+                        }
+                        tos[r] = v;
+                    }
+                } else if (LK && op == VNM_EX_LOOKUP_U8) {
+                    // table[code]: the table is a few bytes per distinct value and stays in cache
+                    const vnm_dcol& c = a.cols[in.arg];
+                    const vnm_dcol& t = a.cols[in.imm_i];
+                    const int32_t* codes = (const int32_t*)c.values + c.offset;
+                    const uint8_t* tab = (const uint8_t*)t.values + t.offset;
+#pragma unroll
+                    for (int r = 0; r < PJ_R; r++) {
+                        const int64_t row = base + (r >> 1) * (2 * PJ_BLOCK) + (r & 1);
+                        uint64_t v = 0;
+                        if (row < a.length && col_valid(c, row)) {
+                            const int32_t code = codes[row];
+                            if (code >= 0 && (int64_t)code < t.length) v = tab[code] ? 1ULL : 0ULL;
                         }
                         tos[r] = v;
                     }
@@ -470,9 +493,24 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
     ProjArgs a{};
     a.n_cols = n_cols;
     a.length = length;
+    // the lookup tables of VNM_EX_LOOKUP_U8 are columns of their own length (one byte per dictionary id); every other column
+    // is a row column of the batch
+    bool is_table[PJ_MAX_COLS] = {};
+    int lookup = 0;
+    for (int i = 0; i < n_ins; i++) {
+        if (program[i].op != VNM_EX_LOOKUP_U8) continue;
+        const int64_t t = program[i].imm_i;
+        if (t < 0 || t >= n_cols) return set_error("vnm_project: lookup table index %lld out of range", (long long)t);
+        if (program[i].arg == t) return set_error("vnm_project: a lookup reads its codes from its own table");
+        is_table[t] = true;
+        lookup = 1;
+    }
     for (int c = 0; c < n_cols; c++) {
         if (cols[c].type < VNM_I8 || cols[c].type > VNM_F64) return set_error("vnm_project: column %d: unsupported type %d", c, cols[c].type);
-        if (cols[c].length != length) return set_error("Select expressions have unequal sizes. This is not permitted.");
+        if (is_table[c]) {
+            if (cols[c].type != VNM_U8 || cols[c].validity || cols[c].offset < 0 || cols[c].length < 0)
+                return set_error("vnm_project: lookup table %d must be a uint8 column without NULLs", c);
+        } else if (cols[c].length != length) return set_error("Select expressions have unequal sizes. This is not permitted.");
         a.cols[c] = cols[c];
     }
     enum { T_B = 10, T_WI = 11, T_WF = 12 };   // 0..9 = vnm_type; bool mask; weak Python int / float literal
@@ -522,6 +560,7 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
         switch (in.op) {
             case VNM_EX_COL: {
                 if (in.arg < 0 || in.arg >= n_cols) return set_error("vnm_project: column index %d out of range", in.arg);
+                if (is_table[in.arg]) return set_error("vnm_project: column %d is a lookup table, not a row column", in.arg);
                 if (sp >= PJ_STACK) return set_error("vnm_project: expression too deep");
                 const int ct = cols[in.arg].type;
                 int t = ct;
@@ -542,9 +581,13 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
                 ty[sp++] = in.arg == 1 ? (o.is_f ? VNM_F64 : VNM_I64) : (o.is_f ? T_WF : T_WI);
                 o.arg = 0;
                 break;
+            case VNM_EX_LOOKUP_U8:
             case VNM_EX_IS_NULL:
             case VNM_EX_IS_NOT_NULL:
                 if (in.arg < 0 || in.arg >= n_cols) return set_error("vnm_project: column index %d out of range", in.arg);
+                if (is_table[in.arg]) return set_error("vnm_project: column %d is a lookup table, not a row column", in.arg);
+                if (in.op == VNM_EX_LOOKUP_U8 && cols[in.arg].type != VNM_I32)
+                    return set_error("vnm_project: a lookup reads int32 dictionary codes (column %d)", in.arg);
                 if (sp >= PJ_STACK) return set_error("vnm_project: expression too deep");
                 lit[sp] = -1;
                 cst[sp] = -1;
@@ -727,7 +770,8 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
     int grid = (int)grid64;
     int64_t need = (length + PJ_TILE - 1) / PJ_TILE;
     if (grid > need) grid = (int)need;
-    const void* kern = math == 2 ? (const void*)project_kernel<2> : math == 1 ? (const void*)project_kernel<1> : (const void*)project_kernel<0>;
+    const void* kern = lookup ? (math == 2 ? (const void*)project_kernel<2, 1> : math == 1 ? (const void*)project_kernel<1, 1> : (const void*)project_kernel<0, 1>)
+                              : (math == 2 ? (const void*)project_kernel<2, 0> : math == 1 ? (const void*)project_kernel<1, 0> : (const void*)project_kernel<0, 0>);
     if (lds > 64 * 1024)   // depth >= 10: beyond the default dynamic LDS limit
         VNM_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipStream_t s = as_stream(stream);
@@ -737,15 +781,20 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
         if (!a.neg_pow) return 1;
         VNM_HIP(hipMemsetAsync(a.neg_pow, 0, sizeof(int), s));
     }
-    if (math == 2) {
+    if (lookup) {
+        KernelTimer timer("project_kernel_lookup", s);
+        if (math == 2) project_kernel<2, 1><<<grid, PJ_BLOCK, lds, s>>>(a);
+        else if (math == 1) project_kernel<1, 1><<<grid, PJ_BLOCK, lds, s>>>(a);
+        else project_kernel<0, 1><<<grid, PJ_BLOCK, lds, s>>>(a);
+    } else if (math == 2) {
         KernelTimer timer("project_kernel_math", s);
-        project_kernel<2><<<grid, PJ_BLOCK, lds, s>>>(a);
+        project_kernel<2, 0><<<grid, PJ_BLOCK, lds, s>>>(a);
     } else if (math == 1) {
         KernelTimer timer("project_kernel_exact_fn", s);
-        project_kernel<1><<<grid, PJ_BLOCK, lds, s>>>(a);
+        project_kernel<1, 0><<<grid, PJ_BLOCK, lds, s>>>(a);
     } else {
         KernelTimer timer("project_kernel", s);
-        project_kernel<0><<<grid, PJ_BLOCK, lds, s>>>(a);
+        project_kernel<0, 0><<<grid, PJ_BLOCK, lds, s>>>(a);
     }
     VNM_HIP(hipGetLastError());
     if (pow_check) {

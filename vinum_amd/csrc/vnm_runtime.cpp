@@ -607,6 +607,12 @@ int vnm_memset(void* dst, int value, int64_t bytes) {
     return 0;
 }
 
+int vnm_memcpy_d2d(void* dst, const void* src, int64_t bytes, void* stream) {
+    if (bytes <= 0) return 0;
+    VNM_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, as_stream(stream)));
+    return 0;
+}
+
 // Stage one host Arrow column into HBM.  Only the bytes the slice covers are copied; the device view
 // keeps the sub-byte validity offset so no bitmap realignment pass is needed.
 int vnm_stage_column(const void* host_values, const uint8_t* host_validity, int64_t offset, int64_t length,

@@ -16,6 +16,8 @@
 // the result's codes back (vinum_amd/vinum_lib.py::KeyDictionary).
 #include <algorithm>
 #include <cstring>
+#include <map>
+#include <string>
 #include <vector>
 
 #include "vnm_common.hpp"
@@ -198,6 +200,8 @@ struct SdCompact {
     unsigned long long heap_used;
     int32_t* new_ids;
     int32_t* new_lens;
+    int64_t* id_off;               // id -> heap offset / length of its value (the LIKE matcher's view of the dictionary)
+    int32_t* id_len;
 };
 
 __global__ __launch_bounds__(256) void sd_compact_count_kernel(SdCompact c) {
@@ -266,8 +270,11 @@ __global__ __launch_bounds__(256) void sd_compact_move_kernel(SdCompact c) {
         uint8_t* q = c.heap + c.heap_used + at;
         for (int64_t i = 0; i < len; i++) q[i] = p[i];
         s[2] = c.heap_used + at;
-        c.new_ids[k] = (int32_t)(s[1] - 1);
+        const int32_t id = (int32_t)(s[1] - 1);
+        c.new_ids[k] = id;
         c.new_lens[k] = (int32_t)len;
+        c.id_off[id] = (int64_t)(c.heap_used + at);
+        c.id_len[id] = (int32_t)len;
         k++; at += (unsigned long long)len;
     }
 }
@@ -360,6 +367,77 @@ __global__ __launch_bounds__(256) void sd_code_rank_kernel(const int32_t* codes,
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) { const int32_t c = codes[i]; out[i] = c < 0 ? 0 : rank_of_id[c]; }
 }
 
+// ---- LIKE against the dictionary's values (LikeFunction, vinum/core/functions.py:301-344) -----------------------------------------
+// One lane per dictionary id, the classic wildcard walk: literal runs and single code points advance pattern and value together, a
+// mismatch goes back to the last `%` and lets it take one more code point.  O(value x pattern) at worst, never exponential.  Neither
+// `%` nor `_` matches '\n', so a '\n' of the value is consumed by a literal '\n' of the pattern or the match fails: a `%` that would
+// have to take one ends the walk, and a literal run holding a '\n' fixes the position of everything before it (no `%` before it can
+// move), so it clears the restart point.
+struct LikeArgs {
+    const uint8_t* heap;
+    const int64_t* id_off;
+    const int32_t* id_len;     // -1: an id never handed out
+    const int32_t* tok;        // [ntok][3]: kind (LK_LIT_NL = a literal run with a '\n'), byte start, byte length
+    const uint8_t* pat;
+    int ntok;
+    int flags;
+    int64_t id_begin, id_end;
+    uint8_t* out;
+};
+constexpr int LK_LIT_NL = 3;
+
+__device__ __forceinline__ int64_t lk_cp_len(uint8_t b) { return b < 0xC0 ? 1 : b < 0xE0 ? 2 : b < 0xF0 ? 3 : 4; }
+
+__device__ bool lk_match(const LikeArgs& a, const uint8_t* v, int64_t n) {
+    int p = 0, star = -1;
+    int64_t t = 0, mark = 0;
+    while (t < n) {
+        if (p < a.ntok) {
+            const int kind = a.tok[3 * p];
+            if (kind == VNM_LIKE_TOK_ANY) {
+                if (v[t] != '\n') { t = min(t + lk_cp_len(v[t]), n); p++; continue; }
+            } else if (kind == VNM_LIKE_TOK_STAR) {
+                star = p++; mark = t;
+                continue;
+            } else {
+                const int len = a.tok[3 * p + 2];
+                const uint8_t* q = a.pat + a.tok[3 * p + 1];
+                if (t + len <= n && v[t] == q[0]) {
+                    int k = 1;
+                    while (k < len && v[t + k] == q[k]) k++;
+                    if (k == len) {
+                        t += len; p++;
+                        if (kind == LK_LIT_NL) star = -1;
+                        continue;
+                    }
+                }
+            }
+        }
+        if (star < 0 || v[mark] == '\n') return false;   // (`%` takes no newline)
+        mark = min(mark + lk_cp_len(v[mark]), n);
+        t = mark;
+        p = star + 1;
+    }
+    while (p < a.ntok && a.tok[3 * p] == VNM_LIKE_TOK_STAR) p++;
+    return p == a.ntok;
+}
+
+__global__ __launch_bounds__(256) void sd_like_kernel(LikeArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t id = a.id_begin + (int64_t)blockIdx.x * 256 + threadIdx.x; id < a.id_end; id += stride) {
+        const int32_t len = a.id_len[id];
+        bool m = false;
+        if (len >= 0) {
+            const uint8_t* v = a.heap + a.id_off[id];
+            int64_t n = len;
+            if (a.flags & VNM_LIKE_STRIP_NUL)
+                while (n > 0 && v[n - 1] == 0) n--;
+            m = lk_match(a, v, n) || (n > 0 && v[n - 1] == '\n' && lk_match(a, v, n - 1));   // '$' before a final newline
+        }
+        a.out[id] = m ? 1 : 0;
+    }
+}
+
 }  // namespace vnm
 
 using namespace vnm;
@@ -376,7 +454,30 @@ struct vnm_strdict {
     // the next encode would resolve them through ITS batch's offsets (wrong matches, reads out of range).  Such a handle refuses
     // further use.
     bool failed = false;
+    // id -> heap offset / length (written by the compaction; -1 length: never handed out), for vnm_strdict_like
+    int64_t* id_off = nullptr;
+    int32_t* id_len = nullptr;
+    int64_t id_cap = 0;
+    std::map<std::string, std::pair<int32_t*, int>> like_patterns;   // pattern -> its tokens + bytes on the device, token count
 };
+
+// the id-indexed arrays cover every id handed out so far (ids come in chunks, so they grow even when no value is new)
+static int strdict_ensure_ids(vnm_strdict* h, int64_t ids, hipStream_t s) {
+    if (ids <= h->id_cap) return 0;
+    const int64_t cap = std::max<int64_t>(std::max<int64_t>(ids, 2 * h->id_cap), 1 << 16);
+    int64_t* off = (int64_t*)pool_alloc((size_t)cap * 8);
+    int32_t* len = (int32_t*)pool_alloc((size_t)cap * 4);
+    if (!off || !len) { pool_free(off); pool_free(len); return set_error("vnm_strdict: id table allocation failed"); }
+    if (h->id_cap) {
+        VNM_HIP(hipMemcpyAsync(off, h->id_off, (size_t)h->id_cap * 8, hipMemcpyDeviceToDevice, s));
+        VNM_HIP(hipMemcpyAsync(len, h->id_len, (size_t)h->id_cap * 4, hipMemcpyDeviceToDevice, s));
+    }
+    VNM_HIP(hipMemsetAsync(len + h->id_cap, 0xFF, (size_t)(cap - h->id_cap) * 4, s));
+    pool_free_after(h->id_off, s);
+    pool_free_after(h->id_len, s);
+    h->id_off = off; h->id_len = len; h->id_cap = cap;
+    return 0;
+}
 
 extern "C" {
 
@@ -390,6 +491,9 @@ void vnm_strdict_destroy(vnm_strdict* h) {
     if (h->d.slot) sdict_free(&h->d);
     pool_free(h->heap);
     pool_free(h->gnext);
+    pool_free(h->id_off);
+    pool_free(h->id_len);
+    for (auto& kv : h->like_patterns) pool_free(kv.second.first);
     delete h;
 }
 
@@ -489,6 +593,7 @@ static int strdict_encode_device_impl(vnm_strdict* h, const vnm_dcol* offsets, c
     VNM_HIP(hipStreamSynchronize(s));
     h->ids = (int64_t)gn;
     if (gn >= (1ULL << 31)) return set_error("vnm_strdict: more than 2^31 dictionary ids");
+    VNM_TRY(strdict_ensure_ids(h, (int64_t)gn, s));
     if (!fresh) return 0;
     // ---- the new values -> the heap
     SdCompact c{};
@@ -522,6 +627,8 @@ static int strdict_encode_device_impl(vnm_strdict* h, const vnm_dcol* offsets, c
         h->heap_cap = want;
     }
     c.in = a;
+    c.id_off = h->id_off;
+    c.id_len = h->id_len;
     c.heap = h->heap;
     c.heap_used = (unsigned long long)h->heap_used;
     {
@@ -655,6 +762,74 @@ int vnm_strdict_codes_to_ranks(const int32_t* codes, const int32_t* rank_of_id, 
     if (n <= 0) return 0;
     if (!codes || !rank_of_id || !out_ranks) return set_error("vnm_strdict_codes_to_ranks: null argument");
     sd_code_rank_kernel<<<(int)std::min<int64_t>((n + 255) / 256, (int64_t)device_info().num_cus * 8), 256, 0, as_stream(stream)>>>(codes, rank_of_id, n, out_ranks);
+    VNM_HIP(hipGetLastError());
+    return 0;
+}
+
+int vnm_like_compile(const uint8_t* pattern, int64_t pattern_len, int32_t* out_tokens, int64_t* n_tokens) {
+    if (pattern_len < 0 || (pattern_len > 0 && !pattern) || !out_tokens || !n_tokens) return set_error("vnm_like_compile: null argument");
+    if (pattern_len >= (1LL << 31)) return set_error("vnm_like_compile: pattern too long");
+    int64_t nt = 0;
+    for (int64_t i = 0; i < pattern_len;) {
+        const uint8_t b = pattern[i];
+        if (strchr("\\^$*+?{}[]|()", b) && b)
+            return set_error("no GPU lowering for the LIKE pattern: '%c' has a regex meaning in the reference that LIKE does not restate", b);
+        if (b == '%') {
+            if (nt == 0 || out_tokens[3 * (nt - 1)] != VNM_LIKE_TOK_STAR) { out_tokens[3 * nt] = VNM_LIKE_TOK_STAR; out_tokens[3 * nt + 1] = (int32_t)i; out_tokens[3 * nt + 2] = 1; nt++; }
+            i++;
+        } else if (b == '_' || b == '.') {
+            out_tokens[3 * nt] = VNM_LIKE_TOK_ANY; out_tokens[3 * nt + 1] = (int32_t)i; out_tokens[3 * nt + 2] = 1; nt++;
+            i++;
+        } else {   // a literal run: up to the next wildcard or metacharacter
+            int64_t j = i;
+            while (j < pattern_len && pattern[j] != '%' && pattern[j] != '_' && pattern[j] != '.' && !(pattern[j] && strchr("\\^$*+?{}[]|()", pattern[j]))) j++;
+            out_tokens[3 * nt] = VNM_LIKE_TOK_LIT; out_tokens[3 * nt + 1] = (int32_t)i; out_tokens[3 * nt + 2] = (int32_t)(j - i); nt++;
+            i = j;
+        }
+    }
+    *n_tokens = nt;
+    return 0;
+}
+
+int vnm_strdict_like(vnm_strdict* h, const uint8_t* pattern, int64_t pattern_len, int flags, int64_t id_begin,
+                     uint8_t* out_match_of_id, void* stream) {
+    VNM_TRY(ensure_init());
+    if (!h || !out_match_of_id || pattern_len < 0 || (pattern_len > 0 && !pattern)) return set_error("vnm_strdict_like: null argument");
+    if (h->failed) return set_error("vnm_strdict: an earlier encode failed half-way; the dictionary cannot be used any more (create a new one)");
+    if (flags & ~VNM_LIKE_STRIP_NUL) return set_error("vnm_strdict_like: unknown flags %d", flags);
+    if (id_begin < 0) return set_error("vnm_strdict_like: id_begin < 0");
+    const std::string key(pattern_len ? (const char*)pattern : "", (size_t)pattern_len);
+    auto it = h->like_patterns.find(key);
+    if (it == h->like_patterns.end()) {
+        std::vector<int32_t> tok((size_t)std::max<int64_t>(pattern_len, 1) * 3);
+        int64_t nt = 0;
+        VNM_TRY(vnm_like_compile(pattern, pattern_len, tok.data(), &nt));
+        for (int64_t k = 0; k < nt; k++)   // a literal run holding a newline fixes where everything before it matched
+            if (tok[3 * k] == VNM_LIKE_TOK_LIT && memchr(pattern + tok[3 * k + 1], '\n', (size_t)tok[3 * k + 2])) tok[3 * k] = LK_LIT_NL;
+        const size_t tb = (size_t)std::max<int64_t>(nt, 1) * 12;
+        int32_t* dev = (int32_t*)pool_alloc(tb + (size_t)pattern_len + 1);
+        if (!dev) return 1;
+        std::vector<uint8_t> blob(tb + (size_t)pattern_len + 1, 0);
+        memcpy(blob.data(), tok.data(), (size_t)nt * 12);
+        if (pattern_len) memcpy(blob.data() + tb, pattern, (size_t)pattern_len);
+        if (hipMemcpy(dev, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) { pool_free(dev); return set_error("vnm_strdict_like: pattern upload failed"); }
+        it = h->like_patterns.emplace(key, std::make_pair(dev, (int)nt)).first;
+    }
+    if (id_begin >= h->ids) return 0;
+    LikeArgs a{};
+    a.heap = h->heap; a.id_off = h->id_off; a.id_len = h->id_len;
+    a.tok = it->second.first;
+    a.ntok = it->second.second;
+    a.pat = (const uint8_t*)it->second.first + (size_t)std::max(a.ntok, 1) * 12;
+    a.flags = flags;
+    a.id_begin = id_begin; a.id_end = h->ids;
+    a.out = out_match_of_id;
+    hipStream_t s = as_stream(stream);
+    const int grid = (int)std::min<int64_t>((h->ids - id_begin + 255) / 256, (int64_t)device_info().num_cus * 16);
+    {
+        KernelTimer timer("strdict_like", s);
+        sd_like_kernel<<<grid, 256, 0, s>>>(a);
+    }
     VNM_HIP(hipGetLastError());
     return 0;
 }

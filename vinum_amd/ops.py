@@ -577,6 +577,13 @@ def _emit_expr(expr, col_index, out):
             out.append((L.EX_CONST_F, 1, float(e[1]), 0) if isinstance(e[1], float) else (L.EX_CONST_I, 1, 0.0, int(e[1])))
         elif e[0] in ("is_null", "is_not_null"):
             out.append((L.EX_IS_NULL if e[0] == "is_null" else L.EX_IS_NOT_NULL, col_index[e[1]], 0.0, 0))
+        elif e[0] == "lookup":
+            # ("lookup", code column, table column): table[code] as a predicate (LIKE over a dictionary-coded column, see
+            # core.algebra.lower_like); the table travels as a column of its own length
+            out.append((L.EX_LOOKUP_U8, col_index[e[1]], 0.0, col_index[e[2]]))
+        elif e[0] in ("like", "not_like"):
+            raise NotImplementedError(f"no GPU lowering for {e[0].upper()} outside a FilterOperator / ProjectOperator / "
+                                      "AggregateOperator (they turn it into a dictionary lookup)")
         else:
             if e[0] in ("pi", "e"):
                 out.append((L.EX_CONST_F, 0, float(SCALAR_FUNCS[e[0]]()), 0))
@@ -670,6 +677,28 @@ def project_many(exprs, columns: dict, length=None, stream=None):
             at = pa.uint8() if t == L.MASK_U8 else _ARROW_OF[t]
             result[k] = DeviceColumn(b, None, 0, length, at)
     return result
+
+
+_LIKE_META = frozenset(b"\\^$*+?{}[]|()")
+
+
+def like_tokens(pattern: str):
+    """The LIKE pattern as vnm_strdict_like matches it (vnm_like_compile, host only): [(kind, bytes)] with kind L.LIKE_TOK_LIT
+    (a literal byte run), L.LIKE_TOK_ANY (`_` or `.`: one code point) or L.LIKE_TOK_STAR (`%`, runs folded).  The reference
+    turns the pattern into a regex (functions.py:322-328), so any other regex metacharacter would mean something LIKE does not:
+    NotImplementedError."""
+    if not isinstance(pattern, str):
+        raise NotImplementedError(f"no GPU lowering for a LIKE pattern of type {type(pattern).__name__}: a string literal is required")
+    raw = pattern.encode("utf-8")
+    bad = sorted({chr(b) for b in raw if b in _LIKE_META})
+    if bad:
+        raise NotImplementedError(f"no GPU lowering for the LIKE pattern {pattern!r}: {' '.join(bad)} has a regex meaning in the "
+                                  "reference that a LIKE matcher does not restate")
+    toks = (ctypes.c_int32 * (3 * max(len(raw), 1)))()
+    n = ctypes.c_int64(0)
+    buf = ctypes.create_string_buffer(raw, max(len(raw), 1))
+    L.check(L.load().vnm_like_compile(buf, len(raw), toks, ctypes.byref(n)))
+    return [(toks[3 * k], raw[toks[3 * k + 1]:toks[3 * k + 1] + toks[3 * k + 2]]) for k in range(n.value)]
 
 
 def columns_of(expr):

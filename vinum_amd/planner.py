@@ -12,7 +12,9 @@ A query is a dict (see tests/golden/planner_cases.py):
     expr := column name | int | float | (op, arg...)   with op as in vinum_amd.ops plus ("fn", name, arg...) for the
             aggregate functions count_star / count / sum / avg / min / max and the numeric built-in scalar functions
             (SCALAR_FN_NAMES: abs, sqrt, sin, ..., to_int, pi, e and their np. spellings), which are per-row expressions
-            wherever they appear, like any operator.
+            wherever they appear, like any operator; ("lit", "Berlin") is a string literal (a bare str is a column name),
+            and ("like", column, ("lit", "Jos%")) / ("not_like", ...) are LIKE / NOT LIKE against a utf8 / large_utf8 column
+            (planner.py:189-193) -- in WHERE, HAVING, the SELECT list (a uint8 mask) and aggregate arguments alike.
 
 What the planner does with the aggregate part mirrors planner.py:380-469:
   * DISTINCT = GROUP BY every select expression (:380-382);

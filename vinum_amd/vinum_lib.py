@@ -480,6 +480,9 @@ class KeyDictionary:
         self._chunks = []          # device route: the values each batch added ...
         self._pos = None           # ... and id -> position in their concatenation (-1: an id never handed out)
         self._n_values = 0
+        self._like = {}            # LIKE pattern -> [device table, capacity, ids it covers] (like_table)
+        self.like_launches = 0     # vnm_strdict_like calls and the ids they matched, over every pattern
+        self.like_ids_matched = 0
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -605,6 +608,38 @@ class KeyDictionary:
         out = DeviceBuffer(max(off + n, 1) * 4)
         L.check(lib.vnm_strdict_codes_to_ranks(codes_col.values_ptr + codes_col.offset * 4, rank_of.ptr, n, out.ptr + off * 4, None))
         return DeviceColumn(out, codes_col._validity, off, n, pa.int32(), keep=(rank_of, codes_col))
+
+    def like_table(self, pattern: str):
+        """`column LIKE pattern` for every value of this dictionary: a device uint8 DeviceColumn, entry = 1 when the value with
+        that code matches (vnm_strdict_like: the reference's regex restated, functions.py:301-344; trailing NULs dropped for utf8,
+        whose values reach the reference as a NumPy 'U' array).  Its length is the number of ids handed out so far.  Cached per
+        pattern: a later call matches only the ids the dictionary has handed out since (the table grows by doubling and keeps
+        what it holds), so a stream of batches matches each distinct value once per pattern."""
+        from . import ops
+        from .device import DeviceBuffer, DeviceColumn
+        t = self.type
+        if not (pa.types.is_string(t) or pa.types.is_large_string(t)):
+            raise TypeError(f"LIKE needs a string column, not {t}")    # (the reference's re.match raises on bytes / numbers)
+        ops.like_tokens(pattern)                                         # (NotImplementedError for a regex metacharacter)
+        lib = L.lib()
+        top = int(lib.vnm_strdict_ids(self._h)) if self._h is not None else 0
+        entry = self._like.get(pattern)
+        if entry is None:
+            entry = self._like[pattern] = [DeviceBuffer(max(top, 1)), max(top, 1), 0]
+        buf, cap, covered = entry
+        if top > covered:
+            if top > cap:
+                cap = max(top, 2 * cap)
+                grown = DeviceBuffer(cap)
+                L.check(lib.vnm_memcpy_d2d(grown.ptr, buf.ptr, covered, None))
+                buf = grown
+            raw = pattern.encode("utf-8")
+            L.check(lib.vnm_strdict_like(self._h, raw, len(raw), L.LIKE_STRIP_NUL if pa.types.is_string(t) else 0, covered,
+                                         buf.ptr, None))
+            self.like_launches += 1
+            self.like_ids_matched += top - covered
+            entry[:] = [buf, cap, top]
+        return DeviceColumn(buf, None, 0, entry[2], pa.uint8())
 
     def values_by_code(self) -> pa.Array:
         """The dictionary as an array indexed by CODE (a code the device never handed out: NULL) -- what the ranks exchange to build
