@@ -564,6 +564,26 @@ int64_t vnm_pool_trim(void);
  * vnm_pool_cached_bytes: what the cache holds right now. */
 int vnm_pool_set_idle_trim(int64_t idle_ms, int64_t keep_bytes);
 int64_t vnm_pool_cached_bytes(void);
+/* Guard mode of the caching allocator: TEST INFRASTRUCTURE, off by default (VNM_POOL_GUARD=1|2 sets the initial mode), and while
+ * it is off the allocator does exactly what the paragraphs above say.  mode 1: every block handed out from now on is laid out as
+ * front zone | body (the bytes asked for) | back zone inside its raw block; the front zone is a multiple of 4096 bytes, the back
+ * zone is everything up to the end of the raw block (rounding slack and reuse slack included, at least 4096 bytes); both hold a
+ * canary that is checked on the device when the block is released.  mode 2: the body is also filled with the 64-bit word
+ * 0x7FF8DEAD7FC0BEEF (NaN as float64 and as two float32, huge as an integer) before the caller sees it, and with another such
+ * word once it is released.  The mode synchronises the device at every allocation and release; it never fails a call, it records.
+ * A block remembers how it was allocated, so the mode may change while blocks are live.
+ * vnm_pool_guard_report: checks the zones of every live guarded block too, then writes a summary line and one line per violation
+ * since the last reset: "violation zone=front|back offset=<of the first damaged byte, from the body's end (back, >= 0) or start
+ * (front, < 0)> bytes=<damaged> first=<up to 16 bytes from there, hex> requested=<bytes asked for> block=<raw block bytes> ptr=
+ * mode= site=<library+offset(symbol+offset) of the pool_alloc call> span=<last timed kernel span> test=<$PYTEST_CURRENT_TEST>";
+ * the same line goes to stderr when the violation is found.  Returns the bytes needed including the final 0; *violations and
+ * *blocks_checked count since the last vnm_pool_guard_reset.
+ * vnm_pool_guard_layout: what a fresh block for `bytes` looks like in the CURRENT mode (needs no device): the raw block's size,
+ * the front zone and the smallest back zone (0 and 0 with the guard off, where the block is the rounded size of always). */
+int vnm_pool_set_guard(int mode);
+int64_t vnm_pool_guard_report(char* buf, int64_t cap, int64_t* violations, int64_t* blocks_checked);
+void vnm_pool_guard_reset(void);
+int vnm_pool_guard_layout(int64_t bytes, int64_t* block_bytes, int64_t* front_zone, int64_t* back_zone_min);
 int vnm_memcpy_h2d(void* dst, const void* src, int64_t bytes);
 int vnm_memcpy_d2h(void* dst, const void* src, int64_t bytes);
 int vnm_memset(void* dst, int value, int64_t bytes);

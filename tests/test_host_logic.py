@@ -137,3 +137,34 @@ def test_plan_errors_are_the_reference_messages():
     rc = lib.vnm_agg_plan_host(L.ONE_GROUP, 1, _ints([L.I64]), 0, _ints([]), _ints([]), _ints([]), None,
                                ctypes.byref(nk), ctypes.byref(nw), None, ctypes.byref(nops), None)
     assert rc != 0
+
+
+def _round_size(b):
+    """The caching allocator's rounding as DESIGN.md states it: 1/8 of the leading power of two, at least 4096 bytes."""
+    b = max(b, 1)
+    if b < 4096:
+        return 4096
+    step = (1 << (b.bit_length() - 1)) // 8
+    return (b + step - 1) // step * step
+
+
+@pytest.mark.parametrize("nbytes", [0, 1, 4095, 4096, 4097, 1_000_000, 2**31 + 5])
+def test_pool_guard_layout(nbytes):
+    """Guard mode (vnm_pool_set_guard): front zone | body | back zone inside one raw block; off, the block is the rounded size of
+    always.  The layout call needs no device."""
+    lib = L.load()
+    block, front, back = ctypes.c_int64(-1), ctypes.c_int64(-1), ctypes.c_int64(-1)
+    try:
+        for mode in (1, 2):
+            assert lib.vnm_pool_set_guard(mode) == 0
+            assert lib.vnm_pool_guard_layout(nbytes, ctypes.byref(block), ctypes.byref(front), ctypes.byref(back)) == 0
+            assert front.value > 0 and front.value % 4096 == 0
+            assert back.value >= 4096
+            assert front.value + nbytes + back.value <= block.value
+            assert block.value == _round_size(block.value)          # a size the cache already deals in
+            assert block.value <= 2 * (nbytes + front.value + 4096)  # and no more than the reuse rule's own slack
+    finally:
+        assert lib.vnm_pool_set_guard(0) == 0
+    assert lib.vnm_pool_guard_layout(nbytes, ctypes.byref(block), ctypes.byref(front), ctypes.byref(back)) == 0
+    assert (block.value, front.value, back.value) == (_round_size(nbytes), 0, 0)
+    assert lib.vnm_pool_set_guard(3) != 0 and lib.vnm_pool_guard_layout(-1, None, None, None) != 0

@@ -137,6 +137,10 @@ PROTOTYPES = {
     "vnm_pool_trim": (c_i64, []),
     "vnm_pool_set_idle_trim": (c_int, [c_i64, c_i64]),
     "vnm_pool_cached_bytes": (c_i64, []),
+    "vnm_pool_set_guard": (c_int, [c_int]),
+    "vnm_pool_guard_report": (c_i64, [c_void, c_i64, c_void, c_void]),
+    "vnm_pool_guard_reset": (None, []),
+    "vnm_pool_guard_layout": (c_int, [c_i64, c_void, c_void, c_void]),
     "vnm_route_counts": (c_i64, [c_void, c_i64]),
     "vnm_route_last": (c_i64, [c_void, c_i64]),
     "vnm_route_reset": (None, []),

@@ -5,6 +5,7 @@
 #include <condition_variable>
 #include <functional>
 #include <cstring>
+#include <dlfcn.h>
 #include <map>
 #include <new>
 #include <pthread.h>
@@ -165,8 +166,134 @@ void touch_pool() {
 }
 }  // namespace
 
-void* pool_alloc(size_t bytes) {
-    size_t sz = round_size(bytes ? bytes : 1);
+// ---- guard mode (test infrastructure; vnm_pool_set_guard / VNM_POOL_GUARD) -------------------------------------
+// Off by default; when off the allocator does what it always did, plus one relaxed load per call.  While the mode is 1 or 2 a
+// request is laid out as  front zone | body (the bytes asked for) | back zone  inside one raw block of the same cache: the front
+// zone is GUARD_ZONE bytes (the user pointer keeps its 4096-byte alignment), the back zone is EVERYTHING from the end of the
+// request to the end of the raw block -- the rounding slack and, for a block served from the cache, the reuse slack -- and at
+// least GUARD_ZONE bytes.  Both zones are filled with a canary byte when the block is handed out and checked ON THE DEVICE when it
+// comes back (and, for live blocks, by vnm_pool_guard_report).  Mode 2 also fills the body with a poison word before the caller sees
+// it and with a second one after the caller released it: a quiet NaN as float64, two NaNs as float32, billions as any integer, so
+// that scratch nobody cleared and memory read after its release do not look like the zeros a fresh hipMalloc tends to give.
+// The mode synchronises the device around every allocation and release (the single-stream contract of the pool lets a block be
+// released with kernels still queued); it never fails a call and never aborts: it records, the tests decide.
+namespace {
+constexpr size_t GUARD_ZONE = 4096;
+constexpr int GUARD_CANARY = 0xCB;
+constexpr uint64_t GUARD_POISON_ALLOC = 0x7FF8DEAD7FC0BEEFull;
+constexpr uint64_t GUARD_POISON_FREED = 0x7FF8F4EE7FC0DEADull;
+constexpr size_t GUARD_MAX_RECORDS = 256;   // (the counters go on; the text keeps the first ones)
+
+int guard_mode_from_env() {
+    const char* e = getenv("VNM_POOL_GUARD");
+    const int m = e ? atoi(e) : 0;
+    return m == 1 || m == 2 ? m : 0;
+}
+std::atomic<int> g_guard_mode{guard_mode_from_env()};
+std::atomic<int64_t> g_guard_live{0};          // guarded blocks handed out and not yet released: pool_free's only cost when 0
+
+struct GuardBlock { void* raw; size_t raw_bytes, bytes; void* site; int mode; };
+std::mutex& g_guard_mu = *new std::mutex;
+std::unordered_map<void*, GuardBlock>& g_guard_blocks = *new std::unordered_map<void*, GuardBlock>;   // keyed by the USER pointer
+std::vector<std::string>& g_guard_records = *new std::vector<std::string>;
+int64_t g_guard_violations = 0, g_guard_checked = 0;
+char g_guard_span[64] = "";                    // name of the last KernelTimer span (copied: not every name is a literal)
+unsigned long long* g_guard_result = nullptr;  // device: [0] damaged bytes, [1] offset of the first one in the zone
+
+// bytes of [lo, hi) of `raw` that are not `canary`.  One thread per ALIGNED 16-byte chunk, the bytes outside the zone masked: the
+// raw block starts on hipMalloc's alignment and its size is a multiple of 512, so a whole chunk is always inside the raw block.
+__global__ void guard_check_kernel(const uint8_t* __restrict__ raw, size_t lo, size_t hi, uint32_t canary, unsigned long long* __restrict__ result) {
+    const size_t first_chunk = lo / 16, n_chunks = (hi + 15) / 16 - first_chunk;
+    const uint32_t word = canary * 0x01010101u;
+    unsigned long long bad = 0, first = ~0ull;
+    for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks; c += (size_t)gridDim.x * blockDim.x) {
+        const size_t at = (first_chunk + c) * 16;
+        const uint4 v = *reinterpret_cast<const uint4*>(raw + at);
+        if (at >= lo && at + 16 <= hi && v.x == word && v.y == word && v.z == word && v.w == word) continue;
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        for (int b = 0; b < 16; b++) {
+            const size_t pos = at + b;
+            if (pos < lo || pos >= hi) continue;
+            if (((w[b >> 2] >> (8 * (b & 3))) & 0xffu) != canary) { bad++; if (pos - lo < first) first = pos - lo; }
+        }
+    }
+    if (bad) { atomicAdd(&result[0], bad); atomicMin(&result[1], first); }
+}
+
+// body[0, bytes) = the little-endian bytes of `word`, repeated (the body starts 4096-aligned; its length is whatever was asked for)
+__global__ void guard_fill_kernel(uint8_t* __restrict__ body, size_t bytes, uint64_t word) {
+    const size_t n_words = bytes / 8;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += (size_t)gridDim.x * blockDim.x)
+        reinterpret_cast<uint64_t*>(body)[i] = word;
+    if (blockIdx.x == 0 && threadIdx.x < (bytes & 7)) body[n_words * 8 + threadIdx.x] = (uint8_t)(word >> (8 * threadIdx.x));
+}
+
+int guard_grid(size_t items) { return (int)std::min<size_t>((items + 255) / 256 ? (items + 255) / 256 : 1, 4096); }
+
+void guard_fill(void* body, size_t bytes, uint64_t word) {
+    if (!bytes) return;
+    hipLaunchKernelGGL(guard_fill_kernel, dim3(guard_grid(bytes / 8)), dim3(256), 0, nullptr, (uint8_t*)body, bytes, word);
+}
+
+std::string guard_site(void* addr) {
+    char buf[384];
+    Dl_info info;
+    if (addr && dladdr(addr, &info) && info.dli_fname) {
+        const char* file = strrchr(info.dli_fname, '/');
+        file = file ? file + 1 : info.dli_fname;
+        const size_t off = (size_t)((char*)addr - (char*)info.dli_fbase);
+        if (info.dli_sname) snprintf(buf, sizeof(buf), "%s+0x%zx(%s+0x%zx)", file, off, info.dli_sname, (size_t)((char*)addr - (char*)info.dli_saddr));
+        else snprintf(buf, sizeof(buf), "%s+0x%zx", file, off);
+    } else {
+        snprintf(buf, sizeof(buf), "%p", addr);
+    }
+    return buf;
+}
+
+// checks zone [lo, hi) of the block (device idle, g_guard_mu held); a damaged zone is recorded and re-filled, so that a block
+// that lives on is not reported again for the same bytes
+void guard_check_zone(void* user, const GuardBlock& b, const char* zone, size_t lo, size_t hi) {
+    if (hi <= lo) return;
+    if (!g_guard_result && hipMalloc((void**)&g_guard_result, 16) != hipSuccess) { g_guard_result = nullptr; (void)hipGetLastError(); return; }
+    unsigned long long res[2] = {0, ~0ull};
+    if (hipMemcpy(g_guard_result, res, sizeof(res), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return; }
+    hipLaunchKernelGGL(guard_check_kernel, dim3(guard_grid((hi - lo) / 16 + 2)), dim3(256), 0, nullptr, (const uint8_t*)b.raw, lo, hi, (uint32_t)GUARD_CANARY, g_guard_result);
+    if (hipMemcpy(res, g_guard_result, sizeof(res), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return; }
+    if (!res[0]) return;
+    g_guard_violations++;
+    uint8_t head[16];
+    const size_t first = lo + (size_t)res[1], n_head = std::min<size_t>(16, hi - first);
+    if (hipMemcpy(head, (const uint8_t*)b.raw + first, n_head, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); memset(head, 0, sizeof(head)); }
+    char hex[33];
+    for (size_t i = 0; i < n_head; i++) snprintf(hex + 2 * i, 3, "%02x", head[i]);
+    // offset: of the first damaged byte, from the body's END for the back zone (>= 0), from its START for the front zone (< 0)
+    const long long offset = lo >= GUARD_ZONE + b.bytes ? (long long)(first - (GUARD_ZONE + b.bytes)) : (long long)first - (long long)GUARD_ZONE;
+    const char* test = getenv("PYTEST_CURRENT_TEST");
+    char line[1024];
+    snprintf(line, sizeof(line), "violation zone=%s offset=%lld bytes=%llu first=%s requested=%zu block=%zu ptr=%p mode=%d site=%s span=%s test=%s",
+             zone, offset, res[0], hex, b.bytes, b.raw_bytes, user, b.mode, guard_site(b.site).c_str(), g_guard_span[0] ? g_guard_span : "-", test ? test : "-");
+    fprintf(stderr, "[vnm pool guard] %s\n", line);
+    fflush(stderr);
+    if (g_guard_records.size() < GUARD_MAX_RECORDS) g_guard_records.push_back(line);
+    (void)hipMemset((uint8_t*)b.raw + lo, GUARD_CANARY, hi - lo);
+}
+
+void guard_check_block(void* user, const GuardBlock& b) {   // device idle, g_guard_mu held
+    g_guard_checked++;
+    guard_check_zone(user, b, "front", 0, GUARD_ZONE);
+    guard_check_zone(user, b, "back", GUARD_ZONE + b.bytes, b.raw_bytes);
+}
+}  // namespace
+
+void guard_note_span(const char* name) {
+    if (!g_guard_mode.load(std::memory_order_relaxed)) return;
+    std::lock_guard<std::mutex> g(g_guard_mu);
+    snprintf(g_guard_span, sizeof(g_guard_span), "%s", name ? name : "");
+}
+
+namespace {
+// a raw block of at least `sz` (a rounded size) bytes, from the cache or from the device; *got = its real size
+void* raw_block(size_t sz, size_t* got) {
     touch_pool();
     {
         std::lock_guard<std::mutex> g(g_pool_mu);
@@ -174,6 +301,7 @@ void* pool_alloc(size_t bytes) {
         auto it = g_free.lower_bound(sz);
         if (it != g_free.end() && it->first <= sz * 2) {
             void* p = it->second;
+            if (got) *got = it->first;
             g_cached_bytes -= it->first;
             g_free.erase(it);
             return p;
@@ -189,14 +317,13 @@ void* pool_alloc(size_t bytes) {
             return nullptr;
         }
     }
+    if (got) *got = sz;
     std::lock_guard<std::mutex> g(g_pool_mu);
     g_sizes[p] = sz;
     return p;
 }
 
-void pool_free(void* p) {
-    if (!p) return;
-    touch_pool();
+void raw_release(void* p) {
     std::lock_guard<std::mutex> g(g_pool_mu);
     auto it = g_sizes.find(p);
     if (it == g_sizes.end()) {
@@ -207,12 +334,67 @@ void pool_free(void* p) {
     g_cached_bytes += it->second;
 }
 
+void* guarded_alloc(size_t bytes, int mode, void* site) {
+    GuardBlock b{};
+    b.bytes = bytes; b.site = site; b.mode = mode;
+    b.raw = raw_block(round_size(GUARD_ZONE + bytes + GUARD_ZONE), &b.raw_bytes);
+    if (!b.raw) return nullptr;
+    uint8_t* raw = (uint8_t*)b.raw;
+    (void)hipDeviceSynchronize();   // the last owner may have released the block with kernels still queued
+    (void)hipMemset(raw, GUARD_CANARY, GUARD_ZONE);
+    (void)hipMemset(raw + GUARD_ZONE + bytes, GUARD_CANARY, b.raw_bytes - GUARD_ZONE - bytes);
+    if (mode == 2) guard_fill(raw + GUARD_ZONE, bytes, GUARD_POISON_ALLOC);
+    (void)hipDeviceSynchronize();
+    (void)hipGetLastError();
+    void* user = raw + GUARD_ZONE;
+    std::lock_guard<std::mutex> g(g_guard_mu);
+    g_guard_blocks[user] = b;
+    g_guard_live.fetch_add(1);
+    return user;
+}
+
+// true: `p` was a guarded block; it has been checked and its raw block is back in the cache
+bool guarded_free(void* p) {
+    GuardBlock b;
+    {
+        std::lock_guard<std::mutex> g(g_guard_mu);
+        auto it = g_guard_blocks.find(p);
+        if (it == g_guard_blocks.end()) return false;
+        b = it->second;
+        g_guard_blocks.erase(it);
+        g_guard_live.fetch_sub(1);
+        (void)hipDeviceSynchronize();
+        guard_check_block(p, b);
+        if (b.mode == 2) guard_fill(p, b.bytes, GUARD_POISON_FREED);
+        (void)hipDeviceSynchronize();
+        (void)hipGetLastError();
+    }
+    touch_pool();
+    raw_release(b.raw);
+    return true;
+}
+}  // namespace
+
+// (noinline: guard mode names the CALLER of pool_alloc, also for the callers in this file)
+__attribute__((noinline)) void* pool_alloc(size_t bytes) {
+    if (const int mode = g_guard_mode.load(std::memory_order_relaxed)) return guarded_alloc(bytes, mode, __builtin_return_address(0));
+    return raw_block(round_size(bytes ? bytes : 1), nullptr);
+}
+
+void pool_free(void* p) {
+    if (!p) return;
+    if (g_guard_live.load(std::memory_order_relaxed) && guarded_free(p)) return;
+    touch_pool();
+    raw_release(p);
+}
+
 // A block that kernels already enqueued on `stream` still read (the widened key / input buffers of an aggregate, released
 // right after the launches): it joins the free list only once an event recorded on that stream NOW has completed, so that an
 // allocation from ANOTHER stream or thread -- the CSV reader, a second operator, torch's side streams in distributed.py -- cannot be
 // handed the block while those kernels run.  The waiting blocks are looked at by every pool_alloc (hipEventQuery: no blocking).
 void pool_free_after(void* p, hipStream_t stream) {
     if (!p) return;
+    if (g_guard_live.load(std::memory_order_relaxed) && guarded_free(p)) return;   // (guard mode waits for the whole device itself)
     touch_pool();
     hipEvent_t ev = nullptr;
     {
@@ -290,6 +472,7 @@ std::vector<TimedSpan> g_spans;
 KernelTimer::KernelTimer(const char* name, hipStream_t s) : on(g_profiling), slot(-1), stream(s) {
     static const bool trace = getenv("VNM_TRACE") != nullptr;  // debugging aid: name every timed launch on stderr
     if (trace) { fprintf(stderr, "[vnm] launch %s\n", name); fflush(stderr); (void)hipStreamSynchronize(s); }
+    guard_note_span(name);
     if (!on) return;
     TimedSpan sp;
     sp.name = name;
@@ -567,7 +750,7 @@ int vnm_device_synchronize(void) {
     return 0;
 }
 
-void* vnm_malloc(int64_t bytes) {
+__attribute__((disable_tail_calls)) void* vnm_malloc(int64_t bytes) {   // (so that guard mode's call site is this function, not its caller)
     if (ensure_init()) return nullptr;
     return pool_alloc((size_t)bytes);
 }
@@ -590,6 +773,52 @@ int vnm_pool_set_idle_trim(int64_t idle_ms, int64_t keep_bytes) {
 
 int64_t vnm_pool_trim(void) {
     return (int64_t)pool_trim();
+}
+
+int vnm_pool_set_guard(int mode) {
+    if (mode < 0 || mode > 2) return set_error("vnm_pool_set_guard: mode %d (0 off, 1 red zones, 2 red zones + poison)", mode);
+    g_guard_mode.store(mode);
+    return 0;
+}
+
+int vnm_pool_guard_layout(int64_t bytes, int64_t* block_bytes, int64_t* front_zone, int64_t* back_zone_min) {
+    if (bytes < 0) return set_error("vnm_pool_guard_layout: %lld bytes", (long long)bytes);
+    const bool on = g_guard_mode.load() != 0;
+    const size_t front = on ? GUARD_ZONE : 0;
+    const size_t block = on ? round_size(GUARD_ZONE + (size_t)bytes + GUARD_ZONE) : round_size(bytes ? (size_t)bytes : 1);
+    if (block_bytes) *block_bytes = (int64_t)block;
+    if (front_zone) *front_zone = (int64_t)front;
+    if (back_zone_min) *back_zone_min = on ? (int64_t)(block - front - (size_t)bytes) : 0;
+    return 0;
+}
+
+int64_t vnm_pool_guard_report(char* buf, int64_t cap, int64_t* violations, int64_t* blocks_checked) {
+    std::string out;
+    {
+        std::lock_guard<std::mutex> g(g_guard_mu);
+        if (!g_guard_blocks.empty()) {
+            (void)hipDeviceSynchronize();
+            for (auto& kv : g_guard_blocks) guard_check_block(kv.first, kv.second);
+            (void)hipDeviceSynchronize();
+            (void)hipGetLastError();
+        }
+        out = "pool guard: mode " + std::to_string(g_guard_mode.load()) + ", " + std::to_string(g_guard_checked) + " blocks checked, " +
+              std::to_string(g_guard_violations) + " violations, " + std::to_string(g_guard_blocks.size()) + " guarded blocks live\n";
+        for (auto& r : g_guard_records) out += r + "\n";
+        if ((int64_t)g_guard_records.size() < g_guard_violations)
+            out += "(" + std::to_string(g_guard_violations - (int64_t)g_guard_records.size()) + " more violations not kept)\n";
+        if (violations) *violations = g_guard_violations;
+        if (blocks_checked) *blocks_checked = g_guard_checked;
+    }
+    if (buf && cap > 0) { const size_t n = std::min<size_t>(out.size(), (size_t)cap - 1); memcpy(buf, out.data(), n); buf[n] = 0; }
+    return (int64_t)out.size() + 1;
+}
+
+void vnm_pool_guard_reset(void) {
+    std::lock_guard<std::mutex> g(g_guard_mu);
+    g_guard_records.clear();
+    g_guard_violations = 0;
+    g_guard_checked = 0;
 }
 
 int vnm_memcpy_h2d(void* dst, const void* src, int64_t bytes) {
