@@ -10,7 +10,7 @@
 //   * a grid of 8 x 256 CUs grid-striding 16 B/lane streams 6.3 TB/s.
 // So rows are pre-aggregated in a per-workgroup LDS hash table (keys + 64-bit accumulator words that
 // merge commutatively); only table flushes touch the HBM-resident table, with agent-scope atomics.
-// The fused WHERE predicate is evaluated in the scan, so no filtered batch is ever materialised.
+// The fused WHERE predicate is evaluated in the scan, so no filtered batch is ever materialised.  Host side: this file keeps the handle, the C-ABI entry points, the queue of a stream (queueable, flush_queue) and the widening helpers; vnm_agg_next.inc takes a batch to its kernels (next_device_impl: one stage function per family of routes).
 #include <memory>
 #include <algorithm>
 #include <cmath>
@@ -1111,779 +1111,11 @@ int vnm_agg_estimate_groups(vnm_agg* h, int64_t nrows, const vnm_dcol* key, int6
     return 0;
 }
 
-// rc of next_device_impl when the waiting batches of a stream (h->segs_active) would have to take a path whose kernels read ONE batch:
-// nothing has been aggregated, the caller sends the batches one by one
-constexpr int VNM_RC_SINGLY = 77;
-#define VNM_SEG_ONLY(what) do { if (h->segs_active || h->kn_valid) { if (getenv("VNM_AGG_TRACE")) fprintf(stderr, "[agg] %s: not this way (%s)\n", h->kn_valid ? "nullable key through the dense path" : "stream segments", what); return VNM_RC_SINGLY; } } while (0)
+}  // extern "C"
+// the batch router: Batch / BatchShape / SpillState, the stage functions and next_device_impl, the driver over them
+#include "vnm_agg_next.inc"
+extern "C" {
 
-static bool queueable(const vnm_agg* h, int64_t nrows, const vnm_dcol* keys, const vnm_dcol* inputs, const vnm_dcol* pred, bool* pred_is_v, bool* multi);
-
-static int next_device_impl(vnm_agg* h, int64_t nrows, const vnm_dcol* keys, const vnm_dcol* inputs,
-                            const vnm_dcol* pred, void* stream) {
-    VNM_TRY(ensure_init());
-    if (!h) return set_error("vnm_agg_next_device: null handle");
-    if (h->pred_set && !pred) return set_error("vnm_agg_next_device: predicate set but no predicate column given");
-    hipStream_t s = as_stream(stream);
-    invalidate_result(h);
-    if (inputs && nrows > 0) for (int i = 0; i < h->n_funcs; i++) if (h->func_col[i] >= 0 && inputs[i].validity) h->null_inputs_seen = true;
-    // A NULLABLE single 8-byte key under the hot program: the dense path takes it as it is -- pass 1 reads the key's validity and
-    // sums the NULL-key rows up as the one group they are (single_numerical_hash_aggregate.cpp:24-32), everything after pass 1 never
-    // sees a NULL.  Before round 4 such a key was packed into one word first (key range + pack + unpack passes, the NULL code a
-    // heavy key of the inner operator, run + table merges at the end: 15.7 ms per 5e8 rows at G = 1e8 against 5.2 without NULLs).
-    // The attempt runs this function again with the validity stripped from the key and kept aside; every path but the dense ring
-    // scatter declines (VNM_RC_SINGLY, before any side effect) and the batch takes the packed route below.
-    if (!h->kn_valid && !h->kn_failed && !h->segs_active && h->single && h->plan.n_keys == 1 && !h->inner && keys && inputs && keys[0].validity &&
-        type_width(keys[0].type) == 8 && (keys[0].offset & 1) == 0 && nrows >= env_i64("VNM_AGG_ESTIMATE_MIN_ROWS", 1 << 22) &&
-        getenv("VNM_AGG_NO_DENSE_KN") == nullptr) {
-        vnm_dcol k2 = keys[0];
-        k2.validity = nullptr;
-        bool piv = false, multi = false;
-        if (queueable(h, nrows, &k2, inputs, pred, &piv, &multi) && !multi) {   // (the hot shape: one input column)
-            h->kn_valid = keys[0].validity; h->kn_off = keys[0].offset;
-            const int rc = next_device_impl(h, nrows, &k2, inputs, pred, stream);
-            h->kn_valid = nullptr;
-            if (rc != VNM_RC_SINGLY) return rc;
-            h->kn_failed = true;
-        }
-    }
-    // rows the samplers may read through keys[0] (the first segment of a stream's waiting batches)
-    const int64_t est_rows = h->segs_active ? (*h->segs_active)[0].nrows : nrows;
-    if (nrows <= 0) {
-        if (h->plan.n_keys == 0 || h->hint <= 0) VNM_TRY(ensure_table(h, nrows, s));
-        return 0;
-    }
-    if (nrows >= (1LL << 31)) return set_error("vnm_agg_next_device: batches must be < 2^31 rows (as in the reference, agg_funcs.h:45)");
-
-    // multi-column keys: try the packed single-word form first (see PackParams).  A SINGLE key that the fast paths do
-    // not take as it is (int32 / int16 / float32 ..., NULLs, an odd Arrow offset) is packed the same way when the
-    // group count is large or unknown: one extra pass over the key column (12 B/row) buys the partitioned path instead
-    // of per-row HBM atomics (G = 1e6 int32 keys: 20x).
-    const bool key_plain = h->plan.n_keys == 1 && type_width(keys[0].type) == 8 && !keys[0].validity && (keys[0].offset & 1) == 0;
-    const bool pack_single = h->single && h->plan.n_keys == 1 && !key_plain &&
-                             (h->hint > 2400 || (h->hint == 0 && nrows >= env_i64("VNM_AGG_ESTIMATE_MIN_ROWS", 1 << 22)));
-    if ((!h->single && h->plan.n_keys >= 2) || pack_single || (h->single && h->inner)) {
-        VNM_SEG_ONLY("packed keys");
-        for (int j = 0; j < h->plan.n_keys; j++)
-            if (keys[j].type != h->plan.key_types[j]) return set_error("vnm_agg_next_device: key %d changed type between batches", j);
-        // ... only into an EMPTY handle: an operator that already holds groups of earlier batches in any form (HBM table, run,
-        // deferred dense pass, stream table, the parts of a split program) keeps them -- a single key whose FIRST batch was plain
-        // (no validity bitmap) and whose later batch brings NULL keys takes the general scan for that batch instead
-        // (the inner operator's result used to replace, not join, what the handle held)
-        const bool empty_handle = !h->have_table && !h->have_run && !h->pending && !h->scan_pending && h->parts.empty();
-        if (!h->pack_tried && empty_handle && getenv("VNM_AGG_NO_PACK") == nullptr) {
-            h->pack_tried = true;
-            int err = 0;
-            if (plan_packing(h, keys, nrows, s, &err)) {
-                const int kt = VNM_U64;
-                h->inner = agg_create(VNM_SINGLE_NUMERICAL, 1, &kt, h->n_funcs, h->c_funcs, h->c_in_types, h->c_in_flags,
-                                          h->c_has_ids ? h->c_in_col_ids : nullptr);
-                if (!h->inner) return 1;
-                h->inner->hint = h->hint;
-                // a nullable key column: its NULL code may be a heavy key of the inner operator, whose estimator is not asked when
-                // the caller gave a group count (the dense path then cuts pass 2 into more work items, see heavy_share)
-                for (int j = 0; j < h->plan.n_keys; j++) if (keys[j].validity) h->inner->heavy_share = std::max(h->inner->heavy_share, 0.01);
-            } else if (err) return err;
-            else if (!h->single && getenv("VNM_AGG_NO_TUPLE") == nullptr) {
-                // too wide for one word even as per-column dictionary codes: tuple -> group id through a dictionary
-                // (before: agg_wide_kernel, one HBM atomic per row and accumulator word)
-                VNM_TRY(enter_tuple_mode(h, nrows, s));
-            }
-        }
-        if (h->tuple_mode) { route_note("keys:tuple_dictionary", "%d key columns: tuple -> group id", h->plan.n_keys); return tuple_next(h, nrows, keys, inputs, pred, s); }
-        if (h->inner) {
-            {
-                int ndict = 0;
-                for (int j = 0; j < h->plan.n_keys; j++) ndict += h->pack.dtab[j] != nullptr;
-                route_note(ndict ? "keys:packed_with_dictionary_fields" : "keys:packed", "%d key columns in one 64-bit word (%d dictionary-coded)", h->plan.n_keys, ndict);
-            }
-            for (int j = 0; j < h->plan.n_keys; j++) { h->pack.cols[j] = keys[j]; if (keys[j].validity) h->pack_null_seen = true; }
-            uint64_t* packed = (uint64_t*)pool_alloc((size_t)nrows * 8);
-            unsigned long long* flag = (unsigned long long*)pool_alloc(64);
-            if (!packed || !flag) return 1;
-            VNM_HIP(hipMemsetAsync(flag, 0, 8, s));
-            {
-                KernelTimer timer("agg_pack_keys", s);
-                int grid = (int)std::min<int64_t>((nrows + 255) / 256, (int64_t)device_info().num_cus * 8);
-                key_pack_kernel<<<grid, 256, 0, s>>>(h->pack, nrows, packed, flag);
-            }
-            unsigned long long bad = 0;
-            VNM_HIP(hipMemcpyAsync(&bad, flag, 8, hipMemcpyDeviceToHost, s));
-            VNM_HIP(hipStreamSynchronize(s));
-            pool_free(flag);
-            int rc = 0;
-            if (!bad) {
-                vnm_dcol pk{};
-                pk.values = packed; pk.type = VNM_U64; pk.length = nrows;
-                if (h->pred_set) rc = vnm_agg_set_predicate(h->inner, 1, h->pred_op, h->pred_is_float, h->pred_dval, h->pred_ival);
-                if (!rc) { h->inner->child = true; h->inner->cur_seq = h->cur_seq; rc = vnm_agg_next_device(h->inner, nrows, &pk, inputs, pred, stream); }
-                if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = set_error("aggregate: packed batch failed");
-                pool_free(packed);
-                if (!rc) h->rows_seen += nrows;
-                return rc;
-            }
-            pool_free(packed);
-            if (!h->single && getenv("VNM_AGG_NO_TUPLE") == nullptr) {   // keys outside the packed ranges: on through the tuple dictionary
-                VNM_TRY(packed_to_tuple(h, nrows, s));
-                route_note("keys:tuple_dictionary", "a batch outgrew the packed ranges");
-                return tuple_next(h, nrows, keys, inputs, pred, s);
-            }
-            VNM_TRY(demote_packed(h, s));  // (a packed SINGLE key: its own general path; or the dictionary switched off: the wide-key table)
-        }
-    }
-
-    // more input columns than a partition entry carries (or as many, plus a validity word) and many groups: split the program
-    if (!h->parts.empty()) { VNM_SEG_ONLY("split program"); route_note("split_program:batch", "%zu parts", h->parts.size()); return next_parts(h, nrows, keys, inputs, pred, stream); }
-    if (!h->split_tried && key_plain && h->single && keys[0].type == h->plan.key_types[0] && !h->have_table && !h->have_run && !h->pending &&
-        !h->expr_active && getenv("VNM_AGG_NO_SPLIT") == nullptr) {
-        bool any_null = false, cols8 = true;
-        for (int c = 0; c < h->plan.n_cols; c++) {
-            const vnm_dcol& col = inputs[h->col_first_func[c]];
-            any_null = any_null || col.validity != nullptr;
-            cols8 = cols8 && (col.type == VNM_F64 || col.type == VNM_I64 || col.type == VNM_U64);
-        }
-        const bool est_ok = nrows >= env_i64("VNM_AGG_ESTIMATE_MIN_ROWS", 1 << 22);
-        // (a) more columns than an entry carries; (b) two or more 8-byte columns over a key the dense paths take (round 4)
-        const bool many = h->plan.n_cols + (any_null ? 1 : 0) > env_i64("VNM_AGG_SPLIT_MIN_COLS", 6);
-        const bool by_column = h->plan.n_cols >= 2 && cols8 && !h->rank_aligned && (keys[0].type == VNM_I64 || keys[0].type == VNM_U64) && est_ok &&
-                               getenv("VNM_AGG_NO_SPLIT_SMALL") == nullptr;
-        if (many || by_column) {
-            h->split_tried = true;
-            if (h->hint == 0 && !h->estimated && est_ok && getenv("VNM_AGG_NO_ESTIMATE") == nullptr) {
-                int64_t est = 0;
-                KernelTimer timer("agg_estimate", s);
-                VNM_TRY(estimate_groups(h, keys[0], est_rows, &est, s));
-                if (est) { h->hint = est; h->estimated = true; }
-            }
-            if (h->hint > env_i64("VNM_AGG_PART_MIN_GROUPS", std::min<int64_t>(2400, (int64_t)lds_slots_for(h->plan) * 6 / 10))) {
-                if (by_column) {
-                    if (h->dense_state == 0) {
-                        KernelTimer timer("agg_estimate", s);
-                        VNM_TRY(plan_dense(h, keys[0], est_rows, s));
-                    }
-                    // A few thousand groups in a SMALL key range: too many for the scan's hashed LDS table of this many words (flush
-                    // storms), so the rows used to go through wide partition entries (C = 2 / 3 / 6 columns, G = 1000, 5e8 rows:
-                    // 7.9 / 12.3 / 23.6 ms).  One part per column instead: each is the direct-addressed 2^13-slot LDS scan (16 bytes per
-                    // row and column at the scan's rate: 3.3 / 4.9 / 9.8 ms incl. the join over a few thousand groups).
-                    if (h->dense_state == 2 && h->hint <= (1 << DP_TBITS_MAX)) {
-                        route_note("split_program:small_range_per_column", "%d columns, ~%lld groups in a range of <= 2^13 codes", h->plan.n_cols, (long long)h->hint);
-                        VNM_TRY(make_parts(h, 1));
-                        if (h->segs_active) return VNM_RC_SINGLY;   // (the waiting batches of a stream: one by one into the parts, which record them)
-                        return next_parts(h, nrows, keys, inputs, pred, stream);
-                    }
-                    // MANY groups over a key the dense path takes, three or more columns: the dense path per column (16-byte entries,
-                    // LDS-resident final tables) -- or per PAIR of float64 columns under sums and counts (two-value entries) where
-                    // two scatter levels are needed anyway -- instead of wide entries through hash partitions; parts of the dense path
-                    // over one code map are joined by units of 64 codes (collapse_parts: no sorts, no random gathers).
-                    // 5e8 rows, 3 / 6 columns: G = 1e6 20.0 / 37.6 -> 13.9 / 26.8 ms, G = 1e8 30.1 / 360 -> 24.7 / 44.8.
-                    if (nrows >= env_i64("VNM_AGG_SPLIT_DENSE_MIN_ROWS", 1 << 24) && h->dense_state == 1 &&
-                        h->dense_span <= 32 * h->hint && h->dense_span <= env_i64("VNM_DENSE_SPAN_PER_ROW", 16) * nrows && getenv("VNM_AGG_NO_SPLIT_DENSE") == nullptr) {
-                        bool sums = true;   // every function a sum / count of a plain float64 column: what the two-value entries carry
-                        for (int i = 0; i < h->n_funcs && sums; i++) {
-                            const int f = h->c_funcs[i];
-                            sums = f == VNM_COUNT_STAR || ((f == VNM_SUM || f == VNM_AVG || f == VNM_COUNT) && inputs[i].type == VNM_F64 && !inputs[i].validity);
-                        }
-                        // (the two-value entries have no deferred final pass and take no stream segments: every batch ends in a run that is
-                        // merged into the table -- 30 x 2^24 rows, three columns, G = 1e7: 107 ms against 17 for the same rows as one batch.
-                        // They are for BIG batches; a stream's batches go per column, whose parts record and defer like any one-column stream)
-                        const bool big = !h->segs_active && nrows >= env_i64("VNM_AGG_PAIRS_MIN_ROWS", (int64_t)1 << 27);
-                        const bool pairs = sums && big && h->hint >= env_i64("VNM_AGG_SPLIT_PAIRS_MIN_GROUPS", 4000000);
-                        // (TWO columns: the two-value entries themselves from ~1.5e6 groups on -- two scatter levels -- and one part per column
-                        // below: 5e8 rows, G = 1e4 / 1e5 / 5e5 / 1e6: 8.2 / 10.9 / 14.8 / 10.1 -> 7.3 / 7.8 / 8.1 / 8.7 ms; 2e6: 9.9 against 11.4)
-                        const bool split = h->plan.n_cols >= 3 || !sums || !big || (!pairs && h->hint <= env_i64("VNM_AGG_SPLIT_TWO_MAX_GROUPS", 1500000));
-                        // two or three float64 columns whose values are fixed-point words: ONE pass over the rows (vnm_agg_fxn.inc) before the
-                        // program is cut per column
-                        if (sums && h->plan.n_cols <= 3 && h->parts.empty()) {
-                            const int frc = dense_fxn_aggregate(h, nrows, keys, inputs, pred, s);
-                            if (frc == 1) return 1;
-                            if (frc == 0) { h->rows_seen += nrows; return 0; }
-                        }
-                        if (split) {
-                            route_note(pairs ? "split_program:dense_per_pair" : "split_program:dense_per_column", "%d columns, ~%lld groups over %lld codes, %lld rows", h->plan.n_cols, (long long)h->hint, (long long)h->dense_span, (long long)nrows);
-                            VNM_TRY(make_parts(h, pairs ? 2 : 1));
-                            if (h->segs_active) return VNM_RC_SINGLY;
-                            return next_parts(h, nrows, keys, inputs, pred, stream);
-                        }
-                    }
-                }
-                if (many) {
-                    route_note("split_program:many_columns", "%d columns (+%d validity word), ~%lld groups", h->plan.n_cols, any_null ? 1 : 0, (long long)h->hint);
-                    VNM_TRY(make_parts(h, (int)env_i64("VNM_AGG_SPLIT_COLS", any_null ? 5 : 6)));
-                    if (h->segs_active) return VNM_RC_SINGLY;
-                    return next_parts(h, nrows, keys, inputs, pred, stream);
-                }
-            } else if (many && cols8 && !any_null && h->hint > 0 && h->hint <= env_i64("VNM_AGG_SPLIT_FEW_MAX_GROUPS", 256) && !h->rank_aligned &&
-                       getenv("VNM_AGG_NO_SPLIT_FEW") == nullptr) {
-                // FEW groups under more than six plain 8-byte columns: parts of up to six columns, each through agg_hotn_kernel, instead of the
-                // interpreted scan over all of them (5e8 rows, G = 7: 7 / 8 / 10 columns 11.5 / 12.9 / 15.7 ms at 2.8 TB/s)
-                route_note("split_program:few_groups_many_columns", "%d columns, ~%lld groups", h->plan.n_cols, (long long)h->hint);
-                VNM_TRY(make_parts(h, 6));
-                if (h->segs_active) return VNM_RC_SINGLY;
-                return next_parts(h, nrows, keys, inputs, pred, stream);
-            }
-        }
-    }
-
-    AggArgs a{};
-    a.plan = h->plan;
-    for (int j = 0; j < h->plan.n_keys; j++) {
-        a.keys[j] = keys[j];
-        if (keys[j].type != h->plan.key_types[j]) return set_error("vnm_agg_next_device: key %d changed type between batches", j);
-    }
-    for (int c = 0; c < h->plan.n_cols; c++) a.cols[c] = inputs[h->col_first_func[c]];
-    if (h->pred_set) {
-        a.pred = *pred;
-        a.p = make_predicate(pred->type, pred->validity != nullptr, h->pred_op, h->pred_is_float, h->pred_dval, h->pred_ival);
-    }
-    a.nrows = nrows;
-    a.ntiles = (nrows + AGG_TILE - 1) / AGG_TILE;
-    a.debug = (int)env_i64("VNM_AGG_DEBUG", 0);
-    if (h->expr_active) { a.has_expr = 1; a.expr = h->expr_dev; }
-    const int cus = device_info().num_cus;
-
-    if (h->plan.n_keys == 0) {
-        VNM_SEG_ONLY("no GROUP BY");
-        VNM_TRY(ensure_table(h, nrows, s));
-        a.g = h->g;
-        int grid = cus * 8;
-        int64_t need = (nrows + OG_BLOCK - 1) / OG_BLOCK;
-        if (grid > need) grid = (int)need;
-        KernelTimer timer("agg_scan", s);
-        // every kind at most once over at most one plain 8-byte column, float64 predicate or none: the register kernel
-        bool og_hot = h->plan.n_cols <= 1 && getenv("VNM_AGG_NO_HOT") == nullptr;
-        int vt = -1;
-        if (og_hot && h->plan.n_cols == 1) {
-            const vnm_dcol& c = a.cols[0];
-            og_hot = (c.type == VNM_F64 || c.type == VNM_I64 || c.type == VNM_U64) && !c.validity && (c.offset & 1) == 0;
-            vt = c.type;
-        }
-        for (int k = 0; k < 9; k++) a.hot_w[k] = -1;
-        for (int o = 0; o < h->plan.n_ops && og_hot; o++) {
-            const AccOp& op = h->plan.ops[o];
-            if (op.kind < 0 || op.kind > A_MAX || a.hot_w[op.kind] >= 0 || (op.kind != A_COUNT_ROWS && vt < 0)) og_hot = false;
-            else a.hot_w[op.kind] = op.word;
-        }
-        int pm = 0;
-        if (og_hot && h->pred_set) {
-            og_hot = a.pred.type == VNM_F64 && !a.pred.validity && (a.pred.offset & 1) == 0 && a.p.mode == CMP_F64;
-            pm = og_hot && vt == VNM_F64 && a.pred.values == a.cols[0].values && a.pred.offset == a.cols[0].offset ? 1 : 2;
-        }
-        route_note(og_hot ? "onegroup:register_scan" : "onegroup:lds_scan", "%lld rows, %d columns, %d words", (long long)nrows, h->plan.n_cols, h->plan.n_words);
-        if (og_hot) {
-            const int g2 = (int)std::min<int64_t>((int64_t)cus * 8, std::max<int64_t>(1, (nrows / 2 + OG_BLOCK - 1) / OG_BLOCK));
-#define VNM_OG(VT_)                                                                                                 \
-    do {                                                                                                            \
-        if (pm == 0) agg_onegroup_hot_kernel<VT_, 0><<<g2, OG_BLOCK, 0, s>>>(a);                                    \
-        else if (pm == 1) agg_onegroup_hot_kernel<VT_, 1><<<g2, OG_BLOCK, 0, s>>>(a);                               \
-        else agg_onegroup_hot_kernel<VT_, 2><<<g2, OG_BLOCK, 0, s>>>(a);                                            \
-    } while (0)
-            if (vt == VNM_F64) VNM_OG(VNM_F64); else if (vt == VNM_I64) VNM_OG(VNM_I64); else if (vt == VNM_U64) VNM_OG(VNM_U64); else VNM_OG(-1);
-#undef VNM_OG
-        } else
-        agg_onegroup_kernel<<<grid, OG_BLOCK, (size_t)h->plan.n_words * OG_BLOCK * 8, s>>>(a);
-        VNM_HIP(hipGetLastError());
-        h->rows_seen += nrows;
-        return 0;
-    }
-
-    const int S = lds_slots_for(h->plan);
-    a.lds_slots = S;
-    // hot shape: one 8-byte key, every function in {COUNT(*), COUNT, SUM, AVG} over ONE float64 column,
-    // float64 predicate column (or none), no validity bitmaps, even offsets (16-byte aligned pairs)
-    // hot_scan: what agg_hot_kernel takes (any accumulator kind over at most TWO 8-byte columns without NULLs);
-    // hot: the subset {COUNT(*), COUNT, SUM, AVG} of a float64 column that part_agg_kernel is specialised for
-    bool hot_scan = h->single && h->plan.n_cols <= 2 && type_width(keys[0].type) == 8 && !keys[0].validity &&
-                    (keys[0].offset & 1) == 0 && getenv("VNM_AGG_NO_HOT") == nullptr;
-    a.hot_has_val = h->plan.n_cols >= 1;
-    a.hot_vtype = a.hot_vtype2 = VNM_U64;
-    bool hot_vnull = false;  // ONE nullable input column: agg_hot_kernel<VNULL>
-    for (int c = 0; c < h->plan.n_cols && hot_scan; c++) {
-        const vnm_dcol& col = a.cols[c];
-        if (col.validity && h->plan.n_cols == 1) hot_vnull = true;
-        hot_scan = (col.type == VNM_F64 || col.type == VNM_I64 || col.type == VNM_U64) && (!col.validity || hot_vnull) && (col.offset & 1) == 0;
-        (c == 0 ? a.hot_vtype : a.hot_vtype2) = col.type;
-    }
-    const bool hot_two = hot_scan && h->plan.n_cols == 2;
-    a.hot_w_rows = a.hot_w_valid = a.hot_w_sum = -1;
-    a.hot_comp = 0;
-    for (int w = 0; w < h->plan.n_words; w++) if (h->plan.merge[w] == M_ADD_F64C) a.hot_comp = 1;
-    for (int k = 0; k < 9; k++) a.hot_w[k] = a.hot_w2[k] = -1;
-    bool hot = hot_scan && h->plan.n_cols == 1 && a.hot_vtype == VNM_F64;   // (a nullable column: hot_prog below)
-    if (hot_scan) {
-        for (int o = 0; o < h->plan.n_ops; o++) {
-            const AccOp& op = h->plan.ops[o];
-            int* hw = op.col == 1 ? a.hot_w2 : a.hot_w;
-            const int vt = op.col == 1 ? a.hot_vtype2 : a.hot_vtype;
-            if (op.kind < 0 || op.kind > A_MAX || hw[op.kind] >= 0) { hot_scan = false; break; }  // one word per kind and column
-            if (op.kind == A_SUM_F64 && vt != VNM_F64) { hot_scan = false; break; }
-            hw[op.kind] = op.word;
-            if (op.col == 1) { hot = false; continue; }
-            if (op.kind == A_COUNT_ROWS) a.hot_w_rows = op.word;
-            else if (op.kind == A_COUNT_VALID) a.hot_w_valid = op.word;
-            else if (op.kind == A_SUM_F64) a.hot_w_sum = op.word;
-            else hot = false;
-        }
-    }
-    a.hot_wpack = a.hot_wpack2 = ~0ULL;
-    for (int k = A_COUNT_VALID; k <= A_MAX; k++) {
-        if (a.hot_w[k] >= 0) a.hot_wpack = (a.hot_wpack & ~(63ULL << (6 * k))) | ((unsigned long long)a.hot_w[k] << (6 * k));
-        if (a.hot_w2[k] >= 0) a.hot_wpack2 = (a.hot_wpack2 & ~(63ULL << (6 * k))) | ((unsigned long long)a.hot_w2[k] << (6 * k));
-    }
-    hot = hot && hot_scan;
-    if (hot_scan && h->pred_set) {
-        a.hot_pred_is_v = a.hot_has_val && a.hot_vtype == VNM_F64 && a.pred.values == a.cols[0].values && a.pred.offset == a.cols[0].offset;
-        // a nullable predicate column only as the (nullable) input column itself
-        hot_scan = a.pred.type == VNM_F64 && (!a.pred.validity || (hot_vnull && a.hot_pred_is_v)) && (a.pred.offset & 1) == 0 && a.p.mode == CMP_F64;
-        hot = hot && hot_scan;
-    }
-    // the hot PROGRAM over a nullable column filtered by itself (`WHERE v > x`: a NULL fails the filter): the dense path drops the
-    // NULL rows in pass 1 and everything after it is the hot shape (vn_fold below); every other kernel of the hot shape reads no bitmap
-    const bool hot_prog = hot;
-    if (hot_vnull) hot = false;
-    // three to six plain float64 columns under {COUNT(*), COUNT, SUM, AVG}: agg_hotn_kernel takes the scan
-    bool hotn = !hot_scan && h->single && h->plan.n_cols >= 3 && h->plan.n_cols <= 6 && type_width(keys[0].type) == 8 && !keys[0].validity &&
-                (keys[0].offset & 1) == 0 && !a.has_expr && getenv("VNM_AGG_NO_HOTN") == nullptr && getenv("VNM_AGG_NO_HOT") == nullptr;
-    {
-        int w_rows = -1, w_cnt[6] = {-1, -1, -1, -1, -1, -1};
-        for (int c = 0; c < 6; c++) a.hn_w_sum[c] = -1;
-        a.hn_any_int = a.hn_any_mm = 0;
-        for (int c = 0; c < 6; c++) { a.hn_ctype[c] = VNM_F64; a.hn_wmm[c][0] = a.hn_wmm[c][1] = -1; for (int k = 0; k < 4; k++) a.hn_iw[c][k] = -1; }
-        for (int c = 0; c < h->plan.n_cols && hotn; c++) {
-            const vnm_dcol& col = a.cols[c];
-            hotn = (col.type == VNM_F64 || col.type == VNM_I64 || col.type == VNM_U64) && !col.validity && (col.offset & 1) == 0 && ((uintptr_t)col.values & 15) == 0;
-            a.hn_ctype[c] = col.type;
-            if (col.type != VNM_F64) a.hn_any_int = 1;   // (not the PLAIN instantiation: its values are float64 bit patterns)
-        }
-        for (int o = 0; o < h->plan.n_ops && hotn; o++) {
-            const AccOp& op = h->plan.ops[o];
-            if (op.kind == A_COUNT_ROWS && w_rows < 0) w_rows = op.word;
-            else if (op.kind == A_COUNT_VALID && w_cnt[op.col] < 0) w_cnt[op.col] = op.word;
-            else if (op.kind == A_SUM_F64 && a.hn_w_sum[op.col] < 0) a.hn_w_sum[op.col] = op.word;
-            else if (op.kind >= A_SUM_I64 && op.kind <= A_SUM_HI32U && a.hn_ctype[op.col] != VNM_F64 && a.hn_iw[op.col][op.kind - A_SUM_I64] < 0) {
-                a.hn_iw[op.col][op.kind - A_SUM_I64] = op.word;
-                a.hn_any_int = 1;
-            } else if ((op.kind == A_MIN || op.kind == A_MAX) && a.hn_wmm[op.col][op.kind - A_MIN] < 0) {
-                a.hn_wmm[op.col][op.kind - A_MIN] = op.word;
-                a.hn_any_mm = 1;
-            } else hotn = false;
-        }
-        a.hn_w_base = w_rows;
-        a.hn_n_copy = 0;
-        for (int c = 0; c < h->plan.n_cols && hotn; c++) {
-            if (w_cnt[c] < 0) continue;
-            if (a.hn_w_base < 0) a.hn_w_base = w_cnt[c];
-            else a.hn_w_copy[a.hn_n_copy++] = w_cnt[c];
-        }
-        hotn = hotn && a.hn_w_base >= 0 && ((uintptr_t)keys[0].values & 15) == 0;
-        a.hn_pred_col = -1;
-        if (hotn && h->pred_set) {
-            hotn = a.pred.type == VNM_F64 && !a.pred.validity && (a.pred.offset & 1) == 0 && ((uintptr_t)a.pred.values & 15) == 0 && a.p.mode == CMP_F64;
-            for (int c = 0; c < h->plan.n_cols && hotn; c++)
-                if (a.pred.values == a.cols[c].values && a.pred.offset == a.cols[c].offset) a.hn_pred_col = c;
-        }
-    }
-    // the partitioned path also takes ANY accumulator program over at most one 8-byte input column: its entries
-    // carry (key, raw value bits) and only the final pass interprets them
-    bool part_ok = hot;
-    bool narrow_generic = false;   // a generic program over (key, one plain 8-byte value or none): the dgen_* dense kernels take it too
-    if (!hot && h->single && h->plan.n_cols <= 6 && type_width(keys[0].type) == 8 && !keys[0].validity &&
-        (keys[0].offset & 1) == 0 && getenv("VNM_AGG_NO_PART_GENERIC") == nullptr &&
-        (size_t)(256 + 1) * 8 * (1 + h->plan.n_words) <= 150 * 1024) {   // (the final pass shrinks its LDS table to fit)
-        // narrow entries (key, value): at most one 8-byte input column without NULLs, float64 predicate column
-        bool narrow = h->plan.n_cols <= 1;
-        bool any_null = false;
-        for (int c = 0; c < h->plan.n_cols; c++) {
-            const vnm_dcol& col = a.cols[c];
-            a.part_vtypes[c] = col.type;
-            if (col.validity) any_null = true;
-            if (!((col.type == VNM_I64 || col.type == VNM_U64 || col.type == VNM_F64) && !col.validity && (col.offset & 1) == 0)) narrow = false;
-        }
-        if (h->plan.n_cols >= 1) a.part_vtype = a.cols[0].type;
-        if (narrow && h->pred_set) {
-            narrow = a.pred.type == VNM_F64 && !a.pred.validity && (a.pred.offset & 1) == 0 && a.p.mode == CMP_F64;
-            a.hot_pred_is_v = h->plan.n_cols == 1 && a.pred.values == a.cols[0].values && a.pred.offset == a.cols[0].offset;
-        }
-        // wide entries take the rest: several columns, NULLs, narrow types, any predicate -- while key + values
-        // (+ validity word) fit seven words
-        const bool wide = !narrow && h->plan.n_cols >= 1 && h->plan.n_cols + (any_null ? 1 : 0) <= 6 &&
-                          getenv("VNM_AGG_NO_PART_WIDE") == nullptr;
-        part_ok = narrow || wide;
-        narrow_generic = narrow;
-        a.part_generic = part_ok;
-        a.part_wide = wide;
-        a.part_vmask = wide && any_null;
-        // no input column at all (COUNT(*) only): the entries are the keys alone -- 8 bytes instead of 16 through every
-        // pass, via the wide kernels with E = 1.  Those cannot spill heavy keys; if a region overflows the operator goes
-        // back to (key, unused word) entries with the spill buffer for good.
-        if (narrow && h->plan.n_cols == 0 && !h->key_only_failed && getenv("VNM_AGG_NO_KEY_ONLY") == nullptr) a.part_wide = 1;
-    }
-    // no hint from the caller: estimate the group count once from a sample of the first large batch
-    // Dense-key path (vnm_agg_dense.inc): the north-star shape over an int64 / uint64 key whose (sampled) range fits 29
-    // bits.  It needs to know that G is LARGE, not how large: when the small sample of the estimator cannot settle G, its
-    // lower bound is enough (span <= 32 G: the direct-addressed slots are reasonably filled) and the HyperLogLog pass
-    // (0.85 ms) is skipped; the hash-partitioned path below still estimates properly if the dense attempt fails.
-    // (generic programs: only where the spilled entries -- keys outside the sampled range -- have a kernel to go to)
-    // ... and ONE nullable 8-byte input column (hot_vnull; the predicate column, if any, without NULLs or that column itself): the
-    // entries carry a NULL flag next to the code (vnm_agg_dense.inc, VN kernels); what the dense pass cannot place comes back as
-    // two lists (entries, keys of NULL-value rows) and goes through the scan below as columns
-    const bool dense_vn = !hot && hot_scan && hot_vnull && !hot_two && !a.has_expr && part_ok && h->plan.n_cols == 1 &&
-                          getenv("VNM_AGG_NO_DENSE_VN") == nullptr;
-    const bool vn_fold = dense_vn && hot_prog && h->pred_set && a.hot_pred_is_v && getenv("VNM_AGG_NO_VN_FOLD") == nullptr;
-    const bool dense_generic = ((!hot && narrow_generic && hot_scan && !hot_two && !hot_vnull && !a.has_expr) || dense_vn) &&
-                               getenv("VNM_AGG_NO_DENSE_GENERIC") == nullptr && getenv("VNM_AGG_NO_SPILL") == nullptr;
-    // ... and TWO plain float64 input columns under {COUNT(*), COUNT, SUM, AVG} (dense_two_aggregate: two-value entries)
-    bool dense_two = hot_scan && hot_two && !a.has_expr && !h->rank_aligned && !h->segs_active && !h->kn_valid && a.hot_vtype == VNM_F64 && a.hot_vtype2 == VNM_F64 &&
-                     getenv("VNM_AGG_NO_DENSE_TWO") == nullptr;
-    for (int o = 0; o < h->plan.n_ops && dense_two; o++) {
-        const int k = h->plan.ops[o].kind;
-        dense_two = k == A_COUNT_ROWS || k == A_COUNT_VALID || k == A_SUM_F64;
-    }
-    const bool dense_base = (hot || dense_generic || dense_two) && part_ok && nrows >= env_i64("VNM_AGG_ESTIMATE_MIN_ROWS", 1 << 22) &&
-                            getenv("VNM_AGG_NO_DENSE") == nullptr;
-    bool dense_shape = dense_base && (!h->rank_aligned || h->range_given);   // rank-aligned: only with a code range all ranks agreed on
-    // a batch must bring enough rows for its code range (a final pass over 2^b slots for a handful of rows is all overhead) -- unless a
-    // deferred pass over that very range is waiting anyway: a short batch of a stream then simply joins it (round 4; before, it took
-    // two hash levels -- and, with a nullable key, the general scan)
-    // (evaluated where it is used: plan_dense may only just have set the range)
-    // (16 codes per row of the batch: a 2^24-row batch of a stream opens -- and later batches join -- a deferred pass over 2^27 codes; with 4
-    // such a stream took the hash partitions batch by batch: 59 x 2^24 rows, G = 1e8, synchronous next(): 132.6 -> 21.6 ms; a single
-    // 2^24-row batch over that range: 1.66 -> 1.10 ms)
-    const int64_t span_per_row = env_i64("VNM_DENSE_SPAN_PER_ROW", 16);
-    auto span_fits_now = [&]() { return h->dense_span <= span_per_row * nrows || (h->pending != nullptr && h->dense_state == 1 && memcmp(&h->pending->df.map, &h->dmap, sizeof(DenseMap)) == 0); };
-#define span_fits span_fits_now()
-    bool dense_go = false;
-    // a stream that went dense on the sample's lower bound (no group count exists) and now brings a batch too short for the
-    // code range: this batch and the rest need a number after all (without one they took the LDS scan and its flush storms)
-    if (h->dense_by_bound && h->hint == 0 && !(dense_shape && h->dense_state == 1 && span_fits)) {
-        h->estimated = false;
-        h->dense_by_bound = false;
-    }
-    if (part_ok && h->hint == 0 && !h->estimated && nrows >= env_i64("VNM_AGG_ESTIMATE_MIN_ROWS", 1 << 22) &&
-        getenv("VNM_AGG_NO_ESTIMATE") == nullptr) {
-        int64_t est = 0, dense_lb = 0;
-        KernelTimer timer("agg_estimate", s);
-        // the small sample first: a conclusive (small) group count needs neither the key range nor HyperLogLog
-        VNM_TRY(estimate_groups(h, keys[0], est_rows, &est, s, dense_shape ? &dense_lb : nullptr));
-        if (est == 0) {
-            if (h->dense_state == 0) VNM_TRY(plan_dense(h, keys[0], est_rows, s));
-            // (... or, under skew -- duplicates in the sample pull the bound down -- when the bound at least rules out the LDS scans and the
-            // rows outnumber the code range four to one: the passes over the rows dominate whatever G is, the hash partitions would
-            // cost the same, and the HyperLogLog pass (0.8 ms) buys nothing)
-            const bool rows_dominate = dense_lb >= env_i64("VNM_DENSE_SKEW_MIN_LB", 100000) && h->dense_span * 4 <= nrows;
-            if (h->dense_state == 1 && (h->dense_span <= 32 * dense_lb || rows_dominate) && span_fits) dense_go = true;
-            else VNM_TRY(estimate_groups(h, keys[0], est_rows, &est, s));   // too sparse (or not a code-able key): full estimate
-        }
-        if (est) { h->hint = est; h->estimated = true; }
-        else if (dense_go) { h->estimated = true; h->dense_by_bound = true; }   // later batches of the stream: no sample again
-    }
-    if (dense_shape && !dense_go && h->dense_by_bound && h->hint == 0 && h->dense_state == 1 && span_fits) dense_go = true;
-    // rank-aligned operators (multi-GPU) keep hash partitions so that every rank cuts its result the same way -- which only
-    // the partition-aligned exchange of LARGE results needs; small results travel by one all-gather and are merged by key
-    if (dense_base && h->rank_aligned && h->hint > 0 && h->hint <= env_i64("VNM_ALIGNED_DENSE_MAX", 1 << 19)) dense_shape = true;
-    const int64_t part_min0 = env_i64("VNM_AGG_PART_MIN_GROUPS", std::min<int64_t>(2400, (int64_t)S * 6 / 10));
-    if (dense_shape && !dense_go && h->hint > part_min0) {
-        if (h->dense_state == 0) {
-            KernelTimer timer("agg_estimate", s);
-            VNM_TRY(plan_dense(h, keys[0], est_rows, s));
-        }
-        if (h->dense_state == 1 && h->dense_span <= 32 * h->hint && span_fits) dense_go = true;
-    }
-    ulonglong2* spill = nullptr;  // entries the partitioned / dense paths could not place (heavy keys, keys outside the sampled range): aggregated below
-    int64_t n_spill = 0;
-    uint64_t* nspill = nullptr;   // dense path over a nullable value column: keys of the NULL-value rows it could not place
-    int64_t n_nspill = 0;
-    bool scan_no_pred = false;    // ... whose rows come back as columns with the predicate already applied
-    unsigned int* progress = nullptr;
-    PoolScope unzip;   // spilled wide entries as columns
-    PoolSlotGuard<ulonglong2> spill_guard(&spill);       // both go back to the pool on every way out of this function
-    PoolSlotGuard<uint64_t> nspill_guard(&nspill);
-    PoolSlotGuard<unsigned int> progress_guard(&progress);
-    // the two spill lists of the nullable dense path -> key / value / validity columns for the scan below
-    auto vn_spill_to_columns = [&]() -> int {
-        const int64_t n = n_spill + n_nspill;
-        uint64_t* uk = (uint64_t*)unzip.take((size_t)n * 8);
-        uint64_t* uv = (uint64_t*)unzip.take((size_t)n * 8);
-        unsigned long long* ub = (unsigned long long*)unzip.take((size_t)((n + 63) / 64) * 8);
-        if (!uk || !uv || !ub) return 1;
-        const int ugrid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)device_info().num_cus * 8);
-        dense_vn_unzip_kernel<<<ugrid, 256, 0, s>>>(spill, n_spill, nspill, n_nspill, uk, uv, ub);
-        VNM_HIP(hipGetLastError());
-        a.keys[0].values = uk; a.keys[0].validity = nullptr; a.keys[0].offset = 0; a.keys[0].length = n;
-        a.cols[0].values = uv; a.cols[0].validity = (const uint8_t*)ub; a.cols[0].offset = 0; a.cols[0].length = n;
-        a.ent = nullptr;
-        a.nrows = n;
-        a.p.enabled = 0;
-        scan_no_pred = true;
-        return 0;
-    };
-    // a few hundred to a few thousand groups in a small key range: the direct-addressed LDS scan (vnm_agg_dense.inc)
-    bool dscan_done = false;
-    bool dscan_stream = false;   // the batch went into the stream table (h->scan_pending)
-    if (dense_shape && !dense_go && !dense_two && h->hint >= env_i64("VNM_DSCAN_MIN_GROUPS", 128) && h->hint <= (1 << DP_TBITS_MAX) &&
-        getenv("VNM_AGG_NO_DSCAN") == nullptr) {
-        if (h->dense_state == 0) {
-            KernelTimer timer("agg_estimate", s);
-            VNM_TRY(plan_dense(h, keys[0], est_rows, s));
-        }
-        if (h->dense_state == 2) {
-            if (h->kn_valid || (h->segs_active && (dense_generic || a.has_expr))) VNM_SEG_ONLY("small-range LDS scan");   // (the hot program's scan takes segments)
-            if (h->pending) VNM_TRY(complete_pending(h, s));   // (this path makes a run of its own)
-            if (h->have_run) VNM_TRY(merge_run_into_table(h, s));
-            if (dense_generic && h->scan_pending) VNM_TRY(flush_scan_pending(h, s));
-            route_note(dense_generic ? "dense_scan:generic" : "dense_scan:hot", "~%lld groups in a sampled range of %lld codes (<= 2^13): direct-addressed LDS table, no scatter", (long long)h->hint, (long long)h->dense_span);
-            int prc = dense_scan_aggregate(h, a, nrows, s, &spill, &n_spill, dense_generic, &nspill, &n_nspill);
-            dscan_stream = prc == 0 && !dense_generic;
-            // a generic program whose table for this range does not fit LDS: the same 2^13 codes through one scatter level
-            // (four partitions of 2^11 slots, split final pass) instead
-            if (prc == 2 && dense_generic && h->dense_state == 2) prc = dense_partitioned_aggregate(h, a, nrows, s, &spill, &n_spill, true, &nspill, &n_nspill);
-            if (prc == 1) return 1;
-            if (prc == 0 && !spill && !nspill) { h->rows_seen += nrows; return 0; }
-            if (prc == 0 && dense_vn) {
-                VNM_TRY(vn_spill_to_columns());
-                dscan_done = true;
-            } else if (prc == 0) {  // the scan below runs over the spilled entries only (predicate already applied)
-                a.ent = spill;
-                a.nrows = n_spill;
-                a.p.enabled = 0;
-                dscan_done = true;
-            }
-        }
-    }
-    // (a batch that went another way than the stream table of the small-range scan: that table becomes a run first)
-    if (h->scan_pending && !dscan_stream) VNM_TRY(flush_scan_pending(h, s));
-    // many groups: radix-partitioned path (no per-row HBM atomics); falls through when it does not apply
-    // ... from the point where the groups stop fitting the LDS table of the scan kernel (flush storms otherwise:
-    // MIN+MAX with 2000 groups and a 2048-slot table ran at 38 ms)
-    const int64_t part_min = env_i64("VNM_AGG_PART_MIN_GROUPS", std::min<int64_t>(2400, (int64_t)S * 6 / 10));
-    if (!dscan_done && part_ok && (h->hint > part_min || dense_go) && getenv("VNM_AGG_NO_PART") == nullptr) {
-        if (h->have_run) VNM_TRY(merge_run_into_table(h, s));
-        // wide entries (any program over up to six columns, key-only entries) spill as whole entries; they come back as
-        // plain columns for the general scan below (spill_unzip_kernel)
-        const bool spill_wide = a.part_wide && h->single && !a.has_expr && getenv("VNM_AGG_NO_SPILL") == nullptr && getenv("VNM_AGG_NO_WIDE_SPILL") == nullptr;
-        const bool can_spill = (hot_scan && !hot_two && !hot_vnull && getenv("VNM_AGG_NO_SPILL") == nullptr) || spill_wide;
-        int prc = 2;
-        bool vn_spill = false;        // the spill lists of the nullable dense path (entries + keys of NULL-value rows)
-        bool spill_is_wide = false;   // the spill holds [n][E]-word entries of the wide scatter kernels (not the (key, value) pairs of the hot / dense paths)
-        auto run_partitioned = [&]() {
-            if (h->segs_active || h->kn_valid) return VNM_RC_SINGLY;   // (its kernels read one batch of plain keys)
-            if (h->pending && complete_pending(h, s)) return 1;     // (the hash-partitioned path makes a run of its own)
-            if (h->have_run && merge_run_into_table(h, s)) return 1;
-            route_note(a.part_wide ? "hash_partitions:wide_entries" : (a.part_generic ? "hash_partitions:generic" : "hash_partitions:hot"), "~%lld groups > %lld (the scan's LDS table), dense path %s", (long long)h->hint, (long long)part_min,
-                       h->dense_state == 1 ? "declined or failed" : "not applicable");
-            const int r = partitioned_aggregate(h, a, nrows, s, can_spill ? &spill : nullptr, can_spill ? &n_spill : nullptr);
-            spill_is_wide = r == 0 && spill != nullptr && a.part_wide != 0;
-            return r;
-        };
-        if (dense_go && dense_two && (h->hint > part_min || h->hint == 0)) {
-            if (h->pending && complete_pending(h, s)) return 1;     // (this path makes a run of its own)
-            if (h->have_run && merge_run_into_table(h, s)) return 1;
-            route_note("dense:two_values", "%lld codes, ~%lld groups, %lld rows: (value, value, code) entries", (long long)h->dense_span, (long long)h->hint, (long long)nrows);
-            prc = dense_two_aggregate(h, a, nrows, s);
-            if (prc == 2) h->dense_state = -1;                      // (a key outside the range, a full region, a range it does not take: not again)
-            if (prc == 2 && h->hint == 0) {
-                int64_t est = 0;
-                VNM_TRY(estimate_groups(h, keys[0], est_rows, &est, s));
-                h->hint = est;
-                h->estimated = true;
-            }
-        } else if (dense_go && (h->hint > part_min || h->hint == 0)) {
-            prc = dense_partitioned_aggregate(h, a, nrows, s, &spill, &n_spill, dense_generic && !vn_fold, &nspill, &n_nspill, vn_fold);
-            vn_spill = prc == 0 && dense_vn && (spill || nspill);
-            if (prc == 2 && h->hint == 0) {  // the dense attempt failed before G was ever estimated
-                int64_t est = 0;
-                VNM_TRY(estimate_groups(h, keys[0], est_rows, &est, s));
-                h->hint = est;
-                h->estimated = true;
-            }
-        }
-        if (prc == 2 && h->hint > part_min) prc = run_partitioned();
-        if (prc == 2 && a.part_wide && h->plan.n_cols == 0) {  // key-only entries and a region overflowed: see above
-            h->key_only_failed = true;
-            a.part_wide = 0;
-            prc = run_partitioned();
-        }
-        // more groups than hinted (a partition overflowed its LDS table, or the dense output its allocation): estimate
-        // the group count from the keys (< 1 ms) and partition again (~12 ms per attempt) before giving in to the HBM
-        // table (~300 ms per 1e9 rows)
-        for (int retry = 0; prc == 3 && retry < 2; retry++) {
-            int64_t est = 0;
-            if (retry == 0 && !h->estimated) {
-                VNM_TRY(estimate_groups(h, keys[0], est_rows, &est, s));
-                h->estimated = true;
-            }
-            h->hint = std::min<int64_t>(std::max<int64_t>(h->hint * 4, est + est / 4), (int64_t)1600 * env_i64("VNM_AGG_PART_L1_MAX", 256) * 512);
-            prc = run_partitioned();
-        }
-        if (prc == 0 && !spill && !nspill) { h->rows_seen += nrows; return 0; }
-        if (prc == 1) return 1;
-        if (prc == VNM_RC_SINGLY) { VNM_SEG_ONLY("hash partitions"); }
-        if (prc == 0 && vn_spill) {
-            VNM_TRY(vn_spill_to_columns());
-        } else if (prc == 0 && spill_is_wide) {   // spilled wide entries -> columns; the general scan takes them as a batch of its own
-            const int E = 1 + h->plan.n_cols + (a.part_vmask ? 1 : 0);
-            UnzipArgs u{};
-            u.ent = (const uint64_t*)spill; u.n = n_spill; u.E = E; u.nval = h->plan.n_cols; u.has_vmask = a.part_vmask;
-            u.key = (uint64_t*)unzip.take((size_t)n_spill * 8);
-            bool ok = u.key != nullptr;
-            for (int c = 0; c < h->plan.n_cols && ok; c++) {
-                u.widths[c] = type_width(a.cols[c].type);
-                u.vals[c] = unzip.take((size_t)n_spill * u.widths[c]);
-                u.valid[c] = a.cols[c].validity ? (unsigned long long*)unzip.take((size_t)((n_spill + 63) / 64) * 8) : nullptr;
-                ok = u.vals[c] && (!a.cols[c].validity || u.valid[c]);
-            }
-            if (!ok) return 1;
-            const int ugrid = (int)std::min<int64_t>((n_spill + 255) / 256, (int64_t)cus * 8);
-            spill_unzip_kernel<<<ugrid, 256, 0, s>>>(u);
-            VNM_HIP(hipGetLastError());
-            a.keys[0].values = u.key; a.keys[0].validity = nullptr; a.keys[0].offset = 0; a.keys[0].length = n_spill;
-            for (int c = 0; c < h->plan.n_cols; c++) {
-                a.cols[c].values = u.vals[c]; a.cols[c].validity = (const uint8_t*)u.valid[c]; a.cols[c].offset = 0; a.cols[c].length = n_spill;
-            }
-            a.nrows = n_spill;
-            a.ntiles = (n_spill + AGG_TILE - 1) / AGG_TILE;
-            a.p.enabled = 0;
-            hot_scan = false;
-            hotn = false;   // (columns with validity words, no predicate)
-        } else if (prc == 0) {  // the scan below runs over the spilled entries only (predicate already applied)
-            a.ent = spill;
-            a.nrows = n_spill;
-            a.p.enabled = 0;
-        }
-    }
-    const int64_t scan_n = a.nrows;
-    PoolScope seg_pool;
-    if (h->segs_active && !a.ent) {   // the waiting batches of a stream as segments of one scan (agg_hot_kernel, the hot shape only)
-        if (!(hot_scan && hot) || scan_no_pred || a.has_expr) VNM_SEG_ONLY("general scan");
-    }
-    if (h->kn_valid && !a.ent) VNM_SEG_ONLY("scan over the rows");   // (only the dense path's pass 1 reads the key's validity)
-    VNM_TRY(ensure_table(h, scan_n, s, spill != nullptr || nspill != nullptr));
-    if (hot_scan) a.ntiles = (scan_n + HOT_TILE - 1) / HOT_TILE;
-    hotn = hotn && !a.ent && !scan_no_pred && !hot_scan;
-    const int hotn_tile = AGG_BLOCK * 2 * (h->plan.n_cols == 3 && !h->pred_set ? 4 : 2);   // (agg_hotn_kernel's U)
-    if (hotn) a.ntiles = (scan_n + hotn_tile - 1) / hotn_tile;
-    if (h->segs_active && !a.ent) VNM_TRY(upload_segs(h, HOT_TILE, &a.segs, &a.nseg, &a.ntiles, seg_pool, s));
-    const int lds_tile = AGG_TILE;
-    int grid = h->single ? cus : cus * 4;
-    if (grid > a.ntiles) grid = (int)a.ntiles;
-    a.margin = (int64_t)grid * (h->single ? (a.lds_slots + 2 + (hot_scan || hotn ? HOT_TILE : lds_tile)) : AGG_TILE);
-    progress = (unsigned int*)pool_alloc((size_t)grid * 4);
-    if (!progress) return 1;
-    VNM_HIP(hipMemsetAsync(progress, 0, (size_t)grid * 4, s));
-    a.progress = progress;
-    for (int round = 0;; round++) {
-        // keep the load factor below 0.7 for everything that can be in flight
-        while ((int64_t)(h->g.cap * 7 / 10) < a.margin + 1) VNM_TRY(table_grow(h, h->g.cap * 4, s));
-        VNM_HIP(hipMemsetAsync(h->g.ctl, 0, 16, s));  // [1] overflow flag; [2] fill persists
-        a.g = h->g;
-        a.fill_limit = (int64_t)(h->g.cap * 7 / 10);
-        {
-        if (round == 0)
-            route_note(a.ent ? "scan:spilled_entries" : (hot_scan ? (hot && a.nseg > 0 ? "scan:hot_segments" : (hot ? "scan:hot" : (hot_vnull ? "scan:hot_nullable_value" : (hot_two ? "scan:hot_two_columns" : "scan:hot_generic"))))
-                                                                   : (hotn ? "scan:hotn" : (h->single ? "scan:lds_generic" : "scan:wide_keys"))),
-                       "%lld rows, hint %lld (<= %lld or no partition rule applied), %d words per group, %d LDS slots", (long long)scan_n, (long long)h->hint, (long long)part_min, h->plan.n_words, a.lds_slots);
-        KernelTimer timer("agg_scan", s);
-        if (hot_scan) {
-            size_t lds_bytes = (size_t)(S + 2) * 8 * (1 + h->plan.n_words);
-#define VNM_HOT(P, V, HV, SI)                                                                                  \
-    do {                                                                                                       \
-        VNM_HIP(hipFuncSetAttribute((const void*)agg_hot_kernel<P, V, HV, SI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)); \
-        agg_hot_kernel<P, V, HV, SI><<<grid, AGG_BLOCK, lds_bytes, s>>>(a);                                    \
-    } while (0)
-            if (a.ent) {  // spilled entries of the partitioned path
-                if (hot) {
-                    VNM_HIP(hipFuncSetAttribute((const void*)agg_hot_kernel<false, false, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                    agg_hot_kernel<false, false, true, true, true><<<grid, AGG_BLOCK, lds_bytes, s>>>(a);
-                } else {
-                    VNM_HIP(hipFuncSetAttribute((const void*)agg_hot_kernel<false, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                    agg_hot_kernel<false, false, true, false, true><<<grid, AGG_BLOCK, lds_bytes, s>>>(a);
-                }
-            } else if (hot && a.nseg > 0) {  // ... over the waiting batches of a stream
-#define VNM_HOTS(P, V)                                                                                          \
-    do {                                                                                                       \
-        VNM_HIP(hipFuncSetAttribute((const void*)agg_hot_seg_kernel<P, V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)); \
-        agg_hot_seg_kernel<P, V><<<grid, AGG_BLOCK, lds_bytes, s>>>(a);                                         \
-    } while (0)
-                if (!h->pred_set) VNM_HOTS(false, false);
-                else if (a.hot_pred_is_v) VNM_HOTS(true, true);
-                else VNM_HOTS(true, false);
-#undef VNM_HOTS
-            } else if (hot) {  // the north-star shape
-                if (!h->pred_set) VNM_HOT(false, false, true, true);
-                else if (a.hot_pred_is_v) VNM_HOT(true, true, true, true);
-                else VNM_HOT(true, false, true, true);
-            } else if (hot_vnull) {
-#define VNM_HOTN(P, V)                                                                                          \
-    do {                                                                                                       \
-        VNM_HIP(hipFuncSetAttribute((const void*)agg_hot_kernel<P, V, true, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)); \
-        agg_hot_kernel<P, V, true, false, false, false, true><<<grid, AGG_BLOCK, lds_bytes, s>>>(a);           \
-    } while (0)
-                if (!h->pred_set || scan_no_pred) VNM_HOTN(false, false);
-                else if (a.hot_pred_is_v) VNM_HOTN(true, true);
-                else VNM_HOTN(true, false);
-#undef VNM_HOTN
-            } else if (hot_two && hot_scan) {
-#define VNM_HOT2(P, V)                                                                                          \
-    do {                                                                                                       \
-        VNM_HIP(hipFuncSetAttribute((const void*)agg_hot_kernel<P, V, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)); \
-        agg_hot_kernel<P, V, true, false, false, true><<<grid, AGG_BLOCK, lds_bytes, s>>>(a);                  \
-    } while (0)
-                if (!h->pred_set) VNM_HOT2(false, false);
-                else if (a.hot_pred_is_v) VNM_HOT2(true, true);
-                else VNM_HOT2(true, false);
-#undef VNM_HOT2
-            } else if (!a.hot_has_val) { if (h->pred_set) VNM_HOT(true, false, false, false); else VNM_HOT(false, false, false, false); }
-            else if (!h->pred_set) VNM_HOT(false, false, true, false);
-            else if (a.hot_pred_is_v) VNM_HOT(true, true, true, false);
-            else VNM_HOT(true, false, true, false);
-#undef VNM_HOT
-        } else if (hotn) {
-            size_t lds_bytes = (size_t)(a.lds_slots + 2) * 8 * (1 + h->plan.n_words);
-#define VNM_HN2(NC_, P_, PL_)                                                                                    \
-    do {                                                                                                        \
-        VNM_HIP(hipFuncSetAttribute((const void*)agg_hotn_kernel<NC_, P_, PL_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)); \
-        agg_hotn_kernel<NC_, P_, PL_><<<grid, AGG_BLOCK, lds_bytes, s>>>(a);                                    \
-    } while (0)
-#define VNM_HN(NC_)                                                                                              \
-    do {                                                                                                        \
-        const bool plain_ = !a.hn_any_int && !a.hn_any_mm;                                                      \
-        if (h->pred_set) { if (plain_) VNM_HN2(NC_, true, true); else VNM_HN2(NC_, true, false); }              \
-        else { if (plain_) VNM_HN2(NC_, false, true); else VNM_HN2(NC_, false, false); }                        \
-    } while (0)
-            switch (h->plan.n_cols) {
-                case 3: VNM_HN(3); break;
-                case 4: VNM_HN(4); break;
-                case 5: VNM_HN(5); break;
-                default: VNM_HN(6); break;
-            }
-#undef VNM_HN
-#undef VNM_HN2
-        } else if (h->single) {
-            size_t lds_bytes = (size_t)(a.lds_slots + 2) * 8 * (1 + h->plan.n_words);
-            VNM_HIP(hipFuncSetAttribute((const void*)agg_lds_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            agg_lds_kernel<1024><<<grid, 1024, lds_bytes, s>>>(a);
-        } else {
-            agg_wide_kernel<<<grid, 256, 0, s>>>(a);
-        }
-        }
-        VNM_HIP(hipGetLastError());
-        unsigned long long ctl[4];
-        VNM_HIP(hipMemcpyAsync(ctl, h->g.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
-        VNM_HIP(hipStreamSynchronize(s));
-        if (ctl[1] == 2) return set_error("aggregate: HBM hash table overflow (internal error)");
-        // a hint below the partitioning threshold with far more actual groups ran this scan into flush storms (77 ms per
-        // 1e9 rows at G = 1e7): the table's fill is the lesson for the batches that follow (checking small hints up
-        // front would cost every correctly hinted query ~0.3 ms)
-        if (h->single && nrows >= (1 << 22) && (int64_t)ctl[2] > 2 * 2400 && (int64_t)ctl[2] > h->hint) h->hint = (int64_t)(ctl[2] + ctl[2] / 4);
-        if (!ctl[1]) break;  // no block ran out of room: every tile was processed
-        // grow (x4, or to the projected final size) and relaunch; blocks resume from progress[]
-        uint64_t new_cap = h->g.cap * 4;
-        if (h->hint <= 0 && round >= 1) new_cap = h->g.cap * 16;
-        VNM_TRY(table_grow(h, new_cap, s));
-    }
-    h->rows_seen += nrows;
-    return 0;
-}
-
-#undef span_fits
 // The waiting batches of an asynchronous stream (vnm_agg_set_async) -> the device: as the segments of ONE logical batch where the
 // path's kernels take segments (the dense-key path's ring scatter, the hot-shape LDS scan), one by one otherwise.
 static int flush_queue(vnm_agg* h, void* stream) {
@@ -1926,33 +1158,32 @@ static bool queueable(const vnm_agg* h, int64_t nrows, const vnm_dcol* keys, con
     *multi = false;
     if (!h->single || h->plan.n_keys != 1 || h->plan.n_cols < 1 || h->inner || h->tuple_mode || h->expr_col >= 0) return false;
     if (nrows <= 0 || nrows >= (1LL << 30)) return false;
-    auto plain8 = [](const vnm_dcol& c) { return type_width(c.type) == 8 && !c.validity && (c.offset & 1) == 0 && ((uintptr_t)c.values & 15) == 0; };
     if (h->plan.n_cols > 1) {
         // SEVERAL plain 8-byte input columns over a plain int64 / uint64 key (round 4): the batches wait so that the path is chosen from
         // the stream's total row count (a 2^24-row batch alone is too short for a 2^27-code range: three columns, G = 1e8, 30 batches:
         // 315 ms through the hash partitions); when they go to the device the program is cut into parts (next_parts), which record
         // the batches in turn and launch once each -- or they go one by one, as before, where no part rule applies
-        if (h->rank_aligned || !plain8(keys[0]) || keys[0].type != h->plan.key_types[0] || (keys[0].type != VNM_I64 && keys[0].type != VNM_U64)) return false;
+        if (h->rank_aligned || !plain8_aligned(keys[0]) || keys[0].type != h->plan.key_types[0] || (keys[0].type != VNM_I64 && keys[0].type != VNM_U64)) return false;
         for (int i = 0; i < h->n_funcs; i++)
-            if (h->func_col[i] >= 0 && (!plain8(inputs[i]) || (inputs[i].type != VNM_F64 && inputs[i].type != VNM_I64 && inputs[i].type != VNM_U64))) return false;
-        if (h->pred_set && (!pred || !plain8(*pred) || pred->type != VNM_F64)) return false;
+            if (h->func_col[i] >= 0 && (!plain8_aligned(inputs[i]) || !is_8byte_numeric(inputs[i].type))) return false;
+        if (h->pred_set && (!pred || !plain8_aligned(*pred) || pred->type != VNM_F64)) return false;
         *pred_is_v = false;
         *multi = true;
         return true;
     }
     if (!h->parts.empty()) return false;
     const vnm_dcol& col = inputs[h->col_first_func[0]];
-    if (!plain8(keys[0]) || keys[0].type != h->plan.key_types[0] || !plain8(col) || col.type != VNM_F64) return false;
+    if (!plain8_aligned(keys[0]) || keys[0].type != h->plan.key_types[0] || !plain8_aligned(col) || col.type != VNM_F64) return false;
     for (int o = 0; o < h->plan.n_ops; o++) {
         const int k = h->plan.ops[o].kind;
         if (k != A_COUNT_ROWS && k != A_COUNT_VALID && k != A_SUM_F64) return false;
     }
     for (int i = 0; i < h->n_funcs; i++)   // every function reads that one column (COUNT(*): none)
-        if (h->func_col[i] >= 0 && (inputs[i].values != col.values || inputs[i].offset != col.offset || inputs[i].validity)) return false;
+        if (h->func_col[i] >= 0 && (!same_values(inputs[i], col) || inputs[i].validity)) return false;
     *pred_is_v = false;
     if (h->pred_set) {
-        if (!pred || !plain8(*pred) || pred->type != VNM_F64) return false;
-        *pred_is_v = pred->values == col.values && pred->offset == col.offset;
+        if (!pred || !plain8_aligned(*pred) || pred->type != VNM_F64) return false;
+        *pred_is_v = same_values(*pred, col);
     }
     return true;
 }

@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -103,6 +104,11 @@ struct KernelTimer {
 };
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// Route switches (the VNM_* variables of DESIGN.md section 4.10): is the variable set / not set?  Read on every call -- the tests
+// flip them between cases of one process -- so never cache the answer.
+inline bool env_on(const char* name) { return getenv(name) != nullptr; }
+inline bool env_off(const char* name) { return getenv(name) == nullptr; }
 
 // Which ROUTE an operator call took and why (round 5): every place that commits a batch to a path of DESIGN.md section 4 leaves a note
 // -- a route name (the vocabulary of DESIGN.md) and the reason in numbers.  The library counts the notes per route
