@@ -1,6 +1,127 @@
 // Host side of the partitioned routes: hash partitions, the dense-key path (one / two levels, scan of small ranges, two values), deferred final passes.
 // Part of the aggregate operator; included by vnm_agg.hip (one translation unit: the kernels and the host code share file-local helpers).
 namespace {
+// ---- typed launches ----------------------------------------------------------------------------------------------
+// Run-time values as template arguments: `f` is a generic lambda that gets a std::integral_constant and names the kernel ONCE.
+// Only the values a caller can pass are instantiated (a ladder must not add kernels to the code object).
+template <class F>
+int pick_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+// an int in LO .. HI (below LO: LO, above HI: HI) -- table bits 7 .. 13, 8-byte words of a wide entry 1 .. 7
+template <int LO, int HI, class F>
+int pick_int(int v, F&& f) {
+    if constexpr (LO < HI) { if (v > LO) return pick_int<LO + 1, HI>(v, f); }
+    return f(std::integral_constant<int, LO>{});
+}
+// output mode of a dense final pass: DF_COLS, DF_TABLE, anything else DF_RUN
+template <class F>
+int pick_out(int out, F&& f) {
+    if (out == DF_COLS) return f(std::integral_constant<int, DF_COLS>{});
+    if (out == DF_TABLE) return f(std::integral_constant<int, DF_TABLE>{});
+    return f(std::integral_constant<int, DF_RUN>{});
+}
+// A final-pass kernel as ONE resident set of workgroups (they loop over their work items): at most `occ_max` per CU of what the
+// occupancy of `occ_kernel` allows.  `lds` bytes of dynamic LDS (more than the default limit: the attribute first).
+template <class K, class Q, class... A>
+int launch_resident_as(K kernel, Q occ_kernel, int64_t work, int block, size_t lds, int occ_max, hipStream_t s, const A&... args) {
+    if (lds) VNM_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)occ_kernel, block, lds) != hipSuccess || occ < 1) occ = 1;
+    const int grid = (int)std::min<int64_t>(work, (int64_t)device_info().num_cus * std::min(occ, occ_max));
+    kernel<<<grid, block, lds, s>>>(args...);
+    return 0;
+}
+template <class K, class... A>
+int launch_resident(K kernel, int64_t work, int block, size_t lds, int occ_max, hipStream_t s, const A&... args) {
+    return launch_resident_as(kernel, kernel, work, block, lds, occ_max, s, args...);
+}
+// a kernel with `lds` bytes of dynamic LDS (more than the default limit: the attribute first)
+template <class K, class... A>
+int launch_dyn(K kernel, int grid, int block, size_t lds, hipStream_t s, const A&... args) {
+    VNM_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kernel<<<grid, block, lds, s>>>(args...);
+    return 0;
+}
+// The final pass of the hash partitions: one resident set of workgroups (they loop over the partitions) -- a grid larger than what
+// fits leaves a second, partly filled round.  Four workgroups per CU where the occupancy is not to be had.
+template <class K>
+int launch_part_final(K kernel, int64_t work, size_t lds, hipStream_t s, const PartAggArgs& pa) {
+    const int cus = device_info().num_cus;
+    if (lds) VNM_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int grid = (int)std::min<int64_t>(work, (int64_t)cus * 4), occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)kernel, PA_BLOCK, lds) == hipSuccess && occ > 0)
+        grid = (int)std::min<int64_t>(work, (int64_t)cus * std::min(occ, (int)env_i64("VNM_PA_OCC", 8)));
+    kernel<<<grid, PA_BLOCK, lds, s>>>(pa);
+    return 0;
+}
+
+// ---- the ring scatter of the dense path (dring_scatter_kernel) ----------------------------------------------------------
+// One launch: the grid, the entries per ring, the sub-tile (pairs of rows per lane), and what picks the kernel at run time.
+// limit: VNM_DENSE_RING_LIMIT, spill what two insert / flush rounds of a sub-tile leave pending (skew); seg / kn: pass 1 over the
+// waiting batches of a stream (DPartArgs::segs) / over a nullable key
+struct RingLaunch { int grid, cap, pairs; bool limit, seg, kn; hipStream_t s; };
+// entries per flushed block: 32-bit words leave in blocks of 32
+constexpr int ring_flush_block(bool w32) { return w32 ? 32 : DR_FB; }
+// an even spread of a sub-tile's entries (every row surviving) fits ONE insert / flush round of the rings
+inline bool ring_one_round(int pairs, int nparts, int cap, bool w32) { return 2 * pairs * 1024 <= nparts * (cap - ring_flush_block(w32)); }
+// sub-tile = the largest of 4 / 2 / 1 pairs of rows per lane (at most `want`) whose entries, evenly spread, fit one round of the
+// rings: the round limit then applies (64 partitions: 2 pairs, 32: 1 pair).  A predicate column of its own (pv): three loads per
+// pair of rows, at most two pairs per lane and sub-tile fit the registers.
+inline int ring_sub_tile_pairs(int want, bool pv, bool limit, int nparts, int cap, bool w32) {
+    int pr = want >= 4 && !pv ? 4 : (want >= 2 ? 2 : 1);
+    while (limit && pr > 1 && !ring_one_round(pr, nparts, cap, w32)) pr >>= 1;
+    return pr;
+}
+// Ring capacity = what fits 128 KB of LDS, whole 16-entry blocks only; fan-outs that leave less than two blocks per ring (0) keep
+// the tile-sorting kernel.
+inline int ring_cap_for(int np, size_t esize) {
+    int cap = (int)((size_t)(env_i64("VNM_DENSE_RING_LDS", 128) * 1024) / ((size_t)np * esize) / DR_FB) * DR_FB;
+    // at most 80 entries per ring -- more where few partitions share the LDS, so that an even spread of a four-pair sub-tile
+    // (8192 entries) still fits one round: 32 partitions 272, 64 partitions 144
+    cap = std::min(cap, (int)env_i64("VNM_DENSE_RING_CAP", std::max(80, ((8192 / np + DR_FB + DR_FB - 1) / DR_FB) * DR_FB)));
+    // few partitions: long runs anyway (and 8192 entries per sub-tile on a handful of ring cursors: G = 1e4, four partitions,
+    // pass 1 8.6 ms against 5.0 with the tile-sorting kernel)
+    if (np < env_i64("VNM_DENSE_RING_MIN_NP", 32)) return 0;
+    return cap >= 2 * DR_FB ? cap : 0;
+}
+// (32-bit words: blocks of 32, rings of at least two blocks, at most 256 entries)
+inline int ring_cap_w32(int np) {
+    const int cap = std::min(256, (int)((size_t)128 * 1024 / ((size_t)np * 4) / 32) * 32);
+    return cap >= 64 ? cap : 0;
+}
+
+// the attribute and the launch of one kernel of the family (1024 threads; the rings take nparts * cap entries of LDS)
+template <bool FR, typename CT, bool HV, int PR, bool PV, bool VN, int MAXR, bool SEG, bool KN, bool V2, bool FX, bool W32>
+int launch_ring(int grid, const DPartArgs& d, int cap, hipStream_t s) {
+    constexpr size_t esize = FX ? (W32 ? 4 : 8) : (HV ? (V2 ? 16 : 8) : 0) + sizeof(CT);
+    const size_t lds = (((size_t)d.nparts * cap * esize) + 15) & ~(size_t)15;
+    return launch_dyn(dring_scatter_kernel<FR, CT, HV, 1024, PR, PV, VN, MAXR, SEG, KN, V2, FX, W32>, grid, 1024, lds, s, d, cap);
+}
+// ... with PR pairs per lane.  MAXR = 2 (round limit: two insert / flush rounds per sub-tile) where one round takes an even spread;
+// the SEG and KN kernels exist for pass 1 over a plain value column only (same shapes otherwise).
+template <bool FR, typename CT, bool HV, bool PV, bool VN, bool FX, bool W32, int PR>
+int ring_scatter_pairs(const RingLaunch& r, const DPartArgs& d) {
+    auto go = [&](auto lim, auto seg, auto kn) {
+        return launch_ring<FR, CT, HV, PR, PV, VN, decltype(lim)::value ? 2 : 0, decltype(seg)::value, decltype(kn)::value, false, FX, W32>(r.grid, d, r.cap, r.s);
+    };
+    return pick_bool(r.limit && ring_one_round(PR, d.nparts, r.cap, W32), [&](auto lim) {
+        if constexpr (FR && HV && !VN) {
+            if (r.kn) return go(lim, std::false_type{}, std::true_type{});
+            if (r.seg) return go(lim, std::true_type{}, std::false_type{});
+        }
+        return go(lim, std::false_type{}, std::false_type{});
+    });
+}
+// FR: pass 1 (from rows); CT: the code remainders; HV: entries carry a value; PV: a predicate column of its own; VN: a nullable
+// value column; FX / W32: fixed-point entry words / of 32 bits.  r.pairs comes from ring_sub_tile_pairs (never 4 with PV).
+template <bool FR, typename CT, bool HV, bool PV, bool VN, bool FX = false, bool W32 = false>
+int ring_scatter(const RingLaunch& r, const DPartArgs& d) {
+    if constexpr (!PV) {
+        if (r.pairs == 4) return ring_scatter_pairs<FR, CT, HV, PV, VN, FX, W32, 4>(r, d);
+    }
+    if (r.pairs >= 2) return ring_scatter_pairs<FR, CT, HV, PV, VN, FX, W32, 2>(r, d);
+    return ring_scatter_pairs<FR, CT, HV, PV, VN, FX, W32, 1>(r, d);
+}
+
 
 // returns 0 = done (run stored), 2 = not applicable / overflowed (caller uses the general path), 1 = error
 // spill_out / n_spill_out (optional): entries that did not fit their partition region (heavy keys); the caller
@@ -81,33 +202,18 @@ int partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream
     }
     // (key, value) entries through LDS rings (pring_scatter_kernel) where a level has at most 256 partitions: rings of >= 32 entries, 256-byte blocks
     auto pring_cap = [&](int np) -> int { int cap = (int)((size_t)128 * 1024 / 16 / (size_t)np); cap = std::min(cap, 64) / 16 * 16; return cap; };   // (512 partitions: 16 entries, blocks of 8 -- VNM_PRING8)
+    auto pring_lds = [&](int np) -> size_t { return (size_t)np * pring_cap(np) * 16; };
     const bool ring_ok = !wide && !a.has_expr && !h->pring_off && env_i64("VNM_PART_RING", 7) != 0 && (a.keys[0].offset & 1) == 0 && (!h->plan.n_cols || (a.cols[0].offset & 1) == 0) &&
                          (!h->pred_set || a.hot_pred_is_v || (a.pred.offset & 1) == 0) && h->plan.n_cols > 0;
     // (... and at least 128: a sub-tile's 4096 entries must fit the rings' free room in one or two rounds -- 8 rings of 64 entries took 8)
     const bool ring1 = ring_ok && np1 <= 256 && np1 >= 128 && (env_i64("VNM_PART_RING", 7) & 1);
     const bool ring2 = ring_ok && levels == 2 && np2 <= 256 && np2 >= 128 && (env_i64("VNM_PART_RING", 7) & 2);
     const bool ring2_512 = ring_ok && levels == 2 && np2 == 512 && (env_i64("VNM_PART_RING", 7) & 4);   // (16-entry rings, 128-byte blocks, one pair per lane)
-#define VNM_PRING(FR_, PV_, GRID_, ARGS_, NP_)                                                                          \
-    do {                                                                                                               \
-        const int cap_ = pring_cap(NP_);                                                                               \
-        const size_t lds_ = (size_t)(NP_) * cap_ * 16;                                                                 \
-        VNM_HIP(hipFuncSetAttribute((const void*)pring_scatter_kernel<FR_, 2, 16, PV_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-        pring_scatter_kernel<FR_, 2, 16, PV_><<<GRID_, PT_BLOCK, lds_, s>>>(ARGS_, cap_);                               \
-    } while (0)
     {
         KernelTimer timer("agg_part_scatter1", s);
-        if (ring1) { if (p1.has_pred && !p1.pred_is_v) VNM_PRING(true, true, grid1, p1, np1); else VNM_PRING(true, false, grid1, p1, np1); }
+        if (ring1) VNM_TRY(pick_bool(p1.has_pred && !p1.pred_is_v, [&](auto pv) { return launch_dyn(pring_scatter_kernel<true, 2, 16, decltype(pv)::value>, grid1, PT_BLOCK, pring_lds(np1), s, p1, pring_cap(np1)); }));
         else if (!wide) part_scatter_kernel<true><<<grid1, PT_BLOCK, 0, s>>>(p1);
-        else {
-            const size_t lds = (size_t)pw_tile(E) * ebytes;
-#define VNM_PSW(FR, E_, IT_, GRID, ARGS)                                                                             \
-    do {                                                                                                             \
-        VNM_HIP(hipFuncSetAttribute((const void*)part_scatter_wide_kernel<FR, E_, IT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        part_scatter_wide_kernel<FR, E_, IT_><<<GRID, PT_BLOCK, lds, s>>>(ARGS);                                     \
-    } while (0)
-            if (E == 1) VNM_PSW(true, 1, 8, grid1, p1); else if (E == 2) VNM_PSW(true, 2, 8, grid1, p1); else if (E == 3) VNM_PSW(true, 3, 4, grid1, p1); else if (E == 4) VNM_PSW(true, 4, 4, grid1, p1);
-            else if (E == 5) VNM_PSW(true, 5, 2, grid1, p1); else if (E == 6) VNM_PSW(true, 6, 2, grid1, p1); else VNM_PSW(true, 7, 2, grid1, p1);
-        }
+        else VNM_TRY((pick_int<1, 7>(E, [&](auto e) { return launch_dyn(part_scatter_wide_kernel<true, decltype(e)::value, pw_items(decltype(e)::value)>, grid1, PT_BLOCK, (size_t)pw_tile(E) * ebytes, s, p1); })));
     }
     VNM_HIP(hipGetLastError());
     // A region overflowed (skewed keys, or more rows per partition than the hint implied): stop here.  Carrying on
@@ -153,24 +259,16 @@ int partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream
         p2.has_vmask = a.part_vmask;
         {
             KernelTimer timer("agg_part_scatter2", s);
-            if (ring2) VNM_PRING(false, false, np1 * p2.in_split, p2, np2);
-            else if (ring2_512) {
-                const size_t lds_ = (size_t)512 * 16 * 16;
-                VNM_HIP(hipFuncSetAttribute((const void*)pring_scatter_kernel<false, 1, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_));
-                pring_scatter_kernel<false, 1, 8, false><<<np1 * p2.in_split, PT_BLOCK, lds_, s>>>(p2, 16);
-            }
-            else if (!wide) part_scatter_kernel<false><<<np1 * p2.in_split, PT_BLOCK, 0, s>>>(p2);
-            else {
-                const bool big2 = E <= 2 && np2 >= 128;
-                const size_t lds = (size_t)PT_BLOCK * (big2 ? 8 : (E <= 4 ? 4 : 2)) * ebytes;
-                const int g2 = np1 * p2.in_split;
-                if (E == 1) { if (big2) VNM_PSW(false, 1, 8, g2, p2); else VNM_PSW(false, 1, 4, g2, p2); }
-                else if (E == 2) { if (big2) VNM_PSW(false, 2, 8, g2, p2); else VNM_PSW(false, 2, 4, g2, p2); }
-                else if (E == 3) VNM_PSW(false, 3, 4, g2, p2); else if (E == 4) VNM_PSW(false, 4, 4, g2, p2);
-                else if (E == 5) VNM_PSW(false, 5, 2, g2, p2); else if (E == 6) VNM_PSW(false, 6, 2, g2, p2); else VNM_PSW(false, 7, 2, g2, p2);
-            }
+            const int g2 = np1 * p2.in_split;
+            if (ring2) VNM_TRY(launch_dyn(pring_scatter_kernel<false, 2, 16, false>, g2, PT_BLOCK, pring_lds(np2), s, p2, pring_cap(np2)));
+            else if (ring2_512) VNM_TRY(launch_dyn(pring_scatter_kernel<false, 1, 8, false>, g2, PT_BLOCK, (size_t)512 * 16 * 16, s, p2, 16));
+            else if (!wide) part_scatter_kernel<false><<<g2, PT_BLOCK, 0, s>>>(p2);
+            else VNM_TRY((pick_int<1, 7>(E, [&](auto e) {   // (one- and two-word entries: 8 items per lane only where the level has many sub-partitions)
+                constexpr int EW = decltype(e)::value;
+                if constexpr (EW <= 2) { if (np2 < 128) return launch_dyn(part_scatter_wide_kernel<false, EW, 4>, g2, PT_BLOCK, (size_t)PT_BLOCK * 4 * ebytes, s, p2); }
+                return launch_dyn(part_scatter_wide_kernel<false, EW, pw_items(EW)>, g2, PT_BLOCK, (size_t)PT_BLOCK * pw_items(EW) * ebytes, s, p2);
+            })));
         }
-#undef VNM_PSW
         VNM_HIP(hipGetLastError());
         {
             int ov = overflowed();
@@ -182,7 +280,6 @@ int partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream
             }
             if (ov) return ov < 0 ? set_error("aggregate: partition pass failed") : 2;
         }
-#undef VNM_PRING
         fin_e = e2; fin_c = c2; fin_cap = cap2; nfinal = (int64_t)np1 * np2; fin_regions = p2.in_split;
     }
 
@@ -229,14 +326,6 @@ int partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream
     pa.dkey = rk; pa.dacc = ra; pa.dstride = dstride; pa.flags = flags;
     {
         KernelTimer timer("agg_part_final", s);
-        // one resident set of workgroups (they loop over the partitions): a grid larger than what fits leaves a
-        // second, partly filled round
-        int g3 = (int)std::min<int64_t>(nfinal * splits, (int64_t)cus * 4);
-        auto fit_grid = [&](const void* fn, size_t lds) {
-            int occ = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, PA_BLOCK, lds) == hipSuccess && occ > 0)
-                g3 = (int)std::min<int64_t>(nfinal * splits, (int64_t)cus * std::min(occ, (int)env_i64("VNM_PA_OCC", 8)));
-        };
         if (a.part_generic) {
             pa.n_ops = h->plan.n_ops;
             pa.vtype = a.part_vtype;
@@ -259,19 +348,10 @@ int partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream
                 if (c > 5 || op.kind < 0 || op.kind > A_MAX || op.word >= 63 || ((pa.wpack[c] >> (6 * op.kind)) & 63ULL) != 63) { pa.use_table = 0; break; }
                 pa.wpack[c] = (pa.wpack[c] & ~(63ULL << (6 * op.kind))) | ((unsigned long long)op.word << (6 * op.kind));
             }
-#define VNM_PAG(E_, T_)                                                                                              \
-    do {                                                                                                             \
-        VNM_HIP(hipFuncSetAttribute((const void*)part_agg_generic_kernel<E_, T_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)); \
-        fit_grid((const void*)part_agg_generic_kernel<E_, T_>, lds_bytes);                                           \
-        part_agg_generic_kernel<E_, T_><<<g3, PA_BLOCK, lds_bytes, s>>>(pa);                                         \
-    } while (0)
-            if (pa.use_table) { if (E == 1) VNM_PAG(1, true); else if (E == 2) VNM_PAG(2, true); else if (E == 3) VNM_PAG(3, true); else if (E == 4) VNM_PAG(4, true); else if (E == 5) VNM_PAG(5, true); else if (E == 6) VNM_PAG(6, true); else VNM_PAG(7, true); }
-            else { if (E == 1) VNM_PAG(1, false); else if (E == 2) VNM_PAG(2, false); else if (E == 3) VNM_PAG(3, false); else if (E == 4) VNM_PAG(4, false); else if (E == 5) VNM_PAG(5, false); else if (E == 6) VNM_PAG(6, false); else VNM_PAG(7, false); }
-#undef VNM_PAG
-        } else {
-            fit_grid((const void*)part_agg_kernel, 0);
-            part_agg_kernel<<<g3, PA_BLOCK, 0, s>>>(pa);
-        }
+            VNM_TRY((pick_int<1, 7>(E, [&](auto e) {
+                return pick_bool(pa.use_table != 0, [&](auto t) { return launch_part_final(part_agg_generic_kernel<decltype(e)::value, decltype(t)::value>, nfinal * splits, lds_bytes, s, pa); });
+            })));
+        } else VNM_TRY(launch_part_final(part_agg_kernel, nfinal * splits, 0, s, pa));
     }
     VNM_HIP(hipGetLastError());
     unsigned long long fl[3];
@@ -554,83 +634,53 @@ int dense_scan_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_
 }
 
 // The plain (one workgroup per partition) final pass of the dense path in one of its output modes.
+enum { DFF_LEAN, DFF_FIXED, DFF_LO64, DFF_EXACT, DFF_PLAIN };   // its forms; which (TB, OUT) a form has kernels for is the `if constexpr` in front of it
+template <int TB, int OUT>
+int launch_dense_final_as(int form, const DFinalArgs& df, const DSet* only_set, hipStream_t s) {
+    constexpr int blk = TB >= 13 ? 1024 : (TB == 12 ? VNM_DF12_BLOCK : 512);
+    constexpr int OUT_RC = OUT == DF_COLS ? DF_COLS : DF_RUN;   // the forms that have no DF_TABLE kernel
+    const int occ_max = (int)env_i64("VNM_PA_OCC", 8);
+    switch (form) {
+    case DFF_LEAN: {   // (the grid goes by the occupancy of the form without narrow words or side table, whichever runs)
+        constexpr int lean_blk = TB >= 13 ? 1024 : 512;
+        return pick_bool(df.fx_w32 != 0, [&](auto w32) {
+            if constexpr (OUT != DF_TABLE) {
+                if (df.has_side) return launch_resident_as(dfx_final_kernel<TB, OUT, decltype(w32)::value, true>, dfx_final_kernel<TB, OUT>, df.nfinal, lean_blk, 0, occ_max, s, df, *only_set);
+            }
+            return launch_resident_as(dfx_final_kernel<TB, OUT, decltype(w32)::value>, dfx_final_kernel<TB, OUT>, df.nfinal, lean_blk, 0, occ_max, s, df, *only_set);
+        });
+    }
+    case DFF_FIXED:   // fixed-point entry words: integer sums
+        return launch_resident(dpart_final_kernel<uint16_t, TB, false, OUT, float, true, true>, df.nfinal, blk, 0, occ_max, s, df);
+    case DFF_LO64:    // compensation terms beyond the float range (|sum| > ~1e54): 64-bit terms, tables of at most 2^12 slots
+        if constexpr (TB >= 9 && TB <= 12) return launch_resident(dpart_final_kernel<uint16_t, TB, false, OUT_RC, double>, df.nfinal, blk, 0, occ_max, s, df);
+        break;
+    case DFF_EXACT:   // every add proved exact: {sum, count} slots, non-returning atomics
+        if constexpr (TB >= 12) return launch_resident(dpart_final_kernel<uint16_t, TB, false, OUT_RC, float, true>, df.nfinal, blk, 0, occ_max, s, df);
+        break;
+    default:
+        if constexpr (TB >= 9) return launch_resident(dpart_final_kernel<uint16_t, TB, false, OUT, float>, df.nfinal, blk, 0, occ_max, s, df);
+        break;
+    }
+    return set_error("aggregate: no dense final pass of form %d for tables of 2^%d slots (internal error)", form, TB);
+}
 int launch_dense_final(const DFinalArgs& df, int tb, int out, bool lo64, hipStream_t s, bool exact = false, const DSet* only_set = nullptr) {
-    const int cus = device_info().num_cus;
     KernelTimer timer("agg_part_final", s);
+    int form = DFF_PLAIN, tbk = tb;
     // fixed-point words of ONE batch in large regions, no side table: the lean kernel (dfx_final_kernel)
     if (df.fx_q != 0.0 && only_set && !only_set->pad && only_set->regions > 0 && only_set->regions <= 512 && tb >= 7 && tb <= 13 &&
-        (!df.has_side || (out != DF_TABLE && env_i64("VNM_DFX_LEAN_SIDE", 1))) && env_i64("VNM_DFX_LEAN", 1)) {
-#define VNM_DFX(TB_, OUT_)                                                                                             \
-    do {                                                                                                              \
-        const int blk = TB_ >= 13 ? 1024 : 512;                                                                       \
-        int occ = 0;                                                                                                  \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)dfx_final_kernel<TB_, OUT_>, blk, 0) != hipSuccess || occ < 1) occ = 1; \
-        const int g3 = (int)std::min<int64_t>(df.nfinal, (int64_t)cus * std::min(occ, (int)env_i64("VNM_PA_OCC", 8))); \
-        if (df.has_side && OUT_ != DF_TABLE) {                                                                        \
-            if (df.fx_w32) dfx_final_kernel<TB_, OUT_ == DF_TABLE ? DF_RUN : OUT_, true, true><<<g3, blk, 0, s>>>(df, *only_set);   \
-            else dfx_final_kernel<TB_, OUT_ == DF_TABLE ? DF_RUN : OUT_, false, true><<<g3, blk, 0, s>>>(df, *only_set);            \
-        } else if (df.fx_w32) dfx_final_kernel<TB_, OUT_, true><<<g3, blk, 0, s>>>(df, *only_set);                    \
-        else dfx_final_kernel<TB_, OUT_><<<g3, blk, 0, s>>>(df, *only_set);                                           \
-    } while (0)
-#define VNM_DFX_O(TB_) do { if (out == DF_COLS) VNM_DFX(TB_, DF_COLS); else if (out == DF_TABLE) VNM_DFX(TB_, DF_TABLE); else VNM_DFX(TB_, DF_RUN); } while (0)
-        if (tb == 7) VNM_DFX_O(7); else if (tb == 8) VNM_DFX_O(8); else if (tb == 9) VNM_DFX_O(9); else if (tb == 10) VNM_DFX_O(10); else if (tb == 11) VNM_DFX_O(11); else if (tb == 12) VNM_DFX_O(12); else VNM_DFX_O(13);
-#undef VNM_DFX_O
-#undef VNM_DFX
-        VNM_HIP(hipGetLastError());
-        return 0;
-    }
-#define VNM_DFIN(TB_, OUT_, LOT_)                                                                                      \
-    do {                                                                                                              \
-        const int blk = TB_ >= 13 ? 1024 : (TB_ == 12 ? VNM_DF12_BLOCK : 512);                                       \
-        int occ = 0;                                                                                                  \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)dpart_final_kernel<uint16_t, TB_, false, OUT_, LOT_>, blk, 0) != hipSuccess || occ < 1) occ = 1; \
-        const int g3 = (int)std::min<int64_t>(df.nfinal, (int64_t)cus * std::min(occ, (int)env_i64("VNM_PA_OCC", 8))); \
-        dpart_final_kernel<uint16_t, TB_, false, OUT_, LOT_><<<g3, blk, 0, s>>>(df);                                  \
-    } while (0)
-#define VNM_DFIN_O(TB_)                                                                                                \
-    do {                                                                                                              \
-        if (out == DF_COLS) VNM_DFIN(TB_, DF_COLS, float); else if (out == DF_TABLE) VNM_DFIN(TB_, DF_TABLE, float);   \
-        else VNM_DFIN(TB_, DF_RUN, float);                                                                            \
-    } while (0)
-    if (df.fx_q == 0.0 && lo64) {   // compensation terms beyond the float range (|sum| > ~1e54): 64-bit terms, tables of at most 2^12 slots
-        if (tb == 9) { if (out == DF_COLS) VNM_DFIN(9, DF_COLS, double); else VNM_DFIN(9, DF_RUN, double); }
-        else if (tb == 10) { if (out == DF_COLS) VNM_DFIN(10, DF_COLS, double); else VNM_DFIN(10, DF_RUN, double); }
-        else if (tb == 11) { if (out == DF_COLS) VNM_DFIN(11, DF_COLS, double); else VNM_DFIN(11, DF_RUN, double); }
-        else if (tb == 12) { if (out == DF_COLS) VNM_DFIN(12, DF_COLS, double); else VNM_DFIN(12, DF_RUN, double); }
-        else return set_error("aggregate: no 64-bit compensation variant for this table size (internal error)");
-    } else if (df.fx_q != 0.0) {   // fixed-point entry words: integer sums
-#define VNM_DFIN_F(TB_, OUT_)                                                                                          \
-    do {                                                                                                              \
-        const int blk = TB_ >= 13 ? 1024 : (TB_ == 12 ? VNM_DF12_BLOCK : 512);                                        \
-        int occ = 0;                                                                                                  \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)dpart_final_kernel<uint16_t, TB_, false, OUT_, float, true, true>, blk, 0) != hipSuccess || occ < 1) occ = 1; \
-        const int g3 = (int)std::min<int64_t>(df.nfinal, (int64_t)cus * std::min(occ, (int)env_i64("VNM_PA_OCC", 8))); \
-        dpart_final_kernel<uint16_t, TB_, false, OUT_, float, true, true><<<g3, blk, 0, s>>>(df);                     \
-    } while (0)
-        if (tb == 7) { if (out == DF_COLS) VNM_DFIN_F(7, DF_COLS); else if (out == DF_TABLE) VNM_DFIN_F(7, DF_TABLE); else VNM_DFIN_F(7, DF_RUN); }
-        else if (tb == 8) { if (out == DF_COLS) VNM_DFIN_F(8, DF_COLS); else if (out == DF_TABLE) VNM_DFIN_F(8, DF_TABLE); else VNM_DFIN_F(8, DF_RUN); }
-        else if (tb == 9) { if (out == DF_COLS) VNM_DFIN_F(9, DF_COLS); else if (out == DF_TABLE) VNM_DFIN_F(9, DF_TABLE); else VNM_DFIN_F(9, DF_RUN); }
-        else if (tb == 10) { if (out == DF_COLS) VNM_DFIN_F(10, DF_COLS); else if (out == DF_TABLE) VNM_DFIN_F(10, DF_TABLE); else VNM_DFIN_F(10, DF_RUN); }
-        else if (tb == 11) { if (out == DF_COLS) VNM_DFIN_F(11, DF_COLS); else if (out == DF_TABLE) VNM_DFIN_F(11, DF_TABLE); else VNM_DFIN_F(11, DF_RUN); }
-        else if (tb == 12) { if (out == DF_COLS) VNM_DFIN_F(12, DF_COLS); else if (out == DF_TABLE) VNM_DFIN_F(12, DF_TABLE); else VNM_DFIN_F(12, DF_RUN); }
-        else if (tb == 13) { if (out == DF_COLS) VNM_DFIN_F(13, DF_COLS); else if (out == DF_TABLE) VNM_DFIN_F(13, DF_TABLE); else VNM_DFIN_F(13, DF_RUN); }
-        else return set_error("aggregate: fixed-point entries with this table size (internal error)");
-#undef VNM_DFIN_F
-    } else if (exact && (tb == 12 || tb == 13) && out != DF_TABLE) {   // every add proved exact: {sum, count} slots, non-returning atomics
-#define VNM_DFIN_X(TB_, OUT_)                                                                                          \
-    do {                                                                                                              \
-        const int blk = TB_ >= 13 ? 1024 : VNM_DF12_BLOCK;                                                            \
-        int occ = 0;                                                                                                  \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)dpart_final_kernel<uint16_t, TB_, false, OUT_, float, true>, blk, 0) != hipSuccess || occ < 1) occ = 1; \
-        const int g3 = (int)std::min<int64_t>(df.nfinal, (int64_t)cus * std::min(occ, (int)env_i64("VNM_PA_OCC", 8))); \
-        dpart_final_kernel<uint16_t, TB_, false, OUT_, float, true><<<g3, blk, 0, s>>>(df);                           \
-    } while (0)
-        if (tb == 12) { if (out == DF_COLS) VNM_DFIN_X(12, DF_COLS); else VNM_DFIN_X(12, DF_RUN); }
-        else { if (out == DF_COLS) VNM_DFIN_X(13, DF_COLS); else VNM_DFIN_X(13, DF_RUN); }
-#undef VNM_DFIN_X
-    } else if (tb == 9) VNM_DFIN_O(9); else if (tb == 10) VNM_DFIN_O(10); else if (tb == 11) VNM_DFIN_O(11); else if (tb == 12) VNM_DFIN_O(12); else VNM_DFIN_O(13);
-#undef VNM_DFIN_O
-#undef VNM_DFIN
+        (!df.has_side || (out != DF_TABLE && env_i64("VNM_DFX_LEAN_SIDE", 1))) && env_i64("VNM_DFX_LEAN", 1)) form = DFF_LEAN;
+    else if (df.fx_q == 0.0 && lo64) {
+        if (tb < 9 || tb > 12) return set_error("aggregate: no 64-bit compensation variant for this table size (internal error)");
+        form = DFF_LO64;
+    } else if (df.fx_q != 0.0) {
+        if (tb < 7 || tb > 13) return set_error("aggregate: fixed-point entries with this table size (internal error)");
+        form = DFF_FIXED;
+    } else if (exact && (tb == 12 || tb == 13) && out != DF_TABLE) form = DFF_EXACT;
+    else if (tb < 9 || tb > 12) tbk = 13;
+    VNM_TRY((pick_int<7, 13>(tbk, [&](auto tbc) {
+        return pick_out(out, [&](auto outc) { return launch_dense_final_as<decltype(tbc)::value, decltype(outc)::value>(form, df, only_set, s); });
+    })));
     VNM_HIP(hipGetLastError());
     return 0;
 }
@@ -760,23 +810,45 @@ int complete_pending(vnm_agg* h, hipStream_t s, int out = DF_RUN, const DFinalAr
 }
 
 
-// returns 0 = done (run stored), 2 = not applicable / failed (caller continues with the hash-partitioned path), 1 = error
-// (nspill_out / n_nspill_out: keys of NULL-value rows that found no place -- nullable value column, generic programs only)
-int dense_partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_t s, ulonglong2** spill_out, int64_t* n_spill_out,
-                                bool generic = false, uint64_t** nspill_out = nullptr, int64_t* n_nspill_out = nullptr, bool vn_fold = false) {
-    const int cus = device_info().num_cus;
-    const DenseMap& mp = h->dmap;
-    DGenArgs g{};
-    if (generic && !dgen_program(h, a, &g)) return 2;
-    const bool has_val = generic ? g.has_val != 0 : true;
+// ---- the dense-key partitioned route, stage by stage (dense_partitioned_aggregate below is the driver) ---------------------
+// What one attempt does with a batch: the form of its entries and the whole geometry of the passes.  Filled by plan_dense_entries
+// and plan_dense_geometry, which make no HIP call and leave the handle alone; read-only afterwards.
+struct DensePlan {
+    bool generic, has_val;
+    bool vn, vn_lists;       // nullable value column; ... whose NULL rows may end up in a list of their own (nspill), not vn_fold
+    bool fx_base;            // fixed-point entry words are an option (then the sample decides: h->fx_state)
+    int tb, pbits, levels;   // 2^tb slots per final table, 2^pbits final partitions through one or two scatter levels
+    int p1, p2, np1, np2;
+    int64_t nfinal;
+    int fsplits;             // workgroups that share a final partition (split final pass + merge kernel), 1 = none
+    bool count8;             // COUNT(*) alone: one level of 512 partitions, then one- or two-byte counters over sub-ranges
+    int c8_cb, c8_sub;       // ... bits of a counter; a partition of 2^c8_sub times the table's codes is read once per part
+    bool fx;                 // fixed-point words, of the quantum fx_q = 2^qe (0: float64 entries)
+    double fx_q;
+    bool w32, w32_1;         // the LAST level's words are 32 bits (one level: pass 1 writes them; two: pass 2)
+    int grid1, split2;       // pass-1 workgroups; pass-2 workgroups per first-level partition
+    int64_t cap1, cap2;      // entries per region after pass 1 / pass 2
+    bool c16_1;              // pass-1 remainders fit 16 bits when they are the final slots
+    int pmajor;              // VNM_DENSE_PRODUCER_MAJOR
+    int64_t spill_cap, nspill_cap, dstride;
+    int rcap1, rcap2;        // entries per ring of the ring scatter (0 = the tile-sorting kernel takes the level)
+    bool ring_limit;
+    int ring_pairs1, ring_pairs2;   // pairs of rows per lane and sub-tile, at most
+};
+constexpr int DENSE_REDO = 4;   // a stage's answer: free everything, then the same batch once more (the handle says what changes)
+
+// Stage 2a: is the route applicable, and with which form of entries?  0, or 2 = not applicable.
+int plan_dense_entries(const vnm_agg* h, const AggArgs& a, bool generic, const DGenArgs& g, bool vn_fold, bool null_lists, DensePlan* p) {
+    p->generic = generic;
+    p->has_val = generic ? g.has_val != 0 : true;
     // nullable value column: NULL flags travel with the entries (generic programs) -- or, vn_fold, the hot program filtered by that
     // column itself: pass 1 drops the NULL rows with the filter and nothing after it ever sees a flag
     if ((h->segs_active || h->kn_valid) && generic) return 2;   // (stream segments, nullable keys: the hot program's ring scatter only)
     if (h->kn_valid && h->segs_active) return 2;
-    const bool vn = has_val && a.cols[0].validity != nullptr && (generic || vn_fold);
-    if (vn && ((!vn_fold && !nspill_out) || a.has_expr)) return 2;
+    p->vn = p->has_val && a.cols[0].validity != nullptr && (generic || vn_fold);
+    if (p->vn && ((!vn_fold && !null_lists) || a.has_expr)) return 2;
     if (vn_fold && (generic || !a.hot_pred_is_v)) return 2;
-    if (nspill_out) { *nspill_out = nullptr; *n_nspill_out = 0; }
+    p->vn_lists = p->vn && !vn_fold;
     // FIXED-POINT entries (round 6): when every value of the column is m * 2^qe with |m| < 2^31 -- integers stored as float64, halves,
     // the benchmark's k / 128 -- an entry is ONE 64-bit word (m << remainder bits | remainder): 8 bytes instead of 12 after pass 1 and 10
     // after pass 2, one region stream instead of two, integer adds in the final pass (exact by construction, no compensation words).
@@ -784,38 +856,50 @@ int dense_partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hip
     // finer fraction, a larger magnitude, -0.0, Inf / NaN) fails the attempt: the batch is redone with float64 entries and the operator
     // never tries again.  Same result bits: the correctly rounded exact sum either way.
     // (a nullable KEY: pass 1 sums the NULL-key rows aside as ever; a nullable VALUE filtered by itself, vn_fold: the NULL rows never become entries)
-    const bool fx_base = !generic && has_val && (!vn || vn_fold) && !a.has_expr && !(h->kn_valid && vn) && a.hot_comp && a.hot_w_sum >= 0 &&
-                         env_i64("VNM_DENSE_DEFER", 1) && env_i64("VNM_DENSE_FX", 1) && a.cols[0].type == VNM_F64 && (env_i64("VNM_DENSE_RING", 3) & 3) == 3;
-    if (fx_base && h->fx_state == 0) {
-        h->fx_state = -1;
-        unsigned long long* d = (unsigned long long*)pool_alloc(64);
-        if (!d) return 1;
-        unsigned long long got = 0;
-        VNM_HIP(hipMemsetAsync(d, 0, 8, s));
-        const int64_t srows = h->segs_active ? (*h->segs_active)[0].nrows : nrows;
-        const int64_t m = std::min<int64_t>(srows, 1 << 16);
-        fx_sample_kernel<<<(int)std::min<int64_t>((m + 255) / 256, 256), 256, 0, s>>>((const double*)a.cols[0].values + a.cols[0].offset, srows, m, d);
-        VNM_HIP(hipGetLastError());
-        VNM_HIP(hipMemcpyAsync(&got, d, 8, hipMemcpyDeviceToHost, s));
-        VNM_HIP(hipStreamSynchronize(s));
-        pool_free(d);
-        const uint32_t xinv = (uint32_t)got, xexp = (uint32_t)(got >> 32);
-        if (xinv == 0 && xexp == 0) { h->fx_state = 1; h->fx_qe = -16; }   // (zeros only)
-        else if (xexp < 2047) {
-            const int L = (int)(0xFFFFu - xinv) - 1075, E = (int)xexp - 1022;   // lowest bit 2^L, |v| < 2^E
-            // NARROW words (round 6): up to 16 bits of quanta in the sample leave two spare bits inside 18 -- the words of the LAST scatter
-            // level then are 32 bits, (m << slot bits) | slot with at most 13 slot bits: 4 bytes per entry into the final pass
-            const bool narrow = E - L <= 16 && env_i64("VNM_DENSE_FX_NARROW", 1) != 0;
-            const int room = narrow ? 18 : 31;
-            const int spare = room - (E - L);
-            if (spare >= 0) {
-                int qe = L - spare / 2;          // half of the spare bits below the sampled quantum, the rest above the sampled magnitude
-                if (qe > 0) qe = 0;              // (fx_encode: 2^-qe >= 1)
-                if (qe >= -1000 && E - qe <= room) { h->fx_state = 1; h->fx_qe = qe; h->fx_narrow = narrow; }
-            }
+    p->fx_base = !generic && p->has_val && (!p->vn || vn_fold) && !a.has_expr && !(h->kn_valid && p->vn) && a.hot_comp && a.hot_w_sum >= 0 &&
+                 env_i64("VNM_DENSE_DEFER", 1) && env_i64("VNM_DENSE_FX", 1) && a.cols[0].type == VNM_F64 && (env_i64("VNM_DENSE_RING", 3) & 3) == 3;
+    return 0;
+}
+
+// Stage 1: the quantum of the fixed-point words from a sample of the first batch (h->fx_state, h->fx_qe, h->fx_narrow).
+int sample_fixed_point(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_t s) {
+    h->fx_state = -1;
+    PoolScope pool;
+    unsigned long long* d = (unsigned long long*)pool.take(64);
+    if (!d) return 1;
+    unsigned long long got = 0;
+    VNM_HIP(hipMemsetAsync(d, 0, 8, s));
+    const int64_t srows = h->segs_active ? (*h->segs_active)[0].nrows : nrows;
+    const int64_t m = std::min<int64_t>(srows, 1 << 16);
+    fx_sample_kernel<<<(int)std::min<int64_t>((m + 255) / 256, 256), 256, 0, s>>>((const double*)a.cols[0].values + a.cols[0].offset, srows, m, d);
+    VNM_HIP(hipGetLastError());
+    VNM_HIP(hipMemcpyAsync(&got, d, 8, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));
+    const uint32_t xinv = (uint32_t)got, xexp = (uint32_t)(got >> 32);
+    if (xinv == 0 && xexp == 0) { h->fx_state = 1; h->fx_qe = -16; }   // (zeros only)
+    else if (xexp < 2047) {
+        const int L = (int)(0xFFFFu - xinv) - 1075, E = (int)xexp - 1022;   // lowest bit 2^L, |v| < 2^E
+        // NARROW words (round 6): up to 16 bits of quanta in the sample leave two spare bits inside 18 -- the words of the LAST scatter
+        // level then are 32 bits, (m << slot bits) | slot with at most 13 slot bits: 4 bytes per entry into the final pass
+        const bool narrow = E - L <= 16 && env_i64("VNM_DENSE_FX_NARROW", 1) != 0;
+        const int room = narrow ? 18 : 31;
+        const int spare = room - (E - L);
+        if (spare >= 0) {
+            int qe = L - spare / 2;          // half of the spare bits below the sampled quantum, the rest above the sampled magnitude
+            if (qe > 0) qe = 0;              // (fx_encode: 2^-qe >= 1)
+            if (qe >= -1000 && E - qe <= room) { h->fx_state = 1; h->fx_qe = qe; h->fx_narrow = narrow; }
         }
-        if (getenv("VNM_AGG_TRACE")) fprintf(stderr, "[agg] fixed-point entries: sample says %s (qe %d)\n", h->fx_state == 1 ? "yes" : "no", h->fx_qe);
     }
+    if (getenv("VNM_AGG_TRACE")) fprintf(stderr, "[agg] fixed-point entries: sample says %s (qe %d)\n", h->fx_state == 1 ? "yes" : "no", h->fx_qe);
+    return 0;
+}
+
+// Stage 2b: tables, fan-out, regions and rings of the attempt.  0, or 2 = not applicable.
+int plan_dense_geometry(const vnm_agg* h, const AggArgs& a, int64_t nrows, const DGenArgs& g, DensePlan* p) {
+    const int cus = device_info().num_cus;
+    const DenseMap& mp = h->dmap;
+    const bool generic = p->generic, has_val = p->has_val;
+    const bool fx_ok = p->fx_base && h->fx_state == 1;
     // slots per final partition: the largest table that still leaves >= 2048 final partitions (8 per CU)
     int tb = (int)env_i64("VNM_DENSE_TBITS", 12);
     tb = std::max(DP_TBITS_MIN, std::min(DP_TBITS_MAX, tb));
@@ -833,11 +917,11 @@ int dense_partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hip
     if (mp.bits - tb < 5 && env_i64("VNM_DENSE_MIN_PARTS32", 1)) tb = std::max(9, mp.bits - 5);
     // fixed-point entry words are 8 bytes: 512 rings of two flush blocks fit the LDS, so ranges of 2^20 .. 2^22 codes take ONE level of 512
     // partitions straight into 2^11 .. 2^13-slot tables, one workgroup per partition (no split final pass, no merge kernel)
-    if (fx_base && h->fx_state == 1 && mp.bits >= 20 && mp.bits <= 22 && env_i64("VNM_DENSE_FX_ONE_LEVEL", 1)) tb = mp.bits - 9;
+    if (fx_ok && mp.bits >= 20 && mp.bits <= 22 && env_i64("VNM_DENSE_FX_ONE_LEVEL", 1)) tb = mp.bits - 9;
     // ... and SMALLER ranges, 2^16 .. 2^19 codes (G ~ 6e4 .. 5e5), the same way: 128 .. 512 partitions of 2^9 / 2^10 slots, one workgroup each -- they took
     // 32 .. 256 partitions of float64 entries and a split final pass: 6.0-6.4 ms per 1e9 rows where G = 1e6 takes 4.3 (round 6, the sweep of tuning log S20)
     // (2^15 .. 2^17 codes: tables of 2^7 / 2^8 slots -- fewer slots than the final workgroup has threads -- keep 256 .. 512 partitions)
-    const bool fx_small = fx_base && h->fx_state == 1 && mp.bits >= (int)env_i64("VNM_DENSE_FX_SMALL_MIN_BITS", 15) && mp.bits <= 19 && env_i64("VNM_DENSE_FX_SMALL", 1) != 0;
+    const bool fx_small = fx_ok && mp.bits >= (int)env_i64("VNM_DENSE_FX_SMALL_MIN_BITS", 15) && mp.bits <= 19 && env_i64("VNM_DENSE_FX_SMALL", 1) != 0;
     if (fx_small) tb = std::max(7, mp.bits - 9);
     if (generic) {   // the table must fit 64 KB of LDS (80 KB at most: one workgroup per CU less)
         int tmax = DP_TBITS_MAX;
@@ -855,21 +939,25 @@ int dense_partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hip
     // 64 rows per estimated group; a byte that overflows after all sends the batch through the two levels and switches this off.
     // counter width: a byte for up to 64 rows per estimated group (or no estimate: the dense path went by the sample's lower bound), two
     // bytes up to 16384
-    const int c8_cb = h->count_cb ? h->count_cb : ((h->hint == 0 || nrows <= 64 * h->hint) ? 8 : (nrows <= 16384 * h->hint ? 16 : 0));
-    const int c8_tmax = c8_cb == 8 ? DC8_BITS : DC8_BITS - 1;
-    const bool count8 = generic && !has_val && g.n_lds == 0 && !vn && !h->count8_off && h->heavy_share == 0.0 && c8_cb != 0 && mp.bits >= DP_TBITS_MAX + 10 &&
-                        mp.bits <= c8_tmax + 9 + 1 && env_i64("VNM_DENSE_COUNT8", 1);
-    const int c8_sub = count8 ? std::max(0, mp.bits - c8_tmax - 9) : 0;       // a partition of twice the table's codes is read once per half
-    if (count8) tb = mp.bits - 9 - c8_sub;                                     // 2^14 .. 2^17 counters per table
-    const int pbits = count8 ? 9 : mp.bits - tb;
-    const int levels = pbits > 9 ? 2 : 1;
+    p->c8_cb = h->count_cb ? h->count_cb : ((h->hint == 0 || nrows <= 64 * h->hint) ? 8 : (nrows <= 16384 * h->hint ? 16 : 0));
+    const int c8_tmax = p->c8_cb == 8 ? DC8_BITS : DC8_BITS - 1;
+    p->count8 = generic && !has_val && g.n_lds == 0 && !p->vn && !h->count8_off && h->heavy_share == 0.0 && p->c8_cb != 0 && mp.bits >= DP_TBITS_MAX + 10 &&
+                mp.bits <= c8_tmax + 9 + 1 && env_i64("VNM_DENSE_COUNT8", 1);
+    p->c8_sub = p->count8 ? std::max(0, mp.bits - c8_tmax - 9) : 0;       // a partition of twice the table's codes is read once per half
+    if (p->count8) tb = mp.bits - 9 - p->c8_sub;                            // 2^14 .. 2^17 counters per table
+    p->tb = tb;
+    p->pbits = p->count8 ? 9 : mp.bits - tb;
+    p->levels = p->pbits > 9 ? 2 : 1;
+    const int pbits = p->pbits, levels = p->levels;
+    p->nfinal = (int64_t)1 << pbits;
     // pass 1 moves 12-byte entries out of 16-byte rows, pass 2 moves 10-byte entries out of 12: the SMALLER fan-out goes
     // to pass 1, whose write runs are the shorter ones (measured at b = 27: p1 = 7 / 8 -> 4.9 / 5.6 ms for pass 1)
     // (fixed-point words: 8 bytes in BOTH passes -- the larger fan-out goes first: G = 1e8, p1 = 7 / 8: 7.53 / 7.37 ms)
-    int p1 = levels == 2 ? (int)env_i64("VNM_DENSE_P1", fx_base && h->fx_state == 1 ? (pbits + 1) / 2 : pbits / 2) : pbits;
+    int p1 = levels == 2 ? (int)env_i64("VNM_DENSE_P1", fx_ok ? (pbits + 1) / 2 : pbits / 2) : pbits;
     if (levels == 2) { if (p1 > 9) p1 = 9; if (pbits - p1 > 9) p1 = pbits - 9; }
-    const int p2 = pbits - p1;
-    const int np1 = 1 << p1, np2 = levels == 2 ? 1 << p2 : 0;
+    p->p1 = p1; p->p2 = pbits - p1;
+    p->np1 = 1 << p1; p->np2 = levels == 2 ? 1 << p->p2 : 0;
+    const int np1 = p->np1, np2 = p->np2;
     const int64_t tile1 = PT_TILE;
     const int grid1 = (int)std::min<int64_t>((int64_t)cus * env_i64("VNM_DENSE_GRID1_PER_CU", 2), (nrows + tile1 - 1) / tile1);
     int split2 = std::max(2, (grid1 + PT_MAX_REGIONS - 1) / PT_MAX_REGIONS);
@@ -877,227 +965,155 @@ int dense_partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hip
     // skewed keys (the estimator's sample saw heavy keys): more, smaller work items for pass 2 -- the partition that holds a heavy key
     // has a multiple of the others' entries, and with cus * 2 work items for cus * 2 resident workgroups the heaviest sets the time
     if (h->heavy_share > 0.0) split2 = std::min(grid1, split2 * (int)env_i64("VNM_DENSE_SKEW_SPLIT", 8));
+    p->grid1 = grid1; p->split2 = split2;
     const int64_t tiles_per_wg = ((nrows + tile1 - 1) / tile1 + grid1 - 1) / grid1;
     const int64_t rows_per_wg = tiles_per_wg * tile1;
-    int64_t cap1v = ((rows_per_wg / np1 + rows_per_wg / np1 / 5 + 512) + 15) & ~15LL;
+    int64_t cap1 = ((rows_per_wg / np1 + rows_per_wg / np1 / 5 + 512) + 15) & ~15LL;
     // region stride = an ODD number of 128-byte lines: the lines the resident workgroups keep open in one partition then spread
     // over the L2 sets instead of sharing their low index bits (two sessions of 5-6 process pairs: 11.73 -> 11.25 and 11.27 -> 11.17 ms)
-    if (env_i64("VNM_DENSE_ODD_CAP", 1) && ((cap1v / 16) & 1) == 0) cap1v += 16;
-    if (fx_base && h->fx_state == 1 && h->fx_narrow && levels == 1) { cap1v = (cap1v + 31) & ~31LL; if (((cap1v / 32) & 1) == 0) cap1v += 32; }   // (32-bit words: blocks of 32)
-    const int64_t cap1 = cap1v;
-    const bool c16_1 = levels == 1 && !count8;  // pass-1 remainders fit 16 bits when they are the final slots
+    const bool odd_cap = env_i64("VNM_DENSE_ODD_CAP", 1) != 0;
+    if (odd_cap && ((cap1 / 16) & 1) == 0) cap1 += 16;
+    if (fx_ok && h->fx_narrow && levels == 1) { cap1 = (cap1 + 31) & ~31LL; if (((cap1 / 32) & 1) == 0) cap1 += 32; }   // (32-bit words: blocks of 32)
+    p->cap1 = cap1;
+    p->c16_1 = levels == 1 && !p->count8;
     // final partitions x splits >= ~4 workgroups per CU
     int fsplits = 1;
-    if (levels == 1 && !count8 && ((int64_t)1 << pbits) < (int64_t)cus * 2) {
+    if (levels == 1 && !p->count8 && ((int64_t)1 << pbits) < (int64_t)cus * 2) {
         fsplits = (int)std::min<int64_t>(grid1, ((int64_t)cus * env_i64("VNM_DENSE_SPLIT_WGS", 4) + ((int64_t)1 << pbits) - 1) >> pbits);
         if (fsplits < 2) fsplits = 1;
     }
     if (fx_small && levels == 1) fsplits = 1;   // (128 .. 512 lean final workgroups: a short pass either way)
-    const bool fx = fx_base && h->fx_state == 1 && fsplits == 1 && !count8 && tb >= (fx_small ? 7 : 11) && tb <= 13;
-    const double fx_q = fx ? std::ldexp(1.0, h->fx_qe) : 0.0;
-    const bool w32 = fx && h->fx_narrow;          // the LAST level's words are 32 bits (one level: pass 1 writes them; two: pass 2)
-    const bool w32_1 = w32 && levels == 1;
-    unsigned long long* flags = (unsigned long long*)pool_alloc(128);   // [0..3] status words, [6] exact-add statistics, [7] fixed-point misfit, [8..12] the NULL-key rows of this attempt (nullable key)
-    double* v1 = (double*)pool_alloc(has_val ? (size_t)np1 * grid1 * cap1 * (w32_1 ? 4 : 8) : 8);
-    void* c1 = pool_alloc(fx ? 16 : (size_t)np1 * grid1 * cap1 * (c16_1 ? 2 : 4));
-    uint32_t* n1 = (uint32_t*)pool_alloc((size_t)np1 * grid1 * 4);
-    const int64_t spill_cap = nrows / 2 + (1 << 20);
-    ulonglong2* spill = (ulonglong2*)pool_alloc((size_t)spill_cap * 16);
-    const bool vn_lists = vn && !vn_fold;
-    const int64_t nspill_cap = vn_lists ? nrows / 4 + (1 << 20) : 0;
-    uint64_t* nspill = vn_lists ? (uint64_t*)pool_alloc((size_t)nspill_cap * 8) : nullptr;
-    PoolSlotGuard<uint64_t> nspill_guard(&nspill);   // handed to the caller only on success (below)
-    double* v2 = nullptr; void* c2 = nullptr; uint32_t* n2 = nullptr;
-    uint64_t* rk = nullptr; uint64_t* ra = nullptr;
-    auto release = [&]() { pool_free(flags); pool_free(v1); pool_free(c1); pool_free(n1); pool_free(v2); pool_free(c2); pool_free(n2); };
-    if (!flags || !v1 || !c1 || !n1 || !spill || (vn_lists && !nspill)) { release(); pool_free(spill); return 1;}
-    VNM_HIP(hipMemsetAsync(flags, 0, 128, s));
-    fill_u64_kernel<<<1, 1, 0, s>>>((uint64_t*)flags + 11, F64_NEG_ZERO, 1);   // (the NULL-key rows' sum starts at -0.0: merge_init)
+    p->fsplits = fsplits;
+    p->fx = fx_ok && fsplits == 1 && !p->count8 && tb >= (fx_small ? 7 : 11) && tb <= 13;
+    p->fx_q = p->fx ? std::ldexp(1.0, h->fx_qe) : 0.0;
+    p->w32 = p->fx && h->fx_narrow;
+    p->w32_1 = p->w32 && levels == 1;
+    if (levels == 2) {
+        const int64_t per_pg = (int64_t)grid1 * rows_per_wg / np1 / split2;
+        int64_t cap2 = ((per_pg / np2 + per_pg / np2 / 4 + 256) + 15) & ~15LL;
+        if (odd_cap && ((cap2 / 16) & 1) == 0) cap2 += 16;
+        if (p->w32) { cap2 = (cap2 + 31) & ~31LL; if (((cap2 / 32) & 1) == 0) cap2 += 32; }   // (32-bit words: blocks of 32)
+        p->cap2 = cap2;
+    }
+    p->spill_cap = nrows / 2 + (1 << 20);
+    p->nspill_cap = p->vn_lists ? nrows / 4 + (1 << 20) : 0;
+    p->dstride = std::min<int64_t>(h->dense_span, nrows) + 2;
+    // producer-major regions (a workgroup's 128 output regions adjacent) were tried against TLB pressure: pass 1 unchanged,
+    // pass 2 and the final pass 15-20 % slower (their reads become 150 KB chunks 75 MB apart) -> partition-major stays
+    p->pmajor = (int)env_i64("VNM_DENSE_PRODUCER_MAJOR", 0);
+    // ring-buffer scatter (dring_scatter_kernel): VNM_DENSE_RING bit 0: pass 1, bit 1: pass 2
+    const int use_ring = (int)env_i64("VNM_DENSE_RING", 3);
+    p->ring_limit = env_i64("VNM_DENSE_RING_LIMIT", 1) != 0;
+    p->rcap1 = p->w32_1 ? ring_cap_w32(np1) : ((use_ring & 1) && !a.has_expr ? ring_cap_for(np1, p->fx ? 8 : (has_val ? 8 : 0) + (p->c16_1 ? 2 : 4)) : 0);
+    if (levels == 2) p->rcap2 = p->fx ? (p->w32 ? ring_cap_w32(np2) : ring_cap_for(np2, 8)) : ((use_ring & 2) ? ring_cap_for(np2, (has_val ? 8 : 0) + 2) : 0);
+    // (pass 1 of TWO levels of fixed-point words: sub-tiles of two pairs -- 4.07-4.19 -> 3.85-3.90 ms at G = 1e8, A/B x 3; one level
+    // of 512 rings: four pairs as before)
+    p->ring_pairs1 = (int)env_i64("VNM_DENSE_RING_PAIRS", 4);
+    if (p->fx && levels == 2 && getenv("VNM_DENSE_RING_PAIRS") == nullptr) p->ring_pairs1 = 2;
+    // (32-bit words out of pass 2: 128 rings of up to 256 words take four pairs per lane in one round -- half the barriers: 1.74-1.76 -> 1.56 ms)
+    p->ring_pairs2 = levels == 2 ? (int)env_i64("VNM_DENSE_RING_PAIRS2", p->fx && p->w32 ? 4 : 2) : 0;
+    return 0;
+}
+
+// Stage 3 owns every pool block of the attempt: whatever has not been keep()-ed -- handed to the caller, the handle's run or the
+// pending pass -- goes back on every return path.
+struct DenseBuffers {
+    PoolScope pool;
+    unsigned long long* flags = nullptr;   // [0..3] status words, [6] exact-add statistics, [7] fixed-point misfit, [8..12] the NULL-key rows of this attempt (nullable key)
+    double* v1 = nullptr; void* c1 = nullptr; uint32_t* n1 = nullptr;    // regions of level 1: values / words, code remainders, counts
+    double* v2 = nullptr; void* c2 = nullptr; uint32_t* n2 = nullptr;    // ... of level 2
+    ulonglong2* spill = nullptr;           // entries without a place: the caller's on success
+    uint64_t* nspill = nullptr;            // keys of NULL-value rows without a place: the caller's on success
+    uint64_t* rk = nullptr; uint64_t* ra = nullptr;                      // the run a final pass of this call writes
+    template <class T> void take(T*& p, size_t bytes) { p = (T*)pool.take(bytes); }
+    // before the batch is tried again: the retry finds the blocks in the pool
+    void free_all() { while (pool.n > 0) pool.done(pool.blocks[pool.n - 1]); }
+};
+
+int dense_allocate(const DensePlan& p, DenseBuffers& b, hipStream_t s) {
+    b.take(b.flags, 128);
+    b.take(b.v1, p.has_val ? (size_t)p.np1 * p.grid1 * p.cap1 * (p.w32_1 ? 4 : 8) : 8);
+    b.take(b.c1, p.fx ? 16 : (size_t)p.np1 * p.grid1 * p.cap1 * (p.c16_1 ? 2 : 4));
+    b.take(b.n1, (size_t)p.np1 * p.grid1 * 4);
+    b.take(b.spill, (size_t)p.spill_cap * 16);
+    if (p.vn_lists) b.take(b.nspill, (size_t)p.nspill_cap * 8);
+    if (!b.flags || !b.v1 || !b.c1 || !b.n1 || !b.spill || (p.vn_lists && !b.nspill)) return 1;
+    VNM_HIP(hipMemsetAsync(b.flags, 0, 128, s));
+    fill_u64_kernel<<<1, 1, 0, s>>>((uint64_t*)b.flags + 11, F64_NEG_ZERO, 1);   // (the NULL-key rows' sum starts at -0.0: merge_init)
     VNM_HIP(hipGetLastError());
-    DPartArgs d1{};
-    d1.map = mp;
+    return 0;
+}
+
+// A nullable key: pass 1 sums the NULL-key rows of this ATTEMPT into scratch words; only an attempt that is known good adds them to
+// the NULL slot of the operator's HBM table (here).  A failed attempt -- full spill buffer, output too small, a compensation term
+// out of range: all known only after pass 1 -- leaves the table untouched, and the route that takes the batch instead counts those
+// rows itself (they used to be counted twice: ADVICE r04).
+int fold_null_rows(const vnm_agg* h, const AggArgs& a, const unsigned long long* flags, hipStream_t s) {
+    if (!h->kn_valid) return 0;
+    const GTable& gt = h->g;
+    const uint64_t slot = gt.cap + 1;
+    dnull_fold_kernel<<<1, 64, 0, s>>>(flags + 8, gt.tag + slot,
+                                       a.hot_w_rows >= 0 ? gt.acc + (uint64_t)a.hot_w_rows * gt.stride + slot : nullptr,
+                                       a.hot_w_valid >= 0 ? gt.acc + (uint64_t)a.hot_w_valid * gt.stride + slot : nullptr,
+                                       a.hot_w_sum >= 0 ? gt.acc + (uint64_t)a.hot_w_sum * gt.stride + slot : nullptr,
+                                       a.hot_comp && a.hot_w_sum >= 0 ? (int64_t)gt.stride : 0);
+    VNM_HIP(hipGetLastError());
+    return 0;
+}
+
+// The kernel of level 1: the ring scatter where the rings take the fan-out (p.rcap1), the tile-sorting scatter otherwise.
+int dense_scatter1_launch(vnm_agg* h, const DensePlan& p, DenseBuffers& b, DPartArgs& d1, hipStream_t s) {
+    const bool pv = d1.has_pred && !d1.pred_is_v;   // a predicate column of its own
+    if (!p.rcap1)
+        return pick_bool(p.c16_1, [&](auto c16) {
+            using CT = std::conditional_t<decltype(c16)::value, uint16_t, uint32_t>;
+            if (p.vn) { dpart_scatter_kernel<true, CT, true, true><<<p.grid1, PT_BLOCK, 0, s>>>(d1); return 0; }
+            return pick_bool(p.has_val, [&](auto hv) { dpart_scatter_kernel<true, CT, decltype(hv)::value><<<p.grid1, PT_BLOCK, 0, s>>>(d1); return 0; });
+        });
+    const bool plain_val = p.has_val && !p.vn;   // what the kernels for stream segments and nullable keys read
+    const RingLaunch r{p.grid1, p.rcap1, ring_sub_tile_pairs(p.ring_pairs1, pv, p.ring_limit, p.np1, p.rcap1, p.w32_1), p.ring_limit,
+                       plain_val && h->segs_active != nullptr, plain_val && h->kn_valid != nullptr, s};
+    // the waiting batches of a stream: one segment each, sub-tiles of 2 * pairs * 1024 rows
+    if (r.seg && !r.kn && upload_segs(h, (int64_t)2 * r.pairs * 1024, &d1.segs, &d1.nseg, &d1.nsub, b.pool, s)) return 1;
+    if (p.fx && p.vn)   // (vn_fold: the predicate column is the value column)
+        return pick_bool(p.w32_1, [&](auto w32) { return ring_scatter<true, uint32_t, true, false, true, true, decltype(w32)::value>(r, d1); });
+    if (p.fx)
+        return pick_bool(p.w32_1, [&](auto w32) {
+            return pick_bool(pv, [&](auto pvc) { return ring_scatter<true, uint32_t, true, decltype(pvc)::value, false, true, decltype(w32)::value>(r, d1); });
+        });
+    return pick_bool(p.c16_1, [&](auto c16) {
+        using CT = std::conditional_t<decltype(c16)::value, uint16_t, uint32_t>;
+        return pick_bool(pv, [&](auto pvc) {
+            if (p.vn) return ring_scatter<true, CT, true, decltype(pvc)::value, true>(r, d1);
+            return pick_bool(p.has_val, [&](auto hv) { return ring_scatter<true, CT, decltype(hv)::value, decltype(pvc)::value, false>(r, d1); });
+        });
+    });
+}
+
+// Stage 4: scatter level 1, rows -> np1 partitions (d1 stays: level 2 takes its fixed-point parameters from it).
+int dense_scatter1(vnm_agg* h, const AggArgs& a, int64_t nrows, const DensePlan& p, DenseBuffers& b, DPartArgs& d1, hipStream_t s) {
+    d1.map = h->dmap;
     d1.kp = (const uint64_t*)a.keys[0].values + a.keys[0].offset;
-    d1.vp = has_val ? (const double*)a.cols[0].values + a.cols[0].offset : nullptr;
+    d1.vp = p.has_val ? (const double*)a.cols[0].values + a.cols[0].offset : nullptr;
     d1.has_expr = a.has_expr; d1.expr = a.expr;
     d1.pp = h->pred_set ? (const double*)a.pred.values + a.pred.offset : nullptr;
     d1.has_pred = h->pred_set; d1.pred_is_v = a.hot_pred_is_v; d1.op = a.p.op; d1.thr = a.p.dval;
     d1.nrows = nrows;
-    d1.out_vals = v1; d1.out_codes = c1; d1.out_counts = n1; d1.out_cap = cap1;
-    d1.nparts = np1; d1.out_bits = mp.bits - p1;
-    // producer-major regions (a workgroup's 128 output regions adjacent) were tried against TLB pressure: pass 1 unchanged,
-    // pass 2 and the final pass 15-20 % slower (their reads become 150 KB chunks 75 MB apart) -> partition-major stays
-    const int pmajor = (int)env_i64("VNM_DENSE_PRODUCER_MAJOR", 0);
-    d1.producer_major = pmajor;
+    d1.out_vals = b.v1; d1.out_codes = b.c1; d1.out_counts = b.n1; d1.out_cap = p.cap1;
+    d1.nparts = p.np1; d1.out_bits = h->dmap.bits - p.p1;
+    d1.producer_major = p.pmajor;
     // Non-temporal stores for pass 1's runs when a wide second level follows: pass 2 then reads them 15-20 % faster and the query
     // gains 0.4 ms (1.1 ms in sustained runs) at G = 1e8 (p2 = 8); with p2 = 6 (G = 1e7) or a single level it is neutral to
     // slightly worse, so it stays off there.  In pass 2 itself such stores cost 0.3 ms.  (VNM_DENSE_NT: bit 0 pass 1, bit 1 pass 2)
-    d1.nt_store = (int)env_i64("VNM_DENSE_NT", levels == 2 && np2 >= 256 ? 1 : 0) & 1;
+    d1.nt_store = (int)env_i64("VNM_DENSE_NT", p.levels == 2 && p.np2 >= 256 ? 1 : 0) & 1;
     d1.ready_list = (int)env_i64("VNM_DENSE_READY_LIST", 1) & 1;
-    d1.flags = flags; d1.spill = spill; d1.spill_cap = spill_cap;
-    d1.fx_q = fx_q; d1.fx_inv_q = fx ? std::ldexp(1.0, -h->fx_qe) : 0.0;
-    d1.fx_lim = w32 ? (1LL << 18) - 1 : 2147483647LL;
-    if (vn) { d1.vvalid = a.cols[0].validity; d1.voff = a.cols[0].offset; d1.nspill = nspill; d1.nspill_cap = nspill_cap; }
-    // ring-buffer scatter (dring_scatter_kernel): whole 16-entry blocks only.  Ring capacity = what fits 128 KB of LDS, at
-    // most 64 entries per partition; fan-outs that leave less than two blocks per ring keep the tile-sorting kernel.
-    const int use_ring = (int)env_i64("VNM_DENSE_RING", 3);   // bit 0: pass 1, bit 1: pass 2
-    const int ring_blk = 1024;
-    auto ring_cap_for = [&](int np, size_t esize) -> int {
-        int cap = (int)((size_t)(env_i64("VNM_DENSE_RING_LDS", ring_blk >= 1024 ? 128 : (ring_blk >= 512 ? 72 : 48)) * 1024) / ((size_t)np * esize) / DR_FB) * DR_FB;
-        // at most 80 entries per ring -- more where few partitions share the LDS, so that an even spread of a four-pair sub-tile
-        // (8192 entries) still fits one round: 32 partitions 272, 64 partitions 144
-        cap = std::min(cap, (int)env_i64("VNM_DENSE_RING_CAP", std::max(80, ((8192 / np + DR_FB + DR_FB - 1) / DR_FB) * DR_FB)));
-        // few partitions: long runs anyway (and 8192 entries per sub-tile on a handful of ring cursors: G = 1e4, four partitions,
-        // pass 1 8.6 ms against 5.0 with the tile-sorting kernel)
-        if (np < env_i64("VNM_DENSE_RING_MIN_NP", 32)) return 0;
-        return cap >= 2 * DR_FB ? cap : 0;
-    };
-    const bool ring_limit = env_i64("VNM_DENSE_RING_LIMIT", 1) != 0;   // spill what two insert / flush rounds of a sub-tile leave pending (skew)
-    int ring_pairs = (int)env_i64("VNM_DENSE_RING_PAIRS", 4);   // pass 1; pass 2 (every entry survives, more partitions): VNM_DENSE_RING_PAIRS2
-#define VNM_DRING_B(FR_, CT_, HV_, BLK_, PR_, PV_, VN_, GRID_, ARGS_, CAP_)                                              \
-    do {                                                                                                                \
-        const size_t lds_ = (((size_t)(ARGS_).nparts * (CAP_) * ((HV_ ? 8 : 0) + sizeof(CT_))) + 15) & ~(size_t)15;       \
-        /* the waiting batches of a stream: one segment each, sub-tiles of 2 * PR_ * BLK_ rows (the SEG instantiations) */ \
-        constexpr bool SG_ = FR_ && HV_ && !VN_;                                                                        \
-        const bool seg_ = SG_ && h->segs_active != nullptr;                                                             \
-        const bool kn_ = SG_ && h->kn_valid != nullptr;   /* a nullable key: the KN instantiations (same shapes as SEG) */ \
-        if (kn_) {                                                                                                      \
-            if (2 * PR_ * BLK_ <= (ARGS_).nparts * ((CAP_) - DR_FB) && ring_limit) {                                    \
-                VNM_HIP(hipFuncSetAttribute((const void*)dring_scatter_kernel<FR_, CT_, HV_, BLK_, PR_, PV_, VN_, 2, false, SG_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-                dring_scatter_kernel<FR_, CT_, HV_, BLK_, PR_, PV_, VN_, 2, false, SG_><<<GRID_, BLK_, lds_, s>>>(ARGS_, CAP_); \
-            } else {                                                                                                    \
-                VNM_HIP(hipFuncSetAttribute((const void*)dring_scatter_kernel<FR_, CT_, HV_, BLK_, PR_, PV_, VN_, 0, false, SG_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-                dring_scatter_kernel<FR_, CT_, HV_, BLK_, PR_, PV_, VN_, 0, false, SG_><<<GRID_, BLK_, lds_, s>>>(ARGS_, CAP_); \
-            }                                                                                                           \
-            break;                                                                                                      \
-        }                                                                                                               \
-        if (seg_ && upload_segs(h, (int64_t)2 * PR_ * BLK_, &(ARGS_).segs, &(ARGS_).nseg, &(ARGS_).nsub, seg_pool, s)) { release(); pool_free(spill); return 1; } \
-        /* round limit (skew): two insert / flush rounds per sub-tile, where an even spread of a sub-tile's entries (every */ \
-        /* row surviving) fits ONE */                                                                                   \
-        if (2 * PR_ * BLK_ <= (ARGS_).nparts * ((CAP_) - DR_FB) && ring_limit) {                                        \
-            if (seg_) {                                                                                                 \
-                VNM_HIP(hipFuncSetAttribute((const void*)dring_scatter_kernel<FR_, CT_, HV_, BLK_, PR_, PV_, VN_, 2, SG_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-                dring_scatter_kernel<FR_, CT_, HV_, BLK_, PR_, PV_, VN_, 2, SG_><<<GRID_, BLK_, lds_, s>>>(ARGS_, CAP_); \
-            } else {                                                                                                    \
-                VNM_HIP(hipFuncSetAttribute((const void*)dring_scatter_kernel<FR_, CT_, HV_, BLK_, PR_, PV_, VN_, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-                dring_scatter_kernel<FR_, CT_, HV_, BLK_, PR_, PV_, VN_, 2><<<GRID_, BLK_, lds_, s>>>(ARGS_, CAP_);      \
-            }                                                                                                           \
-        } else if (seg_) {                                                                                              \
-            VNM_HIP(hipFuncSetAttribute((const void*)dring_scatter_kernel<FR_, CT_, HV_, BLK_, PR_, PV_, VN_, 0, SG_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-            dring_scatter_kernel<FR_, CT_, HV_, BLK_, PR_, PV_, VN_, 0, SG_><<<GRID_, BLK_, lds_, s>>>(ARGS_, CAP_);     \
-        } else {                                                                                                        \
-            VNM_HIP(hipFuncSetAttribute((const void*)dring_scatter_kernel<FR_, CT_, HV_, BLK_, PR_, PV_, VN_, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-            dring_scatter_kernel<FR_, CT_, HV_, BLK_, PR_, PV_, VN_, 0><<<GRID_, BLK_, lds_, s>>>(ARGS_, CAP_);          \
-        }                                                                                                               \
-    } while (0)
-    // sub-tile = the largest of 4 / 2 / 1 pairs of rows per lane (at most ring_pairs) whose entries, evenly spread, fit one round
-    // of the rings: the round limit then applies (64 partitions: 2 pairs, 32: 1 pair)
-#define VNM_DRING_P(FR_, CT_, HV_, PV_, VN_, GRID_, ARGS_, CAP_)                                                         \
-    do {                                                                                                                \
-        int pr_ = ring_pairs >= 4 && !PV_ ? 4 : (ring_pairs >= 2 ? 2 : 1);                                              \
-        while (ring_limit && pr_ > 1 && 2 * pr_ * 1024 > (ARGS_).nparts * ((CAP_) - DR_FB)) pr_ >>= 1;                  \
-        if (pr_ == 4 && !PV_) VNM_DRING_B(FR_, CT_, HV_, 1024, 4, PV_, VN_, GRID_, ARGS_, CAP_);                         \
-        else if (pr_ >= 2) VNM_DRING_B(FR_, CT_, HV_, 1024, 2, PV_, VN_, GRID_, ARGS_, CAP_);                            \
-        else VNM_DRING_B(FR_, CT_, HV_, 1024, 1, PV_, VN_, GRID_, ARGS_, CAP_);                                          \
-    } while (0)
-    // (a predicate column of its own: three loads per pair of rows, at most two pairs per lane and sub-tile fit the registers)
-#define VNM_DRING(FR_, CT_, HV_, GRID_, ARGS_, CAP_)                                                                     \
-    do {                                                                                                                \
-        if (FR_ && (ARGS_).has_pred && !(ARGS_).pred_is_v) VNM_DRING_P(FR_, CT_, HV_, FR_, false, GRID_, ARGS_, CAP_);    \
-        else VNM_DRING_P(FR_, CT_, HV_, false, false, GRID_, ARGS_, CAP_);                                               \
-    } while (0)
-    // pass 1 over a nullable value column
-#define VNM_DRING_VN(CT_, GRID_, ARGS_, CAP_)                                                                            \
-    do {                                                                                                                \
-        if ((ARGS_).has_pred && !(ARGS_).pred_is_v) VNM_DRING_P(true, CT_, true, true, true, GRID_, ARGS_, CAP_);         \
-        else VNM_DRING_P(true, CT_, true, false, true, GRID_, ARGS_, CAP_);                                              \
-    } while (0)
-    // fixed-point entries: pass 1 (one batch or stream segments; the predicate column the value column or one of its own) and pass 2
-#define VNM_DRING_FXB(FR_, PR_, PV_, W32_, GRID_, ARGS_, CAP_)                                                           \
-    do {                                                                                                                \
-        const size_t lds_ = (((size_t)(ARGS_).nparts * (CAP_) * (W32_ ? 4 : 8)) + 15) & ~(size_t)15;                     \
-        const bool seg_ = FR_ && h->segs_active != nullptr;                                                             \
-        if (seg_ && upload_segs(h, (int64_t)2 * PR_ * 1024, &(ARGS_).segs, &(ARGS_).nseg, &(ARGS_).nsub, seg_pool, s)) { release(); pool_free(spill); return 1; } \
-        const bool lim_ = 2 * PR_ * 1024 <= (ARGS_).nparts * ((CAP_) - (W32_ ? 32 : DR_FB)) && ring_limit;              \
-        if (lim_ && seg_) {                                                                                             \
-            VNM_HIP(hipFuncSetAttribute((const void*)dring_scatter_kernel<FR_, uint32_t, true, 1024, PR_, PV_, false, 2, FR_, false, false, true, W32_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-            dring_scatter_kernel<FR_, uint32_t, true, 1024, PR_, PV_, false, 2, FR_, false, false, true, W32_><<<GRID_, 1024, lds_, s>>>(ARGS_, CAP_); \
-        } else if (lim_) {                                                                                              \
-            VNM_HIP(hipFuncSetAttribute((const void*)dring_scatter_kernel<FR_, uint32_t, true, 1024, PR_, PV_, false, 2, false, false, false, true, W32_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-            dring_scatter_kernel<FR_, uint32_t, true, 1024, PR_, PV_, false, 2, false, false, false, true, W32_><<<GRID_, 1024, lds_, s>>>(ARGS_, CAP_); \
-        } else if (seg_) {                                                                                              \
-            VNM_HIP(hipFuncSetAttribute((const void*)dring_scatter_kernel<FR_, uint32_t, true, 1024, PR_, PV_, false, 0, FR_, false, false, true, W32_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-            dring_scatter_kernel<FR_, uint32_t, true, 1024, PR_, PV_, false, 0, FR_, false, false, true, W32_><<<GRID_, 1024, lds_, s>>>(ARGS_, CAP_); \
-        } else {                                                                                                        \
-            VNM_HIP(hipFuncSetAttribute((const void*)dring_scatter_kernel<FR_, uint32_t, true, 1024, PR_, PV_, false, 0, false, false, false, true, W32_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-            dring_scatter_kernel<FR_, uint32_t, true, 1024, PR_, PV_, false, 0, false, false, false, true, W32_><<<GRID_, 1024, lds_, s>>>(ARGS_, CAP_); \
-        }                                                                                                               \
-    } while (0)
-#define VNM_DRING_FXW(FR_, PV_, W32_, GRID_, ARGS_, CAP_)                                                                \
-    do {                                                                                                                \
-        /* (pass 1 of TWO levels of fixed-point words: sub-tiles of two pairs -- 4.07-4.19 -> 3.85-3.90 ms at G = 1e8, A/B x 3; one level */ \
-        /* of 512 rings: four pairs as before)                                                                            */ \
-        const int rp_ = (FR_ && levels == 2 && getenv("VNM_DENSE_RING_PAIRS") == nullptr) ? 2 : ring_pairs;               \
-        int pr_ = rp_ >= 4 && !PV_ ? 4 : (rp_ >= 2 ? 2 : 1);                                                            \
-        while (ring_limit && pr_ > 1 && 2 * pr_ * 1024 > (ARGS_).nparts * ((CAP_) - (W32_ ? 32 : DR_FB))) pr_ >>= 1;    \
-        if (pr_ == 4 && !PV_) VNM_DRING_FXB(FR_, 4, PV_, W32_, GRID_, ARGS_, CAP_);                                      \
-        else if (pr_ >= 2) VNM_DRING_FXB(FR_, 2, PV_, W32_, GRID_, ARGS_, CAP_);                                         \
-        else VNM_DRING_FXB(FR_, 1, PV_, W32_, GRID_, ARGS_, CAP_);                                                       \
-    } while (0)
-#define VNM_DRING_FX(FR_, PV_, W32RT_, GRID_, ARGS_, CAP_)                                                               \
-    do { if (W32RT_) VNM_DRING_FXW(FR_, PV_, true, GRID_, ARGS_, CAP_); else VNM_DRING_FXW(FR_, PV_, false, GRID_, ARGS_, CAP_); } while (0)
-    // ... pass 1 over a nullable key (KN_) or a nullable value column filtered by itself (VN_): one batch, no stream segments
-#define VNM_DRING_FXXB(PR_, PV_, VN_, KN_, W32_, GRID_, ARGS_, CAP_)                                                     \
-    do {                                                                                                                \
-        const size_t lds_ = (((size_t)(ARGS_).nparts * (CAP_) * (W32_ ? 4 : 8)) + 15) & ~(size_t)15;                     \
-        const bool lim_ = 2 * PR_ * 1024 <= (ARGS_).nparts * ((CAP_) - (W32_ ? 32 : DR_FB)) && ring_limit;              \
-        if (lim_) {                                                                                                     \
-            VNM_HIP(hipFuncSetAttribute((const void*)dring_scatter_kernel<true, uint32_t, true, 1024, PR_, PV_, VN_, 2, false, KN_, false, true, W32_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-            dring_scatter_kernel<true, uint32_t, true, 1024, PR_, PV_, VN_, 2, false, KN_, false, true, W32_><<<GRID_, 1024, lds_, s>>>(ARGS_, CAP_); \
-        } else {                                                                                                        \
-            VNM_HIP(hipFuncSetAttribute((const void*)dring_scatter_kernel<true, uint32_t, true, 1024, PR_, PV_, VN_, 0, false, KN_, false, true, W32_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-            dring_scatter_kernel<true, uint32_t, true, 1024, PR_, PV_, VN_, 0, false, KN_, false, true, W32_><<<GRID_, 1024, lds_, s>>>(ARGS_, CAP_); \
-        }                                                                                                               \
-    } while (0)
-#define VNM_DRING_FXXW(PV_, VN_, KN_, W32_, GRID_, ARGS_, CAP_)                                                          \
-    do {                                                                                                                \
-        const int rp_ = (levels == 2 && getenv("VNM_DENSE_RING_PAIRS") == nullptr) ? 2 : ring_pairs;                     \
-        int pr_ = rp_ >= 4 && !PV_ ? 4 : (rp_ >= 2 ? 2 : 1);                                                            \
-        while (ring_limit && pr_ > 1 && 2 * pr_ * 1024 > (ARGS_).nparts * ((CAP_) - (W32_ ? 32 : DR_FB))) pr_ >>= 1;    \
-        if (pr_ == 4 && !PV_) VNM_DRING_FXXB(4, PV_, VN_, KN_, W32_, GRID_, ARGS_, CAP_);                                \
-        else if (pr_ >= 2) VNM_DRING_FXXB(2, PV_, VN_, KN_, W32_, GRID_, ARGS_, CAP_);                                   \
-        else VNM_DRING_FXXB(1, PV_, VN_, KN_, W32_, GRID_, ARGS_, CAP_);                                                 \
-    } while (0)
-#define VNM_DRING_FXX(PV_, VN_, KN_, W32RT_, GRID_, ARGS_, CAP_)                                                         \
-    do { if (W32RT_) VNM_DRING_FXXW(PV_, VN_, KN_, true, GRID_, ARGS_, CAP_); else VNM_DRING_FXXW(PV_, VN_, KN_, false, GRID_, ARGS_, CAP_); } while (0)
-    // (32-bit words: blocks of 32, rings of at least two blocks, at most 256 entries)
-    auto ring_cap_w32 = [&](int np) -> int { const int cap = std::min(256, (int)((size_t)128 * 1024 / ((size_t)np * 4) / 32) * 32); return cap >= 64 ? cap : 0; };
-    const int rcap1 = w32_1 ? ring_cap_w32(np1) : ((use_ring & 1) && !a.has_expr ? ring_cap_for(np1, fx ? 8 : (has_val ? 8 : 0) + (c16_1 ? 2 : 4)) : 0);
-    const int rcap2_fx = fx && levels == 2 ? (w32 ? ring_cap_w32(np2) : ring_cap_for(np2, 8)) : 0;
-    if (fx && (!rcap1 || (levels == 2 && !rcap2_fx))) {   // (a fan-out the rings cannot take: float64 entries through the other scatter)
-        h->fx_state = -1; pool_free(flags); pool_free(v1); pool_free(c1); pool_free(n1); pool_free(spill);
-        return dense_partitioned_aggregate(h, a, nrows, s, spill_out, n_spill_out, generic, nspill_out, n_nspill_out, vn_fold);
-    }
-    PoolScope seg_pool;
-    if ((h->segs_active || h->kn_valid) && (!rcap1 || vn)) { release(); pool_free(spill); return 2; }   // (only the ring scatter reads segments / key validity)
-    // A nullable key: pass 1 sums the NULL-key rows of this ATTEMPT into scratch words; only an attempt that is known good adds them to
-    // the NULL slot of the operator's HBM table (fold_null_rows).  A failed attempt -- full spill buffer, output too small, a
-    // compensation term out of range: all known only after pass 1 -- leaves the table untouched, and the route that takes the batch
-    // instead counts those rows itself (they used to be counted twice: ADVICE r04).
-    auto fold_null_rows = [&]() -> int {
-        if (!h->kn_valid) return 0;
-        const GTable& gt = h->g;
-        const uint64_t slot = gt.cap + 1;
-        dnull_fold_kernel<<<1, 64, 0, s>>>(flags + 8, gt.tag + slot,
-                                           a.hot_w_rows >= 0 ? gt.acc + (uint64_t)a.hot_w_rows * gt.stride + slot : nullptr,
-                                           a.hot_w_valid >= 0 ? gt.acc + (uint64_t)a.hot_w_valid * gt.stride + slot : nullptr,
-                                           a.hot_w_sum >= 0 ? gt.acc + (uint64_t)a.hot_w_sum * gt.stride + slot : nullptr,
-                                           a.hot_comp && a.hot_w_sum >= 0 ? (int64_t)gt.stride : 0);
-        VNM_HIP(hipGetLastError());
-        return 0;
-    };
-    if (h->kn_valid) {
-        if (ensure_table(h, 1024, s, true)) { release(); pool_free(spill); return 1; }
-        uint64_t* scr = (uint64_t*)(flags + 8);
+    d1.flags = b.flags; d1.spill = b.spill; d1.spill_cap = p.spill_cap;
+    d1.fx_q = p.fx_q; d1.fx_inv_q = p.fx ? std::ldexp(1.0, -h->fx_qe) : 0.0;
+    d1.fx_lim = p.w32 ? (1LL << 18) - 1 : 2147483647LL;
+    if (p.vn) { d1.vvalid = a.cols[0].validity; d1.voff = a.cols[0].offset; d1.nspill = b.nspill; d1.nspill_cap = p.nspill_cap; }
+    if (h->kn_valid) {   // the NULL-key rows go to scratch words of the flags block (fold_null_rows)
+        if (ensure_table(h, 1024, s, true)) return 1;
+        uint64_t* scr = (uint64_t*)(b.flags + 8);
         d1.kvalid = h->kn_valid; d1.koff = h->kn_off;
         d1.nk_tag = scr;
         d1.nk_rows = a.hot_w_rows >= 0 ? scr + 1 : nullptr;
@@ -1107,271 +1123,258 @@ int dense_partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hip
     }
     {
         KernelTimer timer("agg_part_scatter1", s);
-        if (fx && h->kn_valid) {
-            if (d1.has_pred && !d1.pred_is_v) VNM_DRING_FXX(true, false, true, w32_1, grid1, d1, rcap1); else VNM_DRING_FXX(false, false, true, w32_1, grid1, d1, rcap1);
-        } else if (fx && vn) {
-            VNM_DRING_FXX(false, true, false, w32_1, grid1, d1, rcap1);      // (vn_fold: the predicate column is the value column)
-        } else if (fx) {
-            if (d1.has_pred && !d1.pred_is_v) VNM_DRING_FX(true, true, w32_1, grid1, d1, rcap1); else VNM_DRING_FX(true, false, w32_1, grid1, d1, rcap1);
-        } else if (rcap1 && vn) {
-            if (c16_1) VNM_DRING_VN(uint16_t, grid1, d1, rcap1); else VNM_DRING_VN(uint32_t, grid1, d1, rcap1);
-        } else if (vn) {
-            if (c16_1) dpart_scatter_kernel<true, uint16_t, true, true><<<grid1, PT_BLOCK, 0, s>>>(d1);
-            else dpart_scatter_kernel<true, uint32_t, true, true><<<grid1, PT_BLOCK, 0, s>>>(d1);
-        } else if (rcap1) {
-            if (has_val) { if (c16_1) VNM_DRING(true, uint16_t, true, grid1, d1, rcap1); else VNM_DRING(true, uint32_t, true, grid1, d1, rcap1); }
-            else { if (c16_1) VNM_DRING(true, uint16_t, false, grid1, d1, rcap1); else VNM_DRING(true, uint32_t, false, grid1, d1, rcap1); }
-        } else if (has_val) {
-            if (c16_1) dpart_scatter_kernel<true, uint16_t><<<grid1, PT_BLOCK, 0, s>>>(d1);
-            else dpart_scatter_kernel<true, uint32_t><<<grid1, PT_BLOCK, 0, s>>>(d1);
-        } else {
-            if (c16_1) dpart_scatter_kernel<true, uint16_t, false><<<grid1, PT_BLOCK, 0, s>>>(d1);
-            else dpart_scatter_kernel<true, uint32_t, false><<<grid1, PT_BLOCK, 0, s>>>(d1);
-        }
+        VNM_TRY(dense_scatter1_launch(h, p, b, d1, s));
     }
     VNM_HIP(hipGetLastError());
-    const double* fin_v = v1; const void* fin_c = c1; const uint32_t* fin_n = n1;
-    int64_t fin_cap = cap1;
-    int fin_regions = grid1;
-    if (levels == 2) {
-        const int64_t per_pg = (int64_t)grid1 * rows_per_wg / np1 / split2;
-        int64_t cap2 = ((per_pg / np2 + per_pg / np2 / 4 + 256) + 15) & ~15LL;
-        if (env_i64("VNM_DENSE_ODD_CAP", 1) && ((cap2 / 16) & 1) == 0) cap2 += 16;
-        if (w32) { cap2 = (cap2 + 31) & ~31LL; if (((cap2 / 32) & 1) == 0) cap2 += 32; }   // (32-bit words: blocks of 32)
-        v2 = (double*)pool_alloc(has_val ? (size_t)np1 * np2 * split2 * cap2 * (w32 ? 4 : 8) : 8);
-        c2 = pool_alloc(fx ? 16 : (size_t)np1 * np2 * split2 * cap2 * 2);
-        n2 = (uint32_t*)pool_alloc((size_t)np1 * np2 * split2 * 4);
-        if (!v2 || !c2 || !n2) { release(); pool_free(spill); return 1; }
-        DPartArgs d2{};
-        d2.map = mp;
-        d2.in_vals = v1; d2.in_codes = (const uint32_t*)c1; d2.in_counts = n1; d2.in_cap = cap1;
-        d2.in_regions = grid1; d2.in_split = split2; d2.in_bits = mp.bits - p1;
-        d2.in_pstride = pmajor ? 1 : grid1; d2.in_rstride = pmajor ? np1 : 1;
-        d2.out_vals = v2; d2.out_codes = c2; d2.out_counts = n2; d2.out_cap = cap2;
-        d2.nparts = np2; d2.out_bits = tb;
-        d2.flags = flags; d2.spill = spill; d2.spill_cap = spill_cap;
-        d2.nspill = nspill; d2.nspill_cap = nspill_cap;
-        d2.nt_store = ((int)env_i64("VNM_DENSE_NT", 0) >> 1) & 1;
-        d2.ready_list = ((int)env_i64("VNM_DENSE_READY_LIST", 1) >> 1) & 1;   // (pass 2: every ring completes a block in every round -- the list only costs its atomics: 1.71 -> 1.78 ms)
-        d2.fx_q = d1.fx_q; d2.fx_inv_q = d1.fx_inv_q; d2.fx_lim = d1.fx_lim;
-        const int rcap2 = fx ? rcap2_fx : ((use_ring & 2) ? ring_cap_for(np2, (has_val ? 8 : 0) + 2) : 0);
-        // (32-bit words out of this level: 128 rings of up to 256 words take four pairs per lane in one round -- half the barriers: 1.74-1.76 -> 1.56 ms)
-        ring_pairs = (int)env_i64("VNM_DENSE_RING_PAIRS2", fx && w32 ? 4 : 2);
+    return 0;
+}
+
+// Stage 5: scatter level 2, every first-level partition -> np2 partitions.
+int dense_scatter2(const vnm_agg* h, const DensePlan& p, DenseBuffers& b, const DPartArgs& d1, hipStream_t s) {
+    b.take(b.v2, p.has_val ? (size_t)p.np1 * p.np2 * p.split2 * p.cap2 * (p.w32 ? 4 : 8) : 8);
+    b.take(b.c2, p.fx ? 16 : (size_t)p.np1 * p.np2 * p.split2 * p.cap2 * 2);
+    b.take(b.n2, (size_t)p.np1 * p.np2 * p.split2 * 4);
+    if (!b.v2 || !b.c2 || !b.n2) return 1;
+    DPartArgs d2{};
+    d2.map = h->dmap;
+    d2.in_vals = b.v1; d2.in_codes = (const uint32_t*)b.c1; d2.in_counts = b.n1; d2.in_cap = p.cap1;
+    d2.in_regions = p.grid1; d2.in_split = p.split2; d2.in_bits = h->dmap.bits - p.p1;
+    d2.in_pstride = p.pmajor ? 1 : p.grid1; d2.in_rstride = p.pmajor ? p.np1 : 1;
+    d2.out_vals = b.v2; d2.out_codes = b.c2; d2.out_counts = b.n2; d2.out_cap = p.cap2;
+    d2.nparts = p.np2; d2.out_bits = p.tb;
+    d2.flags = b.flags; d2.spill = b.spill; d2.spill_cap = p.spill_cap;
+    d2.nspill = b.nspill; d2.nspill_cap = p.nspill_cap;
+    d2.nt_store = ((int)env_i64("VNM_DENSE_NT", 0) >> 1) & 1;
+    d2.ready_list = ((int)env_i64("VNM_DENSE_READY_LIST", 1) >> 1) & 1;   // (pass 2: every ring completes a block in every round -- the list only costs its atomics: 1.71 -> 1.78 ms)
+    d2.fx_q = d1.fx_q; d2.fx_inv_q = d1.fx_inv_q; d2.fx_lim = d1.fx_lim;
+    const int grid2 = p.np1 * p.split2;
+    const RingLaunch r{grid2, p.rcap2, ring_sub_tile_pairs(p.ring_pairs2, false, p.ring_limit, p.np2, p.rcap2, p.w32), p.ring_limit, false, false, s};
+    {
+        KernelTimer timer("agg_part_scatter2", s);
+        if (p.fx) VNM_TRY(pick_bool(p.w32, [&](auto w32) { return ring_scatter<false, uint32_t, true, false, false, true, decltype(w32)::value>(r, d2); }));
+        else if (p.rcap2) VNM_TRY(pick_bool(p.has_val, [&](auto hv) { return ring_scatter<false, uint16_t, decltype(hv)::value, false, false>(r, d2); }));
+        else VNM_TRY(pick_bool(p.has_val, [&](auto hv) { dpart_scatter_kernel<false, uint16_t, decltype(hv)::value><<<grid2, PT_BLOCK, 0, s>>>(d2); return 0; }));
+    }
+    VNM_HIP(hipGetLastError());
+    return 0;
+}
+
+// Stage 6, COUNT(*) alone: byte counters over the level's partitions.
+int dense_final_count8(vnm_agg* h, const DensePlan& p, const DenseBuffers& b, DGenArgs& g, hipStream_t s) {
+    // one-byte counters that overflow (a group of 256 rows or more: flags[5]) hand the SAME entries to two-byte counters -- tables of at
+    // most 2^16 codes, so a partition may be read once more often -- before the batch would go back through two scatter levels
+    for (int cb = p.c8_cb;;) {
+        const int tbc = std::min(p.tb, cb == 8 ? DC8_BITS : DC8_BITS - 1), subc = p.c8_sub + (p.tb - tbc);
+        g.tbits = tbc;
+        const size_t lds = ((size_t)1 << tbc) * (size_t)(cb / 8);
         {
-            KernelTimer timer("agg_part_scatter2", s);
-            if (fx) VNM_DRING_FX(false, false, w32, np1 * split2, d2, rcap2);
-            else if (rcap2) { if (has_val) VNM_DRING(false, uint16_t, true, np1 * split2, d2, rcap2); else VNM_DRING(false, uint16_t, false, np1 * split2, d2, rcap2); }
-            else if (has_val) dpart_scatter_kernel<false, uint16_t><<<np1 * split2, PT_BLOCK, 0, s>>>(d2);
-            else dpart_scatter_kernel<false, uint16_t, false><<<np1 * split2, PT_BLOCK, 0, s>>>(d2);
+            KernelTimer timer("agg_part_final", s);
+            VNM_TRY(launch_resident(cb == 8 ? dcount8_final_kernel<8> : dcount8_final_kernel<16>, p.nfinal << subc, 1024, lds, 2, s, g, subc));
         }
         VNM_HIP(hipGetLastError());
-        fin_v = v2; fin_c = c2; fin_n = n2; fin_cap = cap2; fin_regions = split2;
+        if (cb == 16) break;
+        unsigned long long f6[6];
+        VNM_HIP(hipMemcpyAsync(f6, b.flags, sizeof(f6), hipMemcpyDeviceToHost, s));
+        VNM_HIP(hipStreamSynchronize(s));
+        if (!(f6[0] && f6[5])) break;
+        cb = 16;
+        h->count_cb = 16;
+        VNM_HIP(hipMemsetAsync(b.flags, 0, 16, s));          // [0] failure, [1] rows claimed ([2], the scatter's spill count, stays)
+        VNM_HIP(hipMemsetAsync(b.flags + 5, 0, 8, s));
     }
-#undef VNM_DRING_VN
-#undef VNM_DRING
-#undef VNM_DRING_P
-#undef VNM_DRING_B
-#undef VNM_DRING_FX
-#undef VNM_DRING_FXX
-#undef VNM_DRING_FXXW
-#undef VNM_DRING_FXXB
-#undef VNM_DRING_FXW
-#undef VNM_DRING_FXB
-    const int64_t nfinal = (int64_t)1 << pbits;
-    const int64_t dstride = std::min<int64_t>(h->dense_span, nrows) + 2;
-    rk = (uint64_t*)pool_alloc((size_t)dstride * 8 * 2);
-    ra = (uint64_t*)pool_alloc((size_t)dstride * 8 * h->plan.n_words);
-    if (!rk || !ra) { release(); pool_free(spill); pool_free(rk); pool_free(ra); return 1; }
+    return 0;
+}
+
+// Stage 6, generic programs: tables of 2^tb slots in dynamic LDS; few final partitions are shared by `fsplits` workgroups each
+// (partial tables + dgen_merge_kernel).
+int dense_final_generic(const DensePlan& p, DenseBuffers& b, DGenArgs& g, hipStream_t s) {
+    const size_t slots = (size_t)1 << p.tb;
+    const size_t lds = slots * dgen_slot_bytes(g);
+    if (p.fsplits > 1) {
+        const size_t work = (size_t)p.nfinal * p.fsplits;
+        g.part_w = (uint64_t*)b.pool.take(std::max<size_t>(8, work * g.n_lds * slots * 8));
+        g.part_cnt = (uint32_t*)b.pool.take(work * slots * 4);
+        if (!g.part_w || !g.part_cnt) return 1;
+        g.splits = p.fsplits;
+    }
+    KernelTimer timer("agg_part_final", s);
+    VNM_TRY(pick_bool(p.has_val, [&](auto hv) {
+        return pick_bool(p.fsplits > 1, [&](auto sp) {
+            return launch_resident(dgen_final_kernel<decltype(hv)::value, decltype(sp)::value>, p.nfinal * (decltype(sp)::value ? p.fsplits : 1), 512, lds, 8, s, g);
+        });
+    }));
+    if (p.fsplits > 1) dgen_merge_kernel<<<(int)(p.nfinal << (p.tb - 9)), 512, 0, s>>>(g);
+    return 0;
+}
+
+// Stage 6, few final partitions and a run of this call's own: `fsplits` workgroups per partition (partial tables + dpart_merge_kernel).
+int dense_final_split(const DensePlan& p, DenseBuffers& b, DFinalArgs& df, hipStream_t s) {
+    const size_t cells = (size_t)p.nfinal * p.fsplits << p.tb;
+    df.part_sum = (uint64_t*)b.pool.take(cells * 8); df.part_lo = (float*)b.pool.take(cells * 4); df.part_cnt = (uint32_t*)b.pool.take(cells * 4);
+    if (!df.part_sum || !df.part_lo || !df.part_cnt) return 1;
+    df.splits = p.fsplits;
+    KernelTimer timer("agg_part_final", s);
+    VNM_TRY((pick_int<9, 13>(p.tb >= 9 && p.tb <= 12 ? p.tb : 13, [&](auto tbc) {
+        constexpr int TB = decltype(tbc)::value;
+        return launch_resident(dpart_final_kernel<uint16_t, TB, true>, p.nfinal * p.fsplits, TB >= 13 ? 1024 : (TB == 12 ? VNM_DF12_BLOCK : 512), 0, 8, s, df);
+    })));
+    dpart_merge_kernel<<<(int)(p.nfinal << (p.tb - 9)), 512, 0, s>>>(df, p.tb);
+    return 0;
+}
+
+// Stage 6, the usual one: the final pass is DEFERRED -- what it should write depends on what comes next (complete_pending), and the
+// batches of a stream share ONE final pass.  The scatter passes have to be known good first; then the entries join the pending pass
+// of the handle.  0 = done, 2 = the scatter failed, DENSE_REDO = a fixed-point misfit (narrow -> wide -> float64 entries).
+int dense_defer_final(vnm_agg* h, const AggArgs& a, int64_t nrows, const DensePlan& p, DenseBuffers& b, const DSet& fin, DFinalArgs& df, hipStream_t s,
+                      ulonglong2** spill_out, int64_t* n_spill_out) {
+    const DenseMap& mp = h->dmap;
+    unsigned long long fl0[8];
+    VNM_HIP(hipMemcpyAsync(fl0, b.flags, 64, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));
+    route_note(h->kn_valid ? "dense:nullable_key" : (h->segs_active ? "dense:stream_segments" : (p.vn ? "dense:nullable_value" : (p.levels == 1 && p.p1 == 5 && p.tb <= 10 ? "dense:32_partitions" :
+               (p.fsplits > 1 ? "dense:split_final" : (p.levels == 2 ? "dense:two_levels" : "dense:one_level"))))),
+               "2^%d codes, 2^%d-slot final tables, p1 %d p2 %d, final pass deferred%s: %s", mp.bits, p.tb, p.p1, p.p2, p.vn ? ", nullable value" : "", fl0[0] || (p.fx && fl0[7]) ? "scatter FAILED (the batch goes another way)" : "ok");
+    if (getenv("VNM_AGG_TRACE"))
+        fprintf(stderr, "[agg] dense: bits %d tb %d levels %d p1 %d p2 %d -> scatter fail %llu spilled %llu, final pass deferred (bound %lld)\n",
+                mp.bits, p.tb, p.levels, p.p1, p.p2, fl0[0], fl0[2], (long long)p.dstride);
+    if (p.fx && fl0[7]) {   // a value that is not m * 2^qe with |m| < 2^31: float64 entries for this batch and every later one
+        if (h->fx_narrow) {   // (outside the 18 bits of the narrow words: 64-bit words with six more bits below the quantum and 13 more above)
+            h->fx_narrow = false;
+            h->fx_qe = std::max(h->fx_qe - 6, -1000);
+            route_note("dense:fixed_point_misfit", "a value outside 2^%d * [-2^18, 2^18): the batch is redone with 64-bit entry words", h->fx_qe + 6);
+            return DENSE_REDO;
+        }
+        h->fx_state = -1;
+        route_note("dense:fixed_point_misfit", "a value outside 2^%d * [-2^31, 2^31): the batch is redone with float64 entries", h->fx_qe);
+        return DENSE_REDO;
+    }
+    if (fl0[0]) return 2;
+    if (p.fx) route_note("dense:fixed_point", "%s entry words, quantum 2^%d", p.w32 ? (p.levels == 1 ? "4-byte" : "8-byte, then 4-byte") : "8-byte", h->fx_qe);
+    if (fold_null_rows(h, a, b.flags, s)) return 1;
+    b.pool.done(b.rk); b.pool.done(b.ra);   // (the run is allocated when the pass runs)
+    if (fl0[2]) { b.pool.keep(b.spill); *spill_out = b.spill; *n_spill_out = (int64_t)fl0[2]; }   // the caller owns it now
+    else { *spill_out = nullptr; *n_spill_out = 0; }
+    if ((int64_t)fl0[2] > nrows / 16) h->dense_state = -1;
+    DensePending* pd = h->pending;
+    // batches join a pending pass of the same geometry; anything else (or a very long stream) runs it first.  A pass holds the
+    // entries of its batches (10-12 bytes per row) until it runs: at most 1.5 * 2^30 rows of them, so that a stream of any length
+    // keeps a bounded amount of HBM (and far below the 2^32 rows the 32-bit row counts of the final pass's slots could take)
+    const int64_t pending_max_rows = std::min<int64_t>(env_i64("VNM_DENSE_PENDING_MAX_ROWS", 3LL << 29), (1LL << 32) - 1);
+    if (pd && (pd->tb != p.tb || pd->levels != p.levels || pd->p1 != p.p1 || pd->fsplits != p.fsplits || pd->sets.size() >= DP_MAX_SETS ||
+               pd->rows + nrows > pending_max_rows || pd->df.fx_q != p.fx_q || pd->df.fx_w32 != (p.w32 ? 1 : 0) || memcmp(&pd->df.map, &mp, sizeof(DenseMap)) != 0)) {
+        VNM_TRY(complete_pending(h, s));
+        pd = nullptr;
+    }
+    if (!pd) {
+        pd = new DensePending();
+        df.dkey = nullptr; df.dacc = nullptr;
+        pd->df = df; pd->tb = p.tb; pd->levels = p.levels; pd->p1 = p.p1; pd->fsplits = p.fsplits; pd->nfinal = p.nfinal; pd->dstride = 0;
+        b.pool.keep(b.flags); pd->blocks.push_back(b.flags);   // the pass's flags block from here on
+        h->pending = pd;
+    }
+    pd->dstride = std::min<int64_t>(h->dense_span, pd->dstride + nrows) + 2;
+    pd->rows += nrows;
+    // exact-add statistics of this batch's entries (kept by the ring scatter over plain value columns only)
+    if (p.rcap1 && p.has_val && !a.has_expr && !p.fx) { pd->x_inv = std::max(pd->x_inv, (uint32_t)fl0[6]); pd->x_exp = std::max(pd->x_exp, (uint32_t)(fl0[6] >> 32)); }
+    else pd->x_known = false;
+    pd->sets.push_back(fin);
+    // the entries belong to the pass (two levels: the first level's regions have been consumed by the second scatter pass)
+    void* const held[3] = {p.levels == 2 ? (void*)b.v2 : (void*)b.v1, p.levels == 2 ? b.c2 : b.c1, p.levels == 2 ? (void*)b.n2 : (void*)b.n1};
+    for (void* blk : held) { b.pool.keep(blk); pd->blocks.push_back(blk); }
+    return 0;
+}
+
+// Stage 7 (the passes that wrote a run of their own): read the flags, hand the run to the handle and the lists to the caller.
+// 0 = done, 2 = failed (the batch goes another way), DENSE_REDO = byte counters overflowed (two scatter levels take the batch).
+int dense_hand_over(vnm_agg* h, const AggArgs& a, int64_t nrows, const DensePlan& p, DenseBuffers& b, hipStream_t s, ulonglong2** spill_out, int64_t* n_spill_out,
+                    uint64_t** nspill_out, int64_t* n_nspill_out) {
+    VNM_HIP(hipGetLastError());
+    unsigned long long fl[4];
+    VNM_HIP(hipMemcpyAsync(fl, b.flags, 32, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));
+    if (!fl[0]) {
+        if (fold_null_rows(h, a, b.flags, s)) return 1;
+        VNM_HIP(hipStreamSynchronize(s));   // (the fold reads the flags block, which goes back when this attempt's owner does)
+    }
+    route_note(p.count8 ? "dense:count_bytes" : p.generic ? (p.fsplits > 1 ? "dense:generic_split_final" : "dense:generic") : (p.vn ? "dense:nullable_value" : (p.fsplits > 1 ? "dense:split_final" : "dense:run")),
+               "2^%d codes, 2^%d-slot final tables, levels %d, p1 %d p2 %d, %d final splits: %s", h->dmap.bits, p.tb, p.levels, p.p1, p.p2, p.fsplits, fl[0] ? "FAILED (the batch goes another way)" : "ok");
+    if (getenv("VNM_AGG_TRACE"))
+        fprintf(stderr, "[agg] dense%s%s: bits %d tb %d levels %d p1 %d p2 %d splits %d -> fail %llu groups %llu spilled %llu + %llu NULL-value rows (dstride %lld)\n",
+                p.generic ? " generic" : "", p.vn ? " nullable" : "", h->dmap.bits, p.tb, p.levels, p.p1, p.p2, p.fsplits, fl[0], fl[1], fl[2], fl[3], (long long)p.dstride);
+    if (fl[0]) {  // spill buffer full, dense output too small, or a compensation term beyond float range
+        if (!p.count8) return 2;
+        h->count8_off = true;   // (a group of 256 rows or more, most likely: flags[5]) the two scatter levels take the batch, and every later one
+        return DENSE_REDO;
+    }
+    if (fl[2]) { b.pool.keep(b.spill); *spill_out = b.spill; *n_spill_out = (int64_t)fl[2]; }   // the caller owns the lists now
+    else { *spill_out = nullptr; *n_spill_out = 0; }
+    if (p.vn && fl[3]) { b.pool.keep(b.nspill); *nspill_out = b.nspill; *n_nspill_out = (int64_t)fl[3]; }
+    if ((int64_t)(fl[2] + fl[3]) > nrows / 16) h->dense_state = -1;  // the sampled range does not describe the data: stop trying
+    b.pool.keep(b.rk); b.pool.keep(b.ra);   // the run belongs to the handle
+    h->run_key = b.rk; h->run_acc = b.ra; h->run_stride = p.dstride; h->run_n = (int64_t)fl[1];
+    h->run_dir = nullptr; h->run_nfin = 0;
+    h->have_run = true;
+    return 0;
+}
+
+// The driver.  returns 0 = done (run stored), 2 = not applicable / failed (caller continues with the hash-partitioned path), 1 = error
+// (nspill_out / n_nspill_out: keys of NULL-value rows that found no place -- nullable value column, generic programs only)
+int dense_partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_t s, ulonglong2** spill_out, int64_t* n_spill_out,
+                                bool generic = false, uint64_t** nspill_out = nullptr, int64_t* n_nspill_out = nullptr, bool vn_fold = false) {
+    DGenArgs g{};
+    if (generic && !dgen_program(h, a, &g)) return 2;
+    DensePlan p{};
+    VNM_TRY(plan_dense_entries(h, a, generic, g, vn_fold, nspill_out != nullptr, &p));
+    if (nspill_out) { *nspill_out = nullptr; *n_nspill_out = 0; }
+    if (p.fx_base && h->fx_state == 0) VNM_TRY(sample_fixed_point(h, a, nrows, s));
+    VNM_TRY(plan_dense_geometry(h, a, nrows, g, &p));
+    DenseBuffers b;
+    // the same batch once more, by what the handle says now: the blocks go back first, so that the retry finds them
+    auto redo = [&]() { b.free_all(); return dense_partitioned_aggregate(h, a, nrows, s, spill_out, n_spill_out, generic, nspill_out, n_nspill_out, vn_fold); };
+    VNM_TRY(dense_allocate(p, b, s));
+    if (p.fx && (!p.rcap1 || (p.levels == 2 && !p.rcap2))) { h->fx_state = -1; return redo(); }   // (a fan-out the rings cannot take: float64 entries through the other scatter)
+    if ((h->segs_active || h->kn_valid) && (!p.rcap1 || p.vn)) return 2;   // (only the ring scatter reads segments / key validity)
+    DPartArgs d1{};
+    VNM_TRY(dense_scatter1(h, a, nrows, p, b, d1, s));
+    if (p.levels == 2) VNM_TRY(dense_scatter2(h, p, b, d1, s));
+    // the entries the final pass reads: the last level's regions
+    DSet fin{b.v1, b.c1, b.n1, p.cap1, p.grid1, 1, p.grid1, 0};
+    if (p.levels == 2) fin = DSet{b.v2, b.c2, b.n2, p.cap2, p.split2, 1, p.split2, 0};
+    else if (p.pmajor) { fin.pstride = 1; fin.rstride = p.np1; }
+    fin.pad = fin.cap < 2048 ? 1 : 0;   // small regions: one wave per region in the final pass
+    b.take(b.rk, (size_t)p.dstride * 8 * 2);
+    b.take(b.ra, (size_t)p.dstride * 8 * h->plan.n_words);
+    if (!b.rk || !b.ra) return 1;
     DFinalArgs df{};
-    df.map = mp;
-    df.vals = fin_v; df.codes = fin_c; df.counts = fin_n; df.cap = fin_cap; df.regions = fin_regions; df.nfinal = nfinal;
-    df.pstride = fin_regions; df.rstride = 1;
-    if (levels == 1 && pmajor) { df.pstride = 1; df.rstride = np1; }
+    df.map = h->dmap;
+    df.vals = fin.vals; df.codes = fin.codes; df.counts = fin.counts; df.cap = fin.cap; df.regions = fin.regions; df.nfinal = p.nfinal;
+    df.pstride = fin.pstride; df.rstride = fin.rstride;
     df.w_rows = a.hot_w_rows; df.w_valid = a.hot_w_valid; df.w_sum = a.hot_w_sum;
     df.w_lo = a.hot_comp && a.hot_w_sum >= 0 ? a.hot_w_sum + 1 : -1;
-    df.dkey = rk; df.dacc = ra; df.dstride = dstride; df.flags = flags;
-    df.fx_q = fx_q; df.fx_w32 = w32 ? 1 : 0;
-    uint64_t* psum = nullptr; float* plo = nullptr; uint32_t* pcnt = nullptr;
+    df.dkey = b.rk; df.dacc = b.ra; df.dstride = p.dstride; df.flags = b.flags;
+    df.fx_q = p.fx_q; df.fx_w32 = p.w32 ? 1 : 0;
     // the branches that write a run of their own: a pending (deferred) pass of earlier batches runs first and its run makes room
     const bool own_run = generic || !env_i64("VNM_DENSE_DEFER", 1);
     if (own_run && h->pending) {
         int rc = complete_pending(h, s);
         if (!rc) rc = merge_run_into_table(h, s);
-        if (rc) { release(); pool_free(spill); pool_free(rk); pool_free(ra); return 1; }
+        if (rc) return 1;
     }
-    if (count8) {
-        g.map = mp; g.tbits = tb;
-        g.pstride = df.pstride; g.rstride = df.rstride;
-        g.vals = nullptr; g.codes = fin_c; g.counts = fin_n; g.cap = fin_cap; g.regions = fin_regions; g.nfinal = nfinal;
-        g.dkey = rk; g.dacc = ra; g.dstride = dstride; g.flags = flags;
-        // one-byte counters that overflow (a group of 256 rows or more: flags[5]) hand the SAME entries to two-byte counters -- tables of at
-        // most 2^16 codes, so a partition may be read once more often -- before the batch would go back through two scatter levels
-        for (int cb = c8_cb;;) {
-            const int tbc = std::min(tb, cb == 8 ? DC8_BITS : DC8_BITS - 1), subc = c8_sub + (tb - tbc);
-            g.tbits = tbc;
-            const size_t lds = ((size_t)1 << tbc) * (size_t)(cb / 8);
-            auto kern = cb == 8 ? dcount8_final_kernel<8> : dcount8_final_kernel<16>;
-            {
-                KernelTimer timer("agg_part_final", s);
-                VNM_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                int occ = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)kern, 1024, lds) != hipSuccess || occ < 1) occ = 1;
-                const int g3 = (int)std::min<int64_t>(nfinal << subc, (int64_t)cus * std::min(occ, 2));
-                kern<<<g3, 1024, lds, s>>>(g, subc);
-            }
-            VNM_HIP(hipGetLastError());
-            if (cb == 16) break;
-            unsigned long long f6[6];
-            VNM_HIP(hipMemcpyAsync(f6, flags, sizeof(f6), hipMemcpyDeviceToHost, s));
-            VNM_HIP(hipStreamSynchronize(s));
-            if (!(f6[0] && f6[5])) break;
-            cb = 16;
-            h->count_cb = 16;
-            VNM_HIP(hipMemsetAsync(flags, 0, 16, s));          // [0] failure, [1] rows claimed ([2], the scatter's spill count, stays)
-            VNM_HIP(hipMemsetAsync(flags + 5, 0, 8, s));
-        }
-    } else if (generic) {
-        const size_t slots = (size_t)1 << tb;
-        const size_t lds = slots * dgen_slot_bytes(g);
-        g.map = mp; g.tbits = tb;
-        g.pstride = df.pstride; g.rstride = df.rstride;
-        g.vals = fin_v; g.codes = fin_c; g.counts = fin_n; g.cap = fin_cap; g.regions = fin_regions; g.nfinal = nfinal;
-        g.dkey = rk; g.dacc = ra; g.dstride = dstride; g.flags = flags;
-        if (fsplits > 1) {
-            const size_t work = (size_t)nfinal * fsplits;
-            psum = (uint64_t*)pool_alloc(std::max<size_t>(8, work * g.n_lds * slots * 8));
-            pcnt = (uint32_t*)pool_alloc(work * slots * 4);
-            if (!psum || !pcnt) { release(); pool_free(spill); pool_free(rk); pool_free(ra); pool_free(psum); pool_free(pcnt); return 1; }
-            g.splits = fsplits; g.part_w = psum; g.part_cnt = pcnt;
-        }
-        KernelTimer timer("agg_part_final", s);
-#define VNM_DGFIN(HV_, SP_)                                                                                            \
-    do {                                                                                                              \
-        VNM_HIP(hipFuncSetAttribute((const void*)dgen_final_kernel<HV_, SP_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        int occ = 0;                                                                                                  \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)dgen_final_kernel<HV_, SP_>, 512, lds) != hipSuccess || occ < 1) occ = 1; \
-        const int g3 = (int)std::min<int64_t>(nfinal * (SP_ ? fsplits : 1), (int64_t)cus * std::min(occ, 8));         \
-        dgen_final_kernel<HV_, SP_><<<g3, 512, lds, s>>>(g);                                                          \
-    } while (0)
-        if (fsplits > 1) {
-            if (has_val) VNM_DGFIN(true, true); else VNM_DGFIN(false, true);
-            dgen_merge_kernel<<<(int)(nfinal << (tb - 9)), 512, 0, s>>>(g);
-        } else {
-            if (has_val) VNM_DGFIN(true, false); else VNM_DGFIN(false, false);
-        }
-#undef VNM_DGFIN
-    } else if (fsplits > 1 && own_run) {
-        const size_t cells = (size_t)nfinal * fsplits << tb;
-        psum = (uint64_t*)pool_alloc(cells * 8); plo = (float*)pool_alloc(cells * 4); pcnt = (uint32_t*)pool_alloc(cells * 4);
-        if (!psum || !plo || !pcnt) { release(); pool_free(spill); pool_free(rk); pool_free(ra); pool_free(psum); pool_free(plo); pool_free(pcnt); return 1; }
-        df.splits = fsplits; df.part_sum = psum; df.part_lo = plo; df.part_cnt = pcnt;
-        KernelTimer timer("agg_part_final", s);
-#define VNM_DFINS(TB_)                                                                                                 \
-    do {                                                                                                              \
-        const int blk = TB_ >= 13 ? 1024 : (TB_ == 12 ? VNM_DF12_BLOCK : 512);                                       \
-        int occ = 0;                                                                                                  \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)dpart_final_kernel<uint16_t, TB_, true>, blk, 0) != hipSuccess || occ < 1) occ = 1; \
-        const int g3 = (int)std::min<int64_t>(nfinal * fsplits, (int64_t)cus * std::min(occ, 8));                     \
-        dpart_final_kernel<uint16_t, TB_, true><<<g3, blk, 0, s>>>(df);                                               \
-    } while (0)
-        if (tb == 9) VNM_DFINS(9); else if (tb == 10) VNM_DFINS(10); else if (tb == 11) VNM_DFINS(11); else if (tb == 12) VNM_DFINS(12); else VNM_DFINS(13);
-#undef VNM_DFINS
-        dpart_merge_kernel<<<(int)(nfinal << (tb - 9)), 512, 0, s>>>(df, tb);
-    } else if (env_i64("VNM_DENSE_DEFER", 1)) {
-        // The final pass is DEFERRED: what it should write depends on what comes next (complete_pending), and the batches of a
-        // stream share ONE final pass.  The scatter passes have to be known good first.
-        unsigned long long fl0[8];
-        VNM_HIP(hipMemcpyAsync(fl0, flags, 64, hipMemcpyDeviceToHost, s));
-        VNM_HIP(hipStreamSynchronize(s));
-        route_note(h->kn_valid ? "dense:nullable_key" : (h->segs_active ? "dense:stream_segments" : (vn ? "dense:nullable_value" : (levels == 1 && p1 == 5 && tb <= 10 ? "dense:32_partitions" :
-                   (fsplits > 1 ? "dense:split_final" : (levels == 2 ? "dense:two_levels" : "dense:one_level"))))),
-                   "2^%d codes, 2^%d-slot final tables, p1 %d p2 %d, final pass deferred%s: %s", mp.bits, tb, p1, p2, vn ? ", nullable value" : "", fl0[0] || (fx && fl0[7]) ? "scatter FAILED (the batch goes another way)" : "ok");
-        if (getenv("VNM_AGG_TRACE"))
-            fprintf(stderr, "[agg] dense: bits %d tb %d levels %d p1 %d p2 %d -> scatter fail %llu spilled %llu, final pass deferred (bound %lld)\n",
-                    mp.bits, tb, levels, p1, p2, fl0[0], fl0[2], (long long)dstride);
-        if (fx && fl0[7]) {   // a value that is not m * 2^qe with |m| < 2^31: float64 entries for this batch and every later one
-            release(); pool_free(rk); pool_free(ra); pool_free(spill);
-            if (h->fx_narrow) {   // (outside the 18 bits of the narrow words: 64-bit words with six more bits below the quantum and 13 more above)
-                h->fx_narrow = false;
-                h->fx_qe = std::max(h->fx_qe - 6, -1000);
-                route_note("dense:fixed_point_misfit", "a value outside 2^%d * [-2^18, 2^18): the batch is redone with 64-bit entry words", h->fx_qe + 6);
-                return dense_partitioned_aggregate(h, a, nrows, s, spill_out, n_spill_out, generic, nspill_out, n_nspill_out, vn_fold);
-            }
-            h->fx_state = -1;
-            route_note("dense:fixed_point_misfit", "a value outside 2^%d * [-2^31, 2^31): the batch is redone with float64 entries", h->fx_qe);
-            return dense_partitioned_aggregate(h, a, nrows, s, spill_out, n_spill_out, generic, nspill_out, n_nspill_out, vn_fold);
-        }
-        if (fl0[0]) { release(); pool_free(rk); pool_free(ra); pool_free(spill); return 2; }
-        if (fx) route_note("dense:fixed_point", "%s entry words, quantum 2^%d", w32 ? (levels == 1 ? "4-byte" : "8-byte, then 4-byte") : "8-byte", h->fx_qe);
-        if (fold_null_rows()) { release(); pool_free(rk); pool_free(ra); pool_free(spill); return 1; }
-        pool_free(rk); pool_free(ra);   // (the run is allocated when the pass runs)
-        if (fl0[2]) { *spill_out = spill; *n_spill_out = (int64_t)fl0[2]; }
-        else { pool_free(spill); *spill_out = nullptr; *n_spill_out = 0; }
-        if ((int64_t)fl0[2] > nrows / 16) h->dense_state = -1;
-        DensePending* pd = h->pending;
-        // batches join a pending pass of the same geometry; anything else (or a very long stream) runs it first.  A pass holds the
-        // entries of its batches (10-12 bytes per row) until it runs: at most 1.5 * 2^30 rows of them, so that a stream of any length
-        // keeps a bounded amount of HBM (and far below the 2^32 rows the 32-bit row counts of the final pass's slots could take)
-        const int64_t pending_max_rows = std::min<int64_t>(env_i64("VNM_DENSE_PENDING_MAX_ROWS", 3LL << 29), (1LL << 32) - 1);
-        if (pd && (pd->tb != tb || pd->levels != levels || pd->p1 != p1 || pd->fsplits != fsplits || pd->sets.size() >= DP_MAX_SETS ||
-                   pd->rows + nrows > pending_max_rows || pd->df.fx_q != fx_q || pd->df.fx_w32 != (w32 ? 1 : 0) || memcmp(&pd->df.map, &mp, sizeof(DenseMap)) != 0)) {
-            const int rc = complete_pending(h, s);
-            if (rc) { release(); return rc; }
-            pd = nullptr;
-        }
-        if (!pd) {
-            pd = new DensePending();
-            df.dkey = nullptr; df.dacc = nullptr;
-            pd->df = df; pd->tb = tb; pd->levels = levels; pd->p1 = p1; pd->fsplits = fsplits; pd->nfinal = nfinal; pd->dstride = 0;
-            pd->blocks.push_back(flags);
-            h->pending = pd;
-        } else pool_free(flags);
-        pd->dstride = std::min<int64_t>(h->dense_span, pd->dstride + nrows) + 2;
-        pd->rows += nrows;
-        // exact-add statistics of this batch's entries (kept by the ring scatter over plain value columns only)
-        if (rcap1 && has_val && !a.has_expr && !fx) { pd->x_inv = std::max(pd->x_inv, (uint32_t)fl0[6]); pd->x_exp = std::max(pd->x_exp, (uint32_t)(fl0[6] >> 32)); }
-        else pd->x_known = false;
-        DSet st{};
-        st.vals = fin_v; st.codes = fin_c; st.counts = fin_n; st.cap = fin_cap; st.pstride = df.pstride; st.rstride = df.rstride; st.regions = fin_regions;
-        st.pad = fin_cap < 2048 ? 1 : 0;   // small regions: one wave per region in the final pass
-        pd->sets.push_back(st);
-        if (levels == 2) {   // the first level's regions have been consumed by the second scatter pass
-            pool_free(v1); pool_free(c1); pool_free(n1);
-            pd->blocks.push_back(v2); pd->blocks.push_back(c2); pd->blocks.push_back(n2);
-        } else { pd->blocks.push_back(v1); pd->blocks.push_back(c1); pd->blocks.push_back(n1); }
-        return 0;
-    } else {
-        VNM_TRY(launch_dense_final(df, tb, DF_RUN, false, s));
+    if (generic) {   // (count8 included: the generic kernels' view of the entries and the run)
+        g.map = h->dmap; g.tbits = p.tb;
+        g.pstride = fin.pstride; g.rstride = fin.rstride;
+        g.vals = p.count8 ? nullptr : fin.vals; g.codes = fin.codes; g.counts = fin.counts; g.cap = fin.cap; g.regions = fin.regions; g.nfinal = p.nfinal;
+        g.dkey = b.rk; g.dacc = b.ra; g.dstride = p.dstride; g.flags = b.flags;
     }
-    VNM_HIP(hipGetLastError());
-    unsigned long long fl[4];
-    VNM_HIP(hipMemcpyAsync(fl, flags, 32, hipMemcpyDeviceToHost, s));
-    VNM_HIP(hipStreamSynchronize(s));
-    if (!fl[0] && fold_null_rows()) { release(); pool_free(psum); pool_free(plo); pool_free(pcnt); pool_free(rk); pool_free(ra); pool_free(spill); return 1; }
-    if (!fl[0]) VNM_HIP(hipStreamSynchronize(s));   // (the fold reads the flags block release() gives back)
-    release();
-    pool_free(psum); pool_free(plo); pool_free(pcnt);
-    route_note(count8 ? "dense:count_bytes" : generic ? (fsplits > 1 ? "dense:generic_split_final" : "dense:generic") : (vn ? "dense:nullable_value" : (fsplits > 1 ? "dense:split_final" : "dense:run")),
-               "2^%d codes, 2^%d-slot final tables, levels %d, p1 %d p2 %d, %d final splits: %s", mp.bits, tb, levels, p1, p2, fsplits, fl[0] ? "FAILED (the batch goes another way)" : "ok");
-    if (getenv("VNM_AGG_TRACE"))
-        fprintf(stderr, "[agg] dense%s%s: bits %d tb %d levels %d p1 %d p2 %d splits %d -> fail %llu groups %llu spilled %llu + %llu NULL-value rows (dstride %lld)\n",
-                generic ? " generic" : "", vn ? " nullable" : "", mp.bits, tb, levels, p1, p2, fsplits, fl[0], fl[1], fl[2], fl[3], (long long)dstride);
-    if (fl[0]) {  // spill buffer full, dense output too small, or a compensation term beyond float range
-        pool_free(rk); pool_free(ra); pool_free(spill);
-        if (count8) {   // (a group of 256 rows or more, most likely: flags[5]) the two scatter levels take the batch, and every later one
-            h->count8_off = true;
-            return dense_partitioned_aggregate(h, a, nrows, s, spill_out, n_spill_out, generic, nspill_out, n_nspill_out, vn_fold);
-        }
-        return 2;
-    }
-    if (fl[2]) { *spill_out = spill; *n_spill_out = (int64_t)fl[2]; }
-    else { pool_free(spill); *spill_out = nullptr; *n_spill_out = 0; }
-    if (vn && fl[3]) { *nspill_out = nspill; *n_nspill_out = (int64_t)fl[3]; nspill = nullptr; }
-    if ((int64_t)(fl[2] + fl[3]) > nrows / 16) h->dense_state = -1;  // the sampled range does not describe the data: stop trying
-    h->run_key = rk; h->run_acc = ra; h->run_stride = dstride; h->run_n = (int64_t)fl[1];
-    h->run_dir = nullptr; h->run_nfin = 0;
-    h->have_run = true;
-    return 0;
+    if (p.count8) VNM_TRY(dense_final_count8(h, p, b, g, s));
+    else if (generic) VNM_TRY(dense_final_generic(p, b, g, s));
+    else if (p.fsplits > 1 && own_run) VNM_TRY(dense_final_split(p, b, df, s));
+    else if (env_i64("VNM_DENSE_DEFER", 1)) {
+        const int rc = dense_defer_final(h, a, nrows, p, b, fin, df, s, spill_out, n_spill_out);
+        return rc == DENSE_REDO ? redo() : rc;
+    } else VNM_TRY(launch_dense_final(df, p.tb, DF_RUN, false, s));
+    const int rc = dense_hand_over(h, a, nrows, p, b, s, spill_out, n_spill_out, nspill_out, n_nspill_out);
+    return rc == DENSE_REDO ? redo() : rc;
 }
 
 
@@ -1436,18 +1439,13 @@ int dense_two_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_t
     d1.nt_store = 1;
     d1.ready_list = (int)env_i64("VNM_DENSE_READY_LIST", 1) & 1;
     d1.flags = flags; d1.spill = nullptr; d1.spill_cap = 0;
-#define VNM_DRING2(FR_, CT_, PR_, PV_, GRID_, ARGS_, CAP_)                                                                       \
-    do {                                                                                                                        \
-        const size_t lds_ = (((size_t)(ARGS_).nparts * (CAP_) * (16 + sizeof(CT_))) + 15) & ~(size_t)15;                         \
-        VNM_HIP(hipFuncSetAttribute((const void*)dring_scatter_kernel<FR_, CT_, true, 1024, PR_, PV_, false, 0, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-        dring_scatter_kernel<FR_, CT_, true, 1024, PR_, PV_, false, 0, false, false, true><<<GRID_, 1024, lds_, s>>>(ARGS_, CAP_); \
-    } while (0)
-    {
+    {   // (two-value entries, V2: no round limit, no segments; two pairs of rows per lane where an even spread of the sub-tile fits one round)
         KernelTimer timer("agg_part_scatter1", s);
-        const bool pv = h->pred_set && !a.hot_pred_is_v;
-        const bool two_pairs = 2 * 2 * 1024 <= np1 * (rcap1 - DR_FB);
-        if (pv) { if (two_pairs) VNM_DRING2(true, uint32_t, 2, true, grid1, d1, rcap1); else VNM_DRING2(true, uint32_t, 1, true, grid1, d1, rcap1); }
-        else { if (two_pairs) VNM_DRING2(true, uint32_t, 2, false, grid1, d1, rcap1); else VNM_DRING2(true, uint32_t, 1, false, grid1, d1, rcap1); }
+        VNM_TRY(pick_bool(h->pred_set && !a.hot_pred_is_v, [&](auto pv) {
+            return pick_bool(ring_one_round(2, np1, rcap1, false), [&](auto two) {
+                return launch_ring<true, uint32_t, true, decltype(two)::value ? 2 : 1, decltype(pv)::value, false, 0, false, false, true, false, false>(grid1, d1, rcap1, s);
+            });
+        }));
     }
     VNM_HIP(hipGetLastError());
     DPartArgs d2{};
@@ -1460,10 +1458,10 @@ int dense_two_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_t
     d2.flags = flags; d2.spill = nullptr; d2.spill_cap = 0;
     {
         KernelTimer timer("agg_part_scatter2", s);
-        if (2 * 2 * 1024 <= np2 * (rcap2 - DR_FB)) VNM_DRING2(false, uint16_t, 2, false, np1 * split2, d2, rcap2);
-        else VNM_DRING2(false, uint16_t, 1, false, np1 * split2, d2, rcap2);
+        VNM_TRY(pick_bool(ring_one_round(2, np2, rcap2, false), [&](auto two) {
+            return launch_ring<false, uint16_t, true, decltype(two)::value ? 2 : 1, false, false, 0, false, false, true, false, false>(np1 * split2, d2, rcap2, s);
+        }));
     }
-#undef VNM_DRING2
     VNM_HIP(hipGetLastError());
     DFinalArgs df{};
     df.map = mp;
