@@ -455,6 +455,79 @@ def test_topk_multi_key_equals_full_sort_prefix(shape, k):
         util.assert_batches_equal(got, exp, what=f"multi-key topk {shape} k={k} orders={orders}")
 
 
+def _route_count(route):
+    import ctypes
+    from vinum_amd import _lib as L
+    buf = ctypes.create_string_buffer(int(L.lib().vnm_route_counts(None, 0)) + 16)
+    L.lib().vnm_route_counts(buf, len(buf))
+    for line in buf.value.decode().splitlines():
+        name, _, count = line.rpartition("=")
+        if name == route:
+            return int(count)
+    return 0
+
+
+# case: (n, k, keys, every key equal, VNM_SORT_NO_SMALL), then which timed spans fire and whether the LSD passes answer
+_TOPK_ROUTES = {
+    "block_winners_small_sort": ((300_000, 10, 1, False, False),
+                                 dict(topk_sample=True, topk_select=True, topk_small_sort=True, radix_pass=False, sort_encode=False, lsd=False)),
+    "sorted_sample_small_sort": ((70_000, 10, 1, False, False),
+                                 dict(topk_sample=False, topk_select=True, topk_small_sort=True, radix_pass=True, sort_encode=False, lsd=False)),
+    "sorted_sample_radix_groups": ((2_000_000, 50_000, 1, False, False),
+                                   dict(topk_sample=False, topk_select=True, topk_small_sort=False, radix_pass=True, sort_encode=False, lsd=False)),
+    "block_winners_radix_groups": ((300_000, 10, 1, False, True),
+                                   dict(topk_sample=True, topk_select=True, topk_small_sort=False, radix_pass=True, sort_encode=False, lsd=False)),
+    "candidates_outgrow_cap": ((1_100_000, 1000, 1, True, False),
+                               dict(topk_sample=False, topk_select=True, topk_small_sort=False, radix_pass=False, sort_encode=True, lsd=True)),
+    "two_keys": ((300_000, 10, 2, False, False),
+                 dict(topk_sample=True, topk_select=True, topk_small_sort=False, radix_pass=True, sort_encode=True, lsd=False)),
+}
+
+
+@pytest.mark.parametrize("case", list(_TOPK_ROUTES))
+def test_topk_takes_the_expected_finder_and_finisher(case, monkeypatch):
+    """LIMIT K finds its threshold one of two ways and finishes the candidates one of three (vnm_sort.hip); the results are the same
+    whichever ran, so this pins WHICH ran, by the timed spans that fired and by whether the sort:lsd_radix note was written:
+      * threshold: the block winners (topk_sample) when the sample has 4096 * 64 keys and the rank is below 1024, else a radix-sorted
+        2^18-key sample (radix_pass, no topk_sample);
+      * finisher: one workgroup in LDS (topk_small_sort) up to 8192 candidates, else three radix pass groups (radix_pass); several
+        keys: the candidates through the multi-key sort (sort_encode, no sort:lsd_radix note);
+      * more candidates than the buffer holds (at least 2^20, so the column of equal keys has more rows than that; its codes
+        have no digit to sort by: no radix_pass anywhere): the LSD passes over the whole column answer.
+    The first K row ids are those of the stable full sort."""
+    import ctypes
+    import torch
+    from vinum_amd import _lib as L
+    from vinum_amd import ops
+    from vinum_amd.device import DeviceColumn
+    (n, k, n_keys, equal, no_small), expected = _TOPK_ROUTES[case]
+    rng = np.random.default_rng(n + k)
+    v = np.full(n, 2.5) if equal else rng.normal(11.0, 9.0, n)
+    cols = [DeviceColumn.from_torch(torch.from_numpy(v).cuda())]
+    if n_keys == 2:
+        cols.append(DeviceColumn.from_torch(torch.from_numpy(rng.integers(-50, 50, n).astype(np.float64)).cuda()))
+    orders = [L.ASC] * n_keys
+    monkeypatch.setenv("VNM_SORT_NO_TOPK", "1")
+    ref = torch.as_tensor(_RawI64(ops.sort_indices(cols, orders, limit=k).ptr, n), device="cuda")[:k].clone()
+    monkeypatch.delenv("VNM_SORT_NO_TOPK")
+    if no_small:
+        monkeypatch.setenv("VNM_SORT_NO_SMALL", "1")
+    lsd_before = _route_count("sort:lsd_radix")
+    L.lib().vnm_set_profiling(1)
+    idx = ops.sort_indices(cols, orders, limit=k)
+    fired = {}
+    for name in expected:
+        if name != "lsd":
+            ms, count = ctypes.c_double(0), ctypes.c_int64(0)
+            L.lib().vnm_profile_query(name.encode(), ctypes.byref(ms), ctypes.byref(count))
+            fired[name] = count.value > 0
+    L.lib().vnm_set_profiling(0)
+    fired["lsd"] = _route_count("sort:lsd_radix") > lsd_before
+    assert fired == expected, case
+    got = torch.as_tensor(_RawI64(idx.ptr, n), device="cuda")[:k]
+    assert bool(torch.equal(got, ref)), f"{case}: {int((got != ref).sum())} of the first {k} row ids differ"
+
+
 @pytest.mark.parametrize("case", ["f64_normal", "f64_desc_nan_negzero", "i64_few_dups", "u64_desc", "runs_of_100", "heavy_value", "heavy_values_and_nans_desc",
                                   "low_cardinality_declines", "tiny_buckets", "odd_size", "fanout_16", "fanout_64_forced", "fanout_512_forced",
                                   "nulls_asc", "nulls_desc_nan_heavy", "half_null_unaligned", "mostly_null_declines"])

@@ -326,6 +326,7 @@ __global__ __launch_bounds__(OS_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))
 }
 
 struct RadixBufs {
+    PoolScope pool;                   // owns the blocks below: they go back when the RadixBufs' scope ends (early returns included)
     uint64_t* code[2];
     uint32_t* val[2];
     unsigned long long* red;          // [0..1] unused, [4] caller's flag word, [8..15] tickets (as uint32 pairs)
@@ -333,48 +334,50 @@ struct RadixBufs {
     unsigned long long* status;       // [ntiles][256] chained-scan status words
     int cur = 0;
     int64_t ntiles = 0;
-    ~RadixBufs();   // gives the blocks back (early returns included)
 };
-static void radix_free(RadixBufs* r);
 
 static int radix_alloc(RadixBufs* r, int64_t n) {
     r->ntiles = (n + OS_TILE - 1) / OS_TILE;
     for (int k = 0; k < 2; k++) {
-        r->code[k] = (uint64_t*)pool_alloc((size_t)(n ? n : 1) * 8);
-        r->val[k] = (uint32_t*)pool_alloc((size_t)(n ? n : 1) * 4);
+        r->code[k] = (uint64_t*)r->pool.take((size_t)(n ? n : 1) * 8);
+        r->val[k] = (uint32_t*)r->pool.take((size_t)(n ? n : 1) * 4);
         if (!r->code[k] || !r->val[k]) return 1;
     }
-    r->red = (unsigned long long*)pool_alloc(128);
-    r->ghist = (unsigned long long*)pool_alloc((size_t)2 * 8 * 256 * 8);
-    r->status = (unsigned long long*)pool_alloc((size_t)(r->ntiles ? r->ntiles : 1) * 256 * 8);
+    r->red = (unsigned long long*)r->pool.take(128);
+    r->ghist = (unsigned long long*)r->pool.take((size_t)2 * 8 * 256 * 8);
+    r->status = (unsigned long long*)r->pool.take((size_t)(r->ntiles ? r->ntiles : 1) * 256 * 8);
     return (r->red && r->ghist && r->status) ? 0 : 1;
 }
-static void radix_free(RadixBufs* r) {   // idempotent: ~RadixBufs calls it again on every way out of a scope
-    for (int k = 0; k < 2; k++) { pool_free(r->code[k]); pool_free(r->val[k]); r->code[k] = nullptr; r->val[k] = nullptr; }
-    pool_free(r->red); pool_free(r->ghist); pool_free(r->status);
-    r->red = nullptr; r->ghist = nullptr; r->status = nullptr;
+
+// raises a kernel's dynamic-LDS limit; every kernel family does it once, in front of its first launch
+template <class Kernel>
+static int allow_dynamic_lds(Kernel kernel, size_t bytes) {
+    VNM_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return 0;
 }
-RadixBufs::~RadixBufs() { radix_free(this); }
 
 // sort (code[cur], val[cur]) stably by the bytes of code that are not constant
 // extra (optional): receives r->red[4], a flag word the caller's previous kernel may have set (read back with the
 // same synchronisation as the digit histograms)
-// idx_out (optional): the caller's int64 row-id buffer.  When this call runs the LAST pass of the whole sort (no class pass
-// will follow: !cls_possible or the flag word is 0) that pass writes the widened row ids straight into it and skips the
-// code output; *wrote_idx tells the caller.
 // hist_ready: r->ghist already holds the digit histograms of the codes (sort_encode_kernel accumulated them)
 // ident (optional, in/out): the row ids r->val[r->cur] are the identity and NOT materialised; the first executed pass makes them up
-// key_out / key_type / key_desc / wrote_key (optional): see OsArgs::key_out; only together with idx_out, and only when the flag
-// word says the key holds no NaN / NULL / -0.0
-static int radix_sort_codes(RadixBufs* r, int64_t n, hipStream_t s, unsigned long long* extra = nullptr, int64_t* idx_out = nullptr,
-                            bool cls_possible = false, bool* wrote_idx = nullptr, bool hist_ready = false, bool* ident = nullptr,
-                            uint64_t* key_out = nullptr, int key_type = 0, int key_desc = 0, bool* wrote_key = nullptr) {
-    if (wrote_key) *wrote_key = false;
-    if (wrote_idx) *wrote_idx = false;
+// last (optional): what the LAST pass of the whole sort may write on its way, see RadixLastPass
+struct RadixLastPass {
+    int64_t* idx_out;     // the caller's int64 row-id buffer.  When this call runs the last pass of the whole sort (no class pass will
+    bool* wrote_idx;      // follow: !cls_possible or the flag word is 0) that pass writes the widened row ids straight into it and skips
+                          // the code output; *wrote_idx tells the caller
+    uint64_t* key_out;    // see OsArgs::key_out; only when the flag word says the key holds no NaN / NULL / -0.0: *wrote_key
+    int key_type, key_desc;
+    bool* wrote_key;
+};
+static int radix_sort_codes(RadixBufs* r, int64_t n, hipStream_t s, unsigned long long* extra = nullptr, bool cls_possible = false,
+                            bool hist_ready = false, bool* ident = nullptr, const RadixLastPass* last = nullptr) {
+    if (last && last->wrote_key) *last->wrote_key = false;
+    if (last && last->wrote_idx) *last->wrote_idx = false;
     if (n <= 1) { if (extra) { VNM_HIP(hipMemcpyAsync(extra, r->red + 4, 8, hipMemcpyDeviceToHost, s)); VNM_HIP(hipStreamSynchronize(s)); } return 0; }
-    static bool attr_set = false;
+    static bool attr_set = false;   // (the one place: onesweep_kernel is launched from this function alone)
     if (!attr_set) {
-        VNM_HIP(hipFuncSetAttribute((const void*)onesweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OS_LDS_BYTES));
+        VNM_TRY(allow_dynamic_lds(onesweep_kernel, OS_LDS_BYTES));
         attr_set = true;
     }
     const int cus = device_info().num_cus;
@@ -415,12 +418,12 @@ static int radix_sort_codes(RadixBufs* r, int64_t n, hipStream_t s, unsigned lon
         a.ticket = (unsigned int*)(r->red + 8) + byte;
         a.tag = (unsigned long long)(byte + 1) << 60;
         a.code_out = r->code[r->cur ^ 1]; a.val_out = r->val[r->cur ^ 1];
-        if (idx_out && !cls_follows && k == n_live - 1) {
-            a.idx_out = idx_out; a.code_out = nullptr;
-            if (wrote_idx) *wrote_idx = true;
-            if (key_out && hist[8 * 256] == 0) {
-                a.key_out = key_out; a.key_type = key_type; a.key_desc = key_desc;
-                if (wrote_key) *wrote_key = true;
+        if (last && last->idx_out && !cls_follows && k == n_live - 1) {
+            a.idx_out = last->idx_out; a.code_out = nullptr;
+            if (last->wrote_idx) *last->wrote_idx = true;
+            if (last->key_out && hist[8 * 256] == 0) {
+                a.key_out = last->key_out; a.key_type = last->key_type; a.key_desc = last->key_desc;
+                if (last->wrote_key) *last->wrote_key = true;
             }
         }
 onesweep_kernel<<<g, OS_BLOCK, OS_LDS_BYTES, s>>>(a);
@@ -663,8 +666,6 @@ static int grid_for(int64_t n, int per_cu = 8) {
     return g > need ? (int)need : g;
 }
 
-static thread_local bool g_rows_clustered = false;   // set by the sample sorts when they decline rows that arrive clustered (ssort_cluster_kernel)
-
 #include "vnm_sort_sample.inc"
 #include "vnm_sort_apx.inc"
 
@@ -688,228 +689,270 @@ __global__ void sort_iota64_kernel(int64_t* idx, int64_t n, int backwards) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) idx[i] = backwards ? n - 1 - i : i;
 }
 
-// Sample sort of one 8-byte key without a validity bitmap (see vnm_sort_sample.inc).  0 = done (idx_out written, *wrote_key),
-// 2 = not applicable / a bucket outgrew its room (the caller sorts with the LSD passes), 1 = error.
-static int sample_sort(const vnm_dcol& key, int desc, int64_t n, int64_t* idx_out, uint64_t* key_out, bool* wrote_key, hipStream_t s) {
-    if (wrote_key) *wrote_key = false;
-    const int cus = device_info().num_cus;
+// ---- the splitter sample sort of one 8-byte key (kernels: vnm_sort_sample.inc), stage by stage -----------------------------------------
+// What the stages hand to each other.  `pool` and `side` own every block named here: they go back when sample_sort returns.
+constexpr size_t SS_SCATTER_LDS = (size_t)SS_B * SS_CAP * 12;
+struct SsRun {
+    vnm_dcol key; int desc; int64_t n; hipStream_t s;
+    int has_null;                               // the key has a validity bitmap
+    int l2; int64_t nb, m;                      // 512 x l2 buckets, m sampled keys
+    PoolScope pool;
+    uint64_t *split, *heavy; unsigned long long *flags, *lb, *hstart; unsigned int *hb, *nheavy_d;
+    int nheavy; int64_t sample_nulls, total_nulls; unsigned long long eq_pairs;   // what the sample said
+    RadixBufs side; int64_t side_cap, side_len;                                   // rows of heavy codes and NULL rows bypass the buckets
+    Level1Geometry g; int64_t cap1, cap2;
+    uint64_t *c1, *c2; uint32_t *r1, *n1, *r2, *n2; unsigned long long* offs;     // the regions of the two levels, the bucket offsets
+    unsigned long long special;                                                   // flags[1] after the scatters: a NaN / -0.0 key
+};
+
+// buckets and sample size
+static void ssort_plan(SsRun* st) {
+    const int64_t n = st->n;
     // 512 x l2 buckets of ~2100-4200 rows: 2^18 at 1e9 rows, fewer below (2^18 buckets whatever n cost ~4.5 ms of fixed time:
     // the 2^23-key sample and 2^18 nearly empty local-sort workgroups; 1.7e7 rows 5.2 ms against 1.4 with the LSD passes)
     int l2 = 8;
     while (l2 < SS_B && n / ((int64_t)SS_B * l2) > 4200) l2 *= 2;
-    l2 = (int)std::min<int64_t>(SS_B, std::max<int64_t>(8, env_sort_i64("VNM_SSORT_L2", l2)));
-    const int64_t nb = (int64_t)SS_B * l2;
+    st->l2 = (int)std::min<int64_t>(SS_B, std::max<int64_t>(8, env_sort_i64("VNM_SSORT_L2", l2)));
+    st->nb = (int64_t)SS_B * st->l2;
     // Samples per bucket: a bucket's share of the rows is ~Gamma(k) / k for k samples per bucket, and a bucket beyond the local
     // sort's room (r times the mean) fails the whole attempt -- P ~ exp(-k (r - 1 - ln r)) per bucket.  At 1e9 rows r = 8192 / 3815
     // = 2.15: with k = 32 about one data set in ten lost a bucket among its 2^18 (and paid the LSD sort on top of the wasted
     // passes: 119 ms); k is chosen for P * buckets < 1e-7.
-    int64_t m;
-    {
-        const double mean = (double)n / (double)nb;
-        const double r = std::min<double>((double)SS_LOCAL, 2.5 * mean + 128.0) / mean;
-        const double need = (std::log((double)nb) + 16.0) / std::max(0.05, r - 1.0 - std::log(r));
-        const int64_t k = std::min<int64_t>(128, std::max<int64_t>(32, (int64_t)std::ceil(need)));
-        m = std::min<int64_t>(n, nb * env_sort_i64("VNM_SSORT_SAMPLES_PER_BUCKET", k));
-    }
+    const double mean = (double)n / (double)st->nb;
+    const double r = std::min<double>((double)SS_LOCAL, 2.5 * mean + 128.0) / mean;
+    const double need = (std::log((double)st->nb) + 16.0) / std::max(0.05, r - 1.0 - std::log(r));
+    const int64_t k = std::min<int64_t>(128, std::max<int64_t>(32, (int64_t)std::ceil(need)));
+    st->m = std::min<int64_t>(n, st->nb * env_sort_i64("VNM_SSORT_SAMPLES_PER_BUCKET", k));
+}
+
+static int ssort_allow_lds() {
     static bool attr_set = false;
-    const size_t lds_sc = (size_t)SS_B * SS_CAP * 12;
-    if (!attr_set) {
-        VNM_HIP(hipFuncSetAttribute((const void*)ssort_scatter_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc));
-        VNM_HIP(hipFuncSetAttribute((const void*)ssort_scatter_kernel<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc));
-        VNM_HIP(hipFuncSetAttribute((const void*)ssort_scatter_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc));
-        VNM_HIP(hipFuncSetAttribute((const void*)ssort_scatter_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc));
-        VNM_HIP(hipFuncSetAttribute((const void*)ssort_local_kernel<512, 10, 4096, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)SS_SMALL * 12 + 4096 * 4)));
-        VNM_HIP(hipFuncSetAttribute((const void*)ssort_local_kernel<1024, 8, 8192, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)SS_LOCAL * 12 + 8192 * 4)));
-        VNM_HIP(hipFuncSetAttribute((const void*)onesweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OS_LDS_BYTES));
-        attr_set = true;
-    }
-    PoolScope pool;
-    // ---- splitters from a sorted sample; heavy codes = runs of equal splitters
-    uint64_t* split = (uint64_t*)pool.take((size_t)nb * 8);
-    unsigned long long* flags = (unsigned long long*)pool.take(64);
-    uint64_t* heavy = (uint64_t*)pool.take((size_t)SS_MAX_HEAVY * 8);
-    unsigned long long* lb = (unsigned long long*)pool.take((size_t)(SS_MAX_HEAVY + 2) * 8 * 2);   // lb[66], then hstart[65] (+ the NULL class)
-    unsigned int* hb = (unsigned int*)pool.take((size_t)(SS_MAX_HEAVY + 2) * 4);                   // hb[64], then the heavy counter
-    if (!split || !flags || !heavy || !lb || !hb) return 1;
-    unsigned long long* hstart = lb + SS_MAX_HEAVY + 2;
-    const int has_null = key.validity != nullptr;
-    unsigned int* nheavy_d = hb + SS_MAX_HEAVY;
+    if (attr_set) return 0;
+    VNM_TRY(allow_dynamic_lds(ssort_scatter_kernel<true, 1>, SS_SCATTER_LDS));
+    VNM_TRY(allow_dynamic_lds(ssort_scatter_kernel<false, 1>, SS_SCATTER_LDS));
+    VNM_TRY(allow_dynamic_lds(ssort_scatter_kernel<true, 2>, SS_SCATTER_LDS));
+    VNM_TRY(allow_dynamic_lds(ssort_scatter_kernel<false, 2>, SS_SCATTER_LDS));
+    VNM_TRY(allow_dynamic_lds(ssort_local_kernel<512, 10, 4096, false>, (size_t)SS_SMALL * 12 + 4096 * 4));
+    VNM_TRY(allow_dynamic_lds(ssort_local_kernel<1024, 8, 8192, true>, (size_t)SS_LOCAL * 12 + 8192 * 4));
+    attr_set = true;
+    return 0;
+}
+
+// Stage 1: splitters from a sorted sample; heavy codes = runs of equal splitters.  2 = declined: too many NULLs or heavy values, or the
+// rows arrive clustered (*clustered).  The sample itself goes back to the pool on return.
+static int ssort_splitters(SsRun* st, bool* clustered) {
+    hipStream_t s = st->s;
+    const int64_t m = st->m, nb = st->nb;
+    st->split = (uint64_t*)st->pool.take((size_t)nb * 8);
+    st->flags = (unsigned long long*)st->pool.take(64);
+    st->heavy = (uint64_t*)st->pool.take((size_t)SS_MAX_HEAVY * 8);
+    st->lb = (unsigned long long*)st->pool.take((size_t)(SS_MAX_HEAVY + 2) * 8 * 2);   // lb[66], then hstart[65] (+ the NULL class)
+    st->hb = (unsigned int*)st->pool.take((size_t)(SS_MAX_HEAVY + 2) * 4);             // hb[64], then the heavy counter
+    if (!st->split || !st->flags || !st->heavy || !st->lb || !st->hb) return 1;
+    st->hstart = st->lb + SS_MAX_HEAVY + 2;
+    st->nheavy_d = st->hb + SS_MAX_HEAVY;
+    unsigned long long* flags = st->flags;
     VNM_HIP(hipMemsetAsync(flags, 0, 64, s));
-    VNM_HIP(hipMemsetAsync(nheavy_d, 0, 4, s));
-    int nheavy = 0;
-    int64_t sample_nulls = 0, total_nulls = 0;
-    unsigned long long eq_pairs = 0;
-    {
-        RadixBufs sr{};
-        VNM_TRY(radix_alloc(&sr, m));
-        {
-            KernelTimer timer("sort_sample", s);
-            ssort_sample_kernel<<<grid_for(m), 256, 0, s>>>(key, desc, n, m, sr.code[0], flags + 5);
-        }
-        sort_iota_kernel<<<grid_for(m), 256, 0, s>>>(sr.val[0], m);
-        sr.cur = 0;
-        VNM_TRY(radix_sort_codes(&sr, m, s));
-        int64_t m_valid = m;     // NULL rows of the sample stand at the end of its sorted order: the splitters come from the rest
-        if (has_null) {
-            unsigned long long sn = 0, tn = 0;
-            ssort_count_nulls_kernel<<<grid_for((n + 7) / 8), 256, 0, s>>>(key.validity, key.offset, n, flags + 6);
-            VNM_HIP(hipMemcpyAsync(&sn, flags + 5, 8, hipMemcpyDeviceToHost, s));
-            VNM_HIP(hipMemcpyAsync(&tn, flags + 6, 8, hipMemcpyDeviceToHost, s));
-            VNM_HIP(hipStreamSynchronize(s));
-            sample_nulls = (int64_t)sn;
-            total_nulls = (int64_t)tn;
-            m_valid = m - sample_nulls;
-            if (m_valid < nb * 4) {
-                if (getenv("VNM_SORT_TRACE")) fprintf(stderr, "[sort] sample sort declined: %lld of %lld sampled rows are NULL\n", (long long)sample_nulls, (long long)m);
-                return 2;
-            }
-        }
-        ssort_splitters_kernel<<<(int)((nb + 255) / 256), 256, 0, s>>>(sr.code[sr.cur], m_valid, nb, split, flags, heavy, nheavy_d);
-        VNM_HIP(hipGetLastError());
-        // rows that arrive clustered (a sorted column): the ring scatters would crawl -- the LSD passes do not care
-        unsigned long long min_span = ~0ULL;
-        VNM_HIP(hipMemsetAsync(flags + 7, 0xFF, 8, s));
-        ssort_cluster_kernel<<<64, 256, 0, s>>>(key, desc, n, sr.code[sr.cur], m_valid, flags + 7);
-        VNM_HIP(hipGetLastError());
-        VNM_HIP(hipMemcpyAsync(&min_span, flags + 7, 8, hipMemcpyDeviceToHost, s));
-        unsigned long long too_many = 0;
-        unsigned int nh = 0;
-        VNM_HIP(hipMemcpyAsync(&eq_pairs, flags + 3, 8, hipMemcpyDeviceToHost, s));
-        uint64_t hcodes[SS_MAX_HEAVY];
-        VNM_HIP(hipMemcpyAsync(&too_many, flags, 8, hipMemcpyDeviceToHost, s));
-        VNM_HIP(hipMemcpyAsync(&nh, nheavy_d, 4, hipMemcpyDeviceToHost, s));
-        VNM_HIP(hipMemcpyAsync(hcodes, heavy, sizeof(hcodes), hipMemcpyDeviceToHost, s));
-        VNM_HIP(hipStreamSynchronize(s));    // (sr goes back to the pool here)
-        if (min_span != ~0ULL && (int64_t)min_span < m_valid / 8 && env_sort_i64("VNM_SSORT_CLUSTER_CHECK", 1)) {
-            g_rows_clustered = true;
-            if (getenv("VNM_SORT_TRACE")) fprintf(stderr, "[sort] sample sort declined: the rows arrive clustered (a tile of 4096 consecutive rows spans %llu of %lld samples)\n", min_span, (long long)m_valid);
+    VNM_HIP(hipMemsetAsync(st->nheavy_d, 0, 4, s));
+    RadixBufs sr{};
+    VNM_TRY(sorted_sample(st->key, st->desc, st->n, m, flags + 5, &sr, s));
+    int64_t m_valid = m;     // NULL rows of the sample stand at the end of its sorted order: the splitters come from the rest
+    if (st->has_null) {
+        unsigned long long sn = 0, tn = 0;
+        ssort_count_nulls_kernel<<<grid_for((st->n + 7) / 8), 256, 0, s>>>(st->key.validity, st->key.offset, st->n, flags + 6);
+        VNM_HIP(hipMemcpyAsync(&sn, flags + 5, 8, hipMemcpyDeviceToHost, s));
+        VNM_HIP(hipMemcpyAsync(&tn, flags + 6, 8, hipMemcpyDeviceToHost, s));
+        VNM_HIP(hipStreamSynchronize(s));
+        st->sample_nulls = (int64_t)sn;
+        st->total_nulls = (int64_t)tn;
+        m_valid = m - st->sample_nulls;
+        if (m_valid < nb * 4) {
+            if (getenv("VNM_SORT_TRACE")) fprintf(stderr, "[sort] sample sort declined: %lld of %lld sampled rows are NULL\n", (long long)st->sample_nulls, (long long)m);
             return 2;
-        }
-        if (too_many || nh > (unsigned int)SS_MAX_HEAVY || getenv("VNM_SSORT_NO_HEAVY") != nullptr && nh) {
-            if (getenv("VNM_SORT_TRACE")) fprintf(stderr, "[sort] sample sort declined: %u heavily duplicated values\n", nh);
-            return 2;
-        }
-        nheavy = (int)nh;
-        if (nheavy) {
-            std::sort(hcodes, hcodes + nheavy);
-            VNM_HIP(hipMemcpyAsync(heavy, hcodes, (size_t)nheavy * 8, hipMemcpyHostToDevice, s));
         }
     }
+    ssort_splitters_kernel<<<(int)((nb + 255) / 256), 256, 0, s>>>(sr.code[sr.cur], m_valid, nb, st->split, flags, st->heavy, st->nheavy_d);
+    VNM_HIP(hipGetLastError());
+    unsigned long long min_span = ~0ULL, too_many = 0;
+    VNM_TRY(sample_cluster_span(st->key, st->desc, st->n, sr.code[sr.cur], m_valid, flags + 7, &min_span, s));
+    unsigned int nh = 0;
+    uint64_t hcodes[SS_MAX_HEAVY];
+    VNM_HIP(hipMemcpyAsync(&st->eq_pairs, flags + 3, 8, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipMemcpyAsync(&too_many, flags, 8, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipMemcpyAsync(&nh, st->nheavy_d, 4, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipMemcpyAsync(hcodes, st->heavy, sizeof(hcodes), hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));
+    if (rows_arrive_clustered(min_span, m_valid)) {
+        *clustered = true;
+        if (getenv("VNM_SORT_TRACE")) fprintf(stderr, "[sort] sample sort declined: the rows arrive clustered (a tile of 4096 consecutive rows spans %llu of %lld samples)\n", min_span, (long long)m_valid);
+        return 2;
+    }
+    if (too_many || nh > (unsigned int)SS_MAX_HEAVY || getenv("VNM_SSORT_NO_HEAVY") != nullptr && nh) {
+        if (getenv("VNM_SORT_TRACE")) fprintf(stderr, "[sort] sample sort declined: %u heavily duplicated values\n", nh);
+        return 2;
+    }
+    st->nheavy = (int)nh;
+    if (st->nheavy) {
+        std::sort(hcodes, hcodes + st->nheavy);
+        VNM_HIP(hipMemcpyAsync(st->heavy, hcodes, (size_t)st->nheavy * 8, hipMemcpyHostToDevice, s));
+    }
+    return 0;
+}
+
+// Stage 2: level 1, rows -> 512 buckets per workgroup region
+static int ssort_level1(SsRun* st) {
+    const int64_t n = st->n;
+    const bool bypass = st->nheavy || st->has_null;
     // rows of heavy codes bypass the buckets: (heavy index << 32 | row id) entries in a side list, sorted below
     // (room: every run of r equal splitters stands for at most (r + 1) buckets' worth of rows)
     // (+ the NULL rows, counted)
-    const double null_rows = (double)total_nulls;
-    const int64_t side_cap = (nheavy || has_null) ? std::min<int64_t>(n, (int64_t)((double)(eq_pairs + 2 * (unsigned long long)nheavy) * (double)n / (double)nb * 1.3 + null_rows) + 65536) : 0;
-    RadixBufs side{};
-    if (nheavy || has_null) VNM_TRY(radix_alloc(&side, side_cap));
-    // ---- level 1
-    const int pairs1 = env_sort_i64("VNM_SSORT_PAIRS1", 1) >= 2 ? 2 : 1;
-    const int64_t sub = 2 * SS_BLOCK * pairs1;
-    const int grid1 = (int)std::min<int64_t>((int64_t)cus * env_sort_i64("VNM_SSORT_GRID1_PER_CU", 1), std::max<int64_t>(1, (n + sub - 1) / sub));
-    const int64_t rows_per_wg = (((n + sub - 1) / sub + grid1 - 1) / grid1) * sub;
-    const int64_t cap1 = ((rows_per_wg / SS_B + rows_per_wg / SS_B / 4 + 96) + 7) & ~7LL;
-    uint64_t* c1 = (uint64_t*)pool.take((size_t)SS_B * grid1 * cap1 * 8);
-    uint32_t* r1 = (uint32_t*)pool.take((size_t)SS_B * grid1 * cap1 * 4);
-    uint32_t* n1 = (uint32_t*)pool.take((size_t)SS_B * grid1 * 4);
-    if (!c1 || !r1 || !n1) return 1;
+    st->side_cap = bypass ? std::min<int64_t>(n, (int64_t)((double)(st->eq_pairs + 2 * (unsigned long long)st->nheavy) * (double)n / (double)st->nb * 1.3 + (double)st->total_nulls) + 65536) : 0;
+    if (bypass) VNM_TRY(radix_alloc(&st->side, st->side_cap));
+    st->g = level1_geometry(n, env_sort_i64("VNM_SSORT_PAIRS1", 1), env_sort_i64("VNM_SSORT_GRID1_PER_CU", 1), env_sort_i64("VNM_SSORT_SPLIT2", 1));
+    const int grid1 = st->g.grid1;
+    st->cap1 = ((st->g.rows_per_wg / SS_B + st->g.rows_per_wg / SS_B / 4 + 96) + 7) & ~7LL;
+    st->c1 = (uint64_t*)st->pool.take((size_t)SS_B * grid1 * st->cap1 * 8);
+    st->r1 = (uint32_t*)st->pool.take((size_t)SS_B * grid1 * st->cap1 * 4);
+    st->n1 = (uint32_t*)st->pool.take((size_t)SS_B * grid1 * 4);
+    if (!st->c1 || !st->r1 || !st->n1) return 1;
     SsArgs a1{};
-    a1.key = key; a1.desc = desc; a1.nrows = n; a1.split = split; a1.l2 = l2;
-    a1.out_code = c1; a1.out_row = r1; a1.out_counts = n1; a1.out_cap = cap1; a1.flags = flags;
-    a1.heavy = heavy; a1.nheavy = nheavy; a1.has_null = has_null;
-    a1.side = (nheavy || has_null) ? (unsigned long long*)side.code[0] : nullptr; a1.side_cap = side_cap;
+    a1.key = st->key; a1.desc = st->desc; a1.nrows = n; a1.split = st->split; a1.l2 = st->l2;
+    a1.out_code = st->c1; a1.out_row = st->r1; a1.out_counts = st->n1; a1.out_cap = st->cap1; a1.flags = st->flags;
+    a1.heavy = st->heavy; a1.nheavy = st->nheavy; a1.has_null = st->has_null;
+    a1.side = bypass ? (unsigned long long*)st->side.code[0] : nullptr; a1.side_cap = st->side_cap;
     {
-        KernelTimer timer("sort_scatter1", s);
-        if (pairs1 == 2) ssort_scatter_kernel<true, 2><<<grid1, SS_BLOCK, lds_sc, s>>>(a1);
-        else ssort_scatter_kernel<true, 1><<<grid1, SS_BLOCK, lds_sc, s>>>(a1);
+        KernelTimer timer("sort_scatter1", st->s);
+        if (st->g.pairs1 == 2) ssort_scatter_kernel<true, 2><<<grid1, SS_BLOCK, SS_SCATTER_LDS, st->s>>>(a1);
+        else ssort_scatter_kernel<true, 1><<<grid1, SS_BLOCK, SS_SCATTER_LDS, st->s>>>(a1);
     }
     VNM_HIP(hipGetLastError());
-    // ---- level 2
-    int split2 = std::max(1, (grid1 + SS_MAX_REGIONS - 1) / SS_MAX_REGIONS);
-    split2 = std::max(split2, (int)env_sort_i64("VNM_SSORT_SPLIT2", 1));
-    const int64_t avg_bucket = n / nb + 1;
-    const int64_t cap2 = ((std::min<int64_t>(SS_LOCAL, avg_bucket * 2 / split2 + avg_bucket / 2 + 128)) + 7) & ~7LL;
-    uint64_t* c2 = (uint64_t*)pool.take((size_t)nb * split2 * cap2 * 8);
-    uint32_t* r2 = (uint32_t*)pool.take((size_t)nb * split2 * cap2 * 4);
-    uint32_t* n2 = (uint32_t*)pool.take((size_t)nb * split2 * 4);
-    unsigned long long* offs = (unsigned long long*)pool.take((size_t)(nb + 1) * 8);
-    if (!c2 || !r2 || !n2 || !offs) return 1;
+    return 0;
+}
+
+// Stage 3: level 2, every level-1 bucket -> l2 buckets.  2 = a region of either level overflowed.
+static int ssort_level2(SsRun* st) {
+    hipStream_t s = st->s;
+    const int64_t nb = st->nb;
+    const int split2 = st->g.split2;
+    const int64_t avg_bucket = st->n / nb + 1;
+    st->cap2 = ((std::min<int64_t>(SS_LOCAL, avg_bucket * 2 / split2 + avg_bucket / 2 + 128)) + 7) & ~7LL;
+    st->c2 = (uint64_t*)st->pool.take((size_t)nb * split2 * st->cap2 * 8);
+    st->r2 = (uint32_t*)st->pool.take((size_t)nb * split2 * st->cap2 * 4);
+    st->n2 = (uint32_t*)st->pool.take((size_t)nb * split2 * 4);
+    st->offs = (unsigned long long*)st->pool.take((size_t)(nb + 1) * 8);
+    if (!st->c2 || !st->r2 || !st->n2 || !st->offs) return 1;
     SsArgs a2{};
-    a2.split = split; a2.l2 = l2; a2.in_code = c1; a2.in_row = r1; a2.in_counts = n1; a2.in_cap = cap1; a2.in_regions = grid1; a2.in_split = split2;
-    a2.out_code = c2; a2.out_row = r2; a2.out_counts = n2; a2.out_cap = cap2; a2.flags = flags;
+    a2.split = st->split; a2.l2 = st->l2; a2.in_code = st->c1; a2.in_row = st->r1; a2.in_counts = st->n1; a2.in_cap = st->cap1; a2.in_regions = st->g.grid1; a2.in_split = split2;
+    a2.out_code = st->c2; a2.out_row = st->r2; a2.out_counts = st->n2; a2.out_cap = st->cap2; a2.flags = st->flags;
     {
         KernelTimer timer("sort_scatter2", s);
-        if (env_sort_i64("VNM_SSORT_PAIRS2", 1) >= 2) ssort_scatter_kernel<false, 2><<<SS_B * split2, SS_BLOCK, lds_sc, s>>>(a2);
-        else ssort_scatter_kernel<false, 1><<<SS_B * split2, SS_BLOCK, lds_sc, s>>>(a2);
+        if (env_sort_i64("VNM_SSORT_PAIRS2", 1) >= 2) ssort_scatter_kernel<false, 2><<<SS_B * split2, SS_BLOCK, SS_SCATTER_LDS, s>>>(a2);
+        else ssort_scatter_kernel<false, 1><<<SS_B * split2, SS_BLOCK, SS_SCATTER_LDS, s>>>(a2);
     }
     VNM_HIP(hipGetLastError());
     unsigned long long fl[3] = {0, 0, 0};
-    VNM_HIP(hipMemcpyAsync(fl, flags, 24, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipMemcpyAsync(fl, st->flags, 24, hipMemcpyDeviceToHost, s));
     VNM_HIP(hipStreamSynchronize(s));
+    st->special = fl[1];
+    st->side_len = (int64_t)fl[2];
     if (fl[0]) {
         if (getenv("VNM_SORT_TRACE")) fprintf(stderr, "[sort] sample sort: a region overflowed (side list %llu of %lld, %lld NULL rows, %lld of %lld samples NULL, %d heavy values), LSD sort instead\n",
-                                              fl[2], (long long)side_cap, (long long)total_nulls, (long long)sample_nulls, (long long)m, nheavy);
+                                              fl[2], (long long)st->side_cap, (long long)st->total_nulls, (long long)st->sample_nulls, (long long)st->m, st->nheavy);
         return 2;
     }
-    // ---- the heavy rows: their side list sorted by (heavy index, row id) is their part of the output
-    const int64_t side_len = (int64_t)fl[2];
-    if (nheavy || has_null) {
-        side.cur = 0;
-        if (side_len > 1) VNM_TRY(radix_sort_codes(&side, side_len, s, nullptr, nullptr, false, nullptr, false, nullptr));
-        ssort_heavy_bounds_kernel<<<1, 128, 0, s>>>((const unsigned long long*)side.code[side.cur], side_len, heavy, nheavy, split, nb, lb, hb, has_null);
+    return 0;
+}
+
+// Stage 4: where every bucket starts in the output.  The heavy rows: their side list sorted by (heavy index, row id) is their part of
+// the output.  2 = a bucket outgrew the local sort's room.
+static int ssort_offsets(SsRun* st) {
+    hipStream_t s = st->s;
+    if (st->nheavy || st->has_null) {
+        st->side.cur = 0;
+        if (st->side_len > 1) VNM_TRY(radix_sort_codes(&st->side, st->side_len, s));
+        ssort_heavy_bounds_kernel<<<1, 128, 0, s>>>((const unsigned long long*)st->side.code[st->side.cur], st->side_len, st->heavy, st->nheavy, st->split, st->nb, st->lb, st->hb, st->has_null);
     }
-    ssort_offsets_kernel<<<1, 1024, 0, s>>>(n2, split2, nb, offs, flags, nheavy, hb, lb, hstart, has_null);
+    ssort_offsets_kernel<<<1, 1024, 0, s>>>(st->n2, st->g.split2, st->nb, st->offs, st->flags, st->nheavy, st->hb, st->lb, st->hstart, st->has_null);
     VNM_HIP(hipGetLastError());
-    VNM_HIP(hipMemcpyAsync(fl, flags, 8, hipMemcpyDeviceToHost, s));
+    unsigned long long fail = 0;
+    VNM_HIP(hipMemcpyAsync(&fail, st->flags, 8, hipMemcpyDeviceToHost, s));
     VNM_HIP(hipStreamSynchronize(s));
     if (getenv("VNM_SORT_TRACE")) fprintf(stderr, "[sort] sample sort: n %lld grid1 %d cap1 %lld split2 %d cap2 %lld heavy %d (%lld rows) -> fail %llu special %llu\n",
-                                          (long long)n, grid1, (long long)cap1, split2, (long long)cap2, nheavy, (long long)side_len, fl[0], fl[1]);
-    if (fl[0]) return 2;
-    {
-        const int dbg = (int)env_sort_i64("VNM_SSORT_DEBUG", 0);
-        if (dbg == 7 || dbg == 8) {
-            uint32_t* seen = (uint32_t*)pool.take((size_t)n * 4);
-            if (!seen) return 1;
-            VNM_HIP(hipMemsetAsync(seen, 0, (size_t)n * 4, s));
-            VNM_HIP(hipMemsetAsync(flags + 4, 0, 8, s));
-            if (dbg == 7) ssort_check_kernel<<<4096, 256, 0, s>>>(r2, n2, cap2, nb * split2, seen, n, flags + 4);
-            else ssort_check_kernel<<<4096, 256, 0, s>>>(r1, n1, cap1, (int64_t)SS_B * grid1, seen, n, flags + 4);
-            std::vector<uint32_t> hs((size_t)n);
-            unsigned long long badv = 0;
-            VNM_HIP(hipMemcpy(hs.data(), seen, (size_t)n * 4, hipMemcpyDeviceToHost));
-            VNM_HIP(hipMemcpy(&badv, flags + 4, 8, hipMemcpyDeviceToHost));
-            int64_t miss = 0, dup = 0, firstmiss = -1;
-            for (int64_t i = 0; i < n; i++) { if (hs[i] == 0) { if (firstmiss < 0) firstmiss = i; miss++; } else if (hs[i] > 1) dup++; }
-            fprintf(stderr, "[sort] debug level %d regions: %lld rows missing (first %lld), %lld duplicated, %llu out of range\n", dbg == 7 ? 2 : 1,
-                    (long long)miss, (long long)firstmiss, (long long)dup, badv);
-        }
+                                          (long long)st->n, st->g.grid1, (long long)st->cap1, st->g.split2, (long long)st->cap2, st->nheavy, (long long)st->side_len, fail, st->special);
+    return fail ? 2 : 0;
+}
+
+// VNM_SSORT_DEBUG = 7 / 8 (after the scatters): is every row in exactly one region of level 2 / 1?  6 (after the local sort): its counters
+static int ssort_debug(SsRun* st, bool after_local_sort) {
+    const int dbg = (int)env_sort_i64("VNM_SSORT_DEBUG", 0);
+    hipStream_t s = st->s;
+    const int64_t n = st->n;
+    if (after_local_sort && dbg == 6) {
+        unsigned long long f6[8];
+        VNM_HIP(hipMemcpy(f6, st->flags, 64, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[sort] debug: %llu positions beyond the end (max %llu), %llu in the long path\n", f6[2], f6[3], f6[4]);
     }
-    // ---- per-bucket LDS sort, straight into the caller's buffers
+    if (after_local_sort || (dbg != 7 && dbg != 8)) return 0;
+    uint32_t* seen = (uint32_t*)st->pool.take((size_t)n * 4);
+    if (!seen) return 1;
+    VNM_HIP(hipMemsetAsync(seen, 0, (size_t)n * 4, s));
+    VNM_HIP(hipMemsetAsync(st->flags + 4, 0, 8, s));
+    if (dbg == 7) ssort_check_kernel<<<4096, 256, 0, s>>>(st->r2, st->n2, st->cap2, st->nb * st->g.split2, seen, n, st->flags + 4);
+    else ssort_check_kernel<<<4096, 256, 0, s>>>(st->r1, st->n1, st->cap1, (int64_t)SS_B * st->g.grid1, seen, n, st->flags + 4);
+    std::vector<uint32_t> hs((size_t)n);
+    unsigned long long badv = 0;
+    VNM_HIP(hipMemcpy(hs.data(), seen, (size_t)n * 4, hipMemcpyDeviceToHost));
+    VNM_HIP(hipMemcpy(&badv, st->flags + 4, 8, hipMemcpyDeviceToHost));
+    int64_t miss = 0, dup = 0, firstmiss = -1;
+    for (int64_t i = 0; i < n; i++) { if (hs[i] == 0) { if (firstmiss < 0) firstmiss = i; miss++; } else if (hs[i] > 1) dup++; }
+    fprintf(stderr, "[sort] debug level %d regions: %lld rows missing (first %lld), %lld duplicated, %llu out of range\n", dbg == 7 ? 2 : 1,
+            (long long)miss, (long long)firstmiss, (long long)dup, badv);
+    return 0;
+}
+
+// Stage 5: per-bucket LDS sort, straight into the caller's buffers
+static int ssort_local(SsRun* st, int64_t* idx_out, uint64_t* key_out, bool* wrote_key) {
+    hipStream_t s = st->s;
+    const int cus = device_info().num_cus;
+    const int64_t nb = st->nb;
     SsLocalArgs la{};
-    la.code = c2; la.row = r2; la.counts = n2; la.cap = cap2; la.split = split2; la.offs = offs; la.nbuckets = nb;
+    la.code = st->c2; la.row = st->r2; la.counts = st->n2; la.cap = st->cap2; la.split = st->g.split2; la.offs = st->offs; la.nbuckets = nb;
     la.idx_out = idx_out;
-    const bool keyed = key_out != nullptr && fl[1] == 0 && !has_null;   // (a sorted key column with NULLs in it: the caller gathers)
-    la.key_out = keyed ? key_out : nullptr; la.key_type = key.type; la.key_desc = desc; la.flags = flags;
+    const bool keyed = key_out != nullptr && st->special == 0 && !st->has_null;   // (a sorted key column with NULLs in it: the caller gathers)
+    la.key_out = keyed ? key_out : nullptr; la.key_type = st->key.type; la.key_desc = st->desc; la.flags = st->flags;
     la.debug = (int)env_sort_i64("VNM_SSORT_DEBUG", 0);
-    la.crowded = (uint32_t*)pool.take((size_t)nb * 4);
+    la.crowded = (uint32_t*)st->pool.take((size_t)nb * 4);
     if (!la.crowded) return 1;
     VNM_HIP(hipMemsetAsync(la.crowded, 0, (size_t)nb * 4, s));
     {
         KernelTimer timer("sort_local", s);
         ssort_local_kernel<512, 10, 4096, false><<<(int)std::min<int64_t>(nb, (int64_t)cus * 64), 512, (size_t)SS_SMALL * 12 + 4096 * 4, s>>>(la);
         ssort_local_kernel<1024, 8, 8192, true><<<(int)std::min<int64_t>(nb, (int64_t)cus * 16), 1024, (size_t)SS_LOCAL * 12 + 8192 * 4, s>>>(la);
-        if ((nheavy || has_null) && side_len > 0)
-            ssort_heavy_write_kernel<<<grid_for(side_len), 256, 0, s>>>((const unsigned long long*)side.code[side.cur], side_len, heavy, lb, hstart, idx_out,
-                                                                        keyed ? key_out : nullptr, key.type, desc, nheavy);
+        if ((st->nheavy || st->has_null) && st->side_len > 0)
+            ssort_heavy_write_kernel<<<grid_for(st->side_len), 256, 0, s>>>((const unsigned long long*)st->side.code[st->side.cur], st->side_len, st->heavy, st->lb, st->hstart, idx_out,
+                                                                            keyed ? key_out : nullptr, st->key.type, st->desc, st->nheavy);
     }
     VNM_HIP(hipGetLastError());
     VNM_HIP(hipStreamSynchronize(s));
-    if (la.debug == 6) {
-        unsigned long long f6[8];
-        VNM_HIP(hipMemcpy(f6, flags, 64, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[sort] debug: %llu positions beyond the end (max %llu), %llu in the long path\n", f6[2], f6[3], f6[4]);
-    }
+    VNM_TRY(ssort_debug(st, true));
     if (wrote_key) *wrote_key = keyed;
     return 0;
+}
+
+// Sample sort of one 8-byte key (see vnm_sort_sample.inc).  0 = done (idx_out written, *wrote_key), 1 = error, 2 = not applicable / a
+// bucket outgrew its room (the caller sorts with the LSD passes); *clustered: declined because the rows arrive clustered.
+static int sample_sort(const vnm_dcol& key, int desc, int64_t n, int64_t* idx_out, uint64_t* key_out, bool* wrote_key, bool* clustered, hipStream_t s) {
+    if (wrote_key) *wrote_key = false;
+    SsRun st{};
+    st.key = key; st.desc = desc; st.n = n; st.s = s; st.has_null = key.validity != nullptr;
+    ssort_plan(&st);
+    VNM_TRY(ssort_allow_lds());
+    VNM_TRY(ssort_splitters(&st, clustered));
+    VNM_TRY(ssort_level1(&st));
+    VNM_TRY(ssort_level2(&st));
+    VNM_TRY(ssort_offsets(&st));
+    VNM_TRY(ssort_debug(&st, false));
+    return ssort_local(&st, idx_out, key_out, wrote_key);
 }
 
 // full stable multi-key sort; result: row ids (uint32) in r->val[r->cur]
@@ -933,8 +976,8 @@ static int full_sort(int n_keys, const vnm_dcol* keys, const int* orders, int64_
         }
         unsigned long long any_special = 0;
         const bool cls_possible = keys[k].validity != nullptr || type_is_float(keys[k].type);
-        VNM_TRY(radix_sort_codes(r, n, s, &any_special, k == 0 ? idx_out : nullptr, cls_possible, wrote_idx, true, &ident,
-                                 k == 0 ? key_out : nullptr, kt0, orders[0] == VNM_DESC, wrote_key));
+        const RadixLastPass last{k == 0 ? idx_out : nullptr, wrote_idx, k == 0 ? key_out : nullptr, kt0, orders[0] == VNM_DESC, wrote_key};
+        VNM_TRY(radix_sort_codes(r, n, s, &any_special, cls_possible, true, &ident, &last));
         // class pass (values < NaN < NULL), more significant than the code, over the classes in the CURRENT order
         if (cls_possible && (any_special & 1ULL) != 0) {   // no NaN / NULL at all: nothing to do
             VNM_HIP(hipMemsetAsync(r->ghist, 0, (size_t)8 * 256 * 8, s));
@@ -943,11 +986,288 @@ static int full_sort(int n_keys, const vnm_dcol* keys, const int* orders, int64_
                 sort_encode_kernel<<<grid_for(n, 64), 256, 0, s>>>(keys[k], orders[k] == VNM_DESC, ident ? nullptr : r->val[r->cur], n,
                                                                    r->code[r->cur], nullptr, nullptr, r->ghist, 1);
             }
-            VNM_TRY(radix_sort_codes(r, n, s, nullptr, k == 0 ? idx_out : nullptr, false, wrote_idx, true, &ident));
+            const RadixLastPass ids{k == 0 ? idx_out : nullptr, wrote_idx, nullptr, 0, 0, nullptr};
+            VNM_TRY(radix_sort_codes(r, n, s, nullptr, false, true, &ident, &ids));
         }
     }
     VNM_HIP(hipGetLastError());
     if (ident && !(wrote_idx && *wrote_idx)) sort_iota_kernel<<<grid_for(n), 256, 0, s>>>(r->val[r->cur], n);   // every key constant
+    return 0;
+}
+
+// ---- the routes of vnm_sort_indices_keyed, in the order it tries them ----------------------------------------------------------------------
+// Every route answers 0 = done (out_indices and *wrote_key0 written, the stream synchronised), 1 = error (set_error has the message),
+// 2 = not applicable or declined: the next route.  What a route allocates goes back to the pool when it returns.
+
+struct TopkThreshold { uint32_t cls; uint64_t code; };   // rows at or below it in (class, code) order are candidates
+
+// Threshold for small ranks: the rnk-th best of the 4096 block winners (one scan of the sample, one workgroup sort)
+static int topk_threshold_of_block_winners(const vnm_dcol& key, int desc, int64_t n, int64_t m, int64_t rnk, TopkThreshold* t, hipStream_t s) {
+    PoolScope pool;
+    uint64_t* bcode = (uint64_t*)pool.take(TB_BLOCKS * 8);
+    uint8_t* bcls = (uint8_t*)pool.take(TB_BLOCKS);
+    unsigned long long* thr = (unsigned long long*)pool.take(64);
+    if (!bcode || !bcls || !thr) return 1;
+    {
+        KernelTimer timer("topk_sample", s);
+        topk_blockbest_kernel<<<TB_BLOCKS, 256, 0, s>>>(key, desc, n, m, bcode, bcls);
+        topk_small_sort_kernel<<<1, 1024, (size_t)TB_BLOCKS * 13, s>>>(bcode, bcls, nullptr, TB_BLOCKS, TB_BLOCKS, rnk, nullptr, thr);
+    }
+    unsigned long long th[2] = {0, 0};
+    VNM_HIP(hipMemcpyAsync(th, thr, 16, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));
+    t->cls = (uint32_t)th[0];
+    t->code = th[1];
+    return 0;
+}
+
+// Threshold for larger ranks: the r01 route -- sort a 2^18-key sample by (class, code) with the grid-wide radix sort and read the
+// threshold off it (its ~130 small launches cost ~1.5 ms, which only matters for small K).  2 = the rank lies beyond the sample.
+static int topk_threshold_of_sorted_sample(const vnm_dcol& key, int desc, int64_t n, int64_t limit, TopkThreshold* t, hipStream_t s) {
+    const int64_t m = std::min<int64_t>(n, 1 << 18);
+    const int64_t rnk = (int64_t)((double)limit / (double)n * (double)m * 1.5) + 64 + (int64_t)(6.0 * sqrt((double)limit / (double)n * (double)m + 1.0));
+    if (rnk >= m - 1) return 2;
+    RadixBufs sr{};
+    VNM_TRY(radix_alloc(&sr, m));
+    PoolScope pool;
+    uint8_t* scls = (uint8_t*)pool.take((size_t)m);
+    if (!scls) return 1;
+    topk_sample_kernel<<<grid_for(m), 256, 0, s>>>(key, desc, n, m, sr.code[0], scls);
+    sort_iota_kernel<<<grid_for(m), 256, 0, s>>>(sr.val[0], m);
+    VNM_TRY(radix_sort_codes(&sr, m, s));
+    uint64_t* scode_sorted = (uint64_t*)pool.take((size_t)m * 8);
+    if (!scode_sorted) return 1;
+    VNM_HIP(hipMemcpyAsync(scode_sorted, sr.code[sr.cur], (size_t)m * 8, hipMemcpyDeviceToDevice, s));
+    gather_u8_kernel<<<grid_for(m), 256, 0, s>>>(scls, sr.val[sr.cur], m, sr.code[sr.cur]);
+    sort_iota_kernel<<<grid_for(m), 256, 0, s>>>(sr.val[sr.cur], m);   // stable secondary key: position in the code order
+    VNM_TRY(radix_sort_codes(&sr, m, s));
+    uint32_t pos_in_code_sorted = 0;
+    uint64_t cls64 = 0;
+    VNM_HIP(hipMemcpyAsync(&pos_in_code_sorted, sr.val[sr.cur] + rnk, 4, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipMemcpyAsync(&cls64, sr.code[sr.cur] + rnk, 8, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));
+    VNM_HIP(hipMemcpyAsync(&t->code, scode_sorted + pos_in_code_sorted, 8, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));
+    t->cls = (uint32_t)cls64;
+    return 0;
+}
+
+// The candidates: (code, class, row id) of every row at or below the threshold, unordered; they live as long as this struct.
+struct TopkCandidates {
+    RadixBufs cr;                 // cr.code[0]: the codes; the finishers sort in it
+    PoolScope pool;
+    uint8_t* cls; uint32_t* rows;
+    int64_t cap, found;           // found > cap: the list is cut short and of no use
+};
+static int topk_select(const vnm_dcol& key, int desc, int64_t n, int64_t limit, const TopkThreshold& t, TopkCandidates* c, hipStream_t s) {
+    c->cap = std::max<int64_t>(limit * 4 + 65536, 1 << 20);
+    VNM_TRY(radix_alloc(&c->cr, c->cap));
+    c->cls = (uint8_t*)c->pool.take((size_t)c->cap);
+    c->rows = (uint32_t*)c->pool.take((size_t)c->cap * 4);
+    unsigned long long* cnt = (unsigned long long*)c->pool.take(64);
+    if (!c->cls || !c->rows || !cnt) return 1;
+    VNM_HIP(hipMemsetAsync(cnt, 0, 8, s));
+    {
+        KernelTimer timer("topk_select", s);
+        topk_select_kernel<<<device_info().num_cus * 8, 256, 0, s>>>(key, desc, n, t.cls, t.code, c->cap, cnt, c->cr.code[0], c->cls, c->rows);
+    }
+    unsigned long long found = 0;
+    VNM_HIP(hipMemcpyAsync(&found, cnt, 8, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));
+    c->found = (int64_t)found;
+    return 0;
+}
+
+// Finisher for several keys: the candidates' key columns gathered, the full multi-key sort over them, the first `limit` row ids gathered
+static int topk_finish_multi_key(int n_keys, const vnm_dcol* keys, const int* orders, int64_t limit, TopkCandidates* cd, int64_t* out_indices, hipStream_t s) {
+    const int64_t c = cd->found;
+    RadixBufs& cr = cd->cr;
+    PoolScope pool;
+    // the candidates in ROW order (the multi-key sort below is stable over it)
+    u32_to_code_kernel<<<grid_for(c), 256, 0, s>>>(cd->rows, c, cr.code[0]);
+    sort_iota_kernel<<<grid_for(c), 256, 0, s>>>(cr.val[0], c);
+    cr.cur = 0;
+    VNM_TRY(radix_sort_codes(&cr, c, s));
+    int64_t* rows64 = (int64_t*)pool.take((size_t)c * 8);
+    int64_t* perm = (int64_t*)pool.take((size_t)c * 8);
+    if (!rows64 || !perm) return 1;
+    VNM_HIP(hipMemcpyAsync(rows64, cr.code[cr.cur], (size_t)c * 8, hipMemcpyDeviceToDevice, s));   // the codes ARE the row ids
+    // their key columns, gathered
+    std::vector<vnm_dcol> sub((size_t)n_keys);
+    for (int j = 0; j < n_keys; j++) {
+        const int w = type_width(keys[j].type);
+        void* dv = pool.take((size_t)c * w);
+        uint8_t* db = keys[j].validity ? (uint8_t*)pool.take((size_t)c) : nullptr;
+        uint8_t* bm = keys[j].validity ? (uint8_t*)pool.take((size_t)(c + 7) / 8 + 8) : nullptr;
+        if (!dv || (keys[j].validity && (!db || !bm))) return 1;
+        take_kernel<<<grid_for(c), 256, 0, s>>>(keys[j], rows64, c, dv, db);
+        if (bm) VNM_TRY(vnm_pack_validity(db, c, bm, (void*)s));
+        sub[j] = keys[j];
+        sub[j].values = dv; sub[j].validity = bm; sub[j].offset = 0; sub[j].length = c;
+    }
+    RadixBufs r2{};
+    VNM_TRY(radix_alloc(&r2, c));
+    bool wrote = false;
+    VNM_TRY(full_sort(n_keys, sub.data(), orders, c, &r2, s, perm, &wrote));
+    if (!wrote) sort_widen_kernel<<<grid_for(c), 256, 0, s>>>(r2.val[r2.cur], c, perm);
+    gather_i64_kernel<<<grid_for(limit), 256, 0, s>>>(rows64, perm, limit, out_indices);
+    VNM_HIP(hipGetLastError());
+    VNM_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// Finisher for few candidates (<= TS_MAX): one workgroup sorts them in LDS and writes the first K row ids
+static int topk_finish_in_lds(int64_t limit, TopkCandidates* cd, int64_t* out_indices, hipStream_t s) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        VNM_TRY(allow_dynamic_lds(topk_small_sort_kernel, (size_t)TS_MAX * 13));
+        attr_set = true;
+    }
+    const int c = (int)cd->found;
+    int np2 = 64;
+    while (np2 < c) np2 <<= 1;
+    {
+        KernelTimer timer("topk_small_sort", s);
+        topk_small_sort_kernel<<<1, 1024, (size_t)np2 * 13, s>>>(cd->cr.code[0], cd->cls, cd->rows, c, np2, limit, out_indices, nullptr);
+    }
+    VNM_HIP(hipGetLastError());
+    VNM_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// Finisher for many candidates, three radix pass groups -- the canonical order: by row id, then (stable) by code, then by class
+static int topk_finish_radix(int64_t limit, TopkCandidates* cd, int64_t* out_indices, hipStream_t s) {
+    const int64_t c = cd->found;
+    RadixBufs& cr = cd->cr;
+    uint64_t* code_keep = (uint64_t*)cd->pool.take((size_t)c * 8);
+    if (!code_keep) return 1;
+    VNM_HIP(hipMemcpyAsync(code_keep, cr.code[0], (size_t)c * 8, hipMemcpyDeviceToDevice, s));
+    // pass group 1: key = row id, value = candidate slot
+    u32_to_code_kernel<<<grid_for(c), 256, 0, s>>>(cd->rows, c, cr.code[0]);
+    sort_iota_kernel<<<grid_for(c), 256, 0, s>>>(cr.val[0], c);
+    cr.cur = 0;
+    VNM_TRY(radix_sort_codes(&cr, c, s));
+    // pass group 2: key = code of the slot
+    gather_u64_kernel<<<grid_for(c), 256, 0, s>>>(code_keep, cr.val[cr.cur], c, cr.code[cr.cur]);
+    VNM_TRY(radix_sort_codes(&cr, c, s));
+    // pass group 3: key = class of the slot
+    gather_u8_kernel<<<grid_for(c), 256, 0, s>>>(cd->cls, cr.val[cr.cur], c, cr.code[cr.cur]);
+    VNM_TRY(radix_sort_codes(&cr, c, s));
+    // slots -> row ids -> int64 output (first `limit` entries)
+    gather_u32_kernel<<<grid_for(limit), 256, 0, s>>>(cd->rows, cr.val[cr.cur], limit, cr.val[cr.cur ^ 1]);
+    sort_widen_kernel<<<grid_for(limit), 256, 0, s>>>(cr.val[cr.cur ^ 1], limit, out_indices);
+    VNM_HIP(hipGetLastError());
+    VNM_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// Route 1, LIMIT K: one scan selects the candidates, only they are sorted.
+// Several sort keys: the same selection on the FIRST key -- every row that beats the threshold on key 0, ties included, is a
+// candidate (a row that loses on key 0 loses whatever its other keys are) -- and the candidates alone go through the full
+// multi-key sort.  2 also when the threshold kept fewer than K rows or more than the candidates' room (ties / NaN / NULL heavy
+// data, or an unlucky sample): the full sort answers.
+static int try_topk(int n_keys, const vnm_dcol* keys, const int* orders, int64_t n, int64_t limit, int64_t* out_indices, int* wrote_key0, hipStream_t s) {
+    if (!(limit > 0 && limit * 8 < n && n >= (1 << 16) && getenv("VNM_SORT_NO_TOPK") == nullptr && (n_keys == 1 || getenv("VNM_SORT_NO_TOPK_MULTI") == nullptr))) return 2;
+    route_note("sort:topk_threshold", "LIMIT %lld of %lld rows, %d keys: sampled threshold, candidates through the full sort", (long long)limit, (long long)n, n_keys);
+    const int desc = orders[0] == VNM_DESC;
+    const int64_t m = std::min<int64_t>(n, 1 << 22);
+    // threshold = the sample element at the expected rank of the K-th row + a safety margin, in (class, code) order
+    const double frac = (double)limit / (double)n;
+    const int64_t rnk = (int64_t)(frac * (double)m * 1.5) + 8 + (int64_t)(6.0 * sqrt(frac * (double)m + 1.0));
+    if (rnk >= m - 1) return 2;
+    TopkThreshold t{};
+    if (rnk < TB_BLOCKS / 4 && m >= TB_BLOCKS * 64) VNM_TRY(topk_threshold_of_block_winners(keys[0], desc, n, m, rnk, &t, s));
+    else VNM_TRY(topk_threshold_of_sorted_sample(keys[0], desc, n, limit, &t, s));
+    TopkCandidates cd{};
+    VNM_TRY(topk_select(keys[0], desc, n, limit, t, &cd, s));
+    if (cd.found < limit || cd.found > cd.cap) return 2;
+    if (n_keys > 1) VNM_TRY(topk_finish_multi_key(n_keys, keys, orders, limit, &cd, out_indices, s));
+    else if (cd.found <= TS_MAX && getenv("VNM_SORT_NO_SMALL") == nullptr) VNM_TRY(topk_finish_in_lds(limit, &cd, out_indices, s));
+    else VNM_TRY(topk_finish_radix(limit, &cd, out_indices, s));
+    if (wrote_key0) *wrote_key0 = 0;
+    return 0;
+}
+
+// Route 2 (and, over a widened copy, route 3), the two sample sorts of one 8-byte key, many rows.  Only the order is asked for: first the
+// entry-word sort (8-byte words, an equalising map of the code + row id -- the sample decides; duplicated keys, lumpy distributions keep
+// the splitters).  Then the splitter sort (two bucket scatters + a sort in LDS instead of eight LSD passes), which can hand back the
+// sorted key as well.  *clustered: declined because the rows arrive clustered -- the splitter sort would decline what the entry-word
+// sort declined for that, so it is not tried then.
+static int try_sample_sorts(const vnm_dcol& key8, const char* what, int desc, int64_t n, int64_t* out_indices, uint64_t* out_sorted_key0, int* wrote_key0,
+                            bool* clustered, hipStream_t s) {
+    *clustered = false;
+    if (!out_sorted_key0 && env_sort_i64("VNM_SORT_APX", 1)) {
+        const int rx = sample_sort_apx(key8, desc, n, out_indices, clustered, s);
+        if (rx == 0) {
+            route_note("sort:sample_sort_words", "%lld rows, %s, order only: an equalising map from a sample, two scatters of 8-byte entry words, per-bucket LDS sort", (long long)n, what);
+            if (wrote_key0) *wrote_key0 = 0;
+        }
+        if (rx != 2) return rx;
+    }
+    if (*clustered) return 2;
+    route_note("sort:sample_sort", "%lld rows, %s: splitters from a sample, two bucket scatters, per-bucket LDS sort", (long long)n, what);
+    bool wrote_key = false;
+    const int rc = sample_sort(key8, desc, n, out_indices, out_sorted_key0, &wrote_key, clustered, s);
+    if (rc == 0 && wrote_key0) *wrote_key0 = wrote_key ? 1 : 0;
+    return rc;
+}
+
+static bool sample_sorts_wanted(int n_keys, int64_t n) {
+    return n_keys == 1 && n >= env_sort_i64("VNM_SSORT_MIN_ROWS", (int64_t)1 << 25) && getenv("VNM_SORT_NO_SAMPLE") == nullptr;
+}
+
+// ... one 4-byte key (float32 / int32 / uint32) the same way (round 5): widened to 8 bytes -- float32 -> float64 is exact and keeps the
+// order, NaNs and signed zeros -- the sample sorts order the copy; 5e8 float32 keys through the LSD passes: 27.9 ms, float64: 15.7.
+// (2: the sample sorts declined -- heavy values, an overflowing bucket: the LSD passes over the original column)
+static int try_widened_sample_sorts(const vnm_dcol& key, int desc, int64_t n, int64_t* out_indices, int* wrote_key0, hipStream_t s) {
+    if (key.validity || !(key.type == VNM_F32 || key.type == VNM_I32 || key.type == VNM_U32) || getenv("VNM_SORT_NO_WIDEN") != nullptr) return 2;
+    PoolScope pool;
+    uint64_t* wide = (uint64_t*)pool.take((size_t)n * 8);
+    if (!wide) return 1;
+    struct IdleStreamAtExit { hipStream_t s; ~IdleStreamAtExit() { (void)hipStreamSynchronize(s); } } idle{s};   // declared after `pool`: no kernel reads `wide` any more when it goes back, whichever way out
+    sort_widen_key_kernel<<<grid_for(n), 256, 0, s>>>(key.values, key.type, key.offset, n, wide);
+    VNM_HIP(hipGetLastError());
+    vnm_dcol key8{};
+    key8.values = wide; key8.length = n;
+    key8.type = key.type == VNM_F32 ? VNM_F64 : (key.type == VNM_I32 ? VNM_I64 : VNM_U64);
+    bool clustered = false;   // (of no use to the caller: the already-sorted check reads 8-byte keys)
+    return try_sample_sorts(key8, "one 4-byte key widened to 8 bytes", desc, n, out_indices, nullptr, wrote_key0, &clustered, s);
+}
+
+// Route 4.  A column that arrives clustered is often simply SORTED already (a time series ordered by its timestamp): see sort_inversions_kernel.
+static int try_already_sorted(const vnm_dcol& key, int desc, int64_t n, int64_t* out_indices, int* wrote_key0, hipStream_t s) {
+    if (key.validity || type_width(key.type) != 8 || getenv("VNM_SORT_NO_SORTED_CHECK") != nullptr) return 2;
+    PoolScope pool;
+    unsigned long long* inv = (unsigned long long*)pool.take(64);
+    if (!inv) return 1;
+    unsigned long long ninv[2] = {1, 1};
+    VNM_HIP(hipMemsetAsync(inv, 0, 16, s));
+    sort_inversions_kernel<<<grid_for(n, 16), 256, 0, s>>>(key, desc, n, inv);
+    VNM_HIP(hipGetLastError());
+    VNM_HIP(hipMemcpyAsync(ninv, inv, 16, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));
+    if (ninv[0] != 0 && ninv[1] != 0) return 2;
+    const int backwards = ninv[0] != 0;
+    route_note("sort:already_sorted", "%lld rows, one 8-byte key: the rows arrive %s: the indices are the row numbers%s", (long long)n,
+               backwards ? "strictly in the opposite order (every row below its predecessor, no ties)" : "in the order asked for (no row below its predecessor)", backwards ? " backwards" : "");
+    sort_iota64_kernel<<<grid_for(n, 16), 256, 0, s>>>(out_indices, n, backwards);
+    VNM_HIP(hipGetLastError());
+    VNM_HIP(hipStreamSynchronize(s));
+    if (wrote_key0) *wrote_key0 = 0;
+    return 0;
+}
+
+// Route 5, always applicable: the LSD passes
+static int lsd_sort(int n_keys, const vnm_dcol* keys, const int* orders, int64_t n, int64_t* out_indices, uint64_t* out_sorted_key0, int* wrote_key0, hipStream_t s) {
+    RadixBufs r{};
+    VNM_TRY(radix_alloc(&r, n));
+    bool wrote = false, wrote_key = false;
+    route_note("sort:lsd_radix", "%lld rows, %d keys: stable LSD passes over order-preserving codes, last key first", (long long)n, n_keys);
+    VNM_TRY(full_sort(n_keys, keys, orders, n, &r, s, out_indices, &wrote, out_sorted_key0, &wrote_key));
+    if (wrote_key0) *wrote_key0 = wrote_key ? 1 : 0;
+    if (!wrote) sort_widen_kernel<<<grid_for(n), 256, 0, s>>>(r.val[r.cur], n, out_indices);
+    VNM_HIP(hipGetLastError());
+    VNM_HIP(hipStreamSynchronize(s));
     return 0;
 }
 
@@ -973,276 +1293,19 @@ int vnm_sort_indices_keyed(int n_keys, const vnm_dcol* keys, const int* orders, 
     if (length == 0) return 0;
     hipStream_t s = as_stream(stream);
     const int64_t n = length;
-
-    // ---- LIMIT K fast path: one scan selects the candidates ----
-    // Several sort keys: the same selection on the FIRST key -- every row that beats the threshold on key 0, ties included, is a
-    // candidate (a row that loses on key 0 loses whatever its other keys are) -- and the candidates alone go through the full
-    // multi-key sort.
-    const bool try_topk = limit > 0 && limit * 8 < n && n >= (1 << 16) && getenv("VNM_SORT_NO_TOPK") == nullptr &&
-                          (n_keys == 1 || getenv("VNM_SORT_NO_TOPK_MULTI") == nullptr);
-    if (try_topk) {
-        route_note("sort:topk_threshold", "LIMIT %lld of %lld rows, %d keys: sampled threshold, candidates through the full sort", (long long)limit, (long long)n, n_keys);
-        const int desc = orders[0] == VNM_DESC;
-        static bool ts_attr = false;
-        if (!ts_attr) {
-            VNM_HIP(hipFuncSetAttribute((const void*)topk_small_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TS_MAX * 13));
-            ts_attr = true;
-        }
-        const int64_t m = std::min<int64_t>(n, 1 << 22);
-        // threshold = the sample element at the expected rank of the K-th row + a safety margin, in (class, code) order
-        // (a threshold that keeps fewer than K rows is noticed below and answered by the full sort)
-        double frac = (double)limit / (double)n;
-        int64_t rnk = (int64_t)(frac * (double)m * 1.5) + 8 + (int64_t)(6.0 * sqrt(frac * (double)m + 1.0));
-        bool ok = rnk < m - 1;
-        uint32_t t_cls = 0;
-        uint64_t t_code = 0;
-        if (ok && rnk < TB_BLOCKS / 4 && m >= TB_BLOCKS * 64) {
-            // small ranks: the rnk-th best of the 4096 block winners (one scan of the sample, one workgroup sort)
-            PoolScope tpool;
-            uint64_t* bcode = (uint64_t*)tpool.take(TB_BLOCKS * 8);
-            uint8_t* bcls = (uint8_t*)tpool.take(TB_BLOCKS);
-            unsigned long long* thr = (unsigned long long*)tpool.take(64);
-            if (!bcode || !bcls || !thr) return 1;
-            {
-                KernelTimer timer("topk_sample", s);
-                topk_blockbest_kernel<<<TB_BLOCKS, 256, 0, s>>>(keys[0], desc, n, m, bcode, bcls);
-                topk_small_sort_kernel<<<1, 1024, (size_t)TB_BLOCKS * 13, s>>>(bcode, bcls, nullptr, TB_BLOCKS, TB_BLOCKS, rnk, nullptr, thr);
-            }
-            unsigned long long th[2] = {0, 0};
-            VNM_HIP(hipMemcpyAsync(th, thr, 16, hipMemcpyDeviceToHost, s));
-            VNM_HIP(hipStreamSynchronize(s));
-            t_cls = (uint32_t)th[0];
-            t_code = th[1];
-        } else if (ok) {
-            // larger ranks: the r01 route -- sort a 2^18-key sample by (class, code) with the grid-wide radix sort and read
-            // the threshold off it (its ~130 small launches cost ~1.5 ms, which only matters for small K)
-            const int64_t ms_ = std::min<int64_t>(n, 1 << 18);
-            rnk = (int64_t)((double)limit / (double)n * (double)ms_ * 1.5) + 64 + (int64_t)(6.0 * sqrt((double)limit / (double)n * (double)ms_ + 1.0));
-            ok = rnk < ms_ - 1;
-            if (ok) {
-                RadixBufs sr{};
-                VNM_TRY(radix_alloc(&sr, ms_));
-                PoolScope spool;
-                uint8_t* scls = (uint8_t*)spool.take((size_t)ms_);
-                if (!scls) return 1;
-                topk_sample_kernel<<<grid_for(ms_), 256, 0, s>>>(keys[0], desc, n, ms_, sr.code[0], scls);
-                sort_iota_kernel<<<grid_for(ms_), 256, 0, s>>>(sr.val[0], ms_);
-                int rc = radix_sort_codes(&sr, ms_, s);
-                uint64_t* scode_sorted = (uint64_t*)spool.take((size_t)ms_ * 8);
-                if (rc || !scode_sorted) return 1;
-                VNM_HIP(hipMemcpyAsync(scode_sorted, sr.code[sr.cur], (size_t)ms_ * 8, hipMemcpyDeviceToDevice, s));
-                gather_u8_kernel<<<grid_for(ms_), 256, 0, s>>>(scls, sr.val[sr.cur], ms_, sr.code[sr.cur]);
-                sort_iota_kernel<<<grid_for(ms_), 256, 0, s>>>(sr.val[sr.cur], ms_);   // stable secondary key: position in the code order
-                rc = radix_sort_codes(&sr, ms_, s);
-                if (rc) return 1;
-                uint32_t pos_in_code_sorted = 0;
-                uint64_t cls64 = 0;
-                VNM_HIP(hipMemcpyAsync(&pos_in_code_sorted, sr.val[sr.cur] + rnk, 4, hipMemcpyDeviceToHost, s));
-                VNM_HIP(hipMemcpyAsync(&cls64, sr.code[sr.cur] + rnk, 8, hipMemcpyDeviceToHost, s));
-                VNM_HIP(hipStreamSynchronize(s));
-                VNM_HIP(hipMemcpyAsync(&t_code, scode_sorted + pos_in_code_sorted, 8, hipMemcpyDeviceToHost, s));
-                VNM_HIP(hipStreamSynchronize(s));
-                t_cls = (uint32_t)cls64;
-                radix_free(&sr);
-            }
-        }
-        if (ok) {
-            const int64_t cap = std::max<int64_t>(limit * 4 + 65536, 1 << 20);
-            RadixBufs cr{};
-            VNM_TRY(radix_alloc(&cr, cap));
-            PoolScope cpool;
-            uint8_t* ccls = (uint8_t*)cpool.take((size_t)cap);
-            uint32_t* crows = (uint32_t*)cpool.take((size_t)cap * 4);
-            unsigned long long* cnt = (unsigned long long*)cpool.take(64);
-            if (!ccls || !crows || !cnt) return 1;
-            VNM_HIP(hipMemsetAsync(cnt, 0, 8, s));
-            {
-                KernelTimer timer("topk_select", s);
-                topk_select_kernel<<<device_info().num_cus * 8, 256, 0, s>>>(keys[0], desc, n, t_cls, t_code, cap, cnt, cr.code[0], ccls, crows);
-            }
-            unsigned long long found = 0;
-            VNM_HIP(hipMemcpyAsync(&found, cnt, 8, hipMemcpyDeviceToHost, s));
-            VNM_HIP(hipStreamSynchronize(s));
-            int rc2 = 0;
-            bool done = false;
-            if (n_keys > 1) {
-                if ((int64_t)found >= limit && (int64_t)found <= cap) {
-                    const int64_t c = (int64_t)found;
-                    PoolScope pool;
-                    // the candidates in ROW order (the multi-key sort below is stable over it)
-                    u32_to_code_kernel<<<grid_for(c), 256, 0, s>>>(crows, c, cr.code[0]);
-                    sort_iota_kernel<<<grid_for(c), 256, 0, s>>>(cr.val[0], c);
-                    cr.cur = 0;
-                    rc2 = radix_sort_codes(&cr, c, s);
-                    int64_t* rows64 = (int64_t*)pool.take((size_t)c * 8);
-                    int64_t* perm = (int64_t*)pool.take((size_t)c * 8);
-                    if (!rc2 && (!rows64 || !perm)) rc2 = 1;
-                    if (!rc2) VNM_HIP(hipMemcpyAsync(rows64, cr.code[cr.cur], (size_t)c * 8, hipMemcpyDeviceToDevice, s));   // the codes ARE the row ids
-                    // their key columns, gathered
-                    std::vector<vnm_dcol> sub((size_t)n_keys);
-                    for (int j = 0; j < n_keys && !rc2; j++) {
-                        const int w = type_width(keys[j].type);
-                        void* dv = pool.take((size_t)c * w);
-                        uint8_t* db = keys[j].validity ? (uint8_t*)pool.take((size_t)c) : nullptr;
-                        uint8_t* bm = keys[j].validity ? (uint8_t*)pool.take((size_t)(c + 7) / 8 + 8) : nullptr;
-                        if (!dv || (keys[j].validity && (!db || !bm))) { rc2 = 1; break; }
-                        take_kernel<<<grid_for(c), 256, 0, s>>>(keys[j], rows64, c, dv, db);
-                        if (bm) rc2 = vnm_pack_validity(db, c, bm, (void*)s);
-                        sub[j] = keys[j];
-                        sub[j].values = dv; sub[j].validity = bm; sub[j].offset = 0; sub[j].length = c;
-                    }
-                    if (!rc2) {
-                        RadixBufs r2{};
-                        rc2 = radix_alloc(&r2, c);
-                        bool wrote = false;
-                        if (!rc2) rc2 = full_sort(n_keys, sub.data(), orders, c, &r2, s, perm, &wrote);
-                        if (!rc2 && !wrote) sort_widen_kernel<<<grid_for(c), 256, 0, s>>>(r2.val[r2.cur], c, perm);
-                        if (!rc2) {
-                            gather_i64_kernel<<<grid_for(limit), 256, 0, s>>>(rows64, perm, limit, out_indices);
-                            VNM_HIP(hipGetLastError());
-                            VNM_HIP(hipStreamSynchronize(s));
-                            done = true;
-                        }
-                        radix_free(&r2);
-                    }
-                }
-            } else if ((int64_t)found >= limit && (int64_t)found <= TS_MAX && getenv("VNM_SORT_NO_SMALL") == nullptr) {
-                // few candidates: one workgroup sorts them in LDS and writes the first K row ids
-                const int c = (int)found;
-                int np2 = 64;
-                while (np2 < c) np2 <<= 1;
-                const size_t lds = (size_t)np2 * 13;
-                {
-                    KernelTimer timer("topk_small_sort", s);
-                    topk_small_sort_kernel<<<1, 1024, lds, s>>>(cr.code[0], ccls, crows, c, np2, limit, out_indices, nullptr);
-                }
-                VNM_HIP(hipGetLastError());
-                VNM_HIP(hipStreamSynchronize(s));
-                done = true;
-            } else if ((int64_t)found >= limit && (int64_t)found <= cap) {
-                const int64_t c = (int64_t)found;
-                // canonical order: by row id, then (stable) by code, then by class
-                uint64_t* code_keep = (uint64_t*)cpool.take((size_t)c * 8);
-                if (!code_keep) return 1;
-                VNM_HIP(hipMemcpyAsync(code_keep, cr.code[0], (size_t)c * 8, hipMemcpyDeviceToDevice, s));
-                // pass group 1: key = row id, value = candidate slot
-                u32_to_code_kernel<<<grid_for(c), 256, 0, s>>>(crows, c, cr.code[0]);
-                sort_iota_kernel<<<grid_for(c), 256, 0, s>>>(cr.val[0], c);
-                cr.cur = 0;
-                rc2 = radix_sort_codes(&cr, c, s);
-                // pass group 2: key = code of the slot
-                if (!rc2) { gather_u64_kernel<<<grid_for(c), 256, 0, s>>>(code_keep, cr.val[cr.cur], c, cr.code[cr.cur]); rc2 = radix_sort_codes(&cr, c, s); }
-                // pass group 3: key = class of the slot
-                if (!rc2) { gather_u8_kernel<<<grid_for(c), 256, 0, s>>>(ccls, cr.val[cr.cur], c, cr.code[cr.cur]); rc2 = radix_sort_codes(&cr, c, s); }
-                if (!rc2) {
-                    // slots -> row ids -> int64 output (first `limit` entries)
-                    gather_u32_kernel<<<grid_for(limit), 256, 0, s>>>(crows, cr.val[cr.cur], limit, cr.val[cr.cur ^ 1]);
-                    sort_widen_kernel<<<grid_for(limit), 256, 0, s>>>(cr.val[cr.cur ^ 1], limit, out_indices);
-                    VNM_HIP(hipGetLastError());
-                    VNM_HIP(hipStreamSynchronize(s));
-                    done = true;
-                }
-            }
-            radix_free(&cr);
-            if (rc2) return rc2;
-            if (done) return 0;
-        }
-        // fall through to the full sort (ties / NaN / NULL heavy data, or an unlucky sample)
+    const vnm_dcol& key = keys[0];
+    const int desc = orders[0] == VNM_DESC;
+    uint64_t* key_out = (uint64_t*)out_sorted_key0;
+    // the routes in order; the first that does not answer 2 (not applicable / declined) is the answer
+    bool clustered = false;   // the sample sorts saw rows that arrive clustered: worth the already-sorted check
+    int rc = try_topk(n_keys, keys, orders, n, limit, out_indices, wrote_key0, s);
+    if (rc == 2 && sample_sorts_wanted(n_keys, n)) {
+        if (key.type == VNM_F64 || key.type == VNM_I64 || key.type == VNM_U64) {
+            if (!key.validity || getenv("VNM_SSORT_NO_NULLS") == nullptr) rc = try_sample_sorts(key, "one 8-byte key", desc, n, out_indices, key_out, wrote_key0, &clustered, s);
+        } else rc = try_widened_sample_sorts(key, desc, n, out_indices, wrote_key0, s);
     }
-
-    // one 8-byte key without NULLs, many rows: sample sort (two bucket scatters + a sort in LDS) instead of eight LSD passes
-    if (n_keys == 1 && (!keys[0].validity || getenv("VNM_SSORT_NO_NULLS") == nullptr) && (keys[0].type == VNM_F64 || keys[0].type == VNM_I64 || keys[0].type == VNM_U64) &&
-        n >= env_sort_i64("VNM_SSORT_MIN_ROWS", (int64_t)1 << 25) && getenv("VNM_SORT_NO_SAMPLE") == nullptr) {
-        bool wk = false;
-        g_rows_clustered = false;
-        // only the order is asked for: 8-byte entry words (an equalising map of the code + row id) instead of (code, row id) -- the
-        // sample decides (duplicated keys, lumpy distributions keep the splitters)
-        if (!out_sorted_key0 && env_sort_i64("VNM_SORT_APX", 1)) {
-            const int rx = sample_sort_apx(keys[0], orders[0] == VNM_DESC, n, out_indices, s);
-            if (rx == 1) return 1;
-            if (rx == 0) {
-                route_note("sort:sample_sort_words", "%lld rows, one 8-byte key, order only: an equalising map from a sample, two scatters of 8-byte entry words, per-bucket LDS sort", (long long)n);
-                if (wrote_key0) *wrote_key0 = 0;
-                return 0;
-            }
-        }
-        if (!g_rows_clustered) {   // (rows that arrive clustered: the splitter sort would decline them as well)
-            route_note("sort:sample_sort", "%lld rows, one 8-byte key: splitters from a sample, two bucket scatters, per-bucket LDS sort", (long long)n);
-            const int rc = sample_sort(keys[0], orders[0] == VNM_DESC, n, out_indices, (uint64_t*)out_sorted_key0, &wk, s);
-            if (rc == 1) return 1;
-            if (rc == 0) { if (wrote_key0) *wrote_key0 = wk ? 1 : 0; return 0; }
-        }
-    }
-    // ... one 4-byte key (float32 / int32 / uint32) the same way (round 5): widened to 8 bytes -- float32 -> float64 is exact and keeps the
-    // order, NaNs and signed zeros -- the sample sort orders the copy; 5e8 float32 keys through the LSD passes: 27.9 ms, float64: 15.7
-    if (n_keys == 1 && !keys[0].validity && (keys[0].type == VNM_F32 || keys[0].type == VNM_I32 || keys[0].type == VNM_U32) &&
-        n >= env_sort_i64("VNM_SSORT_MIN_ROWS", (int64_t)1 << 25) && getenv("VNM_SORT_NO_SAMPLE") == nullptr && getenv("VNM_SORT_NO_WIDEN") == nullptr) {
-        uint64_t* wide = (uint64_t*)pool_alloc((size_t)n * 8);
-        if (!wide) return 1;
-        sort_widen_key_kernel<<<grid_for(n), 256, 0, s>>>(keys[0].values, keys[0].type, keys[0].offset, n, wide);
-        int rc = hipGetLastError() == hipSuccess ? 0 : set_error("vnm_sort_indices: kernel launch failed");
-        if (!rc) {
-            vnm_dcol wk8{};
-            wk8.values = wide; wk8.length = n;
-            wk8.type = keys[0].type == VNM_F32 ? VNM_F64 : (keys[0].type == VNM_I32 ? VNM_I64 : VNM_U64);
-            bool wkey = false;
-            if (env_sort_i64("VNM_SORT_APX", 1)) {
-                const int rx = sample_sort_apx(wk8, orders[0] == VNM_DESC, n, out_indices, s);
-                if (rx == 1) { pool_free(wide); return 1; }
-                if (rx == 0) {
-                    route_note("sort:sample_sort_words", "%lld rows, one 4-byte key widened to 8 bytes, order only: two scatters of 8-byte entry words, per-bucket LDS sort", (long long)n);
-                    (void)hipStreamSynchronize(s);
-                    pool_free(wide);
-                    if (wrote_key0) *wrote_key0 = 0;
-                    return 0;
-                }
-            }
-            route_note("sort:sample_sort", "%lld rows, one 4-byte key widened to 8 bytes: splitters from a sample, two bucket scatters, per-bucket LDS sort", (long long)n);
-            rc = sample_sort(wk8, orders[0] == VNM_DESC, n, out_indices, nullptr, &wkey, s);
-        }
-        if (hipStreamSynchronize(s) != hipSuccess && rc == 0) rc = set_error("vnm_sort_indices: stream sync failed");
-        pool_free(wide);
-        if (rc == 1) return 1;
-        if (rc == 0) { if (wrote_key0) *wrote_key0 = 0; return 0; }
-        // (rc 2: the sample sort declined -- heavy values, an overflowing bucket: the LSD passes over the original column)
-    }
-    if (g_rows_clustered && n_keys == 1 && !keys[0].validity && !out_sorted_key0 && type_width(keys[0].type) == 8 && getenv("VNM_SORT_NO_SORTED_CHECK") == nullptr) {
-        g_rows_clustered = false;
-        unsigned long long* inv = (unsigned long long*)pool_alloc(64);
-        if (!inv) return 1;
-        unsigned long long ninv[2] = {1, 1};
-        int rc = 0;
-        if (hipMemsetAsync(inv, 0, 16, s) != hipSuccess) rc = set_error("vnm_sort_indices: memset failed");
-        if (!rc) {
-            sort_inversions_kernel<<<grid_for(n, 16), 256, 0, s>>>(keys[0], orders[0] == VNM_DESC, n, inv);
-            if (hipGetLastError() != hipSuccess || hipMemcpyAsync(ninv, inv, 16, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-                rc = set_error("vnm_sort_indices: the sortedness check failed");
-        }
-        pool_free(inv);
-        if (rc) return rc;
-        if (ninv[0] == 0 || ninv[1] == 0) {
-            const int backwards = ninv[0] != 0;
-            route_note("sort:already_sorted", "%lld rows, one 8-byte key: the rows arrive %s: the indices are the row numbers%s", (long long)n,
-                       backwards ? "strictly in the opposite order (every row below its predecessor, no ties)" : "in the order asked for (no row below its predecessor)", backwards ? " backwards" : "");
-            sort_iota64_kernel<<<grid_for(n, 16), 256, 0, s>>>(out_indices, n, backwards);
-            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return set_error("vnm_sort_indices: kernel launch failed");
-            if (wrote_key0) *wrote_key0 = 0;
-            return 0;
-        }
-    }
-    g_rows_clustered = false;
-    RadixBufs r{};
-    VNM_TRY(radix_alloc(&r, n));
-    bool wrote = false, wrote_key = false;
-    route_note("sort:lsd_radix", "%lld rows, %d keys: stable LSD passes over order-preserving codes, last key first", (long long)n, n_keys);
-    int rc = full_sort(n_keys, keys, orders, n, &r, s, out_indices, &wrote, (uint64_t*)out_sorted_key0, &wrote_key);
-    if (!rc && wrote_key0) *wrote_key0 = wrote_key ? 1 : 0;
-    if (!rc) {
-        if (!wrote) sort_widen_kernel<<<grid_for(n), 256, 0, s>>>(r.val[r.cur], n, out_indices);
-        if (hipGetLastError() != hipSuccess) rc = set_error("vnm_sort_indices: kernel launch failed");
-        if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = set_error("vnm_sort_indices: stream sync failed");
-    }
-    radix_free(&r);
+    if (rc == 2 && clustered && !key_out) rc = try_already_sorted(key, desc, n, out_indices, wrote_key0, s);
+    if (rc == 2) rc = lsd_sort(n_keys, keys, orders, n, out_indices, key_out, wrote_key0, s);
     return rc;
 }
 

@@ -598,183 +598,207 @@ __global__ __launch_bounds__(XL_BLOCK) __attribute__((amdgpu_waves_per_eu(6, 6))
     if (nties) atomicAdd(&a.flags[5], (unsigned long long)nties);
 }
 
-// 0 = done, 2 = declined / failed (the caller goes on with the splitter sort), 1 = error
-static int sample_sort_apx(const vnm_dcol& key, int desc, int64_t n, int64_t* idx_out, hipStream_t s) {
-    if (n >= ((int64_t)1 << 32)) return 2;
-    const int has_null = key.validity != nullptr;
-    const bool trace = getenv("VNM_SORT_TRACE") != nullptr;
-    const int cus = device_info().num_cus;
-    int l2 = 8;
-    while (l2 < SS_B && n / ((int64_t)SS_B * l2) > 4200) l2 *= 2;
-    {   // (a power of two, 8 .. 512)
-        int64_t want = env_sort_i64("VNM_XSORT_L2", l2);
-        int p2 = 8;
-        while (p2 < SS_B && p2 < want) p2 *= 2;
-        l2 = p2;
-    }
-    int qbits = 0;
-    while ((1 << qbits) < l2) qbits++;
-    const int64_t nb = (int64_t)SS_B * l2;
-    const int64_t m = std::min<int64_t>(n, env_sort_i64("VNM_XSORT_SAMPLE", (int64_t)1 << 21));
-    static bool attr_set = false;
-    const size_t lds1 = ((size_t)SS_B * XS_CAP + XS_K + 1) * 8, lds2 = (size_t)SS_B * XS_CAP * 8;
-    if (!attr_set) {
-        VNM_HIP(hipFuncSetAttribute((const void*)xsort_scatter_kernel<true, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        VNM_HIP(hipFuncSetAttribute((const void*)xsort_scatter_kernel<true, 2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        VNM_HIP(hipFuncSetAttribute((const void*)xsort_scatter_kernel<true, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        VNM_HIP(hipFuncSetAttribute((const void*)xsort_scatter_kernel<true, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        VNM_HIP(hipFuncSetAttribute((const void*)xsort_scatter_kernel<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-        VNM_HIP(hipFuncSetAttribute((const void*)xsort_scatter_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-        VNM_HIP(hipFuncSetAttribute((const void*)ssort_local_kernel<1024, 8, 8192, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)SS_LOCAL * 12 + 8192 * 4)));
-        VNM_HIP(hipFuncSetAttribute((const void*)onesweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OS_LDS_BYTES));
-        attr_set = true;
-    }
+// ---- the entry-word sample sort, stage by stage -----------------------------------------------------------------------------------------------
+// What the stages hand to each other.  `pool` and `side` own every block named here: they go back when sample_sort_apx returns.
+constexpr size_t XS_LDS1 = ((size_t)SS_B * XS_CAP + XS_K + 1) * 8, XS_LDS2 = (size_t)SS_B * XS_CAP * 8;
+struct XsRun {
+    vnm_dcol key; int desc; int64_t n; hipStream_t s;
+    int has_null; bool trace;
+    int l2, qbits, gbits; int64_t nb, m;        // 512 x l2 = 2^(9 + qbits) buckets, m sampled keys, 2^gbits groups of the sample judge the map
     PoolScope pool;
-    unsigned long long* flags = (unsigned long long*)pool.take(64);
-    XsHdr* hdr = (XsHdr*)pool.take(sizeof(XsHdr));
-    uint64_t* fb = (uint64_t*)pool.take((size_t)(XS_K + 1) * 8 * 2);   // [mode][XS_K + 1]
-    if (!flags || !hdr || !fb) return 1;
+    unsigned long long* flags; XsHdr* hdr; uint64_t* fb;
+    XsHdr hh; int xmode; unsigned long long null_counts[2];   // what the sample said; [0] NULL rows of the sample, [1] of the column
+    RadixBufs side;                                           // the NULL rows bypass the buckets
+    Level1Geometry g; int64_t cap1, cap2; int nt, ready_list;
+    uint64_t *w1, *w2; uint32_t *n1, *n2, *todo, *todo_list; unsigned long long* offs;
+    int64_t side_len;
+};
+
+static void xsort_plan(XsRun* st) {
+    int l2 = 8;
+    while (l2 < SS_B && st->n / ((int64_t)SS_B * l2) > 4200) l2 *= 2;
+    const int64_t want = env_sort_i64("VNM_XSORT_L2", l2);   // (a power of two, 8 .. 512)
+    for (l2 = 8; l2 < SS_B && l2 < want;) l2 *= 2;
+    st->l2 = l2;
+    while ((1 << st->qbits) < l2) st->qbits++;
+    st->nb = (int64_t)SS_B * l2;
+    st->m = std::min<int64_t>(st->n, env_sort_i64("VNM_XSORT_SAMPLE", (int64_t)1 << 21));
+    while (((int64_t)1 << st->gbits) < st->nb / 8 && st->gbits < 15) st->gbits++;
+}
+
+static int xsort_allow_lds() {
+    static bool attr_set = false;
+    if (attr_set) return 0;
+    VNM_TRY(allow_dynamic_lds(xsort_scatter_kernel<true, 1, 0>, XS_LDS1));
+    VNM_TRY(allow_dynamic_lds(xsort_scatter_kernel<true, 2, 0>, XS_LDS1));
+    VNM_TRY(allow_dynamic_lds(xsort_scatter_kernel<true, 1, 1>, XS_LDS1));
+    VNM_TRY(allow_dynamic_lds(xsort_scatter_kernel<true, 2, 1>, XS_LDS1));
+    VNM_TRY(allow_dynamic_lds(xsort_scatter_kernel<false, 1>, XS_LDS2));
+    VNM_TRY(allow_dynamic_lds(xsort_scatter_kernel<false, 2>, XS_LDS2));
+    VNM_TRY(allow_dynamic_lds(ssort_local_kernel<1024, 8, 8192, true, true>, (size_t)SS_LOCAL * 12 + 8192 * 4));
+    attr_set = true;
+    return 0;
+}
+
+// Stage 1: the map from a sorted sample, in both spaces, and what the sample says about it.  2 = declined: no map equalises the sample,
+// too many equal keys or NULLs, or the rows arrive clustered (*clustered).  The sample itself goes back to the pool on return.
+static int xsort_map_from_sample(XsRun* st, bool* clustered) {
+    hipStream_t s = st->s;
+    const int64_t n = st->n, m = st->m;
+    st->flags = (unsigned long long*)st->pool.take(64);
+    st->hdr = (XsHdr*)st->pool.take(sizeof(XsHdr));
+    st->fb = (uint64_t*)st->pool.take((size_t)(XS_K + 1) * 8 * 2);   // [mode][XS_K + 1]
+    if (!st->flags || !st->hdr || !st->fb) return 1;
+    unsigned long long* flags = st->flags;
     VNM_HIP(hipMemsetAsync(flags, 0, 64, s));
-    VNM_HIP(hipMemsetAsync(hdr, 0, sizeof(XsHdr), s));
-    XsHdr hh{};
-    unsigned long long null_counts[2] = {0, 0};
+    VNM_HIP(hipMemsetAsync(st->hdr, 0, sizeof(XsHdr), s));
+    const XsHdr& hh = st->hh;
     unsigned long long min_span = ~0ULL;
-    int xmode = 0;
-    int gbits = 0;
-    while (((int64_t)1 << gbits) < nb / 8 && gbits < 15) gbits++;
-    {
-        RadixBufs sr{};
-        VNM_TRY(radix_alloc(&sr, m));
-        {
-            KernelTimer timer("sort_sample", s);
-            ssort_sample_kernel<<<grid_for(m), 256, 0, s>>>(key, desc, n, m, sr.code[0], flags + 6);
-        }
-        sort_iota_kernel<<<grid_for(m), 256, 0, s>>>(sr.val[0], m);
-        sr.cur = 0;
-        VNM_TRY(radix_sort_codes(&sr, m, s));
-        const uint64_t* S = sr.code[sr.cur];
-        xsort_prep_kernel<<<64, 256, 0, s>>>(S, m, hdr, key.type, desc);
-        xsort_map_kernel<<<dim3((XS_K + 1 + 255) / 256, 2), 256, 0, s>>>(S, hdr, fb, key.type, desc, (uint64_t)1 << (41 - 9 - qbits));
-        xsort_balance_kernel<<<dim3((unsigned)((((int64_t)1 << gbits) + 255) / 256), 2), 256, 0, s>>>(S, hdr, fb, gbits, key.type, desc);
-        VNM_HIP(hipGetLastError());
-        if (has_null) ssort_count_nulls_kernel<<<grid_for((n + 7) / 8), 256, 0, s>>>(key.validity, key.offset, n, flags + 7);
-        VNM_HIP(hipMemsetAsync(flags + 3, 0xFF, 8, s));
-        ssort_cluster_kernel<<<64, 256, 0, s>>>(key, desc, n, S, m, flags + 3);    // (rows that arrive clustered: see ssort_cluster_kernel)
-        VNM_HIP(hipGetLastError());
-        VNM_HIP(hipMemcpyAsync(&min_span, flags + 3, 8, hipMemcpyDeviceToHost, s));
-        VNM_HIP(hipMemcpyAsync(&hh, hdr, sizeof(XsHdr), hipMemcpyDeviceToHost, s));
-        VNM_HIP(hipMemcpyAsync(null_counts, flags + 6, 16, hipMemcpyDeviceToHost, s));   // [0] NULL rows of the sample, [1] of the column
-        VNM_HIP(hipStreamSynchronize(s));   // (sr goes back to the pool here)
-    }
-    {
-        // equal neighbours in the sample: values of multiplicity k leave (k - 1) m^2 / 2n of them -- and every row of such a value would
-        // fetch k codes from the key column.  Fetches for up to ~3 % of the rows are accepted.
-        const double me = (double)std::max<long long>(1, hh.m_eff);
-        const double eq_limit = std::max(16.0, (double)env_sort_i64("VNM_XSORT_EQ_PERMILLE", 15) / 1000.0 * me * me / (double)n);
-        const double gmean = me / (double)((int64_t)1 << gbits);
-        const double glimit = gmean * 1.25 + 6.0 * std::sqrt(gmean) + 8.0;
-        int mode = -1;
-        for (int q = 0; q < 2; q++)
-            if (hh.ok[q] && (double)hh.max_group[q] <= glimit && (mode < 0 || hh.max_group[q] < hh.max_group[mode])) mode = q;
-        if (env_sort_i64("VNM_XSORT_MODE", -1) >= 0) { const int want = (int)env_sort_i64("VNM_XSORT_MODE", -1) & 1; mode = hh.ok[want] && (double)hh.max_group[want] <= glimit ? want : -1; }
-        // (NULL rows of the sample carry the all-ones code like NaN: with NULLs, a sample without NaN has m - nulls codes in front of them)
-        const bool clustered = min_span != ~0ULL && (int64_t)min_span < (int64_t)hh.m_eff / 8 && env_sort_i64("VNM_SSORT_CLUSTER_CHECK", 1);
-        if (clustered) g_rows_clustered = true;
-        if (clustered && trace) fprintf(stderr, "[sort] entry-word sample sort: the rows arrive clustered (a tile of 4096 consecutive rows spans %llu of %lld samples)\n", min_span, hh.m_eff);
-        const bool ok = mode >= 0 && !clustered && (double)hh.eq_pairs <= eq_limit && hh.m_eff == m - (long long)null_counts[0] && (!has_null || null_counts[1] < (unsigned long long)n / 2);
-        if (trace) fprintf(stderr, "[sort] entry-word sample sort: sample %lld (%lld in front of NaN), %llu equal neighbours (limit %.0f); largest group of the sample: code cells (2^%lld) %s%llu, "
+    RadixBufs sr{};
+    VNM_TRY(sorted_sample(st->key, st->desc, n, m, flags + 6, &sr, s));
+    const uint64_t* S = sr.code[sr.cur];
+    xsort_prep_kernel<<<64, 256, 0, s>>>(S, m, st->hdr, st->key.type, st->desc);
+    xsort_map_kernel<<<dim3((XS_K + 1 + 255) / 256, 2), 256, 0, s>>>(S, st->hdr, st->fb, st->key.type, st->desc, (uint64_t)1 << (41 - 9 - st->qbits));
+    xsort_balance_kernel<<<dim3((unsigned)((((int64_t)1 << st->gbits) + 255) / 256), 2), 256, 0, s>>>(S, st->hdr, st->fb, st->gbits, st->key.type, st->desc);
+    VNM_HIP(hipGetLastError());
+    if (st->has_null) ssort_count_nulls_kernel<<<grid_for((n + 7) / 8), 256, 0, s>>>(st->key.validity, st->key.offset, n, flags + 7);
+    VNM_TRY(sample_cluster_span(st->key, st->desc, n, S, m, flags + 3, &min_span, s));
+    VNM_HIP(hipMemcpyAsync(&st->hh, st->hdr, sizeof(XsHdr), hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipMemcpyAsync(st->null_counts, flags + 6, 16, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));
+    // equal neighbours in the sample: values of multiplicity k leave (k - 1) m^2 / 2n of them -- and every row of such a value would
+    // fetch k codes from the key column.  Fetches for up to ~3 % of the rows are accepted.
+    const double me = (double)std::max<long long>(1, hh.m_eff);
+    const double eq_limit = std::max(16.0, (double)env_sort_i64("VNM_XSORT_EQ_PERMILLE", 15) / 1000.0 * me * me / (double)n);
+    const double gmean = me / (double)((int64_t)1 << st->gbits);
+    const double glimit = gmean * 1.25 + 6.0 * std::sqrt(gmean) + 8.0;
+    int mode = -1;
+    for (int q = 0; q < 2; q++)
+        if (hh.ok[q] && (double)hh.max_group[q] <= glimit && (mode < 0 || hh.max_group[q] < hh.max_group[mode])) mode = q;
+    if (env_sort_i64("VNM_XSORT_MODE", -1) >= 0) { const int want = (int)env_sort_i64("VNM_XSORT_MODE", -1) & 1; mode = hh.ok[want] && (double)hh.max_group[want] <= glimit ? want : -1; }
+    // (NULL rows of the sample carry the all-ones code like NaN: with NULLs, a sample without NaN has m - nulls codes in front of them)
+    *clustered = rows_arrive_clustered(min_span, (int64_t)hh.m_eff);
+    if (*clustered && st->trace) fprintf(stderr, "[sort] entry-word sample sort: the rows arrive clustered (a tile of 4096 consecutive rows spans %llu of %lld samples)\n", min_span, hh.m_eff);
+    const bool ok = mode >= 0 && !*clustered && (double)hh.eq_pairs <= eq_limit && hh.m_eff == m - (long long)st->null_counts[0] && (!st->has_null || st->null_counts[1] < (unsigned long long)n / 2);
+    if (st->trace) fprintf(stderr, "[sort] entry-word sample sort: sample %lld (%lld in front of NaN), %llu equal neighbours (limit %.0f); largest group of the sample: code cells (2^%lld) %s%llu, "
                                    "value cells %s%llu (mean %.1f, limit %.0f) -> %s\n",
                            (long long)m, hh.m_eff, hh.eq_pairs, eq_limit, hh.sh, hh.ok[0] ? "" : "n/a ", hh.max_group[0], hh.ok[1] ? "" : "n/a ", hh.max_group[1], gmean, glimit,
                            ok ? (mode ? "taken (value cells)" : "taken (code cells)") : "declined");
-        xmode = mode;
-        if (!ok) return 2;
-    }
-    // ---- level 1
-    const int pairs1 = env_sort_i64("VNM_XSORT_PAIRS1", 2) >= 2 ? 2 : 1;
-    const int64_t sub = 2 * SS_BLOCK * pairs1;
-    const int grid1 = (int)std::min<int64_t>((int64_t)cus * env_sort_i64("VNM_XSORT_GRID1_PER_CU", 1), std::max<int64_t>(1, (n + sub - 1) / sub));
-    const int64_t rows_per_wg = (((n + sub - 1) / sub + grid1 - 1) / grid1) * sub;
-    const int64_t cap1 = ((rows_per_wg / SS_B + rows_per_wg / SS_B / 4 + 2 * XS_FB * 4) + XS_FB - 1) & ~(int64_t)(XS_FB - 1);
-    int split2 = std::max(1, (grid1 + SS_MAX_REGIONS - 1) / SS_MAX_REGIONS);
-    split2 = std::max(split2, (int)env_sort_i64("VNM_XSORT_SPLIT2", 1));
-    if (split2 > XL_MAX_SPLIT) return 2;
-    uint64_t* w1 = (uint64_t*)pool.take((size_t)SS_B * grid1 * cap1 * 8);
-    uint32_t* n1 = (uint32_t*)pool.take((size_t)SS_B * grid1 * 4);
-    if (!w1 || !n1) return 1;
+    st->xmode = mode;
+    return ok ? 0 : 2;
+}
+
+// Stage 2: level 1, rows -> entry words in 512 buckets per workgroup region.  2 = more level-1 regions than the local sort reads.
+static int xsort_level1(XsRun* st) {
+    hipStream_t s = st->s;
+    const XsHdr& hh = st->hh;
+    st->g = level1_geometry(st->n, env_sort_i64("VNM_XSORT_PAIRS1", 2), env_sort_i64("VNM_XSORT_GRID1_PER_CU", 1), env_sort_i64("VNM_XSORT_SPLIT2", 1));
+    const int grid1 = st->g.grid1;
+    st->cap1 = ((st->g.rows_per_wg / SS_B + st->g.rows_per_wg / SS_B / 4 + 2 * XS_FB * 4) + XS_FB - 1) & ~(int64_t)(XS_FB - 1);
+    if (st->g.split2 > XL_MAX_SPLIT) return 2;
+    st->w1 = (uint64_t*)st->pool.take((size_t)SS_B * grid1 * st->cap1 * 8);
+    st->n1 = (uint32_t*)st->pool.take((size_t)SS_B * grid1 * 4);
+    if (!st->w1 || !st->n1) return 1;
+    st->nt = (int)env_sort_i64("VNM_XSORT_NT", 0); st->ready_list = (int)env_sort_i64("VNM_XSORT_READY_LIST", 1);
     XsArgs a1{};
-    a1.key = key; a1.desc = desc; a1.nrows = n; a1.fb = fb; a1.qbits = qbits;
-    a1.map.mode = xmode; a1.map.sh = (int)hh.sh; a1.map.base = hh.base; a1.map.u_lo = hh.u_lo; a1.map.inv_w = hh.inv_w;
-    a1.out_words = w1; a1.out_counts = n1; a1.out_cap = cap1; a1.flags = flags; a1.nt = (int)env_sort_i64("VNM_XSORT_NT", 0); a1.ready_list = (int)env_sort_i64("VNM_XSORT_READY_LIST", 1);
-    RadixBufs side{};
-    const int64_t side_cap = has_null ? (int64_t)null_counts[1] + 64 : 0;
-    if (has_null) {
-        VNM_TRY(radix_alloc(&side, side_cap));
-        a1.has_null = 1; a1.side = (unsigned long long*)side.code[0]; a1.side_cap = side_cap;
+    a1.key = st->key; a1.desc = st->desc; a1.nrows = st->n; a1.fb = st->fb; a1.qbits = st->qbits;
+    a1.map.mode = st->xmode; a1.map.sh = (int)hh.sh; a1.map.base = hh.base; a1.map.u_lo = hh.u_lo; a1.map.inv_w = hh.inv_w;
+    a1.out_words = st->w1; a1.out_counts = st->n1; a1.out_cap = st->cap1; a1.flags = st->flags; a1.nt = st->nt; a1.ready_list = st->ready_list;
+    if (st->has_null) {
+        const int64_t side_cap = (int64_t)st->null_counts[1] + 64;
+        VNM_TRY(radix_alloc(&st->side, side_cap));
+        a1.has_null = 1; a1.side = (unsigned long long*)st->side.code[0]; a1.side_cap = side_cap;
     }
     {
         KernelTimer timer("sort_scatter1", s);
-        if (xmode == 0) {
-            if (pairs1 == 2) xsort_scatter_kernel<true, 2, 0><<<grid1, SS_BLOCK, lds1, s>>>(a1);
-            else xsort_scatter_kernel<true, 1, 0><<<grid1, SS_BLOCK, lds1, s>>>(a1);
+        if (st->xmode == 0) {
+            if (st->g.pairs1 == 2) xsort_scatter_kernel<true, 2, 0><<<grid1, SS_BLOCK, XS_LDS1, s>>>(a1);
+            else xsort_scatter_kernel<true, 1, 0><<<grid1, SS_BLOCK, XS_LDS1, s>>>(a1);
         } else {
-            if (pairs1 == 2) xsort_scatter_kernel<true, 2, 1><<<grid1, SS_BLOCK, lds1, s>>>(a1);
-            else xsort_scatter_kernel<true, 1, 1><<<grid1, SS_BLOCK, lds1, s>>>(a1);
+            if (st->g.pairs1 == 2) xsort_scatter_kernel<true, 2, 1><<<grid1, SS_BLOCK, XS_LDS1, s>>>(a1);
+            else xsort_scatter_kernel<true, 1, 1><<<grid1, SS_BLOCK, XS_LDS1, s>>>(a1);
         }
     }
     VNM_HIP(hipGetLastError());
-    // ---- level 2
-    const int64_t avg_bucket = n / nb + 1;
-    const int64_t cap2 = ((std::min<int64_t>(SS_LOCAL, avg_bucket * 3 / 2 / split2 + avg_bucket / 4 + 256)) + XS_FB - 1) & ~(int64_t)(XS_FB - 1);
-    uint64_t* w2 = (uint64_t*)pool.take((size_t)nb * split2 * cap2 * 8);
-    uint32_t* n2 = (uint32_t*)pool.take((size_t)nb * split2 * 4);
-    unsigned long long* offs = (unsigned long long*)pool.take((size_t)(nb + 1) * 8);
+    return 0;
+}
+
+// Stages 3 and 4: level 2 by the next bits of the words, then the buckets' sizes and offsets.  2 = a region or a bucket overflowed.
+static int xsort_level2_and_offsets(XsRun* st) {
+    hipStream_t s = st->s;
+    const int64_t nb = st->nb;
+    const int split2 = st->g.split2;
+    const int64_t avg_bucket = st->n / nb + 1;
+    st->cap2 = ((std::min<int64_t>(SS_LOCAL, avg_bucket * 3 / 2 / split2 + avg_bucket / 4 + 256)) + XS_FB - 1) & ~(int64_t)(XS_FB - 1);
+    st->w2 = (uint64_t*)st->pool.take((size_t)nb * split2 * st->cap2 * 8);
+    st->n2 = (uint32_t*)st->pool.take((size_t)nb * split2 * 4);
+    st->offs = (unsigned long long*)st->pool.take((size_t)(nb + 1) * 8);
     const int nchunks = (int)((nb + XO_CHUNK - 1) / XO_CHUNK);
-    unsigned long long* part = (unsigned long long*)pool.take((size_t)nchunks * 8);
-    uint32_t* todo = (uint32_t*)pool.take((size_t)nb * 4);
-    uint32_t* todo_list = (uint32_t*)pool.take((size_t)nb * 4);
-    if (!w2 || !n2 || !offs || !part || !todo || !todo_list) return 1;
-    VNM_HIP(hipMemsetAsync(todo, 0, (size_t)nb * 4, s));
+    unsigned long long* part = (unsigned long long*)st->pool.take((size_t)nchunks * 8);
+    st->todo = (uint32_t*)st->pool.take((size_t)nb * 4);
+    st->todo_list = (uint32_t*)st->pool.take((size_t)nb * 4);
+    if (!st->w2 || !st->n2 || !st->offs || !part || !st->todo || !st->todo_list) return 1;
+    VNM_HIP(hipMemsetAsync(st->todo, 0, (size_t)nb * 4, s));
     XsArgs a2{};
-    a2.qbits = qbits; a2.in_words = w1; a2.in_counts = n1; a2.in_cap = cap1; a2.in_regions = grid1; a2.in_split = split2;
-    a2.out_words = w2; a2.out_counts = n2; a2.out_cap = cap2; a2.flags = flags; a2.nt = a1.nt; a2.ready_list = a1.ready_list;
+    a2.qbits = st->qbits; a2.in_words = st->w1; a2.in_counts = st->n1; a2.in_cap = st->cap1; a2.in_regions = st->g.grid1; a2.in_split = split2;
+    a2.out_words = st->w2; a2.out_counts = st->n2; a2.out_cap = st->cap2; a2.flags = st->flags; a2.nt = st->nt; a2.ready_list = st->ready_list;
     {
         KernelTimer timer("sort_scatter2", s);
-        if (env_sort_i64("VNM_XSORT_PAIRS2", 2) >= 2) xsort_scatter_kernel<false, 2><<<SS_B * split2, SS_BLOCK, lds2, s>>>(a2);
-        else xsort_scatter_kernel<false, 1><<<SS_B * split2, SS_BLOCK, lds2, s>>>(a2);
+        if (env_sort_i64("VNM_XSORT_PAIRS2", 2) >= 2) xsort_scatter_kernel<false, 2><<<SS_B * split2, SS_BLOCK, XS_LDS2, s>>>(a2);
+        else xsort_scatter_kernel<false, 1><<<SS_B * split2, SS_BLOCK, XS_LDS2, s>>>(a2);
     }
     VNM_HIP(hipGetLastError());
-    xsort_sizes_kernel<<<nchunks, 256, 0, s>>>(n2, split2, nb, part, flags, SS_LOCAL);
-    xsort_offsets_kernel<<<nchunks, 256, 0, s>>>(n2, split2, nb, part, offs);
+    xsort_sizes_kernel<<<nchunks, 256, 0, s>>>(st->n2, split2, nb, part, st->flags, SS_LOCAL);
+    xsort_offsets_kernel<<<nchunks, 256, 0, s>>>(st->n2, split2, nb, part, st->offs);
     VNM_HIP(hipGetLastError());
     unsigned long long fl[3] = {0, 0, 0};
-    VNM_HIP(hipMemcpyAsync(fl, flags, 24, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipMemcpyAsync(fl, st->flags, 24, hipMemcpyDeviceToHost, s));
     VNM_HIP(hipStreamSynchronize(s));
-    if (trace) fprintf(stderr, "[sort] entry-word sample sort: n %lld grid1 %d cap1 %lld split2 %d cap2 %lld buckets %lld -> fail %llu\n",
-                       (long long)n, grid1, (long long)cap1, split2, (long long)cap2, (long long)nb, fl[0]);
-    if (fl[0]) return 2;
-    // ---- per-bucket LDS sort, straight into the caller's buffer
+    if (st->trace) fprintf(stderr, "[sort] entry-word sample sort: n %lld grid1 %d cap1 %lld split2 %d cap2 %lld buckets %lld -> fail %llu\n",
+                           (long long)st->n, st->g.grid1, (long long)st->cap1, split2, (long long)st->cap2, (long long)nb, fl[0]);
+    st->side_len = (int64_t)fl[2];
+    return fl[0] ? 2 : 0;
+}
+
+// Stage 5: per-bucket LDS sort, straight into the caller's buffer; the NULL rows behind everything
+static int xsort_local(XsRun* st, int64_t* idx_out) {
+    hipStream_t s = st->s;
+    const int cus = device_info().num_cus;
+    const int64_t nb = st->nb;
     XlArgs la{};
-    la.words = w2; la.counts = n2; la.cap = cap2; la.split = split2; la.offs = offs; la.nbuckets = nb; la.idx_out = idx_out;
-    la.key = key; la.desc = desc; la.rbits = 32 - qbits; la.todo = todo; la.list = todo_list; la.flags = flags;
+    la.words = st->w2; la.counts = st->n2; la.cap = st->cap2; la.split = st->g.split2; la.offs = st->offs; la.nbuckets = nb; la.idx_out = idx_out;
+    la.key = st->key; la.desc = st->desc; la.rbits = 32 - st->qbits; la.todo = st->todo; la.list = st->todo_list; la.flags = st->flags;
     SsLocalArgs lb{};
-    lb.code = w2; lb.row = nullptr; lb.counts = n2; lb.cap = cap2; lb.split = split2; lb.offs = offs; lb.nbuckets = nb; lb.idx_out = idx_out;
-    lb.key_out = nullptr; lb.key_type = key.type; lb.key_desc = desc; lb.flags = flags; lb.debug = 0; lb.todo = todo; lb.key = key; lb.crowded = nullptr; lb.list = todo_list; lb.list_n = flags + 4;
+    lb.code = st->w2; lb.row = nullptr; lb.counts = st->n2; lb.cap = st->cap2; lb.split = st->g.split2; lb.offs = st->offs; lb.nbuckets = nb; lb.idx_out = idx_out;
+    lb.key_out = nullptr; lb.key_type = st->key.type; lb.key_desc = st->desc; lb.flags = st->flags; lb.debug = 0; lb.todo = st->todo; lb.key = st->key; lb.crowded = nullptr; lb.list = st->todo_list; lb.list_n = st->flags + 4;
     {
         KernelTimer timer("sort_local", s);
         xsort_local_kernel<<<(int)std::min<int64_t>(nb, (int64_t)cus * env_sort_i64("VNM_XSORT_LOCAL_PER_CU", 48)), XL_BLOCK, 0, s>>>(la);
         ssort_local_kernel<1024, 8, 8192, true, true><<<(int)std::min<int64_t>(nb, (int64_t)cus * 16), 1024, (size_t)SS_LOCAL * 12 + 8192 * 4, s>>>(lb);
     }
     VNM_HIP(hipGetLastError());
-    if (has_null && fl[2] > 0) {   // the NULL rows, in row order, behind every value (NaN included): Arrow's SortIndices puts them last in both directions
-        const int64_t side_len = (int64_t)fl[2];
-        side.cur = 0;
-        if (side_len > 1) VNM_TRY(radix_sort_codes(&side, side_len, s, nullptr, nullptr, false, nullptr, false, nullptr));
-        xsort_nulls_kernel<<<grid_for(side_len), 256, 0, s>>>((const unsigned long long*)side.code[side.cur], side_len, offs + nb, idx_out);
+    if (st->has_null && st->side_len > 0) {   // the NULL rows, in row order, behind every value (NaN included): Arrow's SortIndices puts them last in both directions
+        st->side.cur = 0;
+        if (st->side_len > 1) VNM_TRY(radix_sort_codes(&st->side, st->side_len, s));
+        xsort_nulls_kernel<<<grid_for(st->side_len), 256, 0, s>>>((const unsigned long long*)st->side.code[st->side.cur], st->side_len, st->offs + nb, idx_out);
         VNM_HIP(hipGetLastError());
     }
     unsigned long long f8[8];
-    VNM_HIP(hipMemcpyAsync(f8, flags, 64, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipMemcpyAsync(f8, st->flags, 64, hipMemcpyDeviceToHost, s));
     VNM_HIP(hipStreamSynchronize(s));
-    if (trace) fprintf(stderr, "[sort] entry-word sample sort: %llu buckets through the long kernel, %llu entries ordered through the key column\n", f8[4], f8[5]);
+    if (st->trace) fprintf(stderr, "[sort] entry-word sample sort: %llu buckets through the long kernel, %llu entries ordered through the key column\n", f8[4], f8[5]);
     return 0;
+}
+
+// 0 = done, 1 = error, 2 = declined / failed (the caller goes on with the splitter sort); *clustered: the rows arrive clustered
+static int sample_sort_apx(const vnm_dcol& key, int desc, int64_t n, int64_t* idx_out, bool* clustered, hipStream_t s) {
+    if (n >= ((int64_t)1 << 32)) return 2;
+    XsRun st{};
+    st.key = key; st.desc = desc; st.n = n; st.s = s; st.has_null = key.validity != nullptr; st.trace = getenv("VNM_SORT_TRACE") != nullptr;
+    xsort_plan(&st);
+    VNM_TRY(xsort_allow_lds());
+    VNM_TRY(xsort_map_from_sample(&st, clustered));
+    VNM_TRY(xsort_level1(&st));
+    VNM_TRY(xsort_level2_and_offsets(&st));
+    return xsort_local(&st, idx_out);
 }

@@ -777,3 +777,44 @@ __global__ void ssort_check_kernel(const uint32_t* row, const uint32_t* counts, 
         }
     }
 }
+
+// ---- what the two sample sorts (sample_sort in vnm_sort.hip, sample_sort_apx in vnm_sort_apx.inc) do alike ----------------------------
+// m strided keys of the column as codes, sorted.  They stay in r->code[r->cur] for as long as the caller's `r` lives; the sample's NULL rows
+// are counted into *sample_nulls (device) and stand at the end with the all-ones code.
+static int sorted_sample(const vnm_dcol& key, int desc, int64_t n, int64_t m, unsigned long long* sample_nulls, RadixBufs* r, hipStream_t s) {
+    VNM_TRY(radix_alloc(r, m));
+    {
+        KernelTimer timer("sort_sample", s);
+        ssort_sample_kernel<<<grid_for(m), 256, 0, s>>>(key, desc, n, m, r->code[0], sample_nulls);
+    }
+    sort_iota_kernel<<<grid_for(m), 256, 0, s>>>(r->val[0], m);
+    r->cur = 0;
+    return radix_sort_codes(r, m, s);
+}
+// The smallest number of sorted samples S[0 .. m) that a tile of 4096 consecutive rows spans, into *span (device) and, once the caller has
+// synchronised the stream, into *span_host (~0: no tile was looked at).
+static int sample_cluster_span(const vnm_dcol& key, int desc, int64_t n, const uint64_t* S, int64_t m, unsigned long long* span,
+                               unsigned long long* span_host, hipStream_t s) {
+    VNM_HIP(hipMemsetAsync(span, 0xFF, 8, s));
+    ssort_cluster_kernel<<<64, 256, 0, s>>>(key, desc, n, S, m, span);
+    VNM_HIP(hipGetLastError());
+    VNM_HIP(hipMemcpyAsync(span_host, span, 8, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+// rows that arrive clustered (a sorted column): the ring scatters would crawl -- the LSD passes do not care
+static bool rows_arrive_clustered(unsigned long long span, int64_t m_valid) {
+    return span != ~0ULL && (int64_t)span < m_valid / 8 && env_sort_i64("VNM_SSORT_CLUSTER_CHECK", 1);
+}
+
+// Level 1 of either sort: `grid1` workgroups of SS_BLOCK threads, each scattering `rows_per_wg` rows in sub-tiles of `sub`; level 2 reads
+// the grid1 regions of a level-1 bucket in `split2` parts (at most SS_MAX_REGIONS regions per workgroup).
+struct Level1Geometry { int pairs1; int64_t sub; int grid1; int64_t rows_per_wg; int split2; };
+static Level1Geometry level1_geometry(int64_t n, int64_t pairs1, int64_t grid1_per_cu, int64_t split2_min) {
+    Level1Geometry g{};
+    g.pairs1 = pairs1 >= 2 ? 2 : 1;
+    g.sub = 2 * SS_BLOCK * g.pairs1;
+    g.grid1 = (int)std::min<int64_t>((int64_t)device_info().num_cus * grid1_per_cu, std::max<int64_t>(1, (n + g.sub - 1) / g.sub));
+    g.rows_per_wg = (((n + g.sub - 1) / g.sub + g.grid1 - 1) / g.grid1) * g.sub;
+    g.split2 = std::max(std::max(1, (g.grid1 + SS_MAX_REGIONS - 1) / SS_MAX_REGIONS), (int)split2_min);
+    return g;
+}
