@@ -102,7 +102,13 @@ enum vnm_expr_op {
      * predicate value: arg = the int32 code column, imm_i = the index in `cols` of the table -- a VNM_U8 column of one byte
      * per dictionary id (vnm_strdict_like) whose length is the id count, not the batch length; it is read by this opcode only.
      * A NULL code, a negative code and a code past the table push 0 (NOT LIKE = NOT of it: true on NULL rows, as `!=`). */
-    VNM_EX_LOOKUP_U8
+    VNM_EX_LOOKUP_U8,
+    /* A dictionary-coded string / binary column compared with ANOTHER such column (expressions.py:30-36 on the two value arrays).
+     * Same operands as VNM_EX_LOOKUP_U8, the table a VNM_I32 column without NULLs (vnm_strdict_translate: the other dictionary's
+     * code of each id; vnm_strdict_ranks_joint: the rank of each id in the union of both dictionaries).  Pushes table[code] as an
+     * integer VALUE, NULL when the code is NULL, negative or past the table: a comparison with it is False on such rows, `!=`
+     * True, like every comparison with a NULL operand.  Value 38; no earlier value moves. */
+    VNM_EX_LOOKUP_I32
 };
 /* out_type of vnm_project when the expression is a predicate: out_values is a byte mask (1 byte per row) */
 #define VNM_MASK_U8 100
@@ -500,6 +506,19 @@ int vnm_strdict_codes_to_ranks(const int32_t* codes, const int32_t* rank_of_id, 
 int vnm_like_compile(const uint8_t* pattern, int64_t pattern_len, int32_t* out_tokens, int64_t* n_tokens);
 int vnm_strdict_like(vnm_strdict* h, const uint8_t* pattern, int64_t pattern_len, int flags, int64_t id_begin,
                      uint8_t* out_match_of_id, void* stream);
+/* Two dictionaries against each other: what `city_from = city_to` / `city_from < city_to` need when the two columns keep separate
+ * dictionaries.  Bytes are compared exactly (no trailing-NUL rule, as a literal is compared by vnm_strdict_* callers).
+ * vnm_strdict_translate: out_dst_code_of_src_id[id] = the code dst holds for the bytes of src's value id, for every id in
+ * [id_begin, vnm_strdict_ids(src)); -2 where dst does not hold the value or the id was never handed out (-1 stays the NULL code,
+ * valid codes are >= 0).  The encode kernels' probe of dst's table without the insert: dst is only read.  One kernel on `stream`,
+ * launched asynchronously.  A table kept across batches is extended with id_begin = the id count it covers only while dst has
+ * not grown (an absent value can become present).
+ * vnm_strdict_ranks_joint: dense ranks of the values of both dictionaries in the ascending byte order of their union -- the order of
+ * vnm_strdict_ranks_device (a prefix first); equal bytes in a and b get the same rank.  out_rank_of_id_a / _b: DEVICE arrays of
+ * vnm_strdict_ids(a) / (b) int32s; entries of ids never handed out are left untouched.  Enqueued on `stream`; like
+ * vnm_strdict_ranks_device it reads counts back in between and returns when the ranks are written. */
+int vnm_strdict_translate(vnm_strdict* src, vnm_strdict* dst, int64_t id_begin, int32_t* out_dst_code_of_src_id, void* stream);
+int vnm_strdict_ranks_joint(vnm_strdict* a, vnm_strdict* b, int32_t* out_rank_of_id_a, int32_t* out_rank_of_id_b, void* stream);
 
 /* ---- CSV ingest ---------------------------------------------------------------------------------------
  * replaces, for numeric columns, the pyarrow.csv reader behind stream_csv() / read_csv() (vinum/io/arrow.py:58-61,106;

@@ -38,7 +38,7 @@ EQ, NE, GT, GE, LT, LE = range(6)
 (EX_COL, EX_CONST_F, EX_CONST_I, EX_ADD, EX_SUB, EX_MUL, EX_DIV, EX_MOD, EX_NEG, EX_BAND, EX_BOR, EX_BXOR,
  EX_BNOT, EX_EQ, EX_NE, EX_GT, EX_GE, EX_LT, EX_LE, EX_AND, EX_OR, EX_NOT, EX_IS_NULL, EX_IS_NOT_NULL,
  EX_STORE, EX_ABS, EX_SQRT, EX_SIN, EX_COS, EX_TAN, EX_LOG, EX_LOG2, EX_LOG10, EX_POW, EX_TO_F64, EX_TO_I64,
- EX_TO_BOOL, EX_LOOKUP_U8) = range(38)
+ EX_TO_BOOL, EX_LOOKUP_U8, EX_LOOKUP_I32) = range(39)
 LIKE_STRIP_NUL = 1                                       # vnm_strdict_like flags
 LIKE_TOK_LIT, LIKE_TOK_ANY, LIKE_TOK_STAR = 0, 1, 2     # vnm_like_compile token kinds
 MASK_U8 = 100
@@ -125,6 +125,8 @@ PROTOTYPES = {
     "vnm_strdict_codes_to_ranks": (c_int, [c_void, c_void, c_i64, c_void, c_void]),
     "vnm_strdict_encode_spans": (c_int, [c_void, c_void, c_void, c_i64, c_void, c_void, c_void, c_void, c_void]),
     "vnm_strdict_last_new": (c_int, [c_void, c_void, c_void]),
+    "vnm_strdict_translate": (c_int, [c_void, c_void, c_i64, c_void, c_void]),
+    "vnm_strdict_ranks_joint": (c_int, [c_void, c_void, c_void, c_void, c_void]),
     "vnm_like_compile": (c_int, [c_void, c_i64, c_void, c_void]),
     "vnm_strdict_like": (c_int, [c_void, c_void, c_i64, c_int, c_i64, c_void, c_void]),
     "vnm_take_varwidth": (c_int, [c_void, c_void, c_void, c_void, c_i64, c_void, c_void, c_void, c_void, c_void]),

@@ -7,15 +7,17 @@ import pyarrow as pa
 from .. import _lib as L
 from .. import ops
 from .base import DeviceRecordBatch, Operator
-from .algebra import FilterOperator, lower_like
+from .algebra import FilterOperator, lower_column_compares, lower_like
 
 _FUNCS = {"COUNT": L.COUNT, "COUNT_STAR": L.COUNT_STAR, "MIN": L.MIN, "MAX": L.MAX, "SUM": L.SUM, "AVG": L.AVG}
 
 
 def _has_cast(e) -> bool:
-    """to_int / to_bool turn float64 columns into a non-float64 value, LIKE into a mask: such an input is projected, not
-    handed to the kernel"""
-    return isinstance(e, tuple) and (e[0] in ("to_int", "to_bool", "like", "not_like") or any(_has_cast(x) for x in e[1:]))
+    """to_int / to_bool turn float64 columns into a non-float64 value, LIKE and a dictionary lookup into a mask / an int32 value:
+    such an input is projected, not handed to the kernel (a comparison of two dictionary-coded columns never gets there either:
+    their codes are not float64 columns)"""
+    return isinstance(e, tuple) and (e[0] in ("to_int", "to_bool", "like", "not_like", "lookup", "lookup_i32")
+                                     or any(_has_cast(x) for x in e[1:]))
 
 
 class AggregateFunction:
@@ -100,6 +102,7 @@ class AggregateOperator(Operator):
         exprs, used, extra = [], {}, {}
         for e in self._projected:
             e, _ = lower_like(e, batch.columns, extra)    # sum(to_int(name LIKE 'J%')): a dictionary lookup
+            e, _ = lower_column_compares(e, batch.columns, extra)   # sum(to_int(city_from = city_to)): translated codes
             exprs.append(e)
             for c in ops.columns_of(e):
                 used[c] = extra[c] if c in extra else batch.columns[c]

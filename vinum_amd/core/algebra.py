@@ -83,6 +83,87 @@ def lower_like(expr, columns, extra=None):
     return walk(expr), extra
 
 
+_CMP = ("eq", "ne", "lt", "le", "gt", "ge")
+_CMP_NAME = {"==": "eq", "=": "eq", "!=": "ne", "<>": "ne", ">": "gt", ">=": "ge", "<": "lt", "<=": "le"}
+# the arithmetic, bitwise, math and cast operators of ops.compile_expr: what takes a NUMBER, which a dictionary code is not
+_ARITHMETIC = ("add", "sub", "mul", "div", "mod", "neg", "+", "-", "*", "/", "%", "band", "bor", "bxor", "bnot", "abs", "sqrt", "sin",
+               "cos", "tan", "log", "log2", "log10", "power", "to_float", "to_int", "to_bool")
+
+
+def lower_column_compares(expr, columns, extra=None):
+    """Comparisons of a dictionary-coded column (strings, binaries: int32 codes of the column's OWN running dictionary) with
+    ANOTHER such column -- `city_from = city_to`, `city_from < city_to`; the reference compares the two value arrays,
+    vinum/core/expressions.py:30-36.  The codes of two dictionaries mean nothing to each other, so:
+      * both columns share one dictionary object: = / != stay as they are (equal codes <=> equal values), the ordered operators
+        compare the two columns' ranks (KeyDictionary.rank_column);
+      * otherwise = / != become (op, a, ("lookup_i32", b, table)) with b's codes translated into a's
+        (KeyDictionary.translate_table: -2 where a's dictionary does not hold the value), and < <= > >= become
+        (op, ("lookup_i32", a, ranks_a), ("lookup_i32", b, ranks_b)) with the ranks of both dictionaries in the byte order of
+        their union (KeyDictionary.joint_rank_tables).
+    BETWEEN / NOT BETWEEN with a dictionary-coded operand is rewritten onto >= <= / < > first (ops._desugar does it too late for
+    this lowering), so column bounds follow.  Bytes are compared exactly, as a literal's are (no trailing-NUL rule); utf8,
+    large_utf8, binary and large_binary mix freely.  A NULL on either side compares False, `!=` True.
+    What has no meaning raises instead of comparing codes: a dictionary-coded column against a numeric column, literal or
+    expression, IN / NOT IN over one with a list that is not all string / binary literals, and one as the operand of an
+    arithmetic, bitwise, math or cast operator (_ARITHMETIC: TypeError); a pair with a host-route dictionary -- bool, decimal,
+    date64 -- (NotImplementedError).  Any other operator over such a column (a string function, say) passes through untouched
+    and is accepted or refused where it is compiled.  Tables and rank columns are added to `extra`.  Returns (expression, extra)."""
+    extra = {} if extra is None else extra
+
+    def is_dict(x):
+        return isinstance(x, str) and x in columns and columns[x].dictionary is not None
+
+    def is_str_lit(x):
+        return isinstance(x, tuple) and len(x) == 2 and x[0] == "lit" and isinstance(x[1], (str, bytes))
+
+    def rank_name(c):
+        name = f"__rank_{c}"
+        if name not in extra:
+            extra[name] = columns[c].dictionary.rank_column(columns[c])
+        return name
+
+    def walk(e):
+        if not isinstance(e, tuple) or not e or e[0] in ("lit", "strong"):
+            return e
+        op = _CMP_NAME.get(e[0], e[0])
+        if op in ("between", "not_between") and len(e) == 4 and any(is_dict(x) for x in e[1:]):
+            x, lo, hi = e[1:]
+            return walk(("and", ("ge", x, lo), ("le", x, hi)) if op == "between" else ("or", ("lt", x, lo), ("gt", x, hi)))
+        if op in _CMP and len(e) == 3:
+            a, b = e[1], e[2]
+            if is_dict(a) and is_dict(b):
+                da, db = columns[a].dictionary, columns[b].dictionary
+                if da is db:
+                    return e if op in ("eq", "ne") else (op, rank_name(a), rank_name(b))
+                if not (getattr(da, "on_device", False) and getattr(db, "on_device", False)):
+                    raise NotImplementedError(f"no GPU lowering for comparing {a!r} ({da.type}) with {b!r} ({db.type}): only string "
+                                              "and binary columns keep their dictionaries on the device")
+                if op in ("eq", "ne"):
+                    name = f"__codes_of_{b}_in_{a}"
+                    if name not in extra:
+                        extra[name] = db.translate_table(da)
+                    return (op, a, ("lookup_i32", b, name))
+                na, nb = f"__joint_rank_{a}_with_{b}", f"__joint_rank_{b}_with_{a}"
+                if na not in extra:
+                    extra[na], extra[nb] = da.joint_rank_tables(db)
+                return (op, ("lookup_i32", a, na), ("lookup_i32", b, nb))
+            for x, y in ((a, b), (b, a)):
+                if is_dict(x) and not is_str_lit(y):
+                    raise TypeError(f"cannot compare the {columns[x].dictionary.type} column {x!r} with {y!r}: only a string / "
+                                    "binary literal or another such column")
+        elif op in _ARITHMETIC:
+            for x in e[1:]:
+                if is_dict(x):
+                    raise TypeError(f"{op}() over the {columns[x].dictionary.type} column {x!r}: not a numeric operand")
+        if op in ("in", "not_in"):
+            if is_dict(e[1]) and not all(isinstance(v, (str, bytes)) or is_str_lit(v) for v in e[2]):
+                raise TypeError(f"{op.upper().replace('_', ' ')} over the {columns[e[1]].dictionary.type} column {e[1]!r} needs string / "
+                                f"binary literals, got {list(e[2])!r}")
+            return (op, walk(e[1]), e[2])
+        return tuple([e[0]] + [walk(x) for x in e[1:]])
+    return walk(expr), extra
+
+
 class FilterOperator(Operator):
     """algebra.py:108-123: `WHERE column <op> literal`; every column of the batch is compacted (no selection
     vectors in the reference either).  predicate = (column, op, literal)."""
@@ -108,8 +189,10 @@ class FilterOperator(Operator):
         column's order-preserving RANKS (KeyDictionary.rank_column: byte-wise order, as Arrow / NumPy compare such values) against
         the literal's position among the dictionary's values.  NULL rows behave as in every other predicate (compare False,
         `!=` True: vinum/arrow/record_batch.py:112-118).  LIKE / NOT LIKE become lookups in the dictionary's match table
-        (lower_like).  Returns (predicate, extra columns the predicate reads)."""
+        (lower_like); comparisons with ANOTHER dictionary-coded column lookups of translated codes / joint ranks
+        (lower_column_compares, which also raises for a numeric operand).  Returns (predicate, extra columns the predicate reads)."""
         pred, extra = lower_like(pred, batch.columns)
+        pred, extra = lower_column_compares(pred, batch.columns, extra)
 
         def is_dict(x):
             return isinstance(x, str) and x in batch.columns and batch.columns[x].dictionary is not None
@@ -154,6 +237,9 @@ class FilterOperator(Operator):
             if isinstance(lit, (str, bytes)):       # (column, "==", "Berlin") over a dictionary-coded column
                 pred = (self._SYM[op], col, ("lit", lit))
             else:
+                if batch.column(col).dictionary is not None:
+                    raise TypeError(f"cannot compare the {batch.column(col).dictionary.type} column {col!r} with {lit!r}: only a "
+                                    "string / binary literal or another such column")
                 outs, k = ops.filter_cmp(batch.column(col), op, lit, cols)
                 return DeviceRecordBatch(dict(zip(names, outs)), k)
         pred, extra = self.lower_dictionary_predicates(pred, batch)
@@ -184,8 +270,10 @@ class ProjectOperator(Operator):
         exprs, used, extra = [], {}, {}
         for name, arg in zip(self._col_names, self._arguments):
             if not isinstance(arg, str):
-                # LIKE nodes, and only those, become dictionary lookups (a predicate keeps the uint8 mask result type)
+                # LIKE nodes and comparisons of two dictionary-coded columns become dictionary lookups (a predicate keeps the uint8
+                # mask result type)
                 arg, _ = lower_like(arg, batch.columns, extra)
+                arg, _ = lower_column_compares(arg, batch.columns, extra)
                 exprs.append((name, arg))
                 for c in _columns_of(arg):
                     used[c] = extra[c] if c in extra else batch.columns[c]

@@ -38,6 +38,13 @@
 // count, not the batch length.  A table is read by this opcode only; a NULL code, a negative code and a code at or past the
 // table's length push 0.  Programs with a lookup run an LK = 1 instantiation, so the push path of every other program keeps
 // the registers it had.
+//
+// VNM_EX_LOOKUP_I32 (a dictionary-coded string column compared with ANOTHER such column: the codes of one dictionary translated into
+// the other's, or both columns' ranks in the byte order of the union of their dictionaries -- vnm_strdict_translate,
+// vnm_strdict_ranks_joint) pushes table[code] as a VALUE: same operands, the table a VNM_I32 column without NULLs.  The value is held
+// like an int32 column with NULLs -- float64, NaN where the code is NULL, negative or past the table -- so the comparisons' NULL rule
+// applies as it stands (compare False, `!=` True).  Programs with this opcode run the LK = 2 instantiation (both lookups); LK = 0 / 1
+// programs run the code they ran before.
 #include "vnm_common.hpp"
 
 namespace vnm {
@@ -193,7 +200,7 @@ __global__ __launch_bounds__(PJ_BLOCK) void project_kernel(ProjArgs a) {
             const int op = in.op;
             if (op == PJ_NOP) continue;
             if (op == VNM_EX_COL || op == VNM_EX_CONST_F || op == VNM_EX_CONST_I || op == VNM_EX_IS_NULL ||
-                op == VNM_EX_IS_NOT_NULL || (LK && op == VNM_EX_LOOKUP_U8)) {
+                op == VNM_EX_IS_NOT_NULL || (LK && op == VNM_EX_LOOKUP_U8) || (LK == 2 && op == VNM_EX_LOOKUP_I32)) {
                 // ---- push ----
                 if (sp > 0) {
 #pragma unroll
@@ -241,6 +248,22 @@ __global__ __launch_bounds__(PJ_BLOCK) void project_kernel(ProjArgs a) {
                             if (code >= 0 && (int64_t)code < t.length) v = tab[code] ? 1ULL : 0ULL;
                         }
                         tos[r] = v;
+                    }
+                } else if (LK == 2 && op == VNM_EX_LOOKUP_I32) {
+                    // table[code] as a value: one dependent 4-byte gather per row (NaN = NULL: no code, or no entry for it)
+                    const vnm_dcol& c = a.cols[in.arg];
+                    const vnm_dcol& t = a.cols[in.imm_i];
+                    const int32_t* codes = (const int32_t*)c.values + c.offset;
+                    const int32_t* tab = (const int32_t*)t.values + t.offset;
+#pragma unroll
+                    for (int r = 0; r < PJ_R; r++) {
+                        const int64_t row = base + (r >> 1) * (2 * PJ_BLOCK) + (r & 1);
+                        double d = __builtin_nan("");
+                        if (row < a.length && col_valid(c, row)) {
+                            const int32_t code = codes[row];
+                            if (code >= 0 && (int64_t)code < t.length) d = (double)tab[code];
+                        }
+                        tos[r] = pj_dbits(d);
                     }
                 } else if (op == VNM_EX_CONST_F) {
 #pragma unroll
@@ -493,23 +516,27 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
     ProjArgs a{};
     a.n_cols = n_cols;
     a.length = length;
-    // the lookup tables of VNM_EX_LOOKUP_U8 are columns of their own length (one byte per dictionary id); every other column
-    // is a row column of the batch
+    // the lookup tables of VNM_EX_LOOKUP_U8 / _I32 are columns of their own length (one entry per dictionary id); every other
+    // column is a row column of the batch
     bool is_table[PJ_MAX_COLS] = {};
+    int table_type[PJ_MAX_COLS];
     int lookup = 0;
     for (int i = 0; i < n_ins; i++) {
-        if (program[i].op != VNM_EX_LOOKUP_U8) continue;
+        if (program[i].op != VNM_EX_LOOKUP_U8 && program[i].op != VNM_EX_LOOKUP_I32) continue;
         const int64_t t = program[i].imm_i;
+        const int want = program[i].op == VNM_EX_LOOKUP_U8 ? VNM_U8 : VNM_I32;
         if (t < 0 || t >= n_cols) return set_error("vnm_project: lookup table index %lld out of range", (long long)t);
         if (program[i].arg == t) return set_error("vnm_project: a lookup reads its codes from its own table");
+        if (is_table[t] && table_type[t] != want) return set_error("vnm_project: lookup table %lld is read as uint8 and as int32", (long long)t);
         is_table[t] = true;
-        lookup = 1;
+        table_type[t] = want;
+        lookup = std::max(lookup, want == VNM_U8 ? 1 : 2);
     }
     for (int c = 0; c < n_cols; c++) {
         if (cols[c].type < VNM_I8 || cols[c].type > VNM_F64) return set_error("vnm_project: column %d: unsupported type %d", c, cols[c].type);
         if (is_table[c]) {
-            if (cols[c].type != VNM_U8 || cols[c].validity || cols[c].offset < 0 || cols[c].length < 0)
-                return set_error("vnm_project: lookup table %d must be a uint8 column without NULLs", c);
+            if (cols[c].type != table_type[c] || cols[c].validity || cols[c].offset < 0 || cols[c].length < 0)
+                return set_error("vnm_project: lookup table %d must be %s column without NULLs", c, table_type[c] == VNM_U8 ? "a uint8" : "an int32");
         } else if (cols[c].length != length) return set_error("Select expressions have unequal sizes. This is not permitted.");
         a.cols[c] = cols[c];
     }
@@ -582,16 +609,18 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
                 o.arg = 0;
                 break;
             case VNM_EX_LOOKUP_U8:
+            case VNM_EX_LOOKUP_I32:
             case VNM_EX_IS_NULL:
             case VNM_EX_IS_NOT_NULL:
                 if (in.arg < 0 || in.arg >= n_cols) return set_error("vnm_project: column index %d out of range", in.arg);
                 if (is_table[in.arg]) return set_error("vnm_project: column %d is a lookup table, not a row column", in.arg);
-                if (in.op == VNM_EX_LOOKUP_U8 && cols[in.arg].type != VNM_I32)
+                if ((in.op == VNM_EX_LOOKUP_U8 || in.op == VNM_EX_LOOKUP_I32) && cols[in.arg].type != VNM_I32)
                     return set_error("vnm_project: a lookup reads int32 dictionary codes (column %d)", in.arg);
                 if (sp >= PJ_STACK) return set_error("vnm_project: expression too deep");
                 lit[sp] = -1;
                 cst[sp] = -1;
-                ty[sp++] = T_B;
+                o.is_f = in.op == VNM_EX_LOOKUP_I32;                      // an int32 value that can be NULL: float64, NaN
+                ty[sp++] = in.op == VNM_EX_LOOKUP_I32 ? (int)VNM_F64 : (int)T_B;
                 break;
             case VNM_EX_NEG:
             case VNM_EX_BNOT: {
@@ -770,7 +799,8 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
     int grid = (int)grid64;
     int64_t need = (length + PJ_TILE - 1) / PJ_TILE;
     if (grid > need) grid = (int)need;
-    const void* kern = lookup ? (math == 2 ? (const void*)project_kernel<2, 1> : math == 1 ? (const void*)project_kernel<1, 1> : (const void*)project_kernel<0, 1>)
+    const void* kern = lookup == 2 ? (math == 2 ? (const void*)project_kernel<2, 2> : math == 1 ? (const void*)project_kernel<1, 2> : (const void*)project_kernel<0, 2>)
+                     : lookup ? (math == 2 ? (const void*)project_kernel<2, 1> : math == 1 ? (const void*)project_kernel<1, 1> : (const void*)project_kernel<0, 1>)
                               : (math == 2 ? (const void*)project_kernel<2, 0> : math == 1 ? (const void*)project_kernel<1, 0> : (const void*)project_kernel<0, 0>);
     if (lds > 64 * 1024)   // depth >= 10: beyond the default dynamic LDS limit
         VNM_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -781,7 +811,12 @@ static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, cons
         if (!a.neg_pow) return 1;
         VNM_HIP(hipMemsetAsync(a.neg_pow, 0, sizeof(int), s));
     }
-    if (lookup) {
+    if (lookup == 2) {
+        KernelTimer timer("project_kernel_lookup_i32", s);
+        if (math == 2) project_kernel<2, 2><<<grid, PJ_BLOCK, lds, s>>>(a);
+        else if (math == 1) project_kernel<1, 2><<<grid, PJ_BLOCK, lds, s>>>(a);
+        else project_kernel<0, 2><<<grid, PJ_BLOCK, lds, s>>>(a);
+    } else if (lookup) {
         KernelTimer timer("project_kernel_lookup", s);
         if (math == 2) project_kernel<2, 1><<<grid, PJ_BLOCK, lds, s>>>(a);
         else if (math == 1) project_kernel<1, 1><<<grid, PJ_BLOCK, lds, s>>>(a);

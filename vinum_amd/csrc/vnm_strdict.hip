@@ -318,7 +318,8 @@ int sdict_grow(SDict* d, uint64_t new_cap, hipStream_t s) {
 struct SdRankArgs {
     SDict d;
     const uint8_t* heap;
-    uint64_t* voff;     // [D] heap offset
+    uint64_t* voff;     // [D] heap offset (+ base: the joint ranking of two dictionaries lists addresses, its heap is null)
+    uint64_t base;
     uint32_t* vlen;     // [D]
     int32_t* vid;       // [D]
     unsigned long long* ctl;   // [0] next list position  [1] longest value
@@ -332,7 +333,7 @@ __global__ __launch_bounds__(256) void sd_list_kernel(SdRankArgs a) {
         const uint64_t tag = s[0];
         if (tag == SD_EMPTY || tag == SD_LOCKED) continue;
         const unsigned long long k = atomicAdd(&a.ctl[0], 1ULL);
-        a.voff[k] = s[2]; a.vlen[k] = (uint32_t)s[3]; a.vid[k] = (int32_t)(s[1] - 1);
+        a.voff[k] = a.base + s[2]; a.vlen[k] = (uint32_t)s[3]; a.vid[k] = (int32_t)(s[1] - 1);
         if (s[3] > maxlen) maxlen = s[3];
     }
     if (maxlen) atomicMax(&a.ctl[1], maxlen);
@@ -344,7 +345,7 @@ __global__ __launch_bounds__(256) void sd_chunk_kernel(const uint8_t* heap, cons
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
         const int64_t v = perm ? perm[i] : i;
-        const uint8_t* p = heap + voff[v];
+        const uint8_t* p = (const uint8_t*)((uint64_t)heap + voff[v]);
         const int64_t len = vlen[v];
         for (int c = 0; c < nchunks; c++) {
             const int64_t at = (int64_t)(j0 + c) * 8;
@@ -365,6 +366,102 @@ __global__ __launch_bounds__(256) void sd_rank_scatter_kernel(const int64_t* per
 __global__ __launch_bounds__(256) void sd_code_rank_kernel(const int32_t* codes, const int32_t* rank_of_id, int64_t n, int32_t* out) {
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) { const int32_t c = codes[i]; out[i] = c < 0 ? 0 : rank_of_id[c]; }
+}
+
+// ---- two dictionaries against each other (a string column compared with a string column) ------------------------------------------
+// vnm_strdict_translate: one lane per id of `src`, the encode kernel's probe of `dst`'s table without the insert (dst is only
+// read: between two encodes no slot is locked and every `where` is a heap offset).  -2: dst does not hold the value, or the id was
+// never handed out (-1 stays the NULL code).
+struct SdTransArgs {
+    const uint8_t* sheap;
+    const int64_t* s_off;
+    const int32_t* s_len;      // -1: an id never handed out
+    SDict d;                   // dst (slot = null: no value yet)
+    const uint8_t* dheap;
+    int64_t id_begin, id_end;
+    int32_t* out;
+};
+
+__global__ __launch_bounds__(256) void sd_translate_kernel(SdTransArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    const uint64_t mask = a.d.cap - 1;
+    for (int64_t id = a.id_begin + (int64_t)blockIdx.x * 256 + threadIdx.x; id < a.id_end; id += stride) {
+        const int64_t len = a.s_len[id];
+        int32_t code = -2;
+        if (len >= 0 && a.d.slot) {
+            const uint8_t* p = a.sheap + a.s_off[id];
+            const uint64_t tagv = sd_hash(p, len);
+            uint64_t h = (tagv ^ (tagv >> 29)) & mask;
+            for (uint64_t probes = 0; probes < a.d.cap; probes++) {   // (the table is at most 70 % full: an empty slot ends the walk)
+                const uint64_t* s = a.d.slot + h * 4;
+                const uint64_t t = s[0];
+                if (t == SD_EMPTY) break;
+                if (t == tagv && (int64_t)s[3] == len && sd_equal(p, a.dheap + s[2], len)) { code = (int32_t)(s[1] - 1); break; }
+                h = (h + 1) & mask;
+            }
+        }
+        a.out[id] = code;
+    }
+}
+
+// vnm_strdict_ranks_joint: the values of both dictionaries in one list, sorted as vnm_strdict_ranks_device sorts one dictionary's;
+// equal bytes end up next to each other (at most two: each dictionary's values are distinct), so a "differs from its predecessor"
+// flag per sorted position and its inclusive prefix sum are the dense ranks.  Pass A: SD_PER positions per thread, the flags and
+// their exclusive prefix inside the workgroup; pass B: sd_compact_scan_kernel over the workgroup totals; pass C: ranks -> ids.
+struct SdJointArgs {
+    const int64_t* perm;       // sorted position -> index in the value list
+    const uint64_t* vaddr;     // [D] address of the value's bytes
+    const uint32_t* vlen;
+    const int32_t* vid;
+    int64_t n, n_a;            // values; the first n_a belong to dictionary a
+    uint8_t* flag;             // [n]
+    uint32_t* pre;             // [threads]
+    unsigned long long* blk;   // [2 * nblocks + 2] (count, unused) pairs, the layout sd_compact_scan_kernel scans
+    int32_t* rank_a;
+    int32_t* rank_b;
+    int both;                  // one handle given twice: every rank goes to both outputs
+};
+
+__global__ __launch_bounds__(256) void sd_joint_flag_kernel(SdJointArgs a) {
+    __shared__ unsigned sc[256];
+    const int tid = threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * 256 + tid;
+    unsigned cnt = 0;
+    for (int k = 0; k < SD_PER; k++) {
+        const int64_t i = t * SD_PER + k;
+        if (i >= a.n) break;
+        uint8_t f = 0;
+        if (i > 0) {
+            const int64_t v = a.perm[i], u = a.perm[i - 1];
+            f = (a.vlen[v] != a.vlen[u] || !sd_equal((const uint8_t*)a.vaddr[v], (const uint8_t*)a.vaddr[u], (int64_t)a.vlen[v])) ? 1 : 0;
+        }
+        a.flag[i] = f;
+        cnt += f;
+    }
+    sc[tid] = cnt;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {   // inclusive scan
+        const unsigned x = tid >= d ? sc[tid - d] : 0;
+        __syncthreads();
+        sc[tid] += x;
+        __syncthreads();
+    }
+    if (t * SD_PER < a.n) a.pre[t] = sc[tid] - cnt;
+    if (tid == 255) { a.blk[2 * blockIdx.x] = sc[255]; a.blk[2 * blockIdx.x + 1] = 0; }
+}
+
+__global__ __launch_bounds__(256) void sd_joint_rank_kernel(SdJointArgs a) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t * SD_PER >= a.n) return;
+    unsigned long long r = a.blk[2 * blockIdx.x] + a.pre[t];
+    for (int k = 0; k < SD_PER; k++) {
+        const int64_t i = t * SD_PER + k;
+        if (i >= a.n) break;
+        r += a.flag[i];
+        const int64_t v = a.perm[i];
+        (v < a.n_a ? a.rank_a : a.rank_b)[a.vid[v]] = (int32_t)r;
+        if (a.both) a.rank_b[a.vid[v]] = (int32_t)r;
+    }
 }
 
 // ---- LIKE against the dictionary's values (LikeFunction, vinum/core/functions.py:301-344) -----------------------------------------
@@ -687,6 +784,50 @@ int vnm_strdict_fetch_new(vnm_strdict* h, int32_t* ids_host, int32_t* lens_host,
     return 0;
 }
 
+// The value list (heap + voff[i], vlen[i]; D values, the longest `maxlen` bytes) sorted byte-wise: *perm_out[i] = the index of the value
+// at sorted position i.  Scratch comes from `pool`.
+static int sd_sort_value_list(const uint8_t* heap, const uint64_t* voff, const uint32_t* vlen, int64_t D, unsigned long long maxlen,
+                              const char* route, PoolScope& pool, int64_t** perm_out, void* stream) {
+    hipStream_t s = as_stream(stream);
+    int64_t* perm = (int64_t*)pool.take((size_t)D * 8);
+    int64_t* perm2 = (int64_t*)pool.take((size_t)D * 8);
+    int64_t* perm3 = (int64_t*)pool.take((size_t)D * 8);
+    if (!perm || !perm2 || !perm3) return 1;
+    const int m = (int)((maxlen + 7) / 8);                    // chunks of the longest value
+    route_note(route, "%lld distinct values, longest %llu bytes: %d round(s) of up to 15 chunk keys + the length", (long long)D, maxlen, m == 0 ? 1 : (m + 14) / 15);
+    constexpr int PER = 15;                                   // chunk keys per sort call (+ the length: 16 keys)
+    const int rounds = m == 0 ? 1 : (m + PER - 1) / PER;
+    uint64_t* keys = (uint64_t*)pool.take((size_t)D * 8 * (size_t)(std::min(m, PER) + 1));
+    if (!keys) return 1;
+    const int g2 = (int)std::min<int64_t>((D + 255) / 256, (int64_t)device_info().num_cus * 8);
+    bool have_perm = false;
+    for (int r = 0; r < rounds; r++) {                        // least significant round first: the last chunks and the length
+        const int hi = m - r * PER, lo = std::max(0, hi - PER), nc = hi - lo;
+        const int with_len = r == 0 ? 1 : 0;
+        sd_chunk_kernel<<<g2, 256, 0, s>>>(heap, voff, vlen, have_perm ? perm : nullptr, D, lo, nc, with_len, keys);
+        VNM_HIP(hipGetLastError());
+        vnm_dcol kc[16];
+        int orders[16];
+        const int nk = nc + with_len;
+        for (int k = 0; k < nk; k++) {
+            memset(&kc[k], 0, sizeof(vnm_dcol));
+            kc[k].values = keys + (size_t)k * D; kc[k].type = VNM_U64; kc[k].length = D;
+            orders[k] = VNM_ASC;
+        }
+        VNM_TRY(vnm_sort_indices(nk, kc, orders, D, 0, perm2, stream));
+        if (!have_perm) std::swap(perm, perm2);
+        else {                                                // positions in this round's order -> value indices
+            vnm_dcol pc{};
+            pc.values = perm; pc.type = VNM_I64; pc.length = D;
+            VNM_TRY(vnm_take(&pc, perm2, D, perm3, nullptr, stream));
+            std::swap(perm, perm3);
+        }
+        have_perm = true;
+    }
+    *perm_out = perm;
+    return 0;
+}
+
 // Order-preserving ranks of every value in the dictionary: out_rank_of_id[id] = position of the value in ascending byte-wise order
 // (device array of vnm_strdict_ids(h) int32s; ids that were never handed out are left untouched).
 int vnm_strdict_ranks_device(vnm_strdict* h, int32_t* out_rank_of_id, void* stream) {
@@ -707,10 +848,7 @@ int vnm_strdict_ranks_device(vnm_strdict* h, int32_t* out_rank_of_id, void* stre
     a.vlen = (uint32_t*)pool.take((size_t)D * 4);
     a.vid = (int32_t*)pool.take((size_t)D * 4);
     a.ctl = (unsigned long long*)pool.take(64);
-    int64_t* perm = (int64_t*)pool.take((size_t)D * 8);
-    int64_t* perm2 = (int64_t*)pool.take((size_t)D * 8);
-    int64_t* perm3 = (int64_t*)pool.take((size_t)D * 8);
-    if (!a.voff || !a.vlen || !a.vid || !a.ctl || !perm || !perm2 || !perm3) return 1;
+    if (!a.voff || !a.vlen || !a.vid || !a.ctl) return 1;
     VNM_HIP(hipMemsetAsync(a.ctl, 0, 64, s));
     const int grid = (int)std::min<int64_t>(((int64_t)h->d.cap + 255) / 256, (int64_t)device_info().num_cus * 8);
     sd_list_kernel<<<grid, 256, 0, s>>>(a);
@@ -719,37 +857,9 @@ int vnm_strdict_ranks_device(vnm_strdict* h, int32_t* out_rank_of_id, void* stre
     VNM_HIP(hipMemcpyAsync(ctl, a.ctl, 16, hipMemcpyDeviceToHost, s));
     VNM_HIP(hipStreamSynchronize(s));
     if ((int64_t)ctl[0] != D) return set_error("vnm_strdict_ranks_device: %llu values listed, %lld in the table (internal error)", ctl[0], (long long)D);
-    const int m = (int)((ctl[1] + 7) / 8);                    // chunks of the longest value
-    route_note("sort:string_key_ranks", "%lld distinct values, longest %llu bytes: %d round(s) of up to 15 chunk keys + the length", (long long)D, ctl[1], m == 0 ? 1 : (m + 14) / 15);
-    constexpr int PER = 15;                                   // chunk keys per sort call (+ the length: 16 keys)
-    const int rounds = m == 0 ? 1 : (m + PER - 1) / PER;
-    uint64_t* keys = (uint64_t*)pool.take((size_t)D * 8 * (size_t)(std::min(m, PER) + 1));
-    if (!keys) return 1;
+    int64_t* perm = nullptr;
+    VNM_TRY(sd_sort_value_list(h->heap, a.voff, a.vlen, D, ctl[1], "sort:string_key_ranks", pool, &perm, stream));
     const int g2 = (int)std::min<int64_t>((D + 255) / 256, (int64_t)device_info().num_cus * 8);
-    bool have_perm = false;
-    for (int r = 0; r < rounds; r++) {                        // least significant round first: the last chunks and the length
-        const int hi = m - r * PER, lo = std::max(0, hi - PER), nc = hi - lo;
-        const int with_len = r == 0 ? 1 : 0;
-        sd_chunk_kernel<<<g2, 256, 0, s>>>(h->heap, a.voff, a.vlen, have_perm ? perm : nullptr, D, lo, nc, with_len, keys);
-        VNM_HIP(hipGetLastError());
-        vnm_dcol kc[16];
-        int orders[16];
-        const int nk = nc + with_len;
-        for (int k = 0; k < nk; k++) {
-            memset(&kc[k], 0, sizeof(vnm_dcol));
-            kc[k].values = keys + (size_t)k * D; kc[k].type = VNM_U64; kc[k].length = D;
-            orders[k] = VNM_ASC;
-        }
-        VNM_TRY(vnm_sort_indices(nk, kc, orders, D, 0, perm2, stream));
-        if (!have_perm) std::swap(perm, perm2);
-        else {                                                // positions in this round's order -> value indices
-            vnm_dcol pc{};
-            pc.values = perm; pc.type = VNM_I64; pc.length = D;
-            VNM_TRY(vnm_take(&pc, perm2, D, perm3, nullptr, stream));
-            std::swap(perm, perm3);
-        }
-        have_perm = true;
-    }
     sd_rank_scatter_kernel<<<g2, 256, 0, s>>>(perm, a.vid, D, out_rank_of_id);
     VNM_HIP(hipGetLastError());
     VNM_HIP(hipStreamSynchronize(s));
@@ -763,6 +873,92 @@ int vnm_strdict_codes_to_ranks(const int32_t* codes, const int32_t* rank_of_id, 
     if (!codes || !rank_of_id || !out_ranks) return set_error("vnm_strdict_codes_to_ranks: null argument");
     sd_code_rank_kernel<<<(int)std::min<int64_t>((n + 255) / 256, (int64_t)device_info().num_cus * 8), 256, 0, as_stream(stream)>>>(codes, rank_of_id, n, out_ranks);
     VNM_HIP(hipGetLastError());
+    return 0;
+}
+
+// out_dst_code_of_src_id[id] = the code `dst` holds for the bytes of src's value `id`, for id in [id_begin, vnm_strdict_ids(src));
+// -2: dst does not hold them, or the id was never handed out.  One kernel on `stream`, launched asynchronously; dst is only read.
+int vnm_strdict_translate(vnm_strdict* src, vnm_strdict* dst, int64_t id_begin, int32_t* out_dst_code_of_src_id, void* stream) {
+    VNM_TRY(ensure_init());
+    if (!src || !dst || !out_dst_code_of_src_id) return set_error("vnm_strdict_translate: null argument");
+    if (src->failed || dst->failed) return set_error("vnm_strdict: an earlier encode failed half-way; the dictionary cannot be used any more (create a new one)");
+    if (id_begin < 0) return set_error("vnm_strdict_translate: id_begin < 0");
+    if (id_begin >= src->ids) return 0;
+    SdTransArgs a{};
+    a.sheap = src->heap; a.s_off = src->id_off; a.s_len = src->id_len;
+    a.d = dst->d; a.dheap = dst->heap;
+    a.id_begin = id_begin; a.id_end = src->ids;
+    a.out = out_dst_code_of_src_id;
+    hipStream_t s = as_stream(stream);
+    const int grid = (int)std::min<int64_t>((src->ids - id_begin + 255) / 256, (int64_t)device_info().num_cus * 16);
+    {
+        KernelTimer timer("strdict_translate", s);
+        sd_translate_kernel<<<grid, 256, 0, s>>>(a);
+    }
+    VNM_HIP(hipGetLastError());
+    return 0;
+}
+
+// Dense ranks of the values of BOTH dictionaries in the ascending byte order of their union (the order of vnm_strdict_ranks_device);
+// equal bytes in a and b share a rank.  Entries of ids never handed out are left untouched.
+int vnm_strdict_ranks_joint(vnm_strdict* a, vnm_strdict* b, int32_t* out_rank_of_id_a, int32_t* out_rank_of_id_b, void* stream) {
+    VNM_TRY(ensure_init());
+    if (!a || !b || !out_rank_of_id_a || !out_rank_of_id_b) return set_error("vnm_strdict_ranks_joint: null argument");
+    if (a->failed || b->failed) return set_error("vnm_strdict: an earlier encode failed half-way; the dictionary cannot be used any more (create a new one)");
+    hipStream_t s = as_stream(stream);
+    vnm_strdict* hs[2] = {a, a == b ? nullptr : b};     // (one handle twice: its values once, both outputs get its ranks)
+    unsigned long long fill[2] = {0, 0};
+    for (int k = 0; k < 2; k++)
+        if (hs[k] && hs[k]->d.slot) VNM_HIP(hipMemcpyAsync(&fill[k], hs[k]->d.ctl + 2, 8, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));
+    const int64_t Da = (int64_t)fill[0], D = Da + (int64_t)fill[1];
+    if (D == 0) return 0;
+    if (D >= (1LL << 31)) return set_error("vnm_strdict_ranks_joint: more than 2^31 values");
+    PoolScope pool;
+    uint64_t* vaddr = (uint64_t*)pool.take((size_t)D * 8);
+    uint32_t* vlen = (uint32_t*)pool.take((size_t)D * 4);
+    int32_t* vid = (int32_t*)pool.take((size_t)D * 4);
+    unsigned long long* lctl = (unsigned long long*)pool.take(128);
+    if (!vaddr || !vlen || !vid || !lctl) return 1;
+    VNM_HIP(hipMemsetAsync(lctl, 0, 128, s));
+    for (int k = 0; k < 2; k++) {
+        if (!fill[k]) continue;
+        const int64_t at = k ? Da : 0;
+        SdRankArgs l{};
+        l.d = hs[k]->d; l.heap = hs[k]->heap; l.base = (uint64_t)hs[k]->heap;
+        l.voff = vaddr + at; l.vlen = vlen + at; l.vid = vid + at;
+        l.ctl = lctl + 8 * k;
+        const int grid = (int)std::min<int64_t>(((int64_t)hs[k]->d.cap + 255) / 256, (int64_t)device_info().num_cus * 8);
+        sd_list_kernel<<<grid, 256, 0, s>>>(l);
+        VNM_HIP(hipGetLastError());
+    }
+    unsigned long long ctl[16];
+    VNM_HIP(hipMemcpyAsync(ctl, lctl, 128, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));
+    if (ctl[0] != fill[0] || ctl[8] != fill[1])
+        return set_error("vnm_strdict_ranks_joint: %llu + %llu values listed, %llu + %llu in the tables (internal error)", ctl[0], ctl[8], fill[0], fill[1]);
+    int64_t* perm = nullptr;
+    VNM_TRY(sd_sort_value_list(nullptr, vaddr, vlen, D, std::max(ctl[1], ctl[9]), "project:string_joint_ranks", pool, &perm, stream));
+    SdJointArgs j{};
+    j.perm = perm; j.vaddr = vaddr; j.vlen = vlen; j.vid = vid;
+    j.n = D; j.n_a = Da;
+    const int64_t threads = (D + SD_PER - 1) / SD_PER;
+    const int nblocks = (int)((threads + 255) / 256);
+    j.flag = (uint8_t*)pool.take((size_t)D);
+    j.pre = (uint32_t*)pool.take((size_t)nblocks * 256 * 4);
+    j.blk = (unsigned long long*)pool.take(((size_t)nblocks + 1) * 16);
+    if (!j.flag || !j.pre || !j.blk) return 1;
+    j.rank_a = out_rank_of_id_a;
+    j.rank_b = out_rank_of_id_b;
+    j.both = a == b;
+    {
+        KernelTimer timer("strdict_joint_dense_ranks", s);   // (the flag / scan / rank step alone: the list and chunk kernels are untimed, the sort has its own timers)
+        sd_joint_flag_kernel<<<nblocks, 256, 0, s>>>(j);
+        sd_compact_scan_kernel<<<1, 1024, 0, s>>>(j.blk, nblocks);
+        sd_joint_rank_kernel<<<nblocks, 256, 0, s>>>(j);
+    }
+    VNM_HIP(hipGetLastError());
+    VNM_HIP(hipStreamSynchronize(s));     // (the scratch goes back to the pool with this scope)
     return 0;
 }
 

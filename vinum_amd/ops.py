@@ -581,6 +581,10 @@ def _emit_expr(expr, col_index, out):
             # ("lookup", code column, table column): table[code] as a predicate (LIKE over a dictionary-coded column, see
             # core.algebra.lower_like); the table travels as a column of its own length
             out.append((L.EX_LOOKUP_U8, col_index[e[1]], 0.0, col_index[e[2]]))
+        elif e[0] == "lookup_i32":
+            # ("lookup_i32", code column, table column): table[code] as an int32 VALUE, NULL without an entry (two dictionary-coded
+            # columns compared with each other, see core.algebra.lower_column_compares)
+            out.append((L.EX_LOOKUP_I32, col_index[e[1]], 0.0, col_index[e[2]]))
         elif e[0] in ("like", "not_like"):
             raise NotImplementedError(f"no GPU lowering for {e[0].upper()} outside a FilterOperator / ProjectOperator / "
                                       "AggregateOperator (they turn it into a dictionary lookup)")

@@ -483,6 +483,16 @@ class KeyDictionary:
         self._like = {}            # LIKE pattern -> [device table, capacity, ids it covers] (like_table)
         self.like_launches = 0     # vnm_strdict_like calls and the ids they matched, over every pattern
         self.like_ids_matched = 0
+        self._translate = {}       # id(other dictionary) -> [weakref, device table, capacity, ids it covers, own / other's value count]
+        self._joint = {}           # id(other dictionary) -> [weakref, (own, other's value count), own / other's rank table, id counts]
+        self.translate_builds = 0  # vnm_strdict_translate / vnm_strdict_ranks_joint calls this dictionary made (pair tables)
+        self.joint_rank_builds = 0
+
+    @property
+    def on_device(self) -> bool:
+        """True for the four string / binary types, whose dictionary lives in HBM (vnm_strdict); the host-route dictionaries
+        (bool, decimal, date64 ...) have no device tables"""
+        return self._device
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -640,6 +650,77 @@ class KeyDictionary:
             self.like_ids_matched += top - covered
             entry[:] = [buf, cap, top]
         return DeviceColumn(buf, None, 0, entry[2], pa.uint8())
+
+    def _id_count(self) -> int:
+        return int(L.lib().vnm_strdict_ids(self._h)) if self._h is not None else 0
+
+    def _pair_check(self, other, what):
+        if not (self._device and getattr(other, "on_device", False)):
+            raise NotImplementedError(f"no GPU lowering for {what} of a {self.type} and a {other.type} dictionary: the device "
+                                      "dictionaries are the string and binary types")
+
+    @staticmethod
+    def _pair_ref(cache, other):
+        """A weak reference to `other` that drops `other`'s entry (and its device tables) from `cache` when `other` dies."""
+        import weakref
+        key = id(other)
+
+        def drop(ref):
+            entry = cache.get(key)
+            if entry is not None and entry[0] is ref:
+                del cache[key]
+        return weakref.ref(other, drop)
+
+    def translate_table(self, other):
+        """This dictionary's codes in terms of `other`'s: an int32 DeviceColumn with one entry per id handed out here, the code
+        `other` holds for the same BYTES, or -2 where it holds none (vnm_strdict_translate; bytes compared exactly, whatever mix
+        of utf8 / large_utf8 / binary / large_binary the two are).  `a = b` over two dictionary-coded columns then is
+        code_a == table[code_b].  Cached per pair and rebuilt only when a dictionary GREW -- by values: the id counter moves by
+        whole chunks on every encode, so the id counts size the table and the value counts say whether anything is new.  While
+        `other` has not grown only the ids handed out here since the last call are looked up; once it has, an absent value may
+        have become present and the whole table is built again."""
+        from .device import DeviceBuffer, DeviceColumn
+        self._pair_check(other, "a translation")
+        lib = L.lib()
+        top = self._id_count()
+        entry = self._translate.get(id(other))
+        if entry is None or entry[0]() is not other:
+            entry = self._translate[id(other)] = [self._pair_ref(self._translate, other), DeviceBuffer(max(top, 1) * 4), max(top, 1), 0, -1, -1]
+        _, buf, cap, covered, mine, theirs = entry
+        if theirs != other._n_values:
+            covered = 0
+        if (covered == 0 or mine != self._n_values) and top > covered:
+            if top > cap:
+                cap = max(top, 2 * cap)
+                grown = DeviceBuffer(cap * 4)
+                if covered:
+                    L.check(lib.vnm_memcpy_d2d(grown.ptr, buf.ptr, covered * 4, None))
+                buf = grown
+            L.check(lib.vnm_strdict_translate(self.handle(), other.handle(), covered, buf.ptr, None))
+            self.translate_builds += 1
+            covered = top
+        entry[1:] = [buf, cap, covered, self._n_values, other._n_values]
+        return DeviceColumn(buf, None, 0, covered, pa.int32())
+
+    def joint_rank_tables(self, other):
+        """(own table, other's table): int32 DeviceColumns, one entry per id, the dense rank of the value in the ascending byte
+        order of the UNION of both dictionaries (vnm_strdict_ranks_joint: the order of rank_column; equal bytes share a rank), so
+        `a < b` over two dictionary-coded columns is table_a[code_a] < table_b[code_b].  Cached per pair until either grows (by
+        values, as translate_table)."""
+        from .device import DeviceBuffer, DeviceColumn
+        self._pair_check(other, "joint ranks")
+        lib = L.lib()
+        stamp = (self._n_values, other._n_values)
+        entry = self._joint.get(id(other))
+        if entry is None or entry[0]() is not other or entry[1] != stamp:
+            ids = (self._id_count(), other._id_count())
+            mine, theirs = DeviceBuffer(max(ids[0], 1) * 4), DeviceBuffer(max(ids[1], 1) * 4)
+            L.check(lib.vnm_memset(mine.ptr, 0xFF, max(ids[0], 1) * 4))      # (ids never handed out: no row holds them)
+            L.check(lib.vnm_memset(theirs.ptr, 0xFF, max(ids[1], 1) * 4))
+            L.check(lib.vnm_strdict_ranks_joint(self.handle(), other.handle(), mine.ptr, theirs.ptr, None))
+            self.joint_rank_builds += 1
+            entry = self._joint[id(other)] = [self._pair_ref(self._joint, other), stamp, mine, theirs, ids]
+        return (DeviceColumn(entry[2], None, 0, entry[4][0], pa.int32()), DeviceColumn(entry[3], None, 0, entry[4][1], pa.int32()))
 
     def values_by_code(self) -> pa.Array:
         """The dictionary as an array indexed by CODE (a code the device never handed out: NULL) -- what the ranks exchange to build
