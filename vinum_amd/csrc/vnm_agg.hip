@@ -458,6 +458,9 @@ struct vnm_agg {
     bool pack_null_seen = false;     // packed composite keys: some batch brought a key column with a validity bitmap (NULL codes may be in the words)
     bool pring_off = false;          // the ring form of the hash-partition scatter failed once (a heavy key, a full region): the tile-sorting scatter from then on
     bool fx_narrow = false;          // ... with |m| < 2^18: the words of the last scatter level are 32 bits (dring_scatter_kernel<..., W32>)
+    int fx_L = 0, fx_E = 0;          // ... what the sample saw: lowest set bit 2^fx_L, |v| < 2^fx_E, smallest and largest value
+    double fx_vmin = 0.0, fx_vmax = 0.0;
+    bool fx_narrow1_off = false;     // a row fell outside the window of the first level's 32-bit words once (plan_narrow_first_level): 8-byte words there from then on
     int fxn_state = 0, fxn_qe[3] = {0, 0, 0};   // ... and of the entries of two or three values (vnm_agg_fxn.inc)
     bool null_inputs_seen = false;   // some batch brought an input column with a validity bitmap: the HBM table may hold groups whose COUNT(v) differs
                                      // from COUNT(*) (or whose SUM is NULL) -- the side-table fold of the fused result columns assumes they do not

@@ -109,6 +109,12 @@ struct DPartArgs {
     // (m << remainder bits) | remainder -- 8 bytes instead of 12 after pass 1 and 10 after pass 2, no separate code regions.
     double fx_q, fx_inv_q;      // 2^fx_qe, 2^-fx_qe
     int64_t fx_lim;             // |m| <= fx_lim: 2^31 - 1, or 2^18 - 1 when the words of the LAST scatter level are 32 bits (W32)
+    // 32-bit words out of the FIRST of two levels: the value field is a WINDOW of fx_wbits bits, ((m - fx_wbase) << remainder bits) | remainder,
+    // unsigned (fx_wuns).  Pass 1 checks every row against fx_lim at the operator's quantum first, as ever, then drops fx_sh bits the
+    // sample found unused (the attempt's quantum fx_q is 2^fx_sh times the operator's) and checks the window: flags[7] bit 0 = outside
+    // fx_lim or off the lattice, bit 1 = only outside the window.  fx_wbits = 0: no window (fx_wbase = fx_wuns = fx_sh = 0, signed field).
+    // Pass 2 over such words (IN32) takes the window's base as fx_in_base.
+    int fx_wbits, fx_wbase, fx_wuns, fx_sh, fx_in_base;
 };
 constexpr uint32_t DP_NULL32 = 0x80000000u;
 // v == m * q exactly, |m| < 2^31, v is not -0.0 (its sign would be lost) and finite?  inv_q = 2^-qe with qe <= 0, so t = v * inv_q is
@@ -437,11 +443,16 @@ typedef uint32_t dr_u2 __attribute__((ext_vector_type(2)));
 // and the batch takes the hash partitions
 // FX: fixed-point entries -- ONE 64-bit word per entry, (m << remainder bits) | remainder, in the rings and in the regions (DPartArgs::fx_q)
 template <bool FROM_ROWS, typename CT, bool HAS_VAL, int DR_BLOCK, int DR_PAIRS, bool PV = false, bool VN = false, int MAXR = 0, bool SEG = false, bool KN = false,
-          bool V2 = false, bool FX = false, bool W32 = false>
+          bool V2 = false, bool FX = false, bool W32 = false, bool IN32 = false, bool WIN = false>
 __global__ __launch_bounds__(DR_BLOCK) void dring_scatter_kernel(DPartArgs a, int ring_cap) {
     extern __shared__ uint64_t dr_lds[];
     static_assert(!FX || (HAS_VAL && !V2), "fixed-point entries: one value (VN: only where the filter drops the NULL rows, vn_fold)");
     static_assert(!W32 || FX, "32-bit entry words are fixed-point words");
+    // IN32: the words this pass READS are 32 bits, the first level's window words (DPartArgs::fx_wbits) -- 16 bytes per load all the same
+    static_assert(!IN32 || (W32 && !FROM_ROWS), "32-bit input words: the second of two levels of 32-bit fixed-point words");
+    // WIN: the 32-bit words this pass WRITES are the first level's window words (DPartArgs::fx_wbits; base and signedness are arguments) -- a
+    // compile-time switch so that the one-level kernels, whose words have no window, keep the code they had
+    static_assert(!WIN || (W32 && FROM_ROWS), "window words: 32-bit words out of the first of two levels");
     // W32: the words this pass WRITES are 32 bits -- (m << remainder bits) | remainder with m of at most 32 - remainder bits (the host
     // checks the sampled magnitude, pass 1 every row: DPartArgs::fx_lim) -- in blocks of 32 (128 bytes), four per lane
     constexpr int FB = W32 ? 32 : DR_FB, EPL = FB / 8;
@@ -490,7 +501,7 @@ __global__ __launch_bounds__(DR_BLOCK) void dring_scatter_kernel(DPartArgs a, in
         uint32_t slot = head[p] + r;
         if (slot >= (uint32_t)ring_cap) slot -= ring_cap;
         if (W32) {
-            ((uint32_t*)rv)[(size_t)p * ring_cap + slot] = ((uint32_t)(int32_t)fx_of(v) << a.out_bits) | (c & remmask);
+            ((uint32_t*)rv)[(size_t)p * ring_cap + slot] = ((uint32_t)((int32_t)fx_of(v) - (WIN ? a.fx_wbase : 0)) << a.out_bits) | (c & remmask);
             return true;
         }
         if (FX) {
@@ -505,7 +516,12 @@ __global__ __launch_bounds__(DR_BLOCK) void dring_scatter_kernel(DPartArgs a, in
     // (FX) remainder and value of the entry word at ring index li
     auto fx_rem = [&](size_t li) -> uint32_t { return W32 ? ((const uint32_t*)rv)[li] & remmask : (uint32_t)(((const uint64_t*)rv)[li] & (uint64_t)remmask); };
     auto fx_val = [&](size_t li) -> double {
-        return W32 ? (double)((int32_t)((const uint32_t*)rv)[li] >> a.out_bits) * a.fx_q : (double)((int64_t)((const uint64_t*)rv)[li] >> a.out_bits) * a.fx_q;
+        if (W32) {   // (a signed field, or the first level's window: unsigned, above its base)
+            const uint32_t w = ((const uint32_t*)rv)[li];
+            if (WIN) return (double)((a.fx_wuns ? (int32_t)(w >> a.out_bits) : (int32_t)w >> a.out_bits) + a.fx_wbase) * a.fx_q;
+            return (double)((int32_t)w >> a.out_bits) * a.fx_q;
+        }
+        return (double)((int64_t)((const uint64_t*)rv)[li] >> a.out_bits) * a.fx_q;
     };
     // whole blocks of every ring -> the partition's region.  Eight lanes per partition: lane j moves entries 2j, 2j + 1 of a block
     // (16 bytes of values, 8 / 4 bytes of codes).  `drain`: the last, partial block as well (end of the kernel).
@@ -653,7 +669,19 @@ __global__ __launch_bounds__(DR_BLOCK) void dring_scatter_kernel(DPartArgs a, in
     uint32_t nk_cnt = 0;
     constexpr bool XT = FROM_ROWS && HAS_VAL && !V2 && !FX;   // exact-add statistics of the values that become entries (exact_track)
     uint32_t xinv = 0, xexp = 0;
-    bool fx_bad = false;   // FX: a value of this thread's rows is not m * q with |m| < 2^31 (flags[7]: the batch is redone with float64 entries)
+    uint32_t fx_bad = 0;   // FX: a value of this thread's rows is not m * q with |m| <= fx_lim (bit 0), or only outside the first level's window (bit 1): flags[7]
+    // (FX) the value as the entry carries it: m in quanta of fx_q; false = the row does not fit (the attempt fails: fx_bad)
+    auto fx_entry = [&](double val, double* out) -> bool {
+        int64_t m;
+        if (!fx_encode(val, a.fx_inv_q, &m, a.fx_lim)) { fx_bad |= 1u; return false; }
+        if (WIN) {
+            const int64_t m1 = m >> a.fx_sh;
+            if ((m1 << a.fx_sh) != m || (uint64_t)(m1 - (int64_t)a.fx_wbase) >> a.fx_wbits) { fx_bad |= 2u; return false; }
+            m = m1;
+        }
+        *out = fx_bits(m);
+        return true;
+    };
     if (FROM_ROWS && !SEG) {
         const int64_t sub = (int64_t)NE * DR_BLOCK;
         const int64_t nsub = (a.nrows + sub - 1) / sub;
@@ -719,7 +747,7 @@ __global__ __launch_bounds__(DR_BLOCK) void dring_scatter_kernel(DPartArgs a, in
                 }
                 c[e] = (((uint32_t)d * a.map.mul) & a.map.mask) | (VN && isnull ? DP_NULL32 : 0u);
                 v[e] = VN && isnull ? 0.0 : val;
-                if (FX) { int64_t m; if (!fx_encode(val, a.fx_inv_q, &m, a.fx_lim)) { fx_bad = true; continue; } v[e] = fx_bits(m); }
+                if (FX && !fx_entry(val, &v[e])) continue;
                 if (V2) w2[V2 ? e : 0] = val2;
                 if (XT) exact_track(v[e], xinv, xexp);
                 okmask |= 1u << e;
@@ -787,7 +815,7 @@ __global__ __launch_bounds__(DR_BLOCK) void dring_scatter_kernel(DPartArgs a, in
                 if (d > (uint64_t)a.map.mask) { dense_spill(a, key, val, isnull); continue; }  // outside the sampled range (rare: it comes from a sample)
                 c[e] = (((uint32_t)d * a.map.mul) & a.map.mask) | (VN && isnull ? DP_NULL32 : 0u);
                 v[e] = VN && isnull ? 0.0 : val;
-                if (FX) { int64_t m; if (!fx_encode(val, a.fx_inv_q, &m, a.fx_lim)) { fx_bad = true; continue; } v[e] = fx_bits(m); }
+                if (FX && !fx_entry(val, &v[e])) continue;
                 if (XT) exact_track(v[e], xinv, xexp);
                 okmask |= 1u << e;
             }
@@ -805,62 +833,86 @@ __global__ __launch_bounds__(DR_BLOCK) void dring_scatter_kernel(DPartArgs a, in
         const int first = g * per_max;
         const int per = first + per_max <= a.in_regions ? per_max : (a.in_regions > first ? a.in_regions - first : 0);
         const int64_t region0 = (int64_t)pin * a.in_pstride + (int64_t)first * a.in_rstride;
+        // the concatenated input stream counts load UNITS: pairs of entries (16 + 8 byte loads), as in dpart_scatter_kernel -- or, IN32,
+        // 16 bytes of 32-bit words: four entries (two for the one-pair sub-tile).  Counts and region cursors are in entries either way.
+        constexpr int IU = IN32 ? (DR_PAIRS >= 2 ? 4 : 2) : 2, NU = NE / IU;
         if (tid == 0) {
             uint32_t run = 0;
-            for (int rj = 0; rj < per; rj++) { rstart[rj] = run; run += (a.in_counts[region0 + rj * a.in_rstride] + 1) / 2; }
+            for (int rj = 0; rj < per; rj++) { rstart[rj] = run; run += (a.in_counts[region0 + rj * a.in_rstride] + IU - 1) / IU; }
             rstart[per] = run;
         }
         __syncthreads();
-        // the concatenated input stream counts PAIRS of entries (16 + 8 byte loads), as in dpart_scatter_kernel
         const uint32_t total_in = rstart[per];
-        double2 ev[DR_PAIRS], ev2[V2 ? DR_PAIRS : 1];
-        uint2 ec[DR_PAIRS];
+        double2 ev[IN32 ? 1 : DR_PAIRS], ev2[V2 ? DR_PAIRS : 1];
+        uint2 ec[IN32 ? 1 : DR_PAIRS];
+        uint32_t ew[IN32 ? NE : 1];   // IN32: the words of this lane's units
         uint32_t okm = 0;
-        int reg = 0;   // pairs are visited in ascending order: the region cursor only moves forward
+        int reg = 0;   // units are visited in ascending order: the region cursor only moves forward
         auto load_pairs = [&](uint32_t t0) {
             okm = 0;
 #pragma unroll
-            for (int u = 0; u < DR_PAIRS; u++) {
+            for (int u = 0; u < NU; u++) {
                 const uint32_t v = t0 + (uint32_t)u * DR_BLOCK + tid;
                 if (v < total_in) {
                     int lo = reg;
                     while (rstart[lo + 1] <= v) lo++;
                     reg = lo;
-                    const uint32_t e0 = 2u * (v - rstart[lo]);
+                    const uint32_t e0 = (uint32_t)IU * (v - rstart[lo]);
                     const int64_t rg = region0 + lo * a.in_rstride;
                     const int64_t at = rg * a.in_cap + e0;
-                    if (HAS_VAL) ev[u] = *(const double2*)(a.in_vals + at);
+                    if (IN32) {   // (in_cap is a multiple of 32 words and e0 of IU: aligned, and inside the region whatever its count)
+                        const uint32_t* src = (const uint32_t*)a.in_vals + at;
+                        if (IU == 4) { const uint4 x = *(const uint4*)src; ew[IN32 ? 4 * u : 0] = x.x; ew[IN32 ? 4 * u + 1 : 0] = x.y; ew[IN32 ? 4 * u + 2 : 0] = x.z; ew[IN32 ? 4 * u + 3 : 0] = x.w; }
+                        else { const uint2 x = *(const uint2*)src; ew[IN32 ? 2 * u : 0] = x.x; ew[IN32 ? 2 * u + 1 : 0] = x.y; }
+                        const uint32_t left = a.in_counts[rg] - e0;   // >= 1
+                        okm |= (left >= (uint32_t)IU ? (1u << IU) - 1u : (1u << left) - 1u) << (IU * u);
+                        continue;
+                    }
+                    if (HAS_VAL) ev[IN32 ? 0 : u] = *(const double2*)(a.in_vals + at);
                     if (V2) ev2[V2 ? u : 0] = *(const double2*)(a.in_vals2 + at);
-                    if (!FX) ec[u] = *(const uint2*)(a.in_codes + at);
+                    if (!FX) ec[IN32 ? 0 : u] = *(const uint2*)(a.in_codes + at);
                     okm |= (e0 + 1 < a.in_counts[rg] ? 3u : 1u) << (2 * u);
                 }
             }
         };
         load_pairs(0);
-        for (uint32_t t0 = 0; t0 < total_in; t0 += DR_PAIRS * DR_BLOCK) {
+        for (uint32_t t0 = 0; t0 < total_in; t0 += NU * DR_BLOCK) {
             uint32_t c[NE]; double v[NE]; double w2[V2 ? NE : 1];
+            if (IN32) {   // window word = ((m - fx_in_base) << in_bits) | remainder of in_bits bits, the field unsigned
+                const uint32_t inmask = (1u << a.in_bits) - 1u;
 #pragma unroll
-            for (int u = 0; u < DR_PAIRS; u++) {
-                if (FX) {   // entry word = (m << in_bits) | remainder of in_bits bits
-                    const uint64_t w0 = (uint64_t)__double_as_longlong(ev[u].x), w1 = (uint64_t)__double_as_longlong(ev[u].y);
-                    const uint64_t inmask = ((uint64_t)1 << a.in_bits) - 1;
-                    c[2 * u] = (uint32_t)(w0 & inmask); c[2 * u + 1] = (uint32_t)(w1 & inmask);
-                    v[2 * u] = fx_bits((int64_t)w0 >> a.in_bits); v[2 * u + 1] = fx_bits((int64_t)w1 >> a.in_bits);
-                    continue;
+                for (int e = 0; e < NE; e++) {
+                    const uint32_t w = ew[IN32 ? e : 0];
+                    c[e] = w & inmask;
+                    v[e] = fx_bits((int64_t)((int32_t)(w >> a.in_bits) + a.fx_in_base));
                 }
-                c[2 * u] = ec[u].x; c[2 * u + 1] = ec[u].y;
-                v[2 * u] = HAS_VAL ? ev[u].x : 0.0; v[2 * u + 1] = HAS_VAL ? ev[u].y : 0.0;
-                if (V2) { w2[V2 ? 2 * u : 0] = ev2[V2 ? u : 0].x; w2[V2 ? 2 * u + 1 : 0] = ev2[V2 ? u : 0].y; }
+            } else {
+#pragma unroll
+                for (int u = 0; u < DR_PAIRS; u++) {
+                    if (FX) {   // entry word = (m << in_bits) | remainder of in_bits bits
+                        const uint64_t w0 = (uint64_t)__double_as_longlong(ev[IN32 ? 0 : u].x), w1 = (uint64_t)__double_as_longlong(ev[IN32 ? 0 : u].y);
+                        const uint64_t inmask = ((uint64_t)1 << a.in_bits) - 1;
+                        c[2 * u] = (uint32_t)(w0 & inmask); c[2 * u + 1] = (uint32_t)(w1 & inmask);
+                        v[2 * u] = fx_bits((int64_t)w0 >> a.in_bits); v[2 * u + 1] = fx_bits((int64_t)w1 >> a.in_bits);
+                        continue;
+                    }
+                    c[2 * u] = ec[IN32 ? 0 : u].x; c[2 * u + 1] = ec[IN32 ? 0 : u].y;
+                    v[2 * u] = HAS_VAL ? ev[IN32 ? 0 : u].x : 0.0; v[2 * u + 1] = HAS_VAL ? ev[IN32 ? 0 : u].y : 0.0;
+                    if (V2) { w2[V2 ? 2 * u : 0] = ev2[V2 ? u : 0].x; w2[V2 ? 2 * u + 1 : 0] = ev2[V2 ? u : 0].y; }
+                }
             }
             const uint32_t okmask = okm;
-            load_pairs(t0 + DR_PAIRS * DR_BLOCK);
+            load_pairs(t0 + NU * DR_BLOCK);
             rounds(c, v, w2, okmask);
         }
     }
     flush(true);
     __syncthreads();
     if (tid < np) a.out_counts[out_base + (int64_t)tid * out_stride] = cursor[tid];
-    if (FX && FROM_ROWS) { if (__syncthreads_or(fx_bad ? 1 : 0) && tid == 0) __hip_atomic_store(&a.flags[7], 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    if (FX && FROM_ROWS) {
+        const int bad0 = __syncthreads_or((int)(fx_bad & 1u)), bad1 = WIN ? __syncthreads_or((int)(fx_bad & 2u)) : 0;
+        if ((bad0 || bad1) && tid == 0) __hip_atomic_fetch_or(&a.flags[7], (bad0 ? 1ULL : 0ULL) | (bad1 ? 2ULL : 0ULL), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     if (XT) {   // the workgroup's exact-add statistics -> flags[6] (two 32-bit maxima; s_spill is free by now)
         if (tid < 2) s_spill[tid] = 0;
         __syncthreads();
@@ -2390,17 +2442,40 @@ __global__ __launch_bounds__(512) void dscan_emit_kernel(DFinalArgs a, int slots
 }
 
 // exact_track statistics of a strided sample of a float64 column (fixed-point entries: which quantum? -- dense_partitioned_aggregate)
-__global__ __launch_bounds__(256) void fx_sample_kernel(const double* vals, int64_t nrows, int64_t m, unsigned long long* out) {
+// order-preserving unsigned image of a float64 (never 0 for a number; -0.0 < +0.0), and back
+__host__ __device__ __forceinline__ unsigned long long f64_ordered(double v) {
+    unsigned long long b;
+    memcpy(&b, &v, 8);
+    return (b >> 63) ? ~b : b | 0x8000000000000000ULL;
+}
+__host__ __device__ __forceinline__ double f64_of_ordered(unsigned long long u) {
+    const unsigned long long b = (u >> 63) ? u & 0x7FFFFFFFFFFFFFFFULL : ~u;
+    double v;
+    memcpy(&v, &b, 8);
+    return v;
+}
+// (mm, optional: mm[0] = max of the complemented images = the smallest sampled value, mm[1] = the largest; both start at 0)
+__global__ __launch_bounds__(256) void fx_sample_kernel(const double* vals, int64_t nrows, int64_t m, unsigned long long* out, unsigned long long* mm = nullptr) {
     __shared__ uint32_t sx[2];
-    if (threadIdx.x < 2) sx[threadIdx.x] = 0;
+    __shared__ unsigned long long smm[2];
+    if (threadIdx.x < 2) { sx[threadIdx.x] = 0; smm[threadIdx.x] = 0; }
     __syncthreads();
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     uint32_t xinv = 0, xexp = 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride) exact_track(vals[(int64_t)(((__int128)i * nrows) / m)], xinv, xexp);
+    unsigned long long nmin = 0, vmax = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride) {
+        const double v = vals[(int64_t)(((__int128)i * nrows) / m)];
+        exact_track(v, xinv, xexp);
+        const unsigned long long u = f64_ordered(v);
+        nmin = ~u > nmin ? ~u : nmin;
+        vmax = u > vmax ? u : vmax;
+    }
     if (xinv) atomicMax(&sx[0], xinv);
     if (xexp) atomicMax(&sx[1], xexp);
+    if (mm && vmax) { atomicMax(&smm[0], nmin); atomicMax(&smm[1], vmax); }
     __syncthreads();
     if (threadIdx.x < 2 && sx[threadIdx.x]) atomicMax((uint32_t*)out + threadIdx.x, sx[threadIdx.x]);
+    if (mm && threadIdx.x < 2 && smm[threadIdx.x]) atomicMax(&mm[threadIdx.x], smm[threadIdx.x]);
 }
 
 // min / max of the order-preserving unsigned images of a strided sample of the keys: out[0] = min, out[1] = max.

@@ -90,18 +90,18 @@ inline int ring_cap_w32(int np) {
 }
 
 // the attribute and the launch of one kernel of the family (1024 threads; the rings take nparts * cap entries of LDS)
-template <bool FR, typename CT, bool HV, int PR, bool PV, bool VN, int MAXR, bool SEG, bool KN, bool V2, bool FX, bool W32>
+template <bool FR, typename CT, bool HV, int PR, bool PV, bool VN, int MAXR, bool SEG, bool KN, bool V2, bool FX, bool W32, bool IN32 = false, bool WIN = false>
 int launch_ring(int grid, const DPartArgs& d, int cap, hipStream_t s) {
     constexpr size_t esize = FX ? (W32 ? 4 : 8) : (HV ? (V2 ? 16 : 8) : 0) + sizeof(CT);
     const size_t lds = (((size_t)d.nparts * cap * esize) + 15) & ~(size_t)15;
-    return launch_dyn(dring_scatter_kernel<FR, CT, HV, 1024, PR, PV, VN, MAXR, SEG, KN, V2, FX, W32>, grid, 1024, lds, s, d, cap);
+    return launch_dyn(dring_scatter_kernel<FR, CT, HV, 1024, PR, PV, VN, MAXR, SEG, KN, V2, FX, W32, IN32, WIN>, grid, 1024, lds, s, d, cap);
 }
 // ... with PR pairs per lane.  MAXR = 2 (round limit: two insert / flush rounds per sub-tile) where one round takes an even spread;
 // the SEG and KN kernels exist for pass 1 over a plain value column only (same shapes otherwise).
-template <bool FR, typename CT, bool HV, bool PV, bool VN, bool FX, bool W32, int PR>
+template <bool FR, typename CT, bool HV, bool PV, bool VN, bool FX, bool W32, int PR, bool IN32 = false, bool WIN = false>
 int ring_scatter_pairs(const RingLaunch& r, const DPartArgs& d) {
     auto go = [&](auto lim, auto seg, auto kn) {
-        return launch_ring<FR, CT, HV, PR, PV, VN, decltype(lim)::value ? 2 : 0, decltype(seg)::value, decltype(kn)::value, false, FX, W32>(r.grid, d, r.cap, r.s);
+        return launch_ring<FR, CT, HV, PR, PV, VN, decltype(lim)::value ? 2 : 0, decltype(seg)::value, decltype(kn)::value, false, FX, W32, IN32, WIN>(r.grid, d, r.cap, r.s);
     };
     return pick_bool(r.limit && ring_one_round(PR, d.nparts, r.cap, W32), [&](auto lim) {
         if constexpr (FR && HV && !VN) {
@@ -112,14 +112,14 @@ int ring_scatter_pairs(const RingLaunch& r, const DPartArgs& d) {
     });
 }
 // FR: pass 1 (from rows); CT: the code remainders; HV: entries carry a value; PV: a predicate column of its own; VN: a nullable
-// value column; FX / W32: fixed-point entry words / of 32 bits.  r.pairs comes from ring_sub_tile_pairs (never 4 with PV).
-template <bool FR, typename CT, bool HV, bool PV, bool VN, bool FX = false, bool W32 = false>
+// value column; FX / W32: fixed-point entry words / of 32 bits; IN32: pass 2 over 32-bit words; WIN: pass 1 writes window words.  r.pairs comes from ring_sub_tile_pairs (never 4 with PV).
+template <bool FR, typename CT, bool HV, bool PV, bool VN, bool FX = false, bool W32 = false, bool IN32 = false, bool WIN = false>
 int ring_scatter(const RingLaunch& r, const DPartArgs& d) {
     if constexpr (!PV) {
-        if (r.pairs == 4) return ring_scatter_pairs<FR, CT, HV, PV, VN, FX, W32, 4>(r, d);
+        if (r.pairs == 4) return ring_scatter_pairs<FR, CT, HV, PV, VN, FX, W32, 4, IN32, WIN>(r, d);
     }
-    if (r.pairs >= 2) return ring_scatter_pairs<FR, CT, HV, PV, VN, FX, W32, 2>(r, d);
-    return ring_scatter_pairs<FR, CT, HV, PV, VN, FX, W32, 1>(r, d);
+    if (r.pairs >= 2) return ring_scatter_pairs<FR, CT, HV, PV, VN, FX, W32, 2, IN32, WIN>(r, d);
+    return ring_scatter_pairs<FR, CT, HV, PV, VN, FX, W32, 1, IN32, WIN>(r, d);
 }
 
 
@@ -825,7 +825,10 @@ struct DensePlan {
     int c8_cb, c8_sub;       // ... bits of a counter; a partition of 2^c8_sub times the table's codes is read once per part
     bool fx;                 // fixed-point words, of the quantum fx_q = 2^qe (0: float64 entries)
     double fx_q;
-    bool w32, w32_1;         // the LAST level's words are 32 bits (one level: pass 1 writes them; two: pass 2)
+    bool w32, w32_1;         // the LAST level's words are 32 bits; pass 1 writes 32-bit words (its only level, or the first of two: narrow1)
+    bool narrow1;            // two levels, 32-bit words out of BOTH: the first level's value field is a window of 32 - (remainder bits) bits
+    int fx_qe;               // the quantum of this attempt's words, 2^fx_qe: the operator's, or coarser by the bits narrow1 cannot spare
+    int fx_wbits, fx_wbase;  // narrow1: bits and base of the window, in quanta of 2^fx_qe
     int grid1, split2;       // pass-1 workgroups; pass-2 workgroups per first-level partition
     int64_t cap1, cap2;      // entries per region after pass 1 / pass 2
     bool c16_1;              // pass-1 remainders fit 16 bits when they are the final slots
@@ -867,18 +870,23 @@ int sample_fixed_point(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_t 
     PoolScope pool;
     unsigned long long* d = (unsigned long long*)pool.take(64);
     if (!d) return 1;
-    unsigned long long got = 0;
-    VNM_HIP(hipMemsetAsync(d, 0, 8, s));
+    unsigned long long got3[3] = {0, 0, 0};   // exact_track statistics; ~image of the smallest sampled value; image of the largest
+    VNM_HIP(hipMemsetAsync(d, 0, 24, s));
     const int64_t srows = h->segs_active ? (*h->segs_active)[0].nrows : nrows;
     const int64_t m = std::min<int64_t>(srows, 1 << 16);
-    fx_sample_kernel<<<(int)std::min<int64_t>((m + 255) / 256, 256), 256, 0, s>>>((const double*)a.cols[0].values + a.cols[0].offset, srows, m, d);
+    fx_sample_kernel<<<(int)std::min<int64_t>((m + 255) / 256, 256), 256, 0, s>>>((const double*)a.cols[0].values + a.cols[0].offset, srows, m, d, d + 1);
     VNM_HIP(hipGetLastError());
-    VNM_HIP(hipMemcpyAsync(&got, d, 8, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipMemcpyAsync(got3, d, 24, hipMemcpyDeviceToHost, s));
     VNM_HIP(hipStreamSynchronize(s));
+    const unsigned long long got = got3[0];
     const uint32_t xinv = (uint32_t)got, xexp = (uint32_t)(got >> 32);
-    if (xinv == 0 && xexp == 0) { h->fx_state = 1; h->fx_qe = -16; }   // (zeros only)
-    else if (xexp < 2047) {
-        const int L = (int)(0xFFFFu - xinv) - 1075, E = (int)xexp - 1022;   // lowest bit 2^L, |v| < 2^E
+    const bool zeros = xinv == 0 && xexp == 0;
+    if (zeros || xexp < 2047) {
+        // (zeros only: as if the sample held ones -- narrow words with nine bits on either side of the quantum)
+        const int L = zeros ? 0 : (int)(0xFFFFu - xinv) - 1075, E = zeros ? 0 : (int)xexp - 1022;   // lowest bit 2^L, |v| < 2^E
+        // what the first of two levels needs for a window of its own (plan_narrow_first_level)
+        h->fx_L = L; h->fx_E = E;
+        h->fx_vmin = zeros ? 0.0 : f64_of_ordered(~got3[1]); h->fx_vmax = zeros ? 0.0 : f64_of_ordered(got3[2]);
         // NARROW words (round 6): up to 16 bits of quanta in the sample leave two spare bits inside 18 -- the words of the LAST scatter
         // level then are 32 bits, (m << slot bits) | slot with at most 13 slot bits: 4 bytes per entry into the final pass
         const bool narrow = E - L <= 16 && env_i64("VNM_DENSE_FX_NARROW", 1) != 0;
@@ -890,8 +898,34 @@ int sample_fixed_point(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_t 
             if (qe >= -1000 && E - qe <= room) { h->fx_state = 1; h->fx_qe = qe; h->fx_narrow = narrow; }
         }
     }
-    if (getenv("VNM_AGG_TRACE")) fprintf(stderr, "[agg] fixed-point entries: sample says %s (qe %d)\n", h->fx_state == 1 ? "yes" : "no", h->fx_qe);
+    if (getenv("VNM_AGG_TRACE")) fprintf(stderr, "[agg] fixed-point entries: sample says %s (qe %d, values %g .. %g)\n", h->fx_state == 1 ? "yes" : "no", h->fx_qe, h->fx_vmin, h->fx_vmax);
     return 0;
+}
+
+// Two levels of fixed-point words whose LAST level is narrow: may the FIRST level write 32-bit words as well?  After a fan-out of 2^p1
+// its words keep R1 = bits - p1 remainder bits and V1 = 32 - R1 bits for the value -- an unsigned window [base, base + 2^V1) of quanta that
+// must hold the sampled minimum and maximum.  The quantum: the sampler's rule with min(18, V1) bits instead of 18 (never finer than the
+// operator's: pass 1 checks every row at that one first, so a row that misfits there costs what it always did).  p1 rises, up to 9 and
+// while the second level keeps 32 rings, where that is what makes the span fit (2^27 codes: p1 8 -> 9, V1 13 -> 14).  The window is
+// [0, 2^V1) where that holds the sample -- the exponent bound then promises the fit for every |v| < 2^E -- or its mirror image for
+// negative data; otherwise the sampled span sits in its middle.  false: the first level keeps 8-byte words.
+bool plan_narrow_first_level(const vnm_agg* h, int bits, int pbits, bool p1_given, int* p1, int* qe_out, int* wbits, int* wbase) {
+    if (!h->fx_narrow || h->fx_narrow1_off || env_i64("VNM_DENSE_FX_NARROW", 1) == 2) return false;
+    for (int pc = *p1; pc <= 9 && (pc == *p1 || (!p1_given && pbits - pc >= 5)); pc++) {
+        const int v1 = 32 - (bits - pc);
+        if (v1 < 1 || v1 > 24) continue;
+        const int room = std::min(18, v1);
+        int qe = h->fx_E - h->fx_L <= room ? h->fx_L - (room - (h->fx_E - h->fx_L)) / 2 : h->fx_L;
+        qe = std::max(std::min(qe, 0), h->fx_qe);
+        // (every sampled value is a multiple of 2^L >= 2^qe below 2^18 quanta of the operator's quantum: exact)
+        const int64_t mn = (int64_t)std::ldexp(h->fx_vmin, -qe), mx = (int64_t)std::ldexp(h->fx_vmax, -qe);
+        const int64_t w = (int64_t)1 << v1;
+        if (mx - mn >= w) continue;
+        *p1 = pc; *qe_out = qe; *wbits = v1;
+        *wbase = mn >= 0 && mx < w ? 0 : (mx <= 0 && mn > -w ? (int)(1 - w) : (int)(mn - (w - 1 - (mx - mn)) / 2));
+        return true;
+    }
+    return false;
 }
 
 // Stage 2b: tables, fan-out, regions and rings of the attempt.  0, or 2 = not applicable.
@@ -955,6 +989,9 @@ int plan_dense_geometry(const vnm_agg* h, const AggArgs& a, int64_t nrows, const
     // (fixed-point words: 8 bytes in BOTH passes -- the larger fan-out goes first: G = 1e8, p1 = 7 / 8: 7.53 / 7.37 ms)
     int p1 = levels == 2 ? (int)env_i64("VNM_DENSE_P1", fx_ok ? (pbits + 1) / 2 : pbits / 2) : pbits;
     if (levels == 2) { if (p1 > 9) p1 = 9; if (pbits - p1 > 9) p1 = pbits - 9; }
+    // (two levels never share a final partition and never count bytes: this is what p->fx comes to below)
+    p->fx_qe = h->fx_qe; p->fx_wbits = 0; p->fx_wbase = 0;
+    p->narrow1 = fx_ok && levels == 2 && tb >= 11 && tb <= 13 && plan_narrow_first_level(h, mp.bits, pbits, getenv("VNM_DENSE_P1") != nullptr, &p1, &p->fx_qe, &p->fx_wbits, &p->fx_wbase);
     p->p1 = p1; p->p2 = pbits - p1;
     p->np1 = 1 << p1; p->np2 = levels == 2 ? 1 << p->p2 : 0;
     const int np1 = p->np1, np2 = p->np2;
@@ -973,7 +1010,7 @@ int plan_dense_geometry(const vnm_agg* h, const AggArgs& a, int64_t nrows, const
     // over the L2 sets instead of sharing their low index bits (two sessions of 5-6 process pairs: 11.73 -> 11.25 and 11.27 -> 11.17 ms)
     const bool odd_cap = env_i64("VNM_DENSE_ODD_CAP", 1) != 0;
     if (odd_cap && ((cap1 / 16) & 1) == 0) cap1 += 16;
-    if (fx_ok && h->fx_narrow && levels == 1) { cap1 = (cap1 + 31) & ~31LL; if (((cap1 / 32) & 1) == 0) cap1 += 32; }   // (32-bit words: blocks of 32)
+    if (fx_ok && h->fx_narrow && (levels == 1 || p->narrow1)) { cap1 = (cap1 + 31) & ~31LL; if (((cap1 / 32) & 1) == 0) cap1 += 32; }   // (32-bit words: blocks of 32)
     p->cap1 = cap1;
     p->c16_1 = levels == 1 && !p->count8;
     // final partitions x splits >= ~4 workgroups per CU
@@ -985,9 +1022,10 @@ int plan_dense_geometry(const vnm_agg* h, const AggArgs& a, int64_t nrows, const
     if (fx_small && levels == 1) fsplits = 1;   // (128 .. 512 lean final workgroups: a short pass either way)
     p->fsplits = fsplits;
     p->fx = fx_ok && fsplits == 1 && !p->count8 && tb >= (fx_small ? 7 : 11) && tb <= 13;
-    p->fx_q = p->fx ? std::ldexp(1.0, h->fx_qe) : 0.0;
+    if (!p->fx) p->narrow1 = false;
+    p->fx_q = p->fx ? std::ldexp(1.0, p->fx_qe) : 0.0;
     p->w32 = p->fx && h->fx_narrow;
-    p->w32_1 = p->w32 && levels == 1;
+    p->w32_1 = p->w32 && (levels == 1 || p->narrow1);
     if (levels == 2) {
         const int64_t per_pg = (int64_t)grid1 * rows_per_wg / np1 / split2;
         int64_t cap2 = ((per_pg / np2 + per_pg / np2 / 4 + 256) + 15) & ~15LL;
@@ -1009,6 +1047,8 @@ int plan_dense_geometry(const vnm_agg* h, const AggArgs& a, int64_t nrows, const
     // (pass 1 of TWO levels of fixed-point words: sub-tiles of two pairs -- 4.07-4.19 -> 3.85-3.90 ms at G = 1e8, A/B x 3; one level
     // of 512 rings: four pairs as before)
     p->ring_pairs1 = (int)env_i64("VNM_DENSE_RING_PAIRS", 4);
+    // (32-bit window words out of the first of two levels: two pairs as well -- 6.22-6.23 ms against 6.21-6.23 with four at G = 1e8, and every
+    // two-pair kernel of the family, nullable key included, stays clear of scratch: the four-pair nullable-key kernel spills 12 VGPRs)
     if (p->fx && levels == 2 && getenv("VNM_DENSE_RING_PAIRS") == nullptr) p->ring_pairs1 = 2;
     // (32-bit words out of pass 2: 128 rings of up to 256 words take four pairs per lane in one round -- half the barriers: 1.74-1.76 -> 1.56 ms)
     p->ring_pairs2 = levels == 2 ? (int)env_i64("VNM_DENSE_RING_PAIRS2", p->fx && p->w32 ? 4 : 2) : 0;
@@ -1075,6 +1115,10 @@ int dense_scatter1_launch(vnm_agg* h, const DensePlan& p, DenseBuffers& b, DPart
                        plain_val && h->segs_active != nullptr, plain_val && h->kn_valid != nullptr, s};
     // the waiting batches of a stream: one segment each, sub-tiles of 2 * pairs * 1024 rows
     if (r.seg && !r.kn && upload_segs(h, (int64_t)2 * r.pairs * 1024, &d1.segs, &d1.nseg, &d1.nsub, b.pool, s)) return 1;
+    if (p.fx && p.narrow1) {   // window words out of the first of two levels
+        if (p.vn) return ring_scatter<true, uint32_t, true, false, true, true, true, false, true>(r, d1);
+        return pick_bool(pv, [&](auto pvc) { return ring_scatter<true, uint32_t, true, decltype(pvc)::value, false, true, true, false, true>(r, d1); });
+    }
     if (p.fx && p.vn)   // (vn_fold: the predicate column is the value column)
         return pick_bool(p.w32_1, [&](auto w32) { return ring_scatter<true, uint32_t, true, false, true, true, decltype(w32)::value>(r, d1); });
     if (p.fx)
@@ -1108,8 +1152,9 @@ int dense_scatter1(vnm_agg* h, const AggArgs& a, int64_t nrows, const DensePlan&
     d1.nt_store = (int)env_i64("VNM_DENSE_NT", p.levels == 2 && p.np2 >= 256 ? 1 : 0) & 1;
     d1.ready_list = (int)env_i64("VNM_DENSE_READY_LIST", 1) & 1;
     d1.flags = b.flags; d1.spill = b.spill; d1.spill_cap = p.spill_cap;
-    d1.fx_q = p.fx_q; d1.fx_inv_q = p.fx ? std::ldexp(1.0, -h->fx_qe) : 0.0;
+    d1.fx_q = p.fx_q; d1.fx_inv_q = p.fx ? std::ldexp(1.0, -h->fx_qe) : 0.0;   // (the per-row check is at the operator's quantum)
     d1.fx_lim = p.w32 ? (1LL << 18) - 1 : 2147483647LL;
+    if (p.narrow1) { d1.fx_wbits = p.fx_wbits; d1.fx_wbase = p.fx_wbase; d1.fx_wuns = 1; d1.fx_sh = p.fx_qe - h->fx_qe; }
     if (p.vn) { d1.vvalid = a.cols[0].validity; d1.voff = a.cols[0].offset; d1.nspill = b.nspill; d1.nspill_cap = p.nspill_cap; }
     if (h->kn_valid) {   // the NULL-key rows go to scratch words of the flags block (fold_null_rows)
         if (ensure_table(h, 1024, s, true)) return 1;
@@ -1147,11 +1192,13 @@ int dense_scatter2(const vnm_agg* h, const DensePlan& p, DenseBuffers& b, const 
     d2.nt_store = ((int)env_i64("VNM_DENSE_NT", 0) >> 1) & 1;
     d2.ready_list = ((int)env_i64("VNM_DENSE_READY_LIST", 1) >> 1) & 1;   // (pass 2: every ring completes a block in every round -- the list only costs its atomics: 1.71 -> 1.78 ms)
     d2.fx_q = d1.fx_q; d2.fx_inv_q = d1.fx_inv_q; d2.fx_lim = d1.fx_lim;
+    d2.fx_in_base = d1.fx_wbase;
     const int grid2 = p.np1 * p.split2;
     const RingLaunch r{grid2, p.rcap2, ring_sub_tile_pairs(p.ring_pairs2, false, p.ring_limit, p.np2, p.rcap2, p.w32), p.ring_limit, false, false, s};
     {
         KernelTimer timer("agg_part_scatter2", s);
-        if (p.fx) VNM_TRY(pick_bool(p.w32, [&](auto w32) { return ring_scatter<false, uint32_t, true, false, false, true, decltype(w32)::value>(r, d2); }));
+        if (p.fx && p.narrow1) VNM_TRY((ring_scatter<false, uint32_t, true, false, false, true, true, true>(r, d2)));
+        else if (p.fx) VNM_TRY(pick_bool(p.w32, [&](auto w32) { return ring_scatter<false, uint32_t, true, false, false, true, decltype(w32)::value>(r, d2); }));
         else if (p.rcap2) VNM_TRY(pick_bool(p.has_val, [&](auto hv) { return ring_scatter<false, uint16_t, decltype(hv)::value, false, false>(r, d2); }));
         else VNM_TRY(pick_bool(p.has_val, [&](auto hv) { dpart_scatter_kernel<false, uint16_t, decltype(hv)::value><<<grid2, PT_BLOCK, 0, s>>>(d2); return 0; }));
     }
@@ -1224,7 +1271,7 @@ int dense_final_split(const DensePlan& p, DenseBuffers& b, DFinalArgs& df, hipSt
 
 // Stage 6, the usual one: the final pass is DEFERRED -- what it should write depends on what comes next (complete_pending), and the
 // batches of a stream share ONE final pass.  The scatter passes have to be known good first; then the entries join the pending pass
-// of the handle.  0 = done, 2 = the scatter failed, DENSE_REDO = a fixed-point misfit (narrow -> wide -> float64 entries).
+// of the handle.  0 = done, 2 = the scatter failed, DENSE_REDO = a fixed-point misfit (32-bit words out of both levels -> out of the last only -> 8-byte words -> float64 entries).
 int dense_defer_final(vnm_agg* h, const AggArgs& a, int64_t nrows, const DensePlan& p, DenseBuffers& b, const DSet& fin, DFinalArgs& df, hipStream_t s,
                       ulonglong2** spill_out, int64_t* n_spill_out) {
     const DenseMap& mp = h->dmap;
@@ -1237,6 +1284,11 @@ int dense_defer_final(vnm_agg* h, const AggArgs& a, int64_t nrows, const DensePl
     if (getenv("VNM_AGG_TRACE"))
         fprintf(stderr, "[agg] dense: bits %d tb %d levels %d p1 %d p2 %d -> scatter fail %llu spilled %llu, final pass deferred (bound %lld)\n",
                 mp.bits, p.tb, p.levels, p.p1, p.p2, fl0[0], fl0[2], (long long)p.dstride);
+    if (p.fx && fl0[7] == 2) {   // every value fits the words of the last level, one is outside the first level's window: that level alone goes back to 8-byte words, for this batch and every later one
+        h->fx_narrow1_off = true;
+        route_note("dense:fixed_point_misfit", "a value outside the first level's window, 2^%d * [%d, %d + 2^%d): the batch is redone with 8-byte words out of that level", p.fx_qe, p.fx_wbase, p.fx_wbase, p.fx_wbits);
+        return DENSE_REDO;
+    }
     if (p.fx && fl0[7]) {   // a value that is not m * 2^qe with |m| < 2^31: float64 entries for this batch and every later one
         if (h->fx_narrow) {   // (outside the 18 bits of the narrow words: 64-bit words with six more bits below the quantum and 13 more above)
             h->fx_narrow = false;
@@ -1249,7 +1301,9 @@ int dense_defer_final(vnm_agg* h, const AggArgs& a, int64_t nrows, const DensePl
         return DENSE_REDO;
     }
     if (fl0[0]) return 2;
-    if (p.fx) route_note("dense:fixed_point", "%s entry words, quantum 2^%d", p.w32 ? (p.levels == 1 ? "4-byte" : "8-byte, then 4-byte") : "8-byte", h->fx_qe);
+    if (p.fx) route_note("dense:fixed_point", "%s entry words, quantum 2^%d", p.w32 ? (p.levels == 1 ? "4-byte" : (p.narrow1 ? "4-byte, then 4-byte" : "8-byte, then 4-byte")) : "8-byte", p.fx_qe);
+    if (p.w32 && !p.narrow1) route_note("dense:fixed_point_narrow_last_level", "32-bit words out of the last of %d level(s) only", p.levels);
+    if (p.narrow1) route_note("dense:fixed_point_narrow_levels", "32-bit words out of both levels: p1 %d, a window of %d bits from %d quanta of 2^%d", p.p1, p.fx_wbits, p.fx_wbase, p.fx_qe);
     if (fold_null_rows(h, a, b.flags, s)) return 1;
     b.pool.done(b.rk); b.pool.done(b.ra);   // (the run is allocated when the pass runs)
     if (fl0[2]) { b.pool.keep(b.spill); *spill_out = b.spill; *n_spill_out = (int64_t)fl0[2]; }   // the caller owns it now
