@@ -344,6 +344,8 @@ __device__ __forceinline__ bool table_has_room(const AggArgs& a, unsigned* s_new
 
 #include "vnm_agg_table.inc"
 
+#include "vnm_ring.inc"
+
 #include "vnm_agg_part.inc"
 
 #include "vnm_agg_pack.inc"

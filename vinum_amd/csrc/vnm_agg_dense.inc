@@ -442,6 +442,11 @@ typedef uint32_t dr_u2 __attribute__((ext_vector_type(2)));
 // V2: entries carry TWO values (see DPartArgs::vp2); nothing spills in that mode -- an entry without a place fails the pass (flags[0])
 // and the batch takes the hash partitions
 // FX: fixed-point entries -- ONE 64-bit word per entry, (m << remainder bits) | remainder, in the rings and in the regions (DPartArgs::fx_q)
+// The ring protocol below (fill / head / cursor, insert, flush, rounds) is this kernel's OWN COPY of what vnm_ring.inc holds for the four
+// other ring scatters; only the level-2 region walk comes from there.  The four-pair pass-1 instances sit at 127-128 VGPRs: built on the
+// core's reserve / flush / rounds they spilled 62-99 registers and the one-pair instances lost an occupancy step, and the core's
+// bookkeeping alone (one ready list, ring_init) still left five of them with 12 spilled registers (profiles/r12_ring_core.txt, section 2).
+// A change to the protocol is made there AND here.
 template <bool FROM_ROWS, typename CT, bool HAS_VAL, int DR_BLOCK, int DR_PAIRS, bool PV = false, bool VN = false, int MAXR = 0, bool SEG = false, bool KN = false,
           bool V2 = false, bool FX = false, bool W32 = false, bool IN32 = false, bool WIN = false>
 __global__ __launch_bounds__(DR_BLOCK) void dring_scatter_kernel(DPartArgs a, int ring_cap) {
@@ -827,22 +832,11 @@ __global__ __launch_bounds__(DR_BLOCK) void dring_scatter_kernel(DPartArgs a, in
         }
     } else {
         __shared__ uint32_t rstart[PT_MAX_REGIONS + 1];
-        const int pin = blockIdx.x / a.in_split;
-        const int per_max = (a.in_regions + a.in_split - 1) / a.in_split;
-        const int g = blockIdx.x % a.in_split;
-        const int first = g * per_max;
-        const int per = first + per_max <= a.in_regions ? per_max : (a.in_regions > first ? a.in_regions - first : 0);
-        const int64_t region0 = (int64_t)pin * a.in_pstride + (int64_t)first * a.in_rstride;
         // the concatenated input stream counts load UNITS: pairs of entries (16 + 8 byte loads), as in dpart_scatter_kernel -- or, IN32,
         // 16 bytes of 32-bit words: four entries (two for the one-pair sub-tile).  Counts and region cursors are in entries either way.
         constexpr int IU = IN32 ? (DR_PAIRS >= 2 ? 4 : 2) : 2, NU = NE / IU;
-        if (tid == 0) {
-            uint32_t run = 0;
-            for (int rj = 0; rj < per; rj++) { rstart[rj] = run; run += (a.in_counts[region0 + rj * a.in_rstride] + IU - 1) / IU; }
-            rstart[per] = run;
-        }
-        __syncthreads();
-        const uint32_t total_in = rstart[per];
+        const RingRegions rgs = ring_regions<IU>(rstart, a.in_counts, a.in_regions, a.in_split, a.in_pstride, a.in_rstride);
+        const uint32_t total_in = rgs.total;
         double2 ev[IN32 ? 1 : DR_PAIRS], ev2[V2 ? DR_PAIRS : 1];
         uint2 ec[IN32 ? 1 : DR_PAIRS];
         uint32_t ew[IN32 ? NE : 1];   // IN32: the words of this lane's units
@@ -854,11 +848,8 @@ __global__ __launch_bounds__(DR_BLOCK) void dring_scatter_kernel(DPartArgs a, in
             for (int u = 0; u < NU; u++) {
                 const uint32_t v = t0 + (uint32_t)u * DR_BLOCK + tid;
                 if (v < total_in) {
-                    int lo = reg;
-                    while (rstart[lo + 1] <= v) lo++;
-                    reg = lo;
-                    const uint32_t e0 = (uint32_t)IU * (v - rstart[lo]);
-                    const int64_t rg = region0 + lo * a.in_rstride;
+                    uint32_t e0;
+                    const int64_t rg = rgs.region0 + ring_region_of<IU>(rstart, reg, v, &e0) * a.in_rstride;
                     const int64_t at = rg * a.in_cap + e0;
                     if (IN32) {   // (in_cap is a multiple of 32 words and e0 of IU: aligned, and inside the region whatever its count)
                         const uint32_t* src = (const uint32_t*)a.in_vals + at;

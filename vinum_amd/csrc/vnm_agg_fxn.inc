@@ -59,15 +59,13 @@ template <bool FROM_ROWS, int NV, int PAIRS, bool SEG, bool PV>
 // (one 1024-thread workgroup per CU by its rings: four waves per SIMD, 128 VGPRs each -- left to itself the compiler aims at eight and spills)
 __global__ __launch_bounds__(FXN_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) void fxn_scatter_kernel(FxnArgs a, int ring_cap) {
     extern __shared__ fxn_u4 fxn_ring[];                 // [np][ring_cap]
-    __shared__ uint32_t fill[PT_MAXP], head[PT_MAXP], cursor[PT_MAXP];
-    __shared__ uint32_t s_retry[2];
-    __shared__ uint32_t s_nready[2];            // the rings that completed a block in this round, and which (see dring_scatter_kernel)
-    __shared__ uint16_t ready[2][PT_MAXP];
+    __shared__ uint32_t fill[PT_MAXP], head[PT_MAXP], cursor[PT_MAXP], s_retry[2], s_nready[2];
+    __shared__ uint16_t ready[PT_MAXP];
+    const RingState<uint32_t> rs{fill, head, cursor, s_retry, s_nready, ready};
     constexpr int NE = 2 * PAIRS;
     const int np = a.nparts, tid = threadIdx.x;
     const uint32_t remmask = (1u << a.out_bits) - 1u;
-    for (int i = tid; i < PT_MAXP; i += FXN_BLOCK) { fill[i] = 0; head[i] = 0; cursor[i] = 0; }
-    if (tid < 2) { s_retry[tid] = 0; s_nready[tid] = 0; }
+    ring_init<FXN_BLOCK, PT_MAXP>(rs);
     int ph = 0;
     const bool use_list = a.ready_list != 0;
     __syncthreads();
@@ -78,67 +76,23 @@ __global__ __launch_bounds__(FXN_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4)
     const uint32_t ocap = (uint32_t)a.out_cap;
     bool failed = false, misfit = false;
 
-    auto insert = [&](const fxn_u4& e, uint32_t c) -> bool {
-        const uint32_t p = c >> a.out_bits;
-        const uint32_t r = atomicAdd(&fill[p], 1u);
-        if (r == (uint32_t)FXN_FB - 1u && use_list) ready[ph][atomicAdd(&s_nready[ph], 1u)] = (uint16_t)p;
-        if (r >= (uint32_t)ring_cap) return false;
-        uint32_t slot = head[p] + r;
-        if (slot >= (uint32_t)ring_cap) slot -= ring_cap;
-        fxn_u4 w = e; w.w = c & remmask;
-        fxn_ring[(size_t)p * ring_cap + slot] = w;
-        return true;
-    };
-    // whole blocks of every ring -> the partition's region: sixteen lanes per partition, one entry (16 bytes) each
+    // whole blocks of the rings -> the partition's region: sixteen lanes per partition, one entry (16 bytes) each
     auto flush = [&](bool drain) {
-        const int j = tid & 15;
-        const bool listed = use_list && !drain;
-        const int nwalk = listed ? (int)s_nready[ph] : np;
-        for (int q = tid >> 4; q < nwalk; q += FXN_BLOCK / 16) {
-            const int p = listed ? (int)ready[ph][q] : q;
-            uint32_t f = fill[p];
-            if (f > (uint32_t)ring_cap) f = ring_cap;
-            const uint32_t nb = drain ? (f + FXN_FB - 1) / FXN_FB : f / FXN_FB;
-            if (nb == 0) continue;
-            const uint32_t h = head[p], cur = cursor[p];
-            const int64_t rbase = (out_base + (int64_t)p * out_stride) * a.out_cap;
-            uint32_t done = 0, wrote = 0;
-            for (uint32_t b = 0; b < nb; b++) {
-                uint32_t src = h + b * FXN_FB;
-                if (src >= (uint32_t)ring_cap) src -= ring_cap;
-                const uint32_t n_here = f - b * FXN_FB < (uint32_t)FXN_FB ? f - b * FXN_FB : FXN_FB;
-                if (cur + wrote + FXN_FB <= ocap) {
-                    if ((uint32_t)j < n_here) a.out_ent[rbase + cur + wrote + j] = fxn_ring[(size_t)p * ring_cap + src + j];
-                    wrote += n_here;
-                } else failed = true;     // (a full region: no spill buffer -- the attempt fails)
-                done += n_here;
-            }
-            if (j == 0) {
-                uint32_t nh = h + nb * FXN_FB;
-                while (nh >= (uint32_t)ring_cap) nh -= ring_cap;
-                head[p] = drain ? 0 : nh;
-                fill[p] = f - done;
-                cursor[p] = cur + wrote;
-            }
-        }
+        ring_flush<FXN_FB, 16, FXN_BLOCK, false>(rs, ph, drain, use_list, np, (uint32_t)ring_cap, ocap, [&](int p, uint32_t src, int64_t dst, uint32_t n_here, int j, bool room) {
+            if (!room) failed = true;     // (a full region: no spill buffer -- the attempt fails)
+            else if ((uint32_t)j < n_here) a.out_ent[(out_base + (int64_t)p * out_stride) * a.out_cap + dst + j] = fxn_ring[(size_t)p * ring_cap + src + j];
+        });
     };
     auto rounds = [&](const fxn_u4 (&e)[NE], const uint32_t (&c)[NE], uint32_t okmask) {
-        uint32_t pend = 0;
-#pragma unroll
-        for (int k = 0; k < NE; k++) if (((okmask >> k) & 1u) && !insert(e[k], c[k])) pend |= 1u << k;
-        for (int nr = 0;; nr++) {
-            if (pend) s_retry[ph] = 1;
-            __syncthreads();
-            flush(false);
-            if (tid == 0) { s_retry[ph ^ 1] = 0; s_nready[ph ^ 1] = 0; }
-            __syncthreads();
-            const bool again = s_retry[ph] != 0;
-            ph ^= 1;
-            if (!again) break;
-            if (nr >= 6) { failed = true; break; }      // (skew: one ring takes a sub-tile's worth of entries -- not this path's business)
-#pragma unroll
-            for (int k = 0; k < NE; k++) if (((pend >> k) & 1u) && insert(e[k], c[k])) pend &= ~(1u << k);
-        }
+        ring_rounds<NE>(rs, ph, okmask, [&](int k) -> bool {
+            const uint32_t p = c[k] >> a.out_bits;
+            const uint32_t slot = ring_reserve<FXN_FB>(rs, ph, p, (uint32_t)ring_cap, use_list);
+            if (slot != RING_FULL) { fxn_u4 w = e[k]; w.w = c[k] & remmask; fxn_ring[(size_t)p * ring_cap + slot] = w; }
+            return slot != RING_FULL;
+        }, [&]() { flush(false); }, [&](int nr, uint32_t) {
+            if (nr >= 6) failed = true;      // (skew: one ring takes a sub-tile's worth of entries -- not this path's business)
+            return nr >= 6;
+        });
     };
 
     if (FROM_ROWS) {
@@ -218,19 +172,8 @@ __global__ __launch_bounds__(FXN_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4)
         }
     } else {
         __shared__ uint32_t rstart[PT_MAX_REGIONS + 1];
-        const int pin = blockIdx.x / a.in_split;
-        const int per_max = (a.in_regions + a.in_split - 1) / a.in_split;
-        const int g = blockIdx.x % a.in_split;
-        const int first = g * per_max;
-        const int per = first + per_max <= a.in_regions ? per_max : (a.in_regions > first ? a.in_regions - first : 0);
-        const int64_t region0 = (int64_t)pin * a.in_regions + first;
-        if (tid == 0) {
-            uint32_t run = 0;
-            for (int rj = 0; rj < per; rj++) { rstart[rj] = run; run += a.in_counts[region0 + rj]; }
-            rstart[per] = run;
-        }
-        __syncthreads();
-        const uint32_t total_in = rstart[per];
+        const RingRegions rg = ring_regions<1>(rstart, a.in_counts, a.in_regions, a.in_split, a.in_regions, 1);
+        const uint32_t total_in = rg.total;
         const uint32_t inmask = (1u << a.in_bits) - 1u;
         fxn_u4 ev[NE];
         uint32_t okm = 0;
@@ -241,10 +184,9 @@ __global__ __launch_bounds__(FXN_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4)
             for (int k = 0; k < NE; k++) {
                 const uint32_t v = t0 + (uint32_t)k * FXN_BLOCK + tid;
                 if (v < total_in) {
-                    int lo = reg;
-                    while (rstart[lo + 1] <= v) lo++;
-                    reg = lo;
-                    ev[k] = a.in_ent[(region0 + lo) * a.in_cap + (v - rstart[lo])];
+                    uint32_t e0;
+                    const int64_t r = rg.region0 + ring_region_of<1>(rstart, reg, v, &e0);
+                    ev[k] = a.in_ent[r * a.in_cap + e0];
                     okm |= 1u << k;
                 }
             }

@@ -279,14 +279,13 @@ __global__ __launch_bounds__(PT_BLOCK) void part_scatter_kernel(PartArgs a) {
 template <bool FROM_ROWS, int PAIRS, int FB, bool PV>
 __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) void pring_scatter_kernel(PartArgs a, int ring_cap) {
     extern __shared__ ulonglong2 pr_ring[];              // [np][ring_cap]
-    __shared__ uint32_t fill[PT_MAXP], head[PT_MAXP], cursor[PT_MAXP];
-    __shared__ uint32_t s_retry[2], s_nready[2];
-    __shared__ uint16_t ready[2][PT_MAXP];
+    __shared__ uint32_t fill[PT_MAXP], head[PT_MAXP], cursor[PT_MAXP], s_retry[2], s_nready[2];
+    __shared__ uint16_t ready[PT_MAXP];
+    const RingState<uint32_t> rs{fill, head, cursor, s_retry, s_nready, ready};
     constexpr int NE = 2 * PAIRS;
     const int np = a.nparts, tid = threadIdx.x;
     const uint32_t pmask = (uint32_t)np - 1;
-    for (int i = tid; i < PT_MAXP; i += PT_BLOCK) { fill[i] = 0; head[i] = 0; cursor[i] = 0; }
-    if (tid < 2) { s_retry[tid] = 0; s_nready[tid] = 0; }
+    ring_init<PT_BLOCK, PT_MAXP>(rs);
     int ph = 0;
     __syncthreads();
     int64_t out_base, out_stride;
@@ -295,65 +294,23 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))
     const uint32_t ocap = (uint32_t)a.out_cap;
     bool failed = false;
 
-    auto insert = [&](const ulonglong2& e) -> bool {
-        const uint32_t p = (hash_u64(e.x) >> a.shift) & pmask;
-        const uint32_t r = atomicAdd(&fill[p], 1u);
-        if (r == (uint32_t)FB - 1u) ready[ph][atomicAdd(&s_nready[ph], 1u)] = (uint16_t)p;
-        if (r >= (uint32_t)ring_cap) return false;
-        uint32_t slot = head[p] + r;
-        if (slot >= (uint32_t)ring_cap) slot -= ring_cap;
-        pr_ring[(size_t)p * ring_cap + slot] = e;
-        return true;
-    };
     // whole blocks of the listed rings (drain: of every ring, the partial last block too) -> the partition's region: FB lanes per ring, one entry each
     auto flush = [&](bool drain) {
-        const int j = tid & (FB - 1);
-        const int nwalk = drain ? np : (int)s_nready[ph];
-        for (int q = tid / FB; q < nwalk; q += PT_BLOCK / FB) {
-            const int p = drain ? q : (int)ready[ph][q];
-            uint32_t f = fill[p];
-            if (f > (uint32_t)ring_cap) f = ring_cap;
-            const uint32_t nb = drain ? (f + FB - 1) / FB : f / FB;
-            if (nb == 0) continue;
-            const uint32_t h = head[p], cur = cursor[p];
-            const int64_t rbase = (out_base + (int64_t)p * out_stride) * a.out_cap;
-            uint32_t done = 0, wrote = 0;
-            for (uint32_t b = 0; b < nb; b++) {
-                uint32_t src = h + b * FB;
-                if (src >= (uint32_t)ring_cap) src -= ring_cap;
-                const uint32_t n_here = f - b * FB < (uint32_t)FB ? f - b * FB : FB;
-                if (cur + wrote + FB <= ocap) {
-                    if ((uint32_t)j < n_here) a.out_entries[rbase + cur + wrote + j] = pr_ring[(size_t)p * ring_cap + src + j];
-                    wrote += n_here;
-                } else failed = true;     // (a full region: the attempt fails)
-                done += n_here;
-            }
-            if (j == 0) {
-                uint32_t nh = h + nb * FB;
-                while (nh >= (uint32_t)ring_cap) nh -= ring_cap;
-                head[p] = drain ? 0 : nh;
-                fill[p] = f - done;
-                cursor[p] = cur + wrote;
-            }
-        }
+        ring_flush<FB, FB, PT_BLOCK, false>(rs, ph, drain, true, np, (uint32_t)ring_cap, ocap, [&](int p, uint32_t src, int64_t dst, uint32_t n_here, int j, bool room) {
+            if (!room) failed = true;     // (a full region: the attempt fails)
+            else if ((uint32_t)j < n_here) a.out_entries[(out_base + (int64_t)p * out_stride) * a.out_cap + dst + j] = pr_ring[(size_t)p * ring_cap + src + j];
+        });
     };
     auto rounds = [&](const ulonglong2 (&e)[NE], uint32_t okmask) {
-        uint32_t pend = 0;
-#pragma unroll
-        for (int k = 0; k < NE; k++) if (((okmask >> k) & 1u) && !insert(e[k])) pend |= 1u << k;
-        for (int nr = 0;; nr++) {
-            if (pend) s_retry[ph] = 1;
-            __syncthreads();
-            flush(false);
-            if (tid == 0) { s_retry[ph ^ 1] = 0; s_nready[ph ^ 1] = 0; }
-            __syncthreads();
-            const bool again = s_retry[ph] != 0;
-            ph ^= 1;
-            if (!again) break;
-            if (nr >= 6) { failed = true; break; }      // (skew: one ring takes a sub-tile's worth of entries -- part_scatter_kernel's business)
-#pragma unroll
-            for (int k = 0; k < NE; k++) if (((pend >> k) & 1u) && insert(e[k])) pend &= ~(1u << k);
-        }
+        ring_rounds<NE>(rs, ph, okmask, [&](int k) -> bool {
+            const uint32_t p = (hash_u64(e[k].x) >> a.shift) & pmask;
+            const uint32_t slot = ring_reserve<FB>(rs, ph, p, (uint32_t)ring_cap, true);
+            if (slot != RING_FULL) pr_ring[(size_t)p * ring_cap + slot] = e[k];
+            return slot != RING_FULL;
+        }, [&]() { flush(false); }, [&](int nr, uint32_t) {
+            if (nr >= 6) failed = true;      // (skew: one ring takes a sub-tile's worth of entries -- part_scatter_kernel's business)
+            return nr >= 6;
+        });
     };
 
     if (FROM_ROWS) {
@@ -398,19 +355,8 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))
         }
     } else {
         __shared__ uint32_t rstart[PT_MAX_REGIONS + 1];
-        const int pin = blockIdx.x / a.in_split;
-        const int per_max = (a.in_regions + a.in_split - 1) / a.in_split;
-        const int g = blockIdx.x % a.in_split;
-        const int first = g * per_max;
-        const int per = first + per_max <= a.in_regions ? per_max : (a.in_regions > first ? a.in_regions - first : 0);
-        const int64_t region0 = (int64_t)pin * a.in_regions + first;
-        if (tid == 0) {
-            uint32_t run = 0;
-            for (int rj = 0; rj < per; rj++) { rstart[rj] = run; run += a.in_counts[region0 + rj]; }
-            rstart[per] = run;
-        }
-        __syncthreads();
-        const uint32_t total_in = rstart[per];
+        const RingRegions rg = ring_regions<1>(rstart, a.in_counts, a.in_regions, a.in_split, a.in_regions, 1);
+        const uint32_t total_in = rg.total;
         ulonglong2 ev[NE];
         uint32_t okm = 0;
         int reg = 0;
@@ -420,10 +366,9 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))
             for (int k = 0; k < NE; k++) {
                 const uint32_t v = t0 + (uint32_t)k * PT_BLOCK + tid;
                 if (v < total_in) {
-                    int lo = reg;
-                    while (rstart[lo + 1] <= v) lo++;
-                    reg = lo;
-                    ev[k] = a.in_entries[(region0 + lo) * a.in_cap + (v - rstart[lo])];
+                    uint32_t e0;
+                    const int64_t r = rg.region0 + ring_region_of<1>(rstart, reg, v, &e0);
+                    ev[k] = a.in_entries[r * a.in_cap + e0];
                     okm |= 1u << k;
                 }
             }

@@ -666,6 +666,7 @@ static int grid_for(int64_t n, int per_cu = 8) {
     return g > need ? (int)need : g;
 }
 
+#include "vnm_ring.inc"
 #include "vnm_sort_sample.inc"
 #include "vnm_sort_apx.inc"
 

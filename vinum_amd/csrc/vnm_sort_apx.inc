@@ -169,10 +169,10 @@ __global__ __launch_bounds__(SS_BLOCK) void xsort_scatter_kernel(XsArgs a) {
     extern __shared__ uint64_t xs_lds[];
     uint64_t* const ring = xs_lds;                              // [SS_B][XS_CAP]
     uint64_t* const lut = xs_lds + SS_B * XS_CAP;               // [XS_K + 1] (level 1)
-    __shared__ uint32_t fill[SS_B], head[SS_B], cursor[SS_B];
-    __shared__ uint32_t s_retry[2], s_hcnt[2];
-    __shared__ uint32_t s_nready[2];                  // rings that completed a block in this round (phase ph), and which
-    __shared__ uint16_t ready[2][SS_B];
+    __shared__ uint32_t fill[SS_B], head[SS_B], cursor[SS_B], s_retry[2], s_nready[2];
+    __shared__ uint16_t ready[SS_B];
+    const RingState<uint32_t> rs{fill, head, cursor, s_retry, s_nready, ready};
+    __shared__ uint32_t s_hcnt[2];
     __shared__ unsigned long long s_hbase;
     __shared__ uint32_t rstart[SS_MAX_REGIONS + 2];
     const int tid = threadIdx.x;
@@ -185,81 +185,33 @@ __global__ __launch_bounds__(SS_BLOCK) void xsort_scatter_kernel(XsArgs a) {
         const int g = blockIdx.x % a.in_split;
         out_base = (int64_t)pin * np * a.in_split + g; out_stride = a.in_split;
     }
-    for (int i = tid; i < SS_B; i += SS_BLOCK) { fill[i] = 0; head[i] = 0; cursor[i] = 0; }
+    ring_init<SS_BLOCK, SS_B>(rs);
     if (FROM_KEYS) for (int i = tid; i <= XS_K; i += SS_BLOCK) lut[i] = a.fb[(size_t)MODE * (XS_K + 1) + i];
-    if (tid < 2) { s_retry[tid] = 0; s_hcnt[tid] = 0; s_nready[tid] = 0; }
+    if (tid < 2) s_hcnt[tid] = 0;
     __syncthreads();
     const uint32_t ocap = (uint32_t)a.out_cap;
     int hp = 0;
     int ph = 0;
     const bool use_list = a.ready_list != 0;
 
-    // Every ring starts a round with less than one block (flush(false) takes all whole blocks), so it completes its first block of the
-    // round exactly once: the lane whose entry is the block's last puts the ring on the round's READY LIST, and the flush walks that list
-    // (~256 of 512 rings per round of 4096 entries) instead of asking every ring for its fill.
-    auto insert = [&](uint32_t p, uint64_t w) -> bool {
-        const uint32_t r = atomicAdd(&fill[p], 1u);
-        if (r == (uint32_t)XS_FB - 1u && use_list) ready[ph][atomicAdd(&s_nready[ph], 1u)] = (uint16_t)p;
-        if (r >= (uint32_t)XS_CAP) return false;
-        uint32_t slot = head[p] + r;
-        if (slot >= (uint32_t)XS_CAP) slot -= XS_CAP;
-        ring[p * XS_CAP + slot] = w;
-        return true;
-    };
-    // whole blocks of every ring -> the partition's region: eight lanes per partition, lane j moves words 2j, 2j + 1 of a block
+    // whole blocks of the rings -> the partition's region: eight lanes per partition, lane j moves words 2j, 2j + 1 of a block.  A full
+    // region fails the sort (flags[0]); its count runs on, capped at out_cap
     auto flush = [&](bool drain) {
-        const int j = tid & 7;
-        const bool listed = use_list && !drain;
-        const int nwalk = listed ? (int)s_nready[ph] : np;
-        for (int q = tid >> 3; q < nwalk; q += SS_BLOCK / 8) {
-            const int p = listed ? (int)ready[ph][q] : q;
-            uint32_t f = fill[p];
-            if (f > (uint32_t)XS_CAP) f = XS_CAP;
-            const uint32_t nb = drain ? (f + XS_FB - 1) / XS_FB : f / XS_FB;
-            if (nb == 0) continue;
-            const uint32_t h = head[p], cur = cursor[p];
-            const int64_t rbase = (out_base + (int64_t)p * out_stride) * a.out_cap;
-            uint32_t done = 0;
-            bool full = false;
-            for (uint32_t b = 0; b < nb; b++) {
-                uint32_t src = h + b * XS_FB;
-                if (src >= (uint32_t)XS_CAP) src -= XS_CAP;
-                const uint32_t n_here = f - b * XS_FB < (uint32_t)XS_FB ? f - b * XS_FB : XS_FB;
-                if (cur + done + XS_FB <= ocap) {
-                    if ((uint32_t)(2 * j) < n_here) {
-                        const xs_w2 x = *(const xs_w2*)(ring + p * XS_CAP + (int)src + 2 * j);
-                        xs_w2* const dst = (xs_w2*)(a.out_words + rbase + cur + done + 2 * j);
-                        if (a.nt) __builtin_nontemporal_store(x, dst); else *dst = x;
-                    }
-                } else full = true;
-                done += n_here;
+        ring_flush<XS_FB, 8, SS_BLOCK, true>(rs, ph, drain, use_list, np, XS_CAP, ocap, [&](int p, uint32_t src, int64_t dst, uint32_t n_here, int j, bool room) {
+            if (!room) { if (j == 0) __hip_atomic_store(&a.flags[0], 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+            else if ((uint32_t)(2 * j) < n_here) {
+                const xs_w2 x = *(const xs_w2*)(ring + p * XS_CAP + (int)src + 2 * j);
+                xs_w2* const to = (xs_w2*)(a.out_words + (out_base + (int64_t)p * out_stride) * a.out_cap + dst + 2 * j);
+                if (a.nt) __builtin_nontemporal_store(x, to); else *to = x;
             }
-            if (full && j == 0) __hip_atomic_store(&a.flags[0], 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (j == 0) {
-                uint32_t nh = h + nb * XS_FB;
-                while (nh >= (uint32_t)XS_CAP) nh -= XS_CAP;
-                head[p] = drain ? 0 : nh;
-                fill[p] = f - done;
-                cursor[p] = cur + done < ocap ? cur + done : ocap;
-            }
-        }
+        });
     };
     auto rounds = [&](const uint32_t (&p)[NE], const uint64_t (&w)[NE], uint32_t okmask) {
-        uint32_t pend = 0;
-#pragma unroll
-        for (int e = 0; e < NE; e++) if (((okmask >> e) & 1u) && !insert(p[e], w[e])) pend |= 1u << e;
-        for (;;) {
-            if (pend) s_retry[ph] = 1;
-            __syncthreads();
-            flush(false);
-            if (tid == 0) { s_retry[ph ^ 1] = 0; s_nready[ph ^ 1] = 0; }
-            __syncthreads();
-            const bool again = s_retry[ph] != 0;
-            ph ^= 1;
-            if (!again) break;
-#pragma unroll
-            for (int e = 0; e < NE; e++) if (((pend >> e) & 1u) && insert(p[e], w[e])) pend &= ~(1u << e);
-        }
+        ring_rounds<NE>(rs, ph, okmask, [&](int e) -> bool {
+            const uint32_t slot = ring_reserve<XS_FB>(rs, ph, p[e], XS_CAP, use_list);
+            if (slot != RING_FULL) ring[p[e] * XS_CAP + slot] = w[e];
+            return slot != RING_FULL;
+        }, [&]() { flush(false); }, [](int, uint32_t) { return false; });
     };
 
     if (FROM_KEYS) {
@@ -300,60 +252,21 @@ __global__ __launch_bounds__(SS_BLOCK) void xsort_scatter_kernel(XsArgs a) {
                 }
             }
             load_sub(st + gridDim.x);
-            if (a.has_null) {   // rows whose key is NULL: their row ids go to the side list -- ONE reservation per workgroup and sub-tile (as ssort_scatter_kernel)
-                uint64_t mm[NE]; uint32_t wtot = 0;
-#pragma unroll
-                for (int e = 0; e < NE; e++) {
-                    bool isnull = false;
-                    if ((okmask >> e) & 1u) {
-                        const int64_t vr = a.key.offset + (int64_t)(uint32_t)w[e];
-                        isnull = !((a.key.validity[vr >> 3] >> (vr & 7)) & 1);
-                    }
-                    mm[e] = __ballot(isnull);
-                    wtot += (uint32_t)__popcll(mm[e]);
-                }
-                const int lane = tid & 63;
-                uint32_t woff = 0;
-                if (lane == 0 && wtot) woff = atomicAdd(&s_hcnt[hp], wtot);
-                woff = __shfl(woff, 0);
-                __syncthreads();
-                if (tid == 0) {
-                    const uint32_t t = s_hcnt[hp];
-                    s_hbase = t ? atomicAdd(&a.flags[2], (unsigned long long)t) : 0ULL;
-                    s_hcnt[hp ^ 1] = 0;
-                }
-                __syncthreads();
-                hp ^= 1;
-                if (wtot) {
-                    const uint64_t lt = lane == 0 ? 0ULL : (~0ULL >> (64 - lane));
-                    unsigned long long at = s_hbase + woff;
-#pragma unroll
-                    for (int e = 0; e < NE; e++) {
-                        if ((mm[e] >> lane) & 1ULL) {
-                            const unsigned long long pos = at + __popcll(mm[e] & lt);
-                            if ((int64_t)pos < a.side_cap) a.side[pos] = (unsigned long long)(uint32_t)w[e];
-                            else __hip_atomic_store(&a.flags[0], 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            okmask &= ~(1u << e);
-                        }
-                        at += __popcll(mm[e]);
-                    }
-                }
+            if (a.has_null) {   // rows whose key is NULL: their row ids go to the side list
+                okmask &= ~ring_side_list<NE>(s_hcnt, s_hbase, hp, &a.flags[2], [&](int e) -> bool {
+                    if (!((okmask >> e) & 1u)) return false;
+                    const int64_t vr = a.key.offset + (int64_t)(uint32_t)w[e];
+                    return !((a.key.validity[vr >> 3] >> (vr & 7)) & 1);
+                }, [&](int e, unsigned long long pos) {
+                    if ((int64_t)pos < a.side_cap) a.side[pos] = (unsigned long long)(uint32_t)w[e];
+                    else __hip_atomic_store(&a.flags[0], 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                });
             }
             rounds(p, w, okmask);
         }
     } else {
-        const int per_max = (a.in_regions + a.in_split - 1) / a.in_split;
-        const int g = blockIdx.x % a.in_split;
-        const int first = g * per_max;
-        const int per = first + per_max <= a.in_regions ? per_max : (a.in_regions > first ? a.in_regions - first : 0);
-        const int64_t region0 = (int64_t)pin * a.in_regions + first;
-        if (tid == 0) {
-            uint32_t run = 0;
-            for (int rj = 0; rj < per; rj++) { rstart[rj] = run; run += (a.in_counts[region0 + rj] + 1) / 2; }
-            rstart[per] = run;
-        }
-        __syncthreads();
-        const uint32_t total_in = rstart[per];   // pairs of entries
+        const RingRegions rg2 = ring_regions<2>(rstart, a.in_counts, a.in_regions, a.in_split, a.in_regions, 1);   // pairs of entries
+        const uint32_t total_in = rg2.total;
         const int qsh = 32 - a.qbits;
         xs_w2 ew[SP];
         uint32_t okm = 0;
@@ -364,11 +277,8 @@ __global__ __launch_bounds__(SS_BLOCK) void xsort_scatter_kernel(XsArgs a) {
             for (int u = 0; u < SP; u++) {
                 const uint32_t v = t0 + (uint32_t)u * SS_BLOCK + tid;
                 if (v < total_in) {
-                    int lo = reg;
-                    while (rstart[lo + 1] <= v) lo++;
-                    reg = lo;
-                    const uint32_t e0 = 2u * (v - rstart[lo]);
-                    const int64_t rg = region0 + lo;
+                    uint32_t e0;
+                    const int64_t rg = rg2.region0 + ring_region_of<2>(rstart, reg, v, &e0);
                     ew[u] = *(const xs_w2*)(a.in_words + rg * a.in_cap + e0);
                     okm |= (e0 + 1 < a.in_counts[rg] ? 3u : 1u) << (2 * u);
                 }

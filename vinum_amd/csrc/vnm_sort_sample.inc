@@ -86,11 +86,10 @@ __global__ __launch_bounds__(SS_BLOCK) void ssort_scatter_kernel(SsArgs a) {
     uint32_t* const rc = (uint32_t*)(ss_lds + SS_B * SS_CAP);       // [SS_B][SS_CAP] row ids
     __shared__ uint64_t sp[SS_B];
     __shared__ uint16_t lut[SS_LUT + 2];
-    __shared__ uint32_t fill[SS_B], cursor[SS_B];
-    __shared__ uint16_t head[SS_B];             // (16 bits: the kernel sits 1 KB below the 160 KB of LDS)
-    __shared__ uint32_t s_retry[2], s_hcnt[2];
-    __shared__ uint32_t s_nready[2];            // the rings that completed a block in this round, and which (round 6, see dring_scatter_kernel)
-    __shared__ uint16_t ready[SS_B];            // (one list: a round's inserts start after the barrier that ends the previous round's flush; the counters alternate)
+    __shared__ uint32_t fill[SS_B], cursor[SS_B], s_retry[2], s_nready[2];
+    __shared__ uint16_t head[SS_B], ready[SS_B];   // (16-bit heads: the kernel sits 1 KB below the 160 KB of LDS)
+    const RingState<uint16_t> rs{fill, head, cursor, s_retry, s_nready, ready};
+    __shared__ uint32_t s_hcnt[2];
     __shared__ unsigned long long s_hbase;
     __shared__ uint64_t aux64[(SS_MAX_REGIONS + 2) / 2 + 1];   // level 2: region starts (uint32); level 1: the heavy codes
     uint32_t* const rstart = (uint32_t*)aux64;
@@ -104,12 +103,10 @@ __global__ __launch_bounds__(SS_BLOCK) void ssort_scatter_kernel(SsArgs a) {
         const int g = blockIdx.x % a.in_split;
         out_base = (int64_t)pin * a.l2 * a.in_split + g; out_stride = a.in_split;
     }
-    for (int i = tid; i < SS_B; i += SS_BLOCK) {
-        fill[i] = 0; head[i] = 0; cursor[i] = 0;
-        // (level 2 with fewer than SS_B partitions: the rest get an unreachable lower bound)
-        sp[i] = FROM_KEYS ? a.split[(size_t)i * a.l2] : (i < a.l2 ? a.split[(size_t)pin * a.l2 + i] : ~0ULL);
-    }
-    if (tid < 2) { s_retry[tid] = 0; s_hcnt[tid] = 0; s_nready[tid] = 0; }
+    ring_init<SS_BLOCK, SS_B>(rs);
+    // (level 2 with fewer than SS_B partitions: the rest get an unreachable lower bound)
+    for (int i = tid; i < SS_B; i += SS_BLOCK) sp[i] = FROM_KEYS ? a.split[(size_t)i * a.l2] : (i < a.l2 ? a.split[(size_t)pin * a.l2 + i] : ~0ULL);
+    if (tid < 2) s_hcnt[tid] = 0;
     int ph = 0;
     if (FROM_KEYS && tid < a.nheavy) hv[tid] = a.heavy[tid];
     __syncthreads();
@@ -122,75 +119,27 @@ __global__ __launch_bounds__(SS_BLOCK) void ssort_scatter_kernel(SsArgs a) {
     __syncthreads();
     const uint32_t ocap = (uint32_t)a.out_cap;
 
-    auto insert = [&](uint64_t code, uint32_t row) -> bool {
-        const int p = min(ss_bucket_lut(sp, lut, lut_base, lut_shift, code), np - 1);   // (the all-ones code meets the unreachable bounds)
-        const uint32_t r = atomicAdd(&fill[p], 1u);
-        if (r == (uint32_t)SS_FB - 1u) ready[atomicAdd(&s_nready[ph], 1u)] = (uint16_t)p;
-        if (r >= (uint32_t)SS_CAP) return false;
-        uint32_t slot = head[p] + r;
-        if (slot >= (uint32_t)SS_CAP) slot -= SS_CAP;
-        rv[p * SS_CAP + slot] = code;
-        rc[p * SS_CAP + slot] = row;
-        return true;
-    };
-    // four lanes per partition, lane j moves entries 2j, 2j + 1 of a block (16 bytes of codes, 8 of row ids)
+    // four lanes per partition, lane j moves entries 2j, 2j + 1 of a block (16 bytes of codes, 8 of row ids).  A full region fails
+    // the sort (flags[0]); its count runs on, capped at out_cap.  Every pass lists its ready rings.
     auto flush = [&](bool drain) {
-        const int j = tid & 3;
-        const int nwalk = drain ? SS_B : (int)s_nready[ph];
-        for (int q = tid >> 2; q < nwalk; q += SS_BLOCK / 4) {
-            const int p = drain ? q : (int)ready[q];
-            uint32_t f = fill[p];
-            if (f > (uint32_t)SS_CAP) f = SS_CAP;
-            const uint32_t nb = drain ? (f + SS_FB - 1) / SS_FB : f / SS_FB;
-            if (nb == 0) continue;
-            const uint32_t h = head[p], cur = cursor[p];
-            const int64_t rbase = (out_base + (int64_t)p * out_stride) * a.out_cap;
-            uint32_t done = 0;
-            bool full = false;
-            for (uint32_t b = 0; b < nb; b++) {
-                uint32_t src = h + b * SS_FB;
-                if (src >= (uint32_t)SS_CAP) src -= SS_CAP;
-                const uint32_t n_here = f - b * SS_FB < (uint32_t)SS_FB ? f - b * SS_FB : SS_FB;
-                if (cur + done + SS_FB <= ocap) {
-                    if ((uint32_t)(2 * j) < n_here) {
-                        const int li = p * SS_CAP + (int)src + 2 * j;
-                        const int64_t at = rbase + cur + done + 2 * j;
-                        *(ulonglong2*)(a.out_code + at) = *(const ulonglong2*)(rv + li);
-                        *(uint2*)(a.out_row + at) = *(const uint2*)(rc + li);
-                    }
-                } else full = true;
-                done += n_here;
+        ring_flush<SS_FB, 4, SS_BLOCK, true>(rs, ph, drain, true, np, SS_CAP, ocap, [&](int p, uint32_t src, int64_t dst, uint32_t n_here, int j, bool room) {
+            if (!room) { if (j == 0) __hip_atomic_store(&a.flags[0], 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+            else if ((uint32_t)(2 * j) < n_here) {
+                const int li = p * SS_CAP + (int)src + 2 * j;
+                const int64_t at = (out_base + (int64_t)p * out_stride) * a.out_cap + dst + 2 * j;
+                *(ulonglong2*)(a.out_code + at) = *(const ulonglong2*)(rv + li);
+                *(uint2*)(a.out_row + at) = *(const uint2*)(rc + li);
             }
-            if (full && j == 0) __hip_atomic_store(&a.flags[0], 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (j == 0) {
-                uint32_t nh = h + nb * SS_FB;
-                while (nh >= (uint32_t)SS_CAP) nh -= SS_CAP;
-                head[p] = (uint16_t)(drain ? 0 : nh);
-                fill[p] = f - done;
-                cursor[p] = cur + done < ocap ? cur + done : ocap;
-            }
-        }
+        });
     };
-    // (the pending entries are a BIT MASK, as in dring_scatter_kernel: with two bools the compiler specialised the loop for lanes
-    //  that have nothing to insert -- a second copy of the barriers, executed by the same wave when only some of its lanes hold
-    //  rows: the partial last sub-tile lost entries)
     int hp = 0;
     auto rounds = [&](const uint64_t (&c)[NE], const uint32_t (&r)[NE], uint32_t okmask) {
-        uint32_t pend = 0;
-#pragma unroll
-        for (int e = 0; e < NE; e++) if (((okmask >> e) & 1u) && !insert(c[e], r[e])) pend |= 1u << e;
-        for (;;) {
-            if (pend) s_retry[ph] = 1;
-            __syncthreads();
-            flush(false);
-            if (tid == 0) { s_retry[ph ^ 1] = 0; s_nready[ph ^ 1] = 0; }
-            __syncthreads();
-            const bool again = s_retry[ph] != 0;
-            ph ^= 1;
-            if (!again) break;
-#pragma unroll
-            for (int e = 0; e < NE; e++) if (((pend >> e) & 1u) && insert(c[e], r[e])) pend &= ~(1u << e);
-        }
+        ring_rounds<NE>(rs, ph, okmask, [&](int e) -> bool {
+            const int p = min(ss_bucket_lut(sp, lut, lut_base, lut_shift, c[e]), np - 1);   // (the all-ones code meets the unreachable bounds)
+            const uint32_t slot = ring_reserve<SS_FB>(rs, ph, (uint32_t)p, SS_CAP, true);
+            if (slot != RING_FULL) { rv[p * SS_CAP + slot] = c[e]; rc[p * SS_CAP + slot] = r[e]; }
+            return slot != RING_FULL;
+        }, [&]() { flush(false); }, [](int, uint32_t) { return false; });
     };
 
     if (FROM_KEYS) {
@@ -221,11 +170,9 @@ __global__ __launch_bounds__(SS_BLOCK) void ssort_scatter_kernel(SsArgs a) {
                 }
             }
             load_sub(st + gridDim.x);
-            if (a.nheavy || a.has_null) {   // rows of a heavy code (and NULL rows: class nheavy) go to the side list: ONE reservation per
-                              // workgroup and sub-tile (one per wave and entry was ~1e6 atomics on one address per 1e9 rows with 0.2 % heavy rows: 14 ms)
-                uint64_t mm[NE]; int hidx[NE]; uint32_t wtot = 0;
-#pragma unroll
-                for (int e = 0; e < NE; e++) {
+            if (a.nheavy || a.has_null) {   // rows of a heavy code (and NULL rows: class nheavy) go to the side list
+                int hidx[NE];
+                okmask &= ~ring_side_list<NE>(s_hcnt, s_hbase, hp, &a.flags[2], [&](int e) -> bool {
                     int lo = 0, hi = a.nheavy - 1, hit = -1;
                     if ((okmask >> e) & 1u) {
                         const int64_t vr = a.key.offset + (int64_t)rr[e];
@@ -234,52 +181,18 @@ __global__ __launch_bounds__(SS_BLOCK) void ssort_scatter_kernel(SsArgs a) {
                         while (lo <= hi) { const int mid = (lo + hi) >> 1; const uint64_t x = hv[mid]; if (x == c[e]) { hit = mid; break; } if (x < c[e]) lo = mid + 1; else hi = mid - 1; }
                     }
                     hidx[e] = hit;
-                    mm[e] = __ballot(hit >= 0);
-                    wtot += (uint32_t)__popcll(mm[e]);
-                }
-                const int lane = tid & 63;
-                uint32_t woff = 0;
-                if (lane == 0 && wtot) woff = atomicAdd(&s_hcnt[hp], wtot);
-                woff = __shfl(woff, 0);
-                __syncthreads();
-                if (tid == 0) {
-                    const uint32_t t = s_hcnt[hp];
-                    s_hbase = t ? atomicAdd(&a.flags[2], (unsigned long long)t) : 0ULL;
-                    s_hcnt[hp ^ 1] = 0;
-                }
-                __syncthreads();
-                hp ^= 1;
-                if (wtot) {
-                    const uint64_t lt = lane == 0 ? 0ULL : (~0ULL >> (64 - lane));
-                    unsigned long long at = s_hbase + woff;
-#pragma unroll
-                    for (int e = 0; e < NE; e++) {
-                        if (hidx[e] >= 0) {
-                            const unsigned long long pos = at + __popcll(mm[e] & lt);
-                            if ((int64_t)pos < a.side_cap) a.side[pos] = ((unsigned long long)hidx[e] << 32) | rr[e];
-                            else __hip_atomic_store(&a.flags[0], 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            okmask &= ~(1u << e);
-                        }
-                        at += __popcll(mm[e]);
-                    }
-                }
+                    return hit >= 0;
+                }, [&](int e, unsigned long long pos) {
+                    if ((int64_t)pos < a.side_cap) a.side[pos] = ((unsigned long long)hidx[e] << 32) | rr[e];
+                    else __hip_atomic_store(&a.flags[0], 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                });
             }
             rounds(c, rr, okmask);
         }
         if (special) atomicOr(&a.flags[1], (unsigned long long)special);
     } else {
-        const int per_max = (a.in_regions + a.in_split - 1) / a.in_split;
-        const int g = blockIdx.x % a.in_split;
-        const int first = g * per_max;
-        const int per = first + per_max <= a.in_regions ? per_max : (a.in_regions > first ? a.in_regions - first : 0);
-        const int64_t region0 = (int64_t)pin * a.in_regions + first;
-        if (tid == 0) {
-            uint32_t run = 0;
-            for (int rj = 0; rj < per; rj++) { rstart[rj] = run; run += (a.in_counts[region0 + rj] + 1) / 2; }
-            rstart[per] = run;
-        }
-        __syncthreads();
-        const uint32_t total_in = rstart[per];   // pairs of entries
+        const RingRegions rg2 = ring_regions<2>(rstart, a.in_counts, a.in_regions, a.in_split, a.in_regions, 1);   // pairs of entries
+        const uint32_t total_in = rg2.total;
         ulonglong2 ec[SP];
         uint2 er[SP];
         uint32_t okm = 0;
@@ -290,11 +203,8 @@ __global__ __launch_bounds__(SS_BLOCK) void ssort_scatter_kernel(SsArgs a) {
             for (int u = 0; u < SP; u++) {
                 const uint32_t v = t0 + (uint32_t)u * SS_BLOCK + tid;
                 if (v < total_in) {
-                    int lo = reg;
-                    while (rstart[lo + 1] <= v) lo++;
-                    reg = lo;
-                    const uint32_t e0 = 2u * (v - rstart[lo]);
-                    const int64_t rg = region0 + lo;
+                    uint32_t e0;
+                    const int64_t rg = rg2.region0 + ring_region_of<2>(rstart, reg, v, &e0);
                     const int64_t at = rg * a.in_cap + e0;
                     ec[u] = *(const ulonglong2*)(a.in_code + at);
                     er[u] = *(const uint2*)(a.in_row + at);
