@@ -520,6 +520,35 @@ int vnm_strdict_like(vnm_strdict* h, const uint8_t* pattern, int64_t pattern_len
 int vnm_strdict_translate(vnm_strdict* src, vnm_strdict* dst, int64_t id_begin, int32_t* out_dst_code_of_src_id, void* stream);
 int vnm_strdict_ranks_joint(vnm_strdict* a, vnm_strdict* b, int32_t* out_rank_of_id_a, int32_t* out_rank_of_id_b, void* stream);
 
+/* ---- IN / NOT IN against a list of any length: the list as a device-resident set ---------------------------
+ * replaces np.isin(x, values[, invert]) (vinum/core/expressions.py:39-40; the parser hands it ONE Literal holding the whole list,
+ * vinum/parser/parser.py:151-160) for lists the projection interpreter's OR chain of `==` cannot hold.
+ * vnm_in_set_create: the list as NumPy's array holds it -- n int64 values, or n float64 values as soon as one member is a float
+ * (list_is_float = 1).  Needs no device; n == 0 fails with "ValueError: IN with an empty list".
+ * vnm_in_set_probe: out_mask[i] = 1 / 0 for row i of `col` (invert: NOT IN), one byte per row, one kernel on `stream`, launched
+ * asynchronously.  out_mask is a DEVICE buffer of `length` bytes, 4-byte aligned.  Column and list are compared in the domain the
+ * chain of `==` compares them in, so both give the same mask:
+ *   VNM_IN_DOM_I64  an integer column other than uint64 without validity, int64 list: exact; the column value is widened
+ *   VNM_IN_DOM_U64  a uint64 column without validity, int64 list: exact; negative members and values >= 2^63 match nothing
+ *   VNM_IN_DOM_F64  a float column, a float64 list, or a column with a validity bitmap (it reaches NumPy as float64 with NaN,
+ *                   vinum/arrow/record_batch.py:112-118): members and values as float64, compared with == (-0.0 == 0.0, NaN and
+ *                   NULL rows are in no list).
+ * A domain's canonical table (sorted, distinct; NaN members dropped, -0.0 folded) is built and uploaded by the first probe that
+ * needs it and kept by the handle.  Routes (vnm_route_last names the one taken): a bitmap where the members' range is at most
+ * 64 bits per member (integer domains), else a branch-free binary search of the sorted table; either from LDS up to 32 KB, else
+ * from global memory.
+ * vnm_in_set_plan_host: what a probe of a column of `col_type` would use -- domain, route, the canonical table (out_table: room
+ * for n 64-bit patterns of the domain's type, *out_members of them written) and the members' range hi - lo + 1 (integer domains;
+ * 0 otherwise).  Host only, no device touched. */
+typedef struct vnm_in_set vnm_in_set;
+enum vnm_in_domain { VNM_IN_DOM_I64 = 0, VNM_IN_DOM_U64 = 1, VNM_IN_DOM_F64 = 2 };
+enum vnm_in_route { VNM_IN_ROUTE_BITMAP_LDS = 0, VNM_IN_ROUTE_BITMAP_GLOBAL = 1, VNM_IN_ROUTE_SORTED_LDS = 2, VNM_IN_ROUTE_SORTED_GLOBAL = 3 };
+int vnm_in_set_create(int list_is_float, const void* values_host, int64_t n, vnm_in_set** out);
+void vnm_in_set_destroy(vnm_in_set* h);
+int vnm_in_set_probe(vnm_in_set* h, const vnm_dcol* col, int64_t length, int invert, uint8_t* out_mask, void* stream);
+int vnm_in_set_plan_host(int list_is_float, const void* values_host, int64_t n, int col_type, int col_has_validity, int* out_domain,
+                         int* out_route, int64_t* out_members, uint64_t* out_table, uint64_t* out_range);
+
 /* ---- CSV ingest ---------------------------------------------------------------------------------------
  * replaces, for numeric columns, the pyarrow.csv reader behind stream_csv() / read_csv() (vinum/io/arrow.py:58-61,106;
  * FileReaderOperator vinum/core/algebra.py:268-279): one block of CSV text (must end with '\n'; < 2 GiB) is staged once

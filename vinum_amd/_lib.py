@@ -41,6 +41,8 @@ EQ, NE, GT, GE, LT, LE = range(6)
  EX_TO_BOOL, EX_LOOKUP_U8, EX_LOOKUP_I32) = range(39)
 LIKE_STRIP_NUL = 1                                       # vnm_strdict_like flags
 LIKE_TOK_LIT, LIKE_TOK_ANY, LIKE_TOK_STAR = 0, 1, 2     # vnm_like_compile token kinds
+IN_DOM_I64, IN_DOM_U64, IN_DOM_F64 = range(3)           # vnm_in_set compare domains
+IN_ROUTES = ("in_set:bitmap_lds", "in_set:bitmap_global", "in_set:sorted_lds", "in_set:sorted_global")   # enum vnm_in_route
 MASK_U8 = 100
 OUT_F16 = 101
 OUT_U64, OUT_I64, OUT_F64, OUT_F32, OUT_DEC128, OUT_I32 = range(6)
@@ -129,6 +131,10 @@ PROTOTYPES = {
     "vnm_strdict_ranks_joint": (c_int, [c_void, c_void, c_void, c_void, c_void]),
     "vnm_like_compile": (c_int, [c_void, c_i64, c_void, c_void]),
     "vnm_strdict_like": (c_int, [c_void, c_void, c_i64, c_int, c_i64, c_void, c_void]),
+    "vnm_in_set_create": (c_int, [c_int, c_void, c_i64, c_void]),
+    "vnm_in_set_destroy": (None, [c_void]),
+    "vnm_in_set_probe": (c_int, [c_void, c_void, c_i64, c_int, c_void, c_void]),
+    "vnm_in_set_plan_host": (c_int, [c_int, c_void, c_i64, c_int, c_int, c_void, c_void, c_void, c_void, c_void]),
     "vnm_take_varwidth": (c_int, [c_void, c_void, c_void, c_void, c_i64, c_void, c_void, c_void, c_void, c_void]),
     "vnm_take_bits": (c_int, [c_void, c_i64, c_void, c_i64, c_void, c_void]),
     "vnm_take_fixed16": (c_int, [c_void, c_void, c_i64, c_void, c_void]),

@@ -7,7 +7,7 @@ import pyarrow as pa
 from .. import _lib as L
 from .. import ops
 from .base import DeviceRecordBatch, Operator
-from .algebra import FilterOperator, lower_column_compares, lower_like
+from .algebra import FilterOperator
 
 _FUNCS = {"COUNT": L.COUNT, "COUNT_STAR": L.COUNT_STAR, "MIN": L.MIN, "MAX": L.MAX, "SUM": L.SUM, "AVG": L.AVG}
 
@@ -15,9 +15,12 @@ _FUNCS = {"COUNT": L.COUNT, "COUNT_STAR": L.COUNT_STAR, "MIN": L.MIN, "MAX": L.M
 def _has_cast(e) -> bool:
     """to_int / to_bool turn float64 columns into a non-float64 value, LIKE and a dictionary lookup into a mask / an int32 value:
     such an input is projected, not handed to the kernel (a comparison of two dictionary-coded columns never gets there either:
-    their codes are not float64 columns)"""
-    return isinstance(e, tuple) and (e[0] in ("to_int", "to_bool", "like", "not_like", "lookup", "lookup_i32")
-                                     or any(_has_cast(x) for x in e[1:]))
+    their codes are not float64 columns).  So is an input holding an IN / NOT IN list that is probed as a set (ops.lower_in_sets):
+    neither the kernel evaluator nor the library's internal projection pass can hold it"""
+    def cast(x):
+        return isinstance(x, tuple) and (x[0] in ("to_int", "to_bool", "like", "not_like", "lookup", "lookup_i32")
+                                         or any(cast(y) for y in x[1:]))
+    return cast(e) or ops.has_in_set(e)
 
 
 class AggregateFunction:
@@ -101,8 +104,9 @@ class AggregateOperator(Operator):
     def _with_projected(self, batch: DeviceRecordBatch) -> DeviceRecordBatch:
         exprs, used, extra = [], {}, {}
         for e in self._projected:
-            e, _ = lower_like(e, batch.columns, extra)    # sum(to_int(name LIKE 'J%')): a dictionary lookup
-            e, _ = lower_column_compares(e, batch.columns, extra)   # sum(to_int(city_from = city_to)): translated codes
+            # sum(to_int(name LIKE 'J%')): a dictionary lookup; sum(to_int(city_from = city_to)): translated codes; sum(to_int(city IN
+            # ('a', ...))): the list's codes
+            e, _ = FilterOperator.lower_dictionary_predicates(e, batch, extra)
             exprs.append(e)
             for c in ops.columns_of(e):
                 used[c] = extra[c] if c in extra else batch.columns[c]

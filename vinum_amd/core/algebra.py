@@ -182,7 +182,7 @@ class FilterOperator(Operator):
     _SYM = {"==": "eq", "!=": "ne", ">": "gt", ">=": "ge", "<": "lt", "<=": "le"}
 
     @classmethod
-    def lower_dictionary_predicates(cls, pred, batch: DeviceRecordBatch):
+    def lower_dictionary_predicates(cls, pred, batch: DeviceRecordBatch, extra=None):
         """Comparisons of a dictionary-coded column (strings, binaries: int32 codes in HBM) with a LITERAL -- `city = 'Berlin'`,
         `name < 'M'`, `city IN ('a', 'b')`; literals are ("lit", value) nodes, a bare str is a column name -- become numeric
         comparisons: = / != / IN on the literal's CODE (a value the dictionary does not hold matches no row), < <= > >= on the
@@ -190,8 +190,10 @@ class FilterOperator(Operator):
         the literal's position among the dictionary's values.  NULL rows behave as in every other predicate (compare False,
         `!=` True: vinum/arrow/record_batch.py:112-118).  LIKE / NOT LIKE become lookups in the dictionary's match table
         (lower_like); comparisons with ANOTHER dictionary-coded column lookups of translated codes / joint ranks
-        (lower_column_compares, which also raises for a numeric operand).  Returns (predicate, extra columns the predicate reads)."""
-        pred, extra = lower_like(pred, batch.columns)
+        (lower_column_compares, which also raises for a numeric operand).  An IN list's codes are an int64 list over an int32 column: a
+        long one is probed as a set like any numeric list (ops.lower_in_sets), per batch, because the dictionary grows.
+        Returns (predicate, extra columns the predicate reads); tables are added to `extra` when one is passed in."""
+        pred, extra = lower_like(pred, batch.columns, extra)
         pred, extra = lower_column_compares(pred, batch.columns, extra)
 
         def is_dict(x):
@@ -270,10 +272,9 @@ class ProjectOperator(Operator):
         exprs, used, extra = [], {}, {}
         for name, arg in zip(self._col_names, self._arguments):
             if not isinstance(arg, str):
-                # LIKE nodes and comparisons of two dictionary-coded columns become dictionary lookups (a predicate keeps the uint8
-                # mask result type)
-                arg, _ = lower_like(arg, batch.columns, extra)
-                arg, _ = lower_column_compares(arg, batch.columns, extra)
+                # LIKE nodes and comparisons of two dictionary-coded columns become dictionary lookups, a string literal or list its
+                # codes in the column's dictionary (a predicate keeps the uint8 mask result type)
+                arg, _ = FilterOperator.lower_dictionary_predicates(arg, batch, extra)
                 exprs.append((name, arg))
                 for c in _columns_of(arg):
                     used[c] = extra[c] if c in extra else batch.columns[c]

@@ -3,6 +3,7 @@
 These are the building blocks of the operator mirror in vinum_amd/core/ and of bench.py; they never
 touch the host except for scalar results (row counts) and final result materialisation.
 """
+import collections
 import ctypes
 import os
 
@@ -517,10 +518,7 @@ def _check_project(rc):
         raise
 
 
-def result_type(expr, types) -> pa.DataType:
-    """Type-check `expr` the way vnm_project does (NumPy 2 typing, NumPy's errors such as `power(<integer column>,
-    <negative integer literal>)` -> ValueError) without touching a device: a zero-length call.  types: column name ->
-    (pa.DataType, has_nulls).  Returns the Arrow type of the result (pa.uint8() for a predicate mask)."""
+def _result_type_code(expr, types) -> int:
     names = columns_of(expr)
     prog = compile_expr(expr, {n: i for i, n in enumerate(names)})
     dummy = ctypes.create_string_buffer(8)
@@ -531,7 +529,33 @@ def result_type(expr, types) -> pa.DataType:
         cols[i].validity = ctypes.addressof(dummy) if nulls else None
     ot = ctypes.c_int(0)
     _check_project(L.load().vnm_project(len(prog), prog, len(names), cols, 0, ctypes.addressof(dummy), ctypes.byref(ot), None))
-    return pa.uint8() if ot.value == L.MASK_U8 else _ARROW_OF[ot.value]
+    return ot.value
+
+
+def result_type(expr, types) -> pa.DataType:
+    """Type-check `expr` the way vnm_project does (NumPy 2 typing, NumPy's errors such as `power(<integer column>,
+    <negative integer literal>)` -> ValueError) without touching a device: a zero-length call.  types: column name ->
+    (pa.DataType, has_nulls).  Returns the Arrow type of the result (pa.uint8() for a predicate mask).  A list that
+    lower_in_sets would probe as a set is typed as the mask column it becomes, its operand on its own."""
+    chosen = {id(n) for n in _choose_in_sets(expr)}
+    if chosen:
+        types = dict(types)
+
+        def walk(e):
+            if not isinstance(e, tuple) or not e or e[0] in ("strong", "lit"):
+                return e
+            if id(e) in chosen:
+                if not isinstance(e[1], str):
+                    _check_in_operand(_result_type_code(e[1], types), e[0])
+                name = f"__in_{len(types)}"
+                types[name] = (pa.uint8(), False)
+                return ("ne" if e[0] == "in" else "eq", name, 0)
+            if e[0] in ("in", "not_in"):
+                return (e[0], walk(e[1]), e[2])
+            return (e[0],) + tuple(walk(x) for x in e[1:])
+        expr = walk(expr)
+    ot = _result_type_code(expr, types)
+    return pa.uint8() if ot == L.MASK_U8 else _ARROW_OF[ot]
 
 
 def _desugar(e):
@@ -623,21 +647,29 @@ def compile_expr(expr, col_index):
     return _program(out)
 
 
-def project(expr, columns: dict, length=None, stream=None) -> DeviceColumn:
-    """One fused kernel per output expression (replaces the per-node NumPy ufunc passes of
-    vinum/core/expressions.py:13-24).  columns: name -> DeviceColumn."""
+def _project_typed(expr, columns: dict, length=None, stream=None):
+    """project() plus the out_type code of vnm_project (L.MASK_U8 tells a predicate mask from a uint8 value)"""
+    if length is None:
+        length = next(iter(columns.values())).length if columns else 1
+    lowered, extra = lower_in_sets(expr, columns, length, stream)
+    if extra:
+        columns = {n: extra[n] if n in extra else columns[n] for n in columns_of(lowered)}
     names = list(columns)
     cols = [columns[n] for n in names]
-    if length is None:
-        length = cols[0].length if cols else 1
-    prog = compile_expr(expr, {n: i for i, n in enumerate(names)})
+    prog = compile_expr(lowered, {n: i for i, n in enumerate(names)})
     out = DeviceBuffer(max(length, 1) * 8)
     ot = ctypes.c_int(0)
     _check_project(L.lib().vnm_project(len(prog), prog, len(cols), dcol_array(cols), length, out.ptr, ctypes.byref(ot),
                                 _stream_ptr(stream)))
-    if ot.value == L.MASK_U8:
-        return DeviceColumn(out, None, 0, length, pa.uint8())   # byte mask (predicate program)
-    return DeviceColumn(out, None, 0, length, _ARROW_OF[ot.value])
+    at = pa.uint8() if ot.value == L.MASK_U8 else _ARROW_OF[ot.value]   # (a predicate program writes a byte mask)
+    return DeviceColumn(out, None, 0, length, at), ot.value
+
+
+def project(expr, columns: dict, length=None, stream=None) -> DeviceColumn:
+    """One fused kernel per output expression (replaces the per-node NumPy ufunc passes of
+    vinum/core/expressions.py:13-24).  columns: name -> DeviceColumn.  IN / NOT IN lists too long for the program are probed
+    as sets first (lower_in_sets)."""
+    return _project_typed(expr, columns, length, stream)[0]
 
 
 def project_many(exprs, columns: dict, length=None, stream=None):
@@ -649,6 +681,11 @@ def project_many(exprs, columns: dict, length=None, stream=None):
         return []
     if length is None:
         length = next(iter(columns.values())).length if columns else 1
+    # long IN / NOT IN lists become mask columns first: the programs are packed by what is left to interpret
+    extra = {}
+    exprs = [lower_in_sets(e, columns, length, stream, extra)[0] for e in exprs]
+    if extra:
+        columns = {**columns, **extra}
     # pack expressions into programs that respect the kernel limits (64 instructions, 16 columns, 16 outputs)
     chunks, cur, cur_cols, cur_ins = [], [], [], 0
     for k, e in enumerate(exprs):
@@ -681,6 +718,204 @@ def project_many(exprs, columns: dict, length=None, stream=None):
             at = pa.uint8() if t == L.MASK_U8 else _ARROW_OF[t]
             result[k] = DeviceColumn(b, None, 0, length, at)
     return result
+
+
+# ---- IN / NOT IN lists as device-resident sets (vnm_inset.hip) -----------------------------------
+PJ_MAX_INS = 64          # vnm_project.hip: instructions per program, the final STORE included
+_IN_SET_CACHE_SIZE = 32
+
+
+def in_set_min() -> int:
+    """VNM_IN_SET_MIN: a list of at least this many members is probed as a set.  4 by default: the
+    smallest measured length from which the set route beats the OR chain beyond the run-to-run spread (profiles/r09_in_set.txt;
+    at 17 the bare chain no longer compiles at all).  Read on every call: the tests flip it between cases."""
+    v = os.environ.get("VNM_IN_SET_MIN")
+    return max(int(v), 1) if v else 4
+
+
+def _in_list_array(values):
+    """the list as the array np.isin builds from it: int64, or float64 as soon as one member is a float"""
+    vals = list(values)
+    if not vals:
+        raise ValueError("IN with an empty list")
+    is_float = any(isinstance(v, float) for v in vals)
+    return is_float, np.array([float(v) if is_float else int(v) for v in vals], dtype=np.float64 if is_float else np.int64)
+
+
+class InSet:
+    """Owning handle on a vnm_in_set: the list, and on the device the canonical table of every compare domain a probe has needed."""
+
+    def __init__(self, values):
+        self.is_float, arr = _in_list_array(values)
+        h = ctypes.c_void_p(0)
+        _check_project(L.load().vnm_in_set_create(int(self.is_float), arr.ctypes.data, len(arr), ctypes.byref(h)))
+        self.ptr = h
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            L.load().vnm_in_set_destroy(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_in_sets = collections.OrderedDict()     # (list_is_float, members) -> InSet, least recently used first
+_in_sets_by_id = {}                      # id(the members tuple a handle was made from) -> InSet: no hashing of a long list per batch
+
+
+def in_set_cache_clear():
+    """Destroy every cached handle (their device tables go back to the pool)."""
+    for h in _in_sets.values():
+        h.close()
+    _in_sets.clear()
+    _in_sets_by_id.clear()
+
+
+def in_set(values) -> InSet:
+    """The handle of a list, from a small LRU: a stream of batches uploads its list once.  An evicted handle is destroyed (the
+    library frees its tables once the probes enqueued so far have run)."""
+    h = _in_sets_by_id.get(id(values))
+    if h is not None and h.members is values and h.ptr:
+        _in_sets.move_to_end(h.key)
+        return h
+    vals = tuple(values)
+    key = (any(isinstance(v, float) for v in vals), vals)
+    h = _in_sets.get(key)
+    if h is not None:
+        _in_sets.move_to_end(key)
+        return h
+    h = InSet(vals)
+    h.key, h.members = key, vals
+    _in_sets[key] = h
+    _in_sets_by_id[id(vals)] = h
+    while len(_in_sets) > _IN_SET_CACHE_SIZE:
+        old = _in_sets.popitem(last=False)[1]
+        _in_sets_by_id.pop(id(old.members), None)
+        old.close()
+    return h
+
+
+def in_set_probe(col: DeviceColumn, values, invert=False, length=None, stream=None) -> DeviceColumn:
+    """np.isin(col, values, invert=invert) as a uint8 column (vnm_in_set_probe): one byte per row, a NULL row is in no list."""
+    n = col.length if length is None else int(length)
+    out = DeviceBuffer(max(n, 1))
+    _check_project(L.lib().vnm_in_set_probe(in_set(values).ptr, ctypes.byref(col.dcol()), n, int(bool(invert)), out.ptr,
+                                            _stream_ptr(stream)))
+    return DeviceColumn(out, None, 0, n, pa.uint8())
+
+
+def in_set_plan(values, arrow_type, has_validity=False):
+    """What a probe of such a column would do, on the host (vnm_in_set_plan_host, no device): {'domain': L.IN_DOM_*, 'route':
+    one of L.IN_ROUTES, 'table': the canonical members (sorted, distinct) as a NumPy array of the domain's type, 'range': hi - lo
+    + 1 of the members (integer domains, else 0)}."""
+    is_float, arr = _in_list_array(values)
+    dom, route, m, rng = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_uint64(0)
+    table = np.zeros(len(arr), np.uint64)
+    _check_project(L.load().vnm_in_set_plan_host(int(is_float), arr.ctypes.data, len(arr), physical_type(arrow_type)[0],
+                                                 int(bool(has_validity)), ctypes.byref(dom), ctypes.byref(route), ctypes.byref(m),
+                                                 table.ctypes.data, ctypes.byref(rng)))
+    view = {L.IN_DOM_I64: np.int64, L.IN_DOM_U64: np.uint64, L.IN_DOM_F64: np.float64}[dom.value]
+    return {"domain": dom.value, "route": L.IN_ROUTES[route.value], "table": table[:m.value].view(view), "range": rng.value}
+
+
+class _AnyColumn(dict):
+    def __missing__(self, key):
+        return 0
+
+
+def _count_ins(expr) -> int:
+    tmp = []
+    _emit_expr(expr, _AnyColumn(), tmp)
+    return len(tmp)
+
+
+def _choose_in_sets(expr):
+    """The IN / NOT IN nodes of `expr` that are probed as sets: every list of in_set_min() or more members; after that, as
+    long as the program would still exceed the interpreter's limit, the longest remaining list, until it fits.  Every other
+    list keeps its OR / AND chain."""
+    nodes = []
+
+    def collect(e):
+        if isinstance(e, tuple) and e and e[0] not in ("strong", "lit"):
+            if e[0] in ("in", "not_in"):
+                nodes.append(e)
+                collect(e[1])
+            else:
+                for x in e[1:]:
+                    collect(x)
+    collect(expr)
+    if not nodes:
+        return []
+    least = in_set_min()
+    chosen = [n for n in nodes if len(n[2]) >= least]
+    rest = sorted((n for n in nodes if len(n[2]) < least), key=lambda n: len(n[2]))
+    while rest:
+        ids = {id(n) for n in chosen}
+
+        def stand_in(e):
+            if not isinstance(e, tuple) or not e or e[0] in ("strong", "lit"):
+                return e
+            if id(e) in ids:
+                return ("ne", "__in", 0)
+            if e[0] in ("in", "not_in"):
+                return (e[0], stand_in(e[1]), e[2])
+            return (e[0],) + tuple(stand_in(x) for x in e[1:])
+        try:
+            if _count_ins(stand_in(expr)) + 1 <= PJ_MAX_INS:
+                break
+        except (NotImplementedError, TypeError, ValueError, KeyError):
+            break              # not a program at all: whoever compiles it raises
+        chosen.append(rest.pop())
+    return chosen
+
+
+def has_in_set(expr) -> bool:
+    """Does `expr` hold a list that lower_in_sets would probe as a set (so only project / project_many can evaluate it)?"""
+    return bool(_choose_in_sets(expr))
+
+
+def _check_in_operand(out_type, op):
+    what = op.upper().replace("_", " ")
+    if out_type == L.MASK_U8:
+        raise TypeError(f"{what} over a predicate: the operand of a set probe must be a numeric value (cast it with to_int())")
+    if out_type == L.OUT_F16:
+        raise TypeError(f"{what} over a float16 value: a set probe takes no float16 operand (cast it with to_float())")
+
+
+def lower_in_sets(expr, columns: dict, length=None, stream=None, extra=None):
+    """Rewrite the ("in" | "not_in", operand, values) nodes that _choose_in_sets picks into ("ne" | "eq", "__in_<k>", 0) over a
+    fresh uint8 column holding the probe's mask (np.isin, vinum/core/expressions.py:39-40, for lists the interpreter's program
+    cannot hold).  A plain column is probed as it is; any other operand -- `(a + b) IN (...)` -- is projected into a temporary
+    first and probed with that result's type.  Returns (expression, extra): the mask columns by name, added to `extra` when
+    one is passed in."""
+    extra = {} if extra is None else extra
+    chosen = {id(n) for n in _choose_in_sets(expr)}
+    if not chosen:
+        return expr, extra
+    if length is None:
+        length = next(iter(columns.values())).length if columns else 1
+
+    def walk(e):
+        if not isinstance(e, tuple) or not e or e[0] in ("strong", "lit"):
+            return e
+        if id(e) in chosen:
+            if isinstance(e[1], str):
+                col = columns[e[1]]
+                _check_in_operand(col.vnm_type, e[0])
+            else:
+                col, ot = _project_typed(e[1], {n: columns[n] for n in columns_of(e[1])}, length, stream)
+                _check_in_operand(ot, e[0])
+            name = f"__in_{len(extra)}"
+            extra[name] = in_set_probe(col, e[2], length=length, stream=stream)
+            return ("ne" if e[0] == "in" else "eq", name, 0)
+        if e[0] in ("in", "not_in"):
+            return (e[0], walk(e[1]), e[2])
+        return (e[0],) + tuple(walk(x) for x in e[1:])
+    return walk(expr), extra
 
 
 _LIKE_META = frozenset(b"\\^$*+?{}[]|()")
