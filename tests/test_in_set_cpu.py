@@ -5,6 +5,7 @@ import pyarrow as pa
 import pytest
 
 from vinum_amd import _lib as L
+from vinum_amd import expr as E
 from vinum_amd import ops
 
 I64_MIN, I64_MAX = -2**63, 2**63 - 1
@@ -188,7 +189,7 @@ def test_two_ten_member_lists_rewrite_the_longer_first(fake_probe):
     a, b = tuple(range(10)), tuple(range(11))
     expr = ("and", ("in", "x", a), ("in", "y", b))
     with pytest.raises(L.VinumHipError, match="1..63 instructions"):       # what the parent commit does with it
-        ops.result_type(("and",) + tuple(ops._desugar(e) for e in expr[1:]), {"x": (pa.int64(), False), "y": (pa.int64(), False)})
+        ops.result_type(("and",) + tuple(E.desugar(e) for e in expr[1:]), {"x": (pa.int64(), False), "y": (pa.int64(), False)})
     x, y = _FakeColumn(), _FakeColumn()
     got, extra = ops.lower_in_sets(expr, {"x": x, "y": y}, 10)
     assert got == ("and", ("in", "x", a), ("ne", "__in_0", 0)) and fake_probe == [(y, b, 10)]

@@ -9,6 +9,7 @@ import pyarrow as pa
 import pytest
 
 from vinum_amd import binding as B
+from vinum_amd import expr as E
 from vinum_amd import ops
 from vinum_amd import planner as P
 
@@ -73,16 +74,16 @@ def test_unknown_functions_keep_todays_error():
 
 
 def test_literal_folding_keeps_numpy_value_and_type():
-    assert ops._fold(("sqrt", 4)) == ("strong", 2.0)                 # np.sqrt(4) -> np.float64: strong
-    assert ops._fold(("abs", -5)) == ("strong", 5)                   # np.absolute(-5) -> np.int64: strong
-    assert ops._fold(("pi",)) == np.pi and type(ops._fold(("pi",))) is float    # lambda: np.pi -> weak Python float
-    assert ops._fold(("e",)) == np.e and type(ops._fold(("e",))) is float
-    assert ops._fold(("sin", 1.0)) == ("strong", float(np.sin(1.0)))
-    assert ops._fold(("power", 2, 10)) == ("strong", 1024)
-    assert ops._fold(("to_int", ("log10", 1000.0))) == ("strong", 3)
-    assert ops._fold(("add", "x", ("sqrt", 2))) == ("add", "x", ("strong", float(np.sqrt(2))))
+    assert E.fold(("sqrt", 4)) == ("strong", 2.0)                 # np.sqrt(4) -> np.float64: strong
+    assert E.fold(("abs", -5)) == ("strong", 5)                   # np.absolute(-5) -> np.int64: strong
+    assert E.fold(("pi",)) == np.pi and type(E.fold(("pi",))) is float    # lambda: np.pi -> weak Python float
+    assert E.fold(("e",)) == np.e and type(E.fold(("e",))) is float
+    assert E.fold(("sin", 1.0)) == ("strong", float(np.sin(1.0)))
+    assert E.fold(("power", 2, 10)) == ("strong", 1024)
+    assert E.fold(("to_int", ("log10", 1000.0))) == ("strong", 3)
+    assert E.fold(("add", "x", ("sqrt", 2))) == ("add", "x", ("strong", float(np.sqrt(2))))
     with pytest.raises(ValueError, match="Integers to negative integer powers are not allowed"):
-        ops._fold(("power", 2, -1))
+        E.fold(("power", 2, -1))
 
 
 def test_negative_literal_exponent_on_an_integer_column_raises_at_compile_time():

@@ -5,9 +5,11 @@ from typing import Optional, Sequence, Tuple
 import pyarrow as pa
 
 from .. import _lib as L
+from .. import expr as E
 from .. import ops
 from .base import DeviceRecordBatch, Operator
 from .algebra import FilterOperator
+from .lowering import project_lowered
 
 _FUNCS = {"COUNT": L.COUNT, "COUNT_STAR": L.COUNT_STAR, "MIN": L.MIN, "MAX": L.MAX, "SUM": L.SUM, "AVG": L.AVG}
 
@@ -17,10 +19,8 @@ def _has_cast(e) -> bool:
     such an input is projected, not handed to the kernel (a comparison of two dictionary-coded columns never gets there either:
     their codes are not float64 columns).  So is an input holding an IN / NOT IN list that is probed as a set (ops.lower_in_sets):
     neither the kernel evaluator nor the library's internal projection pass can hold it"""
-    def cast(x):
-        return isinstance(x, tuple) and (x[0] in ("to_int", "to_bool", "like", "not_like", "lookup", "lookup_i32")
-                                         or any(cast(y) for y in x[1:]))
-    return cast(e) or ops.has_in_set(e)
+    return any(isinstance(n, tuple) and n and n[0] in ("to_int", "to_bool", "like", "not_like", "lookup", "lookup_i32")
+               for n in E.nodes(e)) or ops.has_in_set(e)
 
 
 class AggregateFunction:
@@ -102,15 +102,9 @@ class AggregateOperator(Operator):
             self._agg.set_input_expr(first, self._kernel_expr, self._kernel_expr_cols)
 
     def _with_projected(self, batch: DeviceRecordBatch) -> DeviceRecordBatch:
-        exprs, used, extra = [], {}, {}
-        for e in self._projected:
-            # sum(to_int(name LIKE 'J%')): a dictionary lookup; sum(to_int(city_from = city_to)): translated codes; sum(to_int(city IN
-            # ('a', ...))): the list's codes
-            e, _ = FilterOperator.lower_dictionary_predicates(e, batch, extra)
-            exprs.append(e)
-            for c in ops.columns_of(e):
-                used[c] = extra[c] if c in extra else batch.columns[c]
-        outs = ops.project_many(exprs, used, length=batch.num_rows)
+        # sum(to_int(name LIKE 'J%')): a dictionary lookup; sum(to_int(city_from = city_to)): translated codes; sum(to_int(city IN
+        # ('a', ...))): the list's codes
+        outs = project_lowered(list(self._projected), batch.columns, batch.num_rows)
         cols = dict(batch.columns)
         for e, o in zip(self._projected, outs):
             cols[self._projected[e]] = o

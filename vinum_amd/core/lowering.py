@@ -1,0 +1,166 @@
+"""What a dictionary-coded column (strings, binaries: int32 codes of the column's own running dictionary in HBM) needs before an
+expression over it is a numeric program: three rewrites of vinum_amd.expr trees (lower_dictionary runs them in order) and the one
+path on which the operators evaluate lowered expressions (project_lowered, used_columns).  `columns` is a batch's name ->
+DeviceColumn; every rewrite returns (expression, extra), `extra` holding the tables, rank and mask columns the result reads by name."""
+from .. import expr as E
+from .. import ops
+
+
+def _is_dict(x, columns) -> bool:
+    return isinstance(x, str) and x in columns and columns[x].dictionary is not None
+
+
+def lower_like(expr, columns, extra=None):
+    """LIKE / NOT LIKE (LikeFunction, vinum/core/functions.py:301-344) -> a lookup in a per-pattern table of the column's
+    dictionary: ("like", col, ("lit", p)) becomes ("lookup", col, table) and ("not_like", ...) ("not", ("lookup", ...)), where
+    `table` names a uint8 column added to `extra` (KeyDictionary.like_table: one byte per dictionary id, matched on the device
+    once per distinct value).  A NULL row looks up 0: LIKE is false, NOT LIKE true -- the project's rule for `=` / `!=`.
+    Only a utf8 / large_utf8 column and a string literal pattern lower; other column types raise TypeError as in the
+    reference, other shapes NotImplementedError."""
+    extra = {} if extra is None else extra
+
+    def f(e):
+        if e[0] not in ("like", "not_like"):
+            return None
+        if len(e) != 3:
+            raise NotImplementedError(f"no GPU lowering for a {e[0].upper()} node with {len(e) - 1} operand(s)")
+        col, pat = e[1], e[2]
+        if not (E.is_str_lit(pat) and isinstance(pat[1], str)):
+            raise NotImplementedError(f"no GPU lowering for {e[0].upper()} with the pattern {pat!r}: a string literal is required")
+        if not isinstance(col, str) or col not in columns:
+            raise NotImplementedError(f"no GPU lowering for {e[0].upper()} over {col!r}: the operand must be a column")
+        c = columns[col]
+        if c.dictionary is None:
+            raise TypeError(f"LIKE needs a string column, {col!r} is {c.arrow_type}")
+        name = f"__like_{len(extra)}_{col}"
+        extra[name] = c.dictionary.like_table(pat[1])
+        node = ("lookup", col, name)
+        return node if e[0] == "like" else ("not", node)
+    return E.rewrite(expr, f), extra
+
+
+# the arithmetic, bitwise, math and cast operators of ops.compile_expr: what takes a NUMBER, which a dictionary code is not
+_ARITHMETIC = ("add", "sub", "mul", "div", "mod", "neg", "+", "-", "*", "/", "%", "band", "bor", "bxor", "bnot", "abs", "sqrt", "sin",
+               "cos", "tan", "log", "log2", "log10", "power", "to_float", "to_int", "to_bool")
+
+
+def lower_column_compares(expr, columns, extra=None):
+    """Comparisons of a dictionary-coded column with ANOTHER such column -- `city_from = city_to`, `city_from < city_to`; the
+    reference compares the two value arrays, vinum/core/expressions.py:30-36.  The codes of two dictionaries mean nothing to each
+    other, so:
+      * both columns share one dictionary object: = / != stay as they are (equal codes <=> equal values), the ordered operators
+        compare the two columns' ranks (KeyDictionary.rank_column);
+      * otherwise = / != become (op, a, ("lookup_i32", b, table)) with b's codes translated into a's
+        (KeyDictionary.translate_table: -2 where a's dictionary does not hold the value), and < <= > >= become
+        (op, ("lookup_i32", a, ranks_a), ("lookup_i32", b, ranks_b)) with the ranks of both dictionaries in the byte order of
+        their union (KeyDictionary.joint_rank_tables).
+    BETWEEN / NOT BETWEEN with a dictionary-coded operand is rewritten onto >= <= / < > first (expr.desugar does it too late for
+    this lowering), so column bounds follow.  Bytes are compared exactly, as a literal's are (no trailing-NUL rule); utf8,
+    large_utf8, binary and large_binary mix freely.  A NULL on either side compares False, `!=` True.
+    What has no meaning raises instead of comparing codes: a dictionary-coded column against a numeric column, literal or
+    expression, IN / NOT IN over one with a list that is not all string / binary literals, and one as the operand of an
+    arithmetic, bitwise, math or cast operator (_ARITHMETIC: TypeError); a pair with a host-route dictionary -- bool, decimal,
+    date64 -- (NotImplementedError).  Any other operator over such a column (a string function, say) passes through untouched
+    and is accepted or refused where it is compiled."""
+    extra = {} if extra is None else extra
+
+    def rank_name(c):
+        name = f"__rank_{c}"
+        if name not in extra:
+            extra[name] = columns[c].dictionary.rank_column(columns[c])
+        return name
+
+    def f(e):
+        op = E.cmp_name(e[0])
+        if e[0] in ("between", "not_between") and len(e) == 4 and any(_is_dict(x, columns) for x in e[1:]):
+            x, lo, hi = e[1:]
+            return E.rewrite(("and", ("ge", x, lo), ("le", x, hi)) if e[0] == "between" else ("or", ("lt", x, lo), ("gt", x, hi)), f)
+        if op and len(e) == 3:
+            a, b = e[1], e[2]
+            if _is_dict(a, columns) and _is_dict(b, columns):
+                da, db = columns[a].dictionary, columns[b].dictionary
+                if da is db:
+                    return e if op in ("eq", "ne") else (op, rank_name(a), rank_name(b))
+                if not (getattr(da, "on_device", False) and getattr(db, "on_device", False)):
+                    raise NotImplementedError(f"no GPU lowering for comparing {a!r} ({da.type}) with {b!r} ({db.type}): only string "
+                                              "and binary columns keep their dictionaries on the device")
+                if op in ("eq", "ne"):
+                    name = f"__codes_of_{b}_in_{a}"
+                    if name not in extra:
+                        extra[name] = db.translate_table(da)
+                    return (op, a, ("lookup_i32", b, name))
+                na, nb = f"__joint_rank_{a}_with_{b}", f"__joint_rank_{b}_with_{a}"
+                if na not in extra:
+                    extra[na], extra[nb] = da.joint_rank_tables(db)
+                return (op, ("lookup_i32", a, na), ("lookup_i32", b, nb))
+            for x, y in ((a, b), (b, a)):
+                if _is_dict(x, columns) and not E.is_str_lit(y):
+                    raise TypeError(f"cannot compare the {columns[x].dictionary.type} column {x!r} with {y!r}: only a string / "
+                                    "binary literal or another such column")
+        elif e[0] in _ARITHMETIC:
+            for x in e[1:]:
+                if _is_dict(x, columns):
+                    raise TypeError(f"{e[0]}() over the {columns[x].dictionary.type} column {x!r}: not a numeric operand")
+        elif e[0] in E.IN_OPS and _is_dict(e[1], columns) and not all(isinstance(v, (str, bytes)) or E.is_str_lit(v) for v in e[2]):
+            raise TypeError(f"{e[0].upper().replace('_', ' ')} over the {columns[e[1]].dictionary.type} column {e[1]!r} needs string / "
+                            f"binary literals, got {list(e[2])!r}")
+        return None
+    return E.rewrite(expr, f), extra
+
+
+def lower_literal_compares(expr, columns, extra=None):
+    """Comparisons of a dictionary-coded column with a LITERAL -- `city = 'Berlin'`, `name < 'M'`, `city IN ('a', 'b')`, in either
+    spelling of the operator and either operand order -- become numeric comparisons: = / != / IN on the literal's CODE (a value the
+    dictionary does not hold matches no row), < <= > >= on the column's order-preserving RANKS (KeyDictionary.rank_column:
+    byte-wise order, as Arrow / NumPy compare such values) against the literal's position among the dictionary's values.  NULL rows
+    behave as in every other predicate (compare False, `!=` True: vinum/arrow/record_batch.py:112-118).  An IN list's codes are an
+    int64 list over an int32 column: a long one is probed as a set like any numeric list (ops.lower_in_sets), per batch, because the
+    dictionary grows."""
+    extra = {} if extra is None else extra
+
+    def f(e):
+        op = E.cmp_name(e[0])
+        if op and len(e) == 3:
+            a, b = e[1], e[2]
+            if E.is_str_lit(a) and _is_dict(b, columns):
+                a, b, op = b, a, E.CMP_FLIP[op]
+            if _is_dict(a, columns) and E.is_str_lit(b):
+                d = columns[a].dictionary
+                if op in ("eq", "ne"):
+                    c = d.code_of(b[1])
+                    return (op, a, -2 if c is None else c)            # (codes are >= 0)
+                name = f"__rank_{a}"
+                if name not in extra:
+                    extra[name] = d.rank_column(columns[a])
+                less, present = d.rank_bounds(b[1])
+                return {"lt": ("lt", name, less), "le": ("lt", name, less + present),
+                        "gt": ("ge", name, less + present), "ge": ("ge", name, less)}[op]
+        if e[0] in E.IN_OPS and _is_dict(e[1], columns) and all(isinstance(v, (str, bytes)) or E.is_str_lit(v) for v in e[2]):
+            d = columns[e[1]].dictionary
+            codes = [d.code_of(v[1] if E.is_str_lit(v) else v) for v in e[2]]
+            return (e[0], e[1], tuple(c for c in codes if c is not None) or (-2,))
+        return None
+    return E.rewrite(expr, f), extra
+
+
+def lower_dictionary(expr, columns, extra=None):
+    """The three lowerings in their order: LIKE, then the column pairs -- which refuse a numeric operand, so they run before the
+    literals turn into codes and ranks -- then the literals; the last two only act where a dictionary-coded column is read at all."""
+    expr, extra = lower_like(expr, columns, extra)
+    if any(_is_dict(c, columns) for c in E.columns_of(expr)):
+        expr, extra = lower_column_compares(expr, columns, extra)
+        expr, extra = lower_literal_compares(expr, columns, extra)
+    return expr, extra
+
+
+def used_columns(exprs, columns, extra):
+    """name -> column of everything the lowered `exprs` read, in first-use order: from `extra` where a lowering made it"""
+    return {c: extra[c] if c in extra else columns[c] for e in exprs for c in E.columns_of(e)}
+
+
+def project_lowered(exprs, columns, length, scalar_length=None):
+    """ops.project_many of `exprs` lowered into one shared `extra`; scalar_length: the length when none of them reads a column"""
+    extra = {}
+    exprs = [lower_dictionary(e, columns, extra)[0] for e in exprs]
+    used = used_columns(exprs, columns, extra)
+    return ops.project_many(exprs, used, length=length if used or scalar_length is None else scalar_length)

@@ -1,0 +1,163 @@
+"""The expression tree of the GPU operators: its grammar, its walkers and the passes that need nothing but the tree.
+
+An expression is a nested prefix tuple.  This docstring is the one written definition of the node forms, and _OPERANDS below the one
+table of where a form keeps its sub-expressions: operands(), with_operands() and the walkers read it, a pass reads the walkers:
+
+    "name"                          a column (a bare str is ALWAYS a column name)
+    1, 2.5                          a number: a weak Python literal, typed by the operand it meets (NumPy 2 rules); bool is none
+    ("strong", v)                   a number with an array's strong type (int64 / float64): what fold() and an IN list produce
+    ("lit", v)                      a string / bytes literal -- `city = 'Berlin'`, a LIKE pattern
+    (op, x[, y...])                 an operator of ops._EX or a comparison (CMP_SYMBOLS, by symbol or by name); n-ary chains fold
+                                    left like VectorizedExpression._apply_binary_args_function (vinum/core/base.py:145-151)
+    ("in" | "not_in", x, values)    values is a tuple of VALUES (numbers, str / bytes, "lit" nodes), not of operands
+    ("is_null" | "is_not_null", column)
+    ("between" | "not_between", x, low, high)
+    ("like" | "not_like", column, ("lit", pattern))
+    ("lookup" | "lookup_i32", code column, table column)     what core.lowering makes of LIKE / of two string columns compared
+    ("fn", name, arg...)            a function by name (planner: the aggregates); name is no operand
+
+"lit" and "strong" nodes are leaves.  Pass-through nodes keep the spelling they came with (`(">", "v", "w")` stays that):
+an operator is canonicalised with cmp_name() only where it is matched.  A new operator is added to ops._EX (and to
+core.lowering._ARITHMETIC when it takes numbers); a new node FORM is a line above and, unless its operands are e[1:], in _OPERANDS.
+No ctypes, no library, no device: this module imports without them.
+"""
+import numpy as np
+
+# comparison spellings -> canonical name; every other comparison table of the package is derived from this one or stands below
+CMP_SYMBOLS = {"==": "eq", "=": "eq", "!=": "ne", "<>": "ne", ">": "gt", ">=": "ge", "<": "lt", "<=": "le"}
+CMP_SYMBOL = {n: s for s, n in reversed(CMP_SYMBOLS.items())}              # name -> its first symbol: "eq" -> "=="
+CMP_FLIP = {"eq": "eq", "ne": "ne", "lt": "gt", "le": "ge", "gt": "lt", "ge": "le"}          # a < b  <=>  b > a
+IN_OPS = ("in", "not_in")
+# where the operands stand, by a node's first slot (the walkers slice with it themselves: operands() is a call more per node)
+_REST, _NONE = slice(1, None), slice(0, 0)
+_OPERANDS = {"lit": _NONE, "strong": _NONE, "in": slice(1, 2), "not_in": slice(1, 2), "fn": slice(2, None)}
+
+
+def cmp_name(op):
+    """The canonical name ("eq" ... "ge") of a comparison operator in either spelling, None for any other operator."""
+    return CMP_SYMBOLS.get(op, op if op in CMP_FLIP else None)
+
+
+def is_number(e) -> bool:
+    return (isinstance(e, (int, float)) and not isinstance(e, bool)) or (isinstance(e, tuple) and len(e) == 2 and e[0] == "strong")
+
+
+def is_str_lit(e) -> bool:
+    return isinstance(e, tuple) and len(e) == 2 and e[0] == "lit" and isinstance(e[1], (str, bytes))
+
+
+def operands(e) -> tuple:
+    """The sub-expressions of a node (none for a column, a number and the "lit" / "strong" leaves)."""
+    return e[_OPERANDS.get(e[0], _REST)] if isinstance(e, tuple) and e else ()
+
+
+def with_operands(e, new):
+    """`e` over as many operands `new`; `e` ITSELF when every one `is` the old one (passes identify nodes by id())."""
+    where = _OPERANDS.get(e[0], _REST) if isinstance(e, tuple) and e else _NONE
+    if len(new) != len(e[where]):
+        raise ValueError(f"{e!r} has {len(e[where])} operand(s), not {len(new)}")
+    return e if all(a is b for a, b in zip(e[where], new)) else e[:where.start] + tuple(new) + (e[where.stop:] if where.stop else ())
+
+
+def transform(e, f):
+    """Rebuild `e` bottom-up: f(node) may replace a node (tuples only, the leaves included; operands first)."""
+    if not isinstance(e, tuple):
+        return e
+    where, new = _OPERANDS.get(e[0], _REST), None
+    for i, x in enumerate(e[where]):
+        if isinstance(x, tuple) and (y := transform(x, f)) is not x:
+            new = list(e[where]) if new is None else new        # no list while nothing changes: the usual case
+            new[i] = y
+    return f(e if new is None else with_operands(e, new))
+
+
+def rewrite(e, f):
+    """Rebuild `e` top-down: what f(node) returns is finished, on None the walk goes on into the operands; f sees operator nodes only."""
+    where = _OPERANDS.get(e[0], _REST) if isinstance(e, tuple) and e else _NONE
+    r, new = (f(e) if where is not _NONE else e), None
+    if r is not None:
+        return r
+    for i, x in enumerate(e[where]):
+        if isinstance(x, tuple) and (y := rewrite(x, f)) is not x:
+            new = list(e[where]) if new is None else new
+            new[i] = y
+    return e if new is None else with_operands(e, new)
+
+
+def nodes(e) -> list:
+    """Every sub-expression of `e`, itself first (pre-order): columns, numbers and leaves included."""
+    out = [e]
+    for x in (e[_OPERANDS.get(e[0], _REST)] if isinstance(e, tuple) and e else ()):
+        if isinstance(x, tuple):
+            out += nodes(x)
+        else:
+            out.append(x)
+    return out
+
+
+def columns_of(expr):
+    """Column names referenced by a (possibly sugared) expression, in first-use order."""
+    return list(dict.fromkeys([n for n in nodes(expr) if isinstance(n, str)]))
+
+
+def desugar(e):
+    """BETWEEN / IN rewrite onto the primitive predicates, exactly what the reference's callables compute:
+    between -> logical_and(x >= low, x <= high), not_between -> logical_or(x < low, x > high)
+    (vinum/core/expressions.py:43-48); in / not_in -> np.isin(x, values[, invert]) (:39-40)."""
+    def f(n):
+        if n[0] == "between":
+            return ("and", ("ge", n[1], n[2]), ("le", n[1], n[3]))
+        if n[0] == "not_between":
+            return ("or", ("lt", n[1], n[2]), ("gt", n[1], n[3]))
+        if n[0] not in IN_OPS:
+            return n
+        vals = list(n[2])
+        if not vals:
+            raise ValueError("IN with an empty list")
+        # np.isin turns the list into an ARRAY (int64 / float64: strong types), unlike a bare literal operand
+        if any(isinstance(v, float) for v in vals):
+            vals = [float(v) for v in vals]
+        chain, cmp = ("or", "eq") if n[0] == "in" else ("and", "ne")
+        terms = tuple((cmp, n[1], ("strong", v)) for v in vals)
+        return (chain,) + terms if len(terms) > 1 else terms[0]
+    return transform(e, f)
+
+
+# The numeric built-ins of the reference's _default_functions_registry (vinum/core/functions.py:353-387) with the callables
+# it registers: what a subtree of literals folds to on the host, so folded constants keep NumPy's value AND scalar type
+# (np.sqrt(4) is a strong np.float64, pi() the weak Python float np.pi)
+SCALAR_FUNCS = {
+    "abs": np.absolute, "sqrt": np.sqrt, "cos": np.cos, "sin": np.sin, "tan": np.tan, "power": np.power,
+    "log": np.log, "log2": np.log2, "log10": np.log10,
+    "to_int": lambda x: np.array(x, dtype="int"), "to_float": lambda x: np.array(x, dtype="float"),
+    "to_bool": lambda x: np.array(x, dtype="bool"),
+    "pi": lambda: np.pi, "e": lambda: np.e,
+}
+SCALAR_ARITY = {"power": 2, "pi": 0, "e": 0}
+
+
+def _lit_value(e):
+    """a literal operand as the Python / NumPy scalar the reference's ufunc receives"""
+    if isinstance(e, tuple):
+        return np.float64(e[1]) if isinstance(e[1], float) else np.int64(e[1])
+    return e
+
+
+def fold(e):
+    """Fold every built-in function whose operands are all literals, with NumPy itself."""
+    def f(n):
+        if n[0] not in SCALAR_FUNCS or not all(is_number(a) for a in n[1:]):
+            return n
+        with np.errstate(all="ignore"):
+            v = SCALAR_FUNCS[n[0]](*[_lit_value(a) for a in n[1:]])
+        if isinstance(v, float) and not isinstance(v, np.floating):
+            return v                                   # pi() / e(): a weak Python float
+        v = np.asarray(v)
+        if v.dtype == np.bool_:
+            raise TypeError("boolean literals are not arithmetic operands")
+        if v.dtype == np.float64:
+            return ("strong", float(v))
+        if v.dtype == np.int64:
+            return ("strong", int(v))
+        raise TypeError(f"a constant of type {v.dtype} is not supported")
+    return transform(e, f)

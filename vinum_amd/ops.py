@@ -11,9 +11,11 @@ import numpy as np
 import pyarrow as pa
 
 from . import _lib as L
+from . import expr as E
 from .device import DeviceBuffer, DeviceColumn, _NP, _WIDTH, arrow_from_numpy, dcol_array, physical_type
+from .expr import SCALAR_ARITY, SCALAR_FUNCS, columns_of  # noqa: F401  (re-exported: the tree-only passes live in vinum_amd.expr)
 
-CMP_OPS = {"==": L.EQ, "=": L.EQ, "!=": L.NE, "<>": L.NE, ">": L.GT, ">=": L.GE, "<": L.LT, "<=": L.LE}
+CMP_OPS = {s: getattr(L, n.upper()) for s, n in E.CMP_SYMBOLS.items()}         # "==" -> L.EQ ...
 
 
 def _stream_ptr(stream):
@@ -448,60 +450,13 @@ def take(col: DeviceColumn, indices: DeviceBuffer, n, stream=None) -> DeviceColu
 _EX = {"add": L.EX_ADD, "sub": L.EX_SUB, "mul": L.EX_MUL, "div": L.EX_DIV, "mod": L.EX_MOD, "neg": L.EX_NEG,
        "band": L.EX_BAND, "bor": L.EX_BOR, "bxor": L.EX_BXOR, "bnot": L.EX_BNOT,
        "+": L.EX_ADD, "-": L.EX_SUB, "*": L.EX_MUL, "/": L.EX_DIV, "%": L.EX_MOD,
-       "eq": L.EX_EQ, "ne": L.EX_NE, "gt": L.EX_GT, "ge": L.EX_GE, "lt": L.EX_LT, "le": L.EX_LE,
-       "==": L.EX_EQ, "=": L.EX_EQ, "!=": L.EX_NE, "<>": L.EX_NE, ">": L.EX_GT, ">=": L.EX_GE, "<": L.EX_LT, "<=": L.EX_LE,
+       **{s: getattr(L, "EX_" + E.cmp_name(s).upper()) for s in (*E.CMP_FLIP, *E.CMP_SYMBOLS)},      # "eq" and "==" -> L.EX_EQ ...
        "and": L.EX_AND, "or": L.EX_OR, "not": L.EX_NOT,
        "abs": L.EX_ABS, "sqrt": L.EX_SQRT, "sin": L.EX_SIN, "cos": L.EX_COS, "tan": L.EX_TAN, "log": L.EX_LOG,
        "log2": L.EX_LOG2, "log10": L.EX_LOG10, "power": L.EX_POW,
        "to_float": L.EX_TO_F64, "to_int": L.EX_TO_I64, "to_bool": L.EX_TO_BOOL}
 _UNARY = (L.EX_NEG, L.EX_BNOT, L.EX_NOT, L.EX_ABS, L.EX_SQRT, L.EX_SIN, L.EX_COS, L.EX_TAN, L.EX_LOG, L.EX_LOG2, L.EX_LOG10,
           L.EX_TO_F64, L.EX_TO_I64, L.EX_TO_BOOL)
-
-# The numeric built-ins of the reference's _default_functions_registry (vinum/core/functions.py:353-387) with the callables
-# it registers: what a subtree of literals folds to on the host, so folded constants keep NumPy's value AND scalar type
-# (np.sqrt(4) is a strong np.float64, pi() the weak Python float np.pi)
-SCALAR_FUNCS = {
-    "abs": np.absolute, "sqrt": np.sqrt, "cos": np.cos, "sin": np.sin, "tan": np.tan, "power": np.power,
-    "log": np.log, "log2": np.log2, "log10": np.log10,
-    "to_int": lambda x: np.array(x, dtype="int"), "to_float": lambda x: np.array(x, dtype="float"),
-    "to_bool": lambda x: np.array(x, dtype="bool"),
-    "pi": lambda: np.pi, "e": lambda: np.e,
-}
-SCALAR_ARITY = {"power": 2, "pi": 0, "e": 0}
-
-
-def _is_lit(e):
-    return (isinstance(e, (int, float)) and not isinstance(e, bool)) or (isinstance(e, tuple) and len(e) == 2 and e[0] == "strong")
-
-
-def _lit_value(e):
-    """a literal operand as the Python / NumPy scalar the reference's ufunc receives"""
-    if isinstance(e, tuple):
-        return np.float64(e[1]) if isinstance(e[1], float) else np.int64(e[1])
-    return e
-
-
-def _fold(e):
-    """Fold every built-in function whose operands are all literals, with NumPy itself."""
-    if not isinstance(e, tuple) or e[0] in ("strong", "lit", "in", "not_in", "is_null", "is_not_null"):
-        return e
-    args = tuple(_fold(x) for x in e[1:])
-    e = (e[0],) + args
-    if e[0] not in SCALAR_FUNCS or not all(_is_lit(a) for a in args):
-        return e
-    with np.errstate(all="ignore"):
-        v = SCALAR_FUNCS[e[0]](*[_lit_value(a) for a in args])
-    if isinstance(v, float) and not isinstance(v, np.floating):
-        return v                                   # pi() / e(): a weak Python float
-    v = np.asarray(v)
-    if v.dtype == np.bool_:
-        raise TypeError("boolean literals are not arithmetic operands")
-    if v.dtype == np.float64:
-        return ("strong", float(v))
-    if v.dtype == np.int64:
-        return ("strong", int(v))
-    raise TypeError(f"a constant of type {v.dtype} is not supported")
-
 
 _ARROW_OF = {L.I8: pa.int8(), L.I16: pa.int16(), L.I32: pa.int32(), L.I64: pa.int64(), L.U8: pa.uint8(), L.U16: pa.uint16(),
              L.U32: pa.uint32(), L.U64: pa.uint64(), L.F32: pa.float32(), L.F64: pa.float64(), L.OUT_F16: pa.float16()}
@@ -537,52 +492,19 @@ def result_type(expr, types) -> pa.DataType:
     <negative integer literal>)` -> ValueError) without touching a device: a zero-length call.  types: column name ->
     (pa.DataType, has_nulls).  Returns the Arrow type of the result (pa.uint8() for a predicate mask).  A list that
     lower_in_sets would probe as a set is typed as the mask column it becomes, its operand on its own."""
-    chosen = {id(n) for n in _choose_in_sets(expr)}
+    chosen = _choose_in_sets(expr)
     if chosen:
         types = dict(types)
 
-        def walk(e):
-            if not isinstance(e, tuple) or not e or e[0] in ("strong", "lit"):
-                return e
-            if id(e) in chosen:
-                if not isinstance(e[1], str):
-                    _check_in_operand(_result_type_code(e[1], types), e[0])
-                name = f"__in_{len(types)}"
-                types[name] = (pa.uint8(), False)
-                return ("ne" if e[0] == "in" else "eq", name, 0)
-            if e[0] in ("in", "not_in"):
-                return (e[0], walk(e[1]), e[2])
-            return (e[0],) + tuple(walk(x) for x in e[1:])
-        expr = walk(expr)
+        def mask(e):
+            if not isinstance(e[1], str):
+                _check_in_operand(_result_type_code(e[1], types), e[0])
+            name = f"__in_{len(types)}"
+            types[name] = (pa.uint8(), False)
+            return name
+        expr = _replace_in_sets(expr, chosen, mask)
     ot = _result_type_code(expr, types)
     return pa.uint8() if ot == L.MASK_U8 else _ARROW_OF[ot]
-
-
-def _desugar(e):
-    """BETWEEN / IN rewrite onto the primitive predicates, exactly what the reference's callables compute:
-    between -> logical_and(x >= low, x <= high), not_between -> logical_or(x < low, x > high)
-    (vinum/core/expressions.py:43-48); in / not_in -> np.isin(x, values[, invert]) (:39-40)."""
-    if not isinstance(e, tuple):
-        return e
-    if e[0] == "strong":
-        return e
-    op, args = e[0], [_desugar(x) for x in e[1:]]
-    if op == "between":
-        return ("and", ("ge", args[0], args[1]), ("le", args[0], args[2]))
-    if op == "not_between":
-        return ("or", ("lt", args[0], args[1]), ("gt", args[0], args[2]))
-    if op in ("in", "not_in"):
-        vals = list(e[2])
-        if not vals:
-            raise ValueError("IN with an empty list")
-        # np.isin turns the list into an ARRAY (int64 / float64: strong types), unlike a bare literal operand
-        if any(isinstance(v, float) for v in vals):
-            vals = [float(v) for v in vals]
-        vals = [("strong", v) for v in vals]
-        if op == "in":
-            return ("or",) + tuple(("eq", args[0], v) for v in vals) if len(vals) > 1 else ("eq", args[0], vals[0])
-        return ("and",) + tuple(("ne", args[0], v) for v in vals) if len(vals) > 1 else ("ne", args[0], vals[0])
-    return (op,) + tuple(args)
 
 
 def _emit_expr(expr, col_index, out):
@@ -593,21 +515,19 @@ def _emit_expr(expr, col_index, out):
             out.append((L.EX_COL, col_index[e], 0.0, 0))
         elif isinstance(e, bool):
             raise TypeError("boolean literals are not arithmetic operands")
-        elif isinstance(e, int):
-            out.append((L.EX_CONST_I, 0, 0.0, int(e)))
-        elif isinstance(e, float):
-            out.append((L.EX_CONST_F, 0, float(e), 0))
-        elif e[0] == "strong":
-            out.append((L.EX_CONST_F, 1, float(e[1]), 0) if isinstance(e[1], float) else (L.EX_CONST_I, 1, 0.0, int(e[1])))
+        elif E.is_number(e):
+            strong = isinstance(e, tuple)          # arg 1: an array's strong type, 0: a weak Python literal
+            v = e[1] if strong else e
+            out.append((L.EX_CONST_F, int(strong), float(v), 0) if isinstance(v, float) else (L.EX_CONST_I, int(strong), 0.0, int(v)))
         elif e[0] in ("is_null", "is_not_null"):
             out.append((L.EX_IS_NULL if e[0] == "is_null" else L.EX_IS_NOT_NULL, col_index[e[1]], 0.0, 0))
         elif e[0] == "lookup":
             # ("lookup", code column, table column): table[code] as a predicate (LIKE over a dictionary-coded column, see
-            # core.algebra.lower_like); the table travels as a column of its own length
+            # core.lowering.lower_like); the table travels as a column of its own length
             out.append((L.EX_LOOKUP_U8, col_index[e[1]], 0.0, col_index[e[2]]))
         elif e[0] == "lookup_i32":
             # ("lookup_i32", code column, table column): table[code] as an int32 VALUE, NULL without an entry (two dictionary-coded
-            # columns compared with each other, see core.algebra.lower_column_compares)
+            # columns compared with each other, see core.lowering.lower_column_compares)
             out.append((L.EX_LOOKUP_I32, col_index[e[1]], 0.0, col_index[e[2]]))
         elif e[0] in ("like", "not_like"):
             raise NotImplementedError(f"no GPU lowering for {e[0].upper()} outside a FilterOperator / ProjectOperator / "
@@ -628,7 +548,7 @@ def _emit_expr(expr, col_index, out):
                 for a in args[1:]:
                     emit(a)
                     out.append((op, 0, 0.0, 0))
-    emit(_fold(_desugar(expr)))
+    emit(E.fold(E.desugar(expr)))
 
 
 def _program(ins):
@@ -639,9 +559,7 @@ def _program(ins):
 
 
 def compile_expr(expr, col_index):
-    """Nested prefix expression -> postfix vnm_expr_ins list.
-    expr := column name | int | float | (op, expr[, expr...]); n-ary chains fold left like
-    VectorizedExpression._apply_binary_args_function (vinum/core/base.py:145-151)."""
+    """Nested prefix expression (the grammar: vinum_amd.expr) -> postfix vnm_expr_ins list."""
     out = []
     _emit_expr(expr, col_index, out)
     return _program(out)
@@ -833,39 +751,25 @@ def _count_ins(expr) -> int:
     return len(tmp)
 
 
+def _replace_in_sets(expr, chosen, mask_name):
+    """`expr` with every node of `chosen` (by identity) replaced by ("ne" for IN | "eq" for NOT IN, mask_name(node), 0)"""
+    ids = {id(n) for n in chosen}
+    return E.rewrite(expr, lambda e: ("ne" if e[0] == "in" else "eq", mask_name(e), 0) if id(e) in ids else None)
+
+
 def _choose_in_sets(expr):
     """The IN / NOT IN nodes of `expr` that are probed as sets: every list of in_set_min() or more members; after that, as
     long as the program would still exceed the interpreter's limit, the longest remaining list, until it fits.  Every other
     list keeps its OR / AND chain."""
-    nodes = []
-
-    def collect(e):
-        if isinstance(e, tuple) and e and e[0] not in ("strong", "lit"):
-            if e[0] in ("in", "not_in"):
-                nodes.append(e)
-                collect(e[1])
-            else:
-                for x in e[1:]:
-                    collect(x)
-    collect(expr)
+    nodes = [n for n in E.nodes(expr) if isinstance(n, tuple) and n and n[0] in E.IN_OPS]
     if not nodes:
         return []
     least = in_set_min()
     chosen = [n for n in nodes if len(n[2]) >= least]
     rest = sorted((n for n in nodes if len(n[2]) < least), key=lambda n: len(n[2]))
     while rest:
-        ids = {id(n) for n in chosen}
-
-        def stand_in(e):
-            if not isinstance(e, tuple) or not e or e[0] in ("strong", "lit"):
-                return e
-            if id(e) in ids:
-                return ("ne", "__in", 0)
-            if e[0] in ("in", "not_in"):
-                return (e[0], stand_in(e[1]), e[2])
-            return (e[0],) + tuple(stand_in(x) for x in e[1:])
         try:
-            if _count_ins(stand_in(expr)) + 1 <= PJ_MAX_INS:
+            if _count_ins(_replace_in_sets(expr, chosen, lambda e: "__in")) + 1 <= PJ_MAX_INS:
                 break
         except (NotImplementedError, TypeError, ValueError, KeyError):
             break              # not a program at all: whoever compiles it raises
@@ -893,29 +797,23 @@ def lower_in_sets(expr, columns: dict, length=None, stream=None, extra=None):
     first and probed with that result's type.  Returns (expression, extra): the mask columns by name, added to `extra` when
     one is passed in."""
     extra = {} if extra is None else extra
-    chosen = {id(n) for n in _choose_in_sets(expr)}
+    chosen = _choose_in_sets(expr)
     if not chosen:
         return expr, extra
     if length is None:
         length = next(iter(columns.values())).length if columns else 1
 
-    def walk(e):
-        if not isinstance(e, tuple) or not e or e[0] in ("strong", "lit"):
-            return e
-        if id(e) in chosen:
-            if isinstance(e[1], str):
-                col = columns[e[1]]
-                _check_in_operand(col.vnm_type, e[0])
-            else:
-                col, ot = _project_typed(e[1], {n: columns[n] for n in columns_of(e[1])}, length, stream)
-                _check_in_operand(ot, e[0])
-            name = f"__in_{len(extra)}"
-            extra[name] = in_set_probe(col, e[2], length=length, stream=stream)
-            return ("ne" if e[0] == "in" else "eq", name, 0)
-        if e[0] in ("in", "not_in"):
-            return (e[0], walk(e[1]), e[2])
-        return (e[0],) + tuple(walk(x) for x in e[1:])
-    return walk(expr), extra
+    def probe(e):
+        if isinstance(e[1], str):
+            col = columns[e[1]]
+            _check_in_operand(col.vnm_type, e[0])
+        else:
+            col, ot = _project_typed(e[1], {n: columns[n] for n in columns_of(e[1])}, length, stream)
+            _check_in_operand(ot, e[0])
+        name = f"__in_{len(extra)}"
+        extra[name] = in_set_probe(col, e[2], length=length, stream=stream)
+        return name
+    return _replace_in_sets(expr, chosen, probe), extra
 
 
 _LIKE_META = frozenset(b"\\^$*+?{}[]|()")
@@ -938,28 +836,6 @@ def like_tokens(pattern: str):
     buf = ctypes.create_string_buffer(raw, max(len(raw), 1))
     L.check(L.load().vnm_like_compile(buf, len(raw), toks, ctypes.byref(n)))
     return [(toks[3 * k], raw[toks[3 * k + 1]:toks[3 * k + 1] + toks[3 * k + 2]]) for k in range(n.value)]
-
-
-def columns_of(expr):
-    """Column names referenced by a (possibly sugared) expression, in first-use order."""
-    seen = []
-
-    def walk(e):
-        if isinstance(e, str):
-            if e not in seen:
-                seen.append(e)
-        elif isinstance(e, tuple):
-            if e[0] == "lit":            # ("lit", "Berlin"): a string / bytes LITERAL (a bare str is a column name)
-                return
-            if e[0] in ("is_null", "is_not_null"):
-                walk(e[1])
-            elif e[0] in ("in", "not_in"):
-                walk(e[1])
-            else:
-                for x in e[1:]:
-                    walk(x)
-    walk(expr)
-    return seen
 
 
 def predicate_mask(expr, columns: dict, length, stream=None) -> DeviceBuffer:

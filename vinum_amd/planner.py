@@ -9,12 +9,11 @@ A query is a dict (see tests/golden/planner_cases.py):
     select     [expr]            aliases [str | None]      distinct bool
     where      expr | None       group_by [expr]           having expr | None
     order_by   [expr]            sort_order ["ASC" | "DESC"]   limit int | None   offset int
-    expr := column name | int | float | (op, arg...)   with op as in vinum_amd.ops plus ("fn", name, arg...) for the
+    expr := the prefix tuples of vinum_amd.expr (the one definition of the node forms), with ("fn", name, arg...) for the
             aggregate functions count_star / count / sum / avg / min / max and the numeric built-in scalar functions
             (SCALAR_FN_NAMES: abs, sqrt, sin, ..., to_int, pi, e and their np. spellings), which are per-row expressions
-            wherever they appear, like any operator; ("lit", "Berlin") is a string literal (a bare str is a column name),
-            and ("like", column, ("lit", "Jos%")) / ("not_like", ...) are LIKE / NOT LIKE against a utf8 / large_utf8 column
-            (planner.py:189-193) -- in WHERE, HAVING, the SELECT list (a uint8 mask) and aggregate arguments alike.
+            wherever they appear, like any operator; LIKE / NOT LIKE against a utf8 / large_utf8 column (planner.py:189-193)
+            may stand in WHERE, HAVING, the SELECT list (a uint8 mask) and aggregate arguments alike.
 
 What the planner does with the aggregate part mirrors planner.py:380-469:
   * DISTINCT = GROUP BY every select expression (:380-382);
@@ -30,7 +29,8 @@ import pyarrow as pa
 
 from .core import (AggregateFunction, AggregateOperator, FileReaderOperator, FilterOperator, MaterializeTableOperator,
                    ProjectOperator, SliceOperator, SortOperator, TableReaderOperator)
-from .ops import columns_of
+from . import expr as E
+from .expr import columns_of
 
 AGG_FUNCS = ("count_star", "count", "sum", "avg", "min", "max")     # vinum/core/functions.py:389-396
 # numeric part of _default_functions_registry (vinum/core/functions.py:353-387) and the `np.` spellings lookup_udf resolves
@@ -45,7 +45,7 @@ def _t(e):
     """JSON lists -> tuples (hashable, and what ops.compile_expr takes); IN value lists stay lists.  A built-in scalar
     function ("fn", "sqrt", x) becomes the operator node ("sqrt", x); aggregate and unknown names stay "fn" nodes."""
     if isinstance(e, (list, tuple)) and e and isinstance(e[0], str):
-        if e[0] in ("in", "not_in"):
+        if e[0] in E.IN_OPS:
             return (e[0], _t(e[1]), tuple(e[2]))
         if e[0] == "fn" and len(e) > 1 and isinstance(e[1], str) and e[1].lower() in SCALAR_FN_NAMES:
             return tuple([SCALAR_FN_NAMES[e[1].lower()]] + [_t(x) for x in e[2:]])
@@ -58,16 +58,7 @@ def _is_fn(e) -> bool:
 
 
 def _has_fn(e) -> bool:
-    return isinstance(e, tuple) and (e[0] == "fn" or any(_has_fn(x) for x in e[1:]))
-
-
-def _map(e, f):
-    """Rebuild e bottom-up, f(node) may replace a node (applied to tuples only, children first)."""
-    if not isinstance(e, tuple):
-        return e
-    if e[0] in ("in", "not_in"):
-        return f((e[0], _map(e[1], f), e[2]))
-    return f(tuple([e[0]] + [_map(x, f) for x in e[1:]]))
+    return any(_is_fn(n) for n in E.nodes(e))
 
 
 def output_names(select: Sequence, aliases: Sequence[Optional[str]]) -> List[str]:
@@ -118,7 +109,7 @@ def plan_query(query: Dict, source, expected_groups: int = 0) -> Plan:
     # ---- column pruning (planner.py:346-371): only what the query touches is staged into HBM
     used: List[str] = []
     for e in select + ([where] if where is not None else []) + group_by + ([having] if having is not None else []) + order_by:
-        for c in ([e] if isinstance(e, str) else columns_of(_strip_fn(e))):
+        for c in columns_of(e):
             if c not in used:
                 used.append(c)
     if isinstance(source, pa.Table):
@@ -179,7 +170,7 @@ def plan_query(query: Dict, source, expected_groups: int = 0) -> Plan:
             """an expression over the aggregate's OUTPUT: functions and group-by expressions become columns"""
             if e in key_of:
                 return key_of[e]
-            return _map(e, lambda n: key_of.get(n, fn_col(n)))
+            return E.transform(e, lambda n: key_of.get(n, fn_col(n)))
 
         select_post = [post(e) for e in select]
         having_post = post(having) if having is not None else None
@@ -232,19 +223,9 @@ def execute(query: Dict, source, expected_groups: int = 0) -> pa.Table:
     return plan_query(query, source, expected_groups).execute()
 
 
-def _strip_fn(e):
-    """the same expression with aggregate function nodes replaced by their argument (for column discovery)"""
-    def f(n):
-        if _is_fn(n):
-            return n[2] if len(n) > 2 else 0
-        return n
-    return _map(e, f) if isinstance(e, tuple) else e
-
-
 def _simple_predicate(e):
     """`column <op> literal` -> the (column, op, literal) triple FilterOperator fuses (vnm_filter_cmp / the aggregate scan)"""
-    ops_ = {"eq": "==", "ne": "!=", "gt": ">", "ge": ">=", "lt": "<", "le": "<="}
-    if (isinstance(e, tuple) and len(e) == 3 and e[0] in ops_ and isinstance(e[1], str)
+    if (isinstance(e, tuple) and len(e) == 3 and e[0] in E.CMP_SYMBOL and isinstance(e[1], str)
             and isinstance(e[2], (int, float)) and not isinstance(e[2], bool)):
-        return (e[1], ops_[e[0]], e[2])
+        return (e[1], E.CMP_SYMBOL[e[0]], e[2])
     return None

@@ -12,6 +12,7 @@ import pyarrow as pa
 
 from .core import (AggregateFunction, AggregateOperator, FileReaderOperator, FilterOperator, MaterializeTableOperator,
                    ProjectOperator, SliceOperator, SortOperator, TableReaderOperator)
+from .expr import columns_of
 
 
 def select(source, columns: Optional[Sequence] = None, where: Optional[Tuple[str, str, object]] = None,
@@ -42,18 +43,15 @@ def select(source, columns: Optional[Sequence] = None, where: Optional[Tuple[str
 
 
 def _needed_columns(columns, where, group_by, aggregates, order_by):
-    from .core.algebra import _columns_of
     need = []
 
     def add(c):
         if c and c not in need:
             need.append(c)
     for c in (columns or []):
-        for x in ([c] if isinstance(c, str) else _columns_of(c[1])):
+        for x in ([c] if isinstance(c, str) else columns_of(c[1])):
             add(x)
     if where:
-        from .ops import columns_of
-        from .core.algebra import FilterOperator
         for c in ([where[0]] if FilterOperator.is_simple(where) else columns_of(where)):
             add(c)
     for c in group_by:
