@@ -468,7 +468,7 @@ struct vnm_agg {
                                      // from COUNT(*) (or whose SUM is NULL) -- the side-table fold of the fused result columns assumes they do not
     bool count8_off = false;    // the counters of COUNT(*)-only programs overflowed once (dcount8_final_kernel): not again
     int count_cb = 0;           // ... their width once the bytes overflowed: 16
-    struct DScanPending* scan_pending = nullptr;   // a stream of small-range batches: their table (see dense_scan_aggregate)
+    struct DScanPending* scan_pending = nullptr;   // a stream of small-range batches: their table (see dense_scan_stream)
     bool dense_by_bound = false;   // the first batch went dense on the sample's LOWER bound of the group count (no estimate exists)
     bool range_given = false;   // vnm_agg_set_dense_range: the code range is the caller's (agreed by all ranks), not a sample's
     // expression input (vnm_agg_set_input_expr): the functions reading plan column expr_col get an expression's value
@@ -637,6 +637,12 @@ void drop_run(vnm_agg* h) {
     h->run_key = h->run_acc = nullptr;
     h->have_run = false;
     h->run_n = h->run_stride = 0;
+}
+// The run belongs to the handle from here on (the caller has keep()-ed its blocks); dir / nfin: the hash partitions' partition directory.
+void adopt_run(vnm_agg* h, uint64_t* key, uint64_t* acc, int64_t stride, int64_t n, unsigned long long* dir = nullptr, int64_t nfin = 0) {
+    h->run_key = key; h->run_acc = acc; h->run_stride = stride; h->run_n = n;
+    h->run_dir = dir; h->run_nfin = nfin;
+    h->have_run = true;
 }
 
 // distinct-key estimate from a strided sample (tiered: a small sample settles small G cheaply)
@@ -836,9 +842,7 @@ static int flush_scan_pending(vnm_agg* h, hipStream_t s) {
     VNM_HIP(hipStreamSynchronize(s));
     if (fl[0]) return set_error("aggregate: the stream table holds more groups than slots (internal error)");
     pool.keep(rk); pool.keep(ra);
-    h->run_key = rk; h->run_acc = ra; h->run_stride = dstride; h->run_n = (int64_t)fl[1];
-    h->run_dir = nullptr; h->run_nfin = 0;
-    h->have_run = true;
+    adopt_run(h, rk, ra, dstride, (int64_t)fl[1]);
     return 0;
 }
 

@@ -105,8 +105,7 @@ int vnm_agg_merge_partitioned(vnm_agg* h, int world, int64_t nlocal, const uint6
         return 2;  // capacity, not an error of the data: the handle is still empty and the caller falls back
     }
     pool.keep(rk); pool.keep(ra);
-    h->run_key = rk; h->run_acc = ra; h->run_stride = dstride; h->run_n = (int64_t)fl[1];
-    h->have_run = true;
+    adopt_run(h, rk, ra, dstride, (int64_t)fl[1]);   // (no directory: the handle was empty)
     return 0;
 }
 

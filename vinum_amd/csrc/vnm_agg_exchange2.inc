@@ -89,9 +89,7 @@ int vnm_agg_merge_dense_tables(vnm_agg* h, const vnm_agg* like, int nsrc, const 
     VNM_HIP(hipStreamSynchronize(s));
     if (fl[0]) return set_error("vnm_agg_merge_dense_tables: output overflow (internal error)");
     pool.keep(rk); pool.keep(ra);
-    h->run_key = rk; h->run_acc = ra; h->run_stride = dstride; h->run_n = (int64_t)fl[1];
-    h->run_dir = nullptr; h->run_nfin = 0;
-    h->have_run = true;
+    adopt_run(h, rk, ra, dstride, (int64_t)fl[1]);
     return 0;
 }
 

@@ -563,8 +563,6 @@ int dense_fxn_aggregate(vnm_agg* h, int64_t nrows, const vnm_dcol* keys, const v
     route_note("dense:fixed_point_columns", "%d columns in 16-byte entries (quanta 2^%d, 2^%d, 2^%d), 2^%d codes, 2^%d-slot tables, %d level(s)%s", NV, h->fxn_qe[0], h->fxn_qe[1],
                NV > 2 ? h->fxn_qe[2] : 0, mp.bits, tb, levels, q ? ", stream segments" : "");
     pool.keep(rk); pool.keep(ra);
-    h->run_key = rk; h->run_acc = ra; h->run_stride = dstride; h->run_n = (int64_t)fl[1];
-    h->run_dir = nullptr; h->run_nfin = 0;
-    h->have_run = true;
+    adopt_run(h, rk, ra, dstride, (int64_t)fl[1]);
     return 0;
 }

@@ -597,7 +597,7 @@ int collapse_parts(vnm_agg* h, hipStream_t s) {
             rc = set_error("aggregate: joining the parts of a split program failed");
         if (!rc && bad) rc = set_error("aggregate: the parts of a split program hold different keys (internal error)");
         if (rc) { pool_free(rk); pool_free(ra); return rc; }
-        h->run_key = rk; h->run_acc = ra; h->run_stride = stride; h->run_n = n; h->have_run = true;
+        adopt_run(h, rk, ra, stride, n);   // (no directory: the handle held no run)
     }
     drop_parts(h);
     return 0;

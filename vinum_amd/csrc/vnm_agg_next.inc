@@ -689,7 +689,7 @@ static int run_small_range_scan(const Batch& b, AggArgs& a, const BatchShape& sh
             if (h->have_run) VNM_TRY(merge_run_into_table(h, s));
             if (sh.dense_generic && h->scan_pending) VNM_TRY(flush_scan_pending(h, s));
             route_note(sh.dense_generic ? "dense_scan:generic" : "dense_scan:hot", "~%lld groups in a sampled range of %lld codes (<= 2^13): direct-addressed LDS table, no scatter", (long long)h->hint, (long long)h->dense_span);
-            int prc = dense_scan_aggregate(h, a, nrows, s, &sp.spill, &sp.n_spill, sh.dense_generic, &sp.nspill, &sp.n_nspill);
+            int prc = sh.dense_generic ? dense_scan_generic(h, a, nrows, s, &sp.spill, &sp.n_spill, &sp.nspill, &sp.n_nspill) : dense_scan_stream(h, a, nrows, s, &sp.spill, &sp.n_spill);
             dscan_stream = prc == 0 && !sh.dense_generic;
             // a generic program whose table for this range does not fit LDS: the same 2^13 codes through one scatter level
             // (four partitions of 2^11 slots, split final pass) instead

@@ -1,4 +1,6 @@
-// Host side of the partitioned routes: hash partitions, the dense-key path (one / two levels, scan of small ranges, two values), deferred final passes.
+// Host side of the partitioned routes, each a driver over stage functions (plan -> blocks -> passes -> hand-over): the hash partitions
+// (partitioned_aggregate), the scans of small ranges (dense_scan_generic, dense_scan_stream), the deferred final pass (complete_pending), the
+// dense-key path (dense_partitioned_aggregate: one / two levels) and its two-value form (dense_two_aggregate).
 // Part of the aggregate operator; included by vnm_agg.hip (one translation unit: the kernels and the host code share file-local helpers).
 namespace {
 // ---- typed launches ----------------------------------------------------------------------------------------------
@@ -122,12 +124,43 @@ int ring_scatter(const RingLaunch& r, const DPartArgs& d) {
     return ring_scatter_pairs<FR, CT, HV, PV, VN, FX, W32, 1, IN32, WIN>(r, d);
 }
 
+// ---- what the routes share --------------------------------------------------------------------------------------------
+// the WHERE comparison of a kernel's arguments (the hash partitions' wide entries add PartArgs::wp / wpred beside the call)
+template <class X> void fill_pred(X& x, const vnm_agg* h, const AggArgs& a) {
+    x.pp = h->pred_set ? (const double*)a.pred.values + a.pred.offset : nullptr;
+    x.has_pred = h->pred_set; x.pred_is_v = a.hot_pred_is_v; x.op = a.p.op; x.thr = a.p.dval;
+}
+// the first words of a flags block, as many as `fl` holds, once the stream has run dry
+template <size_t N> int read_flags(unsigned long long (&fl)[N], const unsigned long long* flags, hipStream_t s) {
+    VNM_HIP(hipMemcpyAsync(fl, flags, N * 8, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+// Every pool block of one attempt: what has not been keep()-ed goes back on every return path; free_all() before the batch is tried again.
+struct AttemptBlocks {
+    PoolScope pool;
+    template <class T> void take(T*& p, size_t bytes) { p = (T*)pool.take(bytes); }
+    void free_all() { while (pool.n > 0) pool.done(pool.blocks[pool.n - 1]); }
+};
+constexpr int ATTEMPT_REDO = 4;   // a stage's answer: free everything, then the same batch once more (the handle says what changes)
 
-// returns 0 = done (run stored), 2 = not applicable / overflowed (caller uses the general path), 1 = error
-// spill_out / n_spill_out (optional): entries that did not fit their partition region (heavy keys); the caller
-// aggregates them with agg_hot_kernel<FROM_ENT> and owns the buffer.  Without them a full region fails the attempt.
-int partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_t s, ulonglong2** spill_out = nullptr,
-                          int64_t* n_spill_out = nullptr) {
+// ---- the hash partitions, stage by stage (partitioned_aggregate below is the driver) ----------------------------------------
+// The whole geometry of one attempt.  Filled by plan_hash_partitions, which makes no HIP call and leaves the handle alone.
+struct HashPlan {
+    int pa_slots;                            // slots of the final pass's LDS table
+    int64_t per_final, nfin;                 // groups per final partition; final partitions (np1, or np1 * np2)
+    int E; bool wide; size_t ebytes;         // 8-byte words per entry; generic column accessors (any width, NULLs, any predicate column)
+    int levels, np1, np2, lg1;               // fan-out of the levels, np1 <= 2^lg1
+    int grid1, split2, fin_regions;          // pass-1 workgroups; pass-2 workgroups per first-level partition; regions per final partition
+    int64_t tile1, rows_per_wg; double slack;
+    int64_t cap1, cap2, spill_cap;           // entries per region after pass 1 / pass 2; of the spill buffer (0: none wanted)
+    bool ring1, ring2, ring2_512;            // (key, value) entries through LDS rings (pring_scatter_kernel), per level
+    int rcap1, rcap2; size_t rlds1, rlds2;   // ... entries per ring, bytes of LDS
+    // hash_plan_final, after the scatters: workgroups that share a final partition; these merge through the HBM table / write partial groups into the run
+    int splits; bool to_table, dup_run; int64_t dstride;
+};
+// Stage 1: partitions, levels, regions, rings.  0, or 2 = would need a third level.
+int plan_hash_partitions(const vnm_agg* h, const AggArgs& a, int64_t nrows, bool want_spill, HashPlan* p) {
     const int cus = device_info().num_cus;
     // final partitions sized for ~900 groups each: enough keys per partition that their sizes concentrate
     // (few keys per partition -> Poisson imbalance overflows the fixed-capacity regions), few enough for
@@ -135,248 +168,247 @@ int partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream
     // Generic programs with three or more accumulator words: a 2048-slot table is 65+ KB, i.e. one or two resident
     // workgroups per CU in a latency-bound pass (5 words, G=1e5: 10 ms).  They get 1024-slot tables and half the groups
     // per partition while two levels still provide enough partitions.
-    const int64_t l1_cap = env_i64("VNM_AGG_PART_L1_MAX", 256) * 512;
+    const int64_t l1_max = env_i64("VNM_AGG_PART_L1_MAX", 256);
     const bool small_tables = a.part_generic && (size_t)(PA_SLOTS + 1) * 8 * (1 + h->plan.n_words) > 54 * 1024 &&
-                              h->hint / 450 < l1_cap && getenv("VNM_AGG_NO_SMALL_TABLES") == nullptr;
+                              h->hint / 450 < l1_max * 512 && getenv("VNM_AGG_NO_SMALL_TABLES") == nullptr;
     int pa_slots = small_tables ? PA_SLOTS / 2 : PA_SLOTS;
     // ... and programs with so many words that even that table exceeds the LDS (three compensated float SUMs + their
     // counts + COUNT(*) = 10 words: 180 KB at 2048 slots) halve it until it fits: more, smaller partitions instead of
     // the HBM-atomics path (300 ms per 1e9 rows)
     while (a.part_generic && pa_slots > 256 && (size_t)(pa_slots + 1) * 8 * (1 + h->plan.n_words) > 150 * 1024) pa_slots /= 2;
-    const int64_t per_final = env_i64("VNM_AGG_PART_GROUPS", 900 * pa_slots / PA_SLOTS);
+    p->pa_slots = pa_slots;
+    p->per_final = env_i64("VNM_AGG_PART_GROUPS", 900 * pa_slots / PA_SLOTS);
     int64_t nfin = 2;
-    while (nfin * per_final < h->hint) nfin *= 2;
-    const int64_t l1_max = env_i64("VNM_AGG_PART_L1_MAX", 256);
+    while (nfin * p->per_final < h->hint) nfin *= 2;
     if (nfin > l1_max * 512) {
         // two levels give at most l1_max * 512 partitions: still fine while a partition's groups fit the LDS table
         if (h->hint / (l1_max * 512) > 1600 * pa_slots / PA_SLOTS) return 2;  // would need a third level
         nfin = l1_max * 512;
     }
     // entry = key + one value (16 bytes, tuned kernels) or key + 2-3 values (wide entries)
-    const int E = a.part_wide ? 1 + h->plan.n_cols + (a.part_vmask ? 1 : 0) : 2;
-    const bool wide = a.part_wide != 0;  // generic column accessors (any width, NULLs, any predicate column)
-    const int64_t tile1 = wide ? pw_tile(E) : PT_TILE;
-    const size_t ebytes = (size_t)E * 8;
+    p->E = a.part_wide ? 1 + h->plan.n_cols + (a.part_vmask ? 1 : 0) : 2;
+    p->wide = a.part_wide != 0; p->ebytes = (size_t)p->E * 8;
+    p->tile1 = p->wide ? pw_tile(p->E) : PT_TILE;
     // twice the usual first-level fan-out still beats a second level that would only split in two (G = 3e5 sparse keys:
     // 512 partitions in one pass 7.4 + 1.9 ms; 256 x 2: 6.7 + 3.7 + 2.0)
-    const int levels = nfin > std::min<int64_t>(l1_max * 2, PT_MAXP) ? 2 : 1;
-    const int np1 = levels == 2 ? (int)l1_max : (int)nfin;
-    const int np2 = levels == 2 ? (int)(nfin / l1_max) : 0;
-    const int grid1 = (int)std::min<int64_t>((int64_t)cus * 2, (nrows + tile1 - 1) / tile1);
-    const int split2 = std::max(2, (grid1 + PT_MAX_REGIONS - 1) / PT_MAX_REGIONS);  // pass-2 workgroups per partition
-    const int64_t tiles_per_wg = ((nrows + tile1 - 1) / tile1 + grid1 - 1) / grid1;
-    const int64_t rows_per_wg = tiles_per_wg * tile1;
+    p->levels = nfin > std::min<int64_t>(l1_max * 2, PT_MAXP) ? 2 : 1;
+    const int np1 = p->np1 = p->levels == 2 ? (int)l1_max : (int)nfin;
+    const int np2 = p->np2 = p->levels == 2 ? (int)(nfin / l1_max) : 0;
+    p->nfin = p->levels == 2 ? (int64_t)np1 * np2 : np1;
+    while ((1 << p->lg1) < np1) p->lg1++;
+    const int64_t tiles = (nrows + p->tile1 - 1) / p->tile1;
+    p->grid1 = (int)std::min<int64_t>((int64_t)cus * 2, tiles);
+    p->split2 = std::max(2, (p->grid1 + PT_MAX_REGIONS - 1) / PT_MAX_REGIONS);
+    p->fin_regions = p->levels == 2 ? p->split2 : p->grid1;
+    p->rows_per_wg = (tiles + p->grid1 - 1) / p->grid1 * p->tile1;
     // region slack: a partition holds per_final / 2 ... per_final keys, so its share of the rows scatters by 1 / sqrt(keys)
     // around the mean (small LDS tables -> few keys per partition -> up to +42 %; measured: 225 keys per partition
     // overflowed the 25 % regions of pass 2 at G = 3e5 and 1e6)
-    const double slack = std::max(0.0, 4.5 / std::sqrt((double)std::max<int64_t>(per_final, 16) / 2.0));
-    const int64_t cap1 = rows_per_wg / np1 + (int64_t)((double)(rows_per_wg / np1) * std::max(0.2, slack)) + 512;
-    PoolScope pool;   // every block of this attempt; the ones handed on are keep()-ed
-    unsigned long long* flags = (unsigned long long*)pool.take(64);
-    ulonglong2* e1 = (ulonglong2*)pool.take((size_t)np1 * grid1 * cap1 * ebytes);
-    uint32_t* c1 = (uint32_t*)pool.take((size_t)np1 * grid1 * 4);
-    if (!flags || !e1 || !c1) return 1;
-    VNM_HIP(hipMemsetAsync(flags, 0, 64, s));
-    const int64_t spill_cap = spill_out ? nrows / 2 + (1 << 20) : 0;
-    ulonglong2* spill = spill_out ? (ulonglong2*)pool.take((size_t)spill_cap * (wide ? ebytes : 16)) : nullptr;   // wide: [spill_cap][E] words
-    if (spill_out && !spill) return 1;
-    PartArgs p1{};
+    p->slack = std::max(0.0, 4.5 / std::sqrt((double)std::max<int64_t>(p->per_final, 16) / 2.0));
+    p->cap1 = p->rows_per_wg / np1 + (int64_t)((double)(p->rows_per_wg / np1) * std::max(0.2, p->slack)) + 512;
+    if (p->levels == 2) {   // worst case: every row survived and spread evenly; 25 % slack + constant
+        const int64_t per_pg = (int64_t)p->grid1 * p->rows_per_wg / np1 / p->split2;
+        p->cap2 = per_pg / np2 + (int64_t)((double)(per_pg / np2) * std::max(0.25, p->slack)) + 256;
+    }
+    p->spill_cap = want_spill ? nrows / 2 + (1 << 20) : 0;
+    // (key, value) entries through LDS rings where a level has at most 256 partitions: rings of >= 32 entries, 256-byte blocks
+    // (512 partitions: 16 entries, blocks of 8, one pair per lane)
+    auto ring_cap = [](int np) { return std::min((int)((size_t)128 * 1024 / 16 / (size_t)np), 64) / 16 * 16; };
+    const int64_t use_ring = env_i64("VNM_PART_RING", 7);   // bit 0: level 1, bit 1: level 2, bit 2: level 2 of 512 partitions
+    const bool ring_ok = !p->wide && !a.has_expr && !h->pring_off && use_ring != 0 && (a.keys[0].offset & 1) == 0 && (!h->plan.n_cols || (a.cols[0].offset & 1) == 0) &&
+                         (!h->pred_set || a.hot_pred_is_v || (a.pred.offset & 1) == 0) && h->plan.n_cols > 0;
+    // (... and at least 128: a sub-tile's 4096 entries must fit the rings' free room in one or two rounds -- 8 rings of 64 entries took 8)
+    p->ring1 = ring_ok && np1 <= 256 && np1 >= 128 && (use_ring & 1);
+    p->ring2 = ring_ok && p->levels == 2 && np2 <= 256 && np2 >= 128 && (use_ring & 2);
+    p->ring2_512 = ring_ok && p->levels == 2 && np2 == 512 && (use_ring & 4);
+    if (p->ring1) { p->rcap1 = ring_cap(np1); p->rlds1 = (size_t)np1 * p->rcap1 * 16; }
+    if (p->ring2 || p->ring2_512) { p->rcap2 = ring_cap(np2); p->rlds2 = (size_t)np2 * p->rcap2 * 16; }
+    return 0;
+}
+
+struct HashBuffers : AttemptBlocks {
+    unsigned long long* flags = nullptr;                // [0] failure, [1] groups written, [2] entries spilled
+    ulonglong2* e1 = nullptr; uint32_t* c1 = nullptr;   // regions of level 1: entries, counts
+    ulonglong2* e2 = nullptr; uint32_t* c2 = nullptr;   // ... of level 2
+    ulonglong2* spill = nullptr;                        // entries that did not fit their region: the caller's on success (wide: [spill_cap][E] words)
+    uint64_t* rk = nullptr; uint64_t* ra = nullptr; unsigned long long* dir = nullptr;   // the run the final pass writes, its partition directory
+    // once the final pass has read them: the regions and the flags go back before the hand-over (folding a run allocates)
+    void release_regions() { for (void* blk : {(void*)e1, (void*)c1, (void*)e2, (void*)c2, (void*)flags}) pool.done(blk); }
+};
+// After a scatter level.  A region overflowed (skewed keys, or more rows per partition than the hint implied): stop here (2).  Carrying
+// on would aggregate partitions that are about to be thrown away -- and the partition holding a heavy key is processed by ONE workgroup
+// (measured: 1.6 s for 1e8 rows with a power-law key distribution).  ATTEMPT_REDO: it went through the rings, which have no spill buffer.
+int hash_check_overflow(const HashBuffers& b, bool rings, hipStream_t s) {
+    unsigned long long f = 0;
+    if (hipMemcpyAsync(&f, b.flags, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return set_error("aggregate: partition pass failed");
+    return !f ? 0 : (rings ? ATTEMPT_REDO : 2);
+}
+// what the arguments of both scatter levels share
+PartArgs hash_part_args(const vnm_agg* h, const AggArgs& a, const HashPlan& p, const HashBuffers& b) {
+    PartArgs x{};
+    x.nval = h->plan.n_cols; x.has_vmask = a.part_vmask; x.flags = b.flags; x.debug = (int)env_i64("VNM_PART_DEBUG", 0);
+    x.spill = b.spill; x.spill_cap = p.spill_cap;
+    return x;
+}
+
+// Stage 2: scatter level 1 (takes its blocks), rows -> np1 partitions by the top hash bits.
+int hash_scatter1(const vnm_agg* h, const AggArgs& a, int64_t nrows, const HashPlan& p, HashBuffers& b, hipStream_t s) {
+    b.take(b.flags, 64); b.take(b.e1, (size_t)p.np1 * p.grid1 * p.cap1 * p.ebytes); b.take(b.c1, (size_t)p.np1 * p.grid1 * 4);
+    if (!b.flags || !b.e1 || !b.c1) return 1;
+    VNM_HIP(hipMemsetAsync(b.flags, 0, 64, s));
+    if (p.spill_cap) b.take(b.spill, (size_t)p.spill_cap * (p.wide ? p.ebytes : 16));
+    if (p.spill_cap && !b.spill) return 1;
+    PartArgs p1 = hash_part_args(h, a, p, b);
     p1.kp = (const uint64_t*)a.keys[0].values + a.keys[0].offset;
     p1.vp = h->plan.n_cols ? (const double*)a.cols[0].values + a.cols[0].offset : (const double*)p1.kp;
     p1.has_expr = a.has_expr; p1.expr = a.expr;
-    p1.pp = h->pred_set ? (const double*)a.pred.values + a.pred.offset : nullptr;
-    p1.has_pred = h->pred_set; p1.pred_is_v = a.hot_pred_is_v; p1.op = a.p.op; p1.thr = a.p.dval;
-    p1.nrows = nrows;
-    p1.out_entries = e1; p1.out_counts = c1; p1.out_cap = cap1;
-    int lg1 = 0;
-    while ((1 << lg1) < np1) lg1++;
-    p1.nparts = np1; p1.shift = 32 - lg1; p1.flags = flags;
-    p1.debug = (int)env_i64("VNM_PART_DEBUG", 0);
-    p1.spill = spill; p1.spill_cap = spill_cap;
-    p1.nval = h->plan.n_cols;
-    p1.has_vmask = a.part_vmask;
-    if (wide) {
+    fill_pred(p1, h, a);
+    p1.nrows = nrows; p1.nparts = p.np1; p1.shift = 32 - p.lg1;
+    p1.out_entries = b.e1; p1.out_counts = b.c1; p1.out_cap = p.cap1;
+    if (p.wide) {
         for (int c = 0; c < h->plan.n_cols; c++) p1.vcols[c] = a.cols[c];
-        p1.wp = a.p;
-        p1.wpred = a.pred;
+        p1.wp = a.p; p1.wpred = a.pred;
     }
-    // (key, value) entries through LDS rings (pring_scatter_kernel) where a level has at most 256 partitions: rings of >= 32 entries, 256-byte blocks
-    auto pring_cap = [&](int np) -> int { int cap = (int)((size_t)128 * 1024 / 16 / (size_t)np); cap = std::min(cap, 64) / 16 * 16; return cap; };   // (512 partitions: 16 entries, blocks of 8 -- VNM_PRING8)
-    auto pring_lds = [&](int np) -> size_t { return (size_t)np * pring_cap(np) * 16; };
-    const bool ring_ok = !wide && !a.has_expr && !h->pring_off && env_i64("VNM_PART_RING", 7) != 0 && (a.keys[0].offset & 1) == 0 && (!h->plan.n_cols || (a.cols[0].offset & 1) == 0) &&
-                         (!h->pred_set || a.hot_pred_is_v || (a.pred.offset & 1) == 0) && h->plan.n_cols > 0;
-    // (... and at least 128: a sub-tile's 4096 entries must fit the rings' free room in one or two rounds -- 8 rings of 64 entries took 8)
-    const bool ring1 = ring_ok && np1 <= 256 && np1 >= 128 && (env_i64("VNM_PART_RING", 7) & 1);
-    const bool ring2 = ring_ok && levels == 2 && np2 <= 256 && np2 >= 128 && (env_i64("VNM_PART_RING", 7) & 2);
-    const bool ring2_512 = ring_ok && levels == 2 && np2 == 512 && (env_i64("VNM_PART_RING", 7) & 4);   // (16-entry rings, 128-byte blocks, one pair per lane)
     {
         KernelTimer timer("agg_part_scatter1", s);
-        if (ring1) VNM_TRY(pick_bool(p1.has_pred && !p1.pred_is_v, [&](auto pv) { return launch_dyn(pring_scatter_kernel<true, 2, 16, decltype(pv)::value>, grid1, PT_BLOCK, pring_lds(np1), s, p1, pring_cap(np1)); }));
-        else if (!wide) part_scatter_kernel<true><<<grid1, PT_BLOCK, 0, s>>>(p1);
-        else VNM_TRY((pick_int<1, 7>(E, [&](auto e) { return launch_dyn(part_scatter_wide_kernel<true, decltype(e)::value, pw_items(decltype(e)::value)>, grid1, PT_BLOCK, (size_t)pw_tile(E) * ebytes, s, p1); })));
+        if (p.ring1) VNM_TRY(pick_bool(p1.has_pred && !p1.pred_is_v, [&](auto pv) { return launch_dyn(pring_scatter_kernel<true, 2, 16, decltype(pv)::value>, p.grid1, PT_BLOCK, p.rlds1, s, p1, p.rcap1); }));
+        else if (!p.wide) part_scatter_kernel<true><<<p.grid1, PT_BLOCK, 0, s>>>(p1);
+        else VNM_TRY((pick_int<1, 7>(p.E, [&](auto e) { return launch_dyn(part_scatter_wide_kernel<true, decltype(e)::value, pw_items(decltype(e)::value)>, p.grid1, PT_BLOCK, (size_t)pw_tile(p.E) * p.ebytes, s, p1); })));
     }
     VNM_HIP(hipGetLastError());
-    // A region overflowed (skewed keys, or more rows per partition than the hint implied): stop here.  Carrying on
-    // would aggregate partitions that are about to be thrown away -- and the partition holding a heavy key is
-    // processed by ONE workgroup (measured: 1.6 s for 1e8 rows with a power-law key distribution).
-    auto overflowed = [&]() -> int {
-        unsigned long long f = 0;
-        if (hipMemcpyAsync(&f, flags, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return -1;
-        return f ? 1 : 0;
-    };
+    return hash_check_overflow(b, p.ring1, s);
+}
+
+// Stage 3: scatter level 2 (takes its blocks), every first-level partition -> np2 partitions by the hash bits [23:15] (pass 1 used [31:24]).
+int hash_scatter2(const vnm_agg* h, const AggArgs& a, const HashPlan& p, HashBuffers& b, hipStream_t s) {
+    b.take(b.e2, (size_t)p.np1 * p.np2 * p.split2 * p.cap2 * p.ebytes); b.take(b.c2, (size_t)p.np1 * p.np2 * p.split2 * 4);
+    if (!b.e2 || !b.c2) return 1;
+    PartArgs p2 = hash_part_args(h, a, p, b);
+    p2.in_entries = b.e1; p2.in_counts = b.c1; p2.in_cap = p.cap1; p2.in_regions = p.grid1; p2.in_split = p.split2;
+    p2.out_entries = b.e2; p2.out_counts = b.c2; p2.out_cap = p.cap2;
+    p2.nparts = p.np2; p2.shift = 15;
     {
-        int ov = overflowed();
-        if (ov > 0 && ring1) {   // (a full region / a heavy key: the ring form has no spill buffer -- once more through the tile-sorting scatter)
-            h->pring_off = true;
-            route_note("hash_partitions:rings_failed", "a region overflowed or a sub-tile needed too many rounds: the tile-sorting scatter takes the batch and every later one");
-            pool.done(e1); pool.done(c1); pool.done(flags); pool.done(spill);
-            return partitioned_aggregate(h, a, nrows, s, spill_out, n_spill_out);
-        }
-        if (ov) return ov < 0 ? set_error("aggregate: partition pass failed") : 2;
+        KernelTimer timer("agg_part_scatter2", s);
+        const int g2 = p.np1 * p.split2;
+        const int np2 = p.np2; const size_t ebytes = p.ebytes;
+        if (p.ring2) VNM_TRY(launch_dyn(pring_scatter_kernel<false, 2, 16, false>, g2, PT_BLOCK, p.rlds2, s, p2, p.rcap2));
+        else if (p.ring2_512) VNM_TRY(launch_dyn(pring_scatter_kernel<false, 1, 8, false>, g2, PT_BLOCK, p.rlds2, s, p2, p.rcap2));
+        else if (!p.wide) part_scatter_kernel<false><<<g2, PT_BLOCK, 0, s>>>(p2);
+        else VNM_TRY((pick_int<1, 7>(p.E, [&](auto e) {   // (one- and two-word entries: 8 items per lane only where the level has many sub-partitions)
+            constexpr int EW = decltype(e)::value;
+            if constexpr (EW <= 2) { if (np2 < 128) return launch_dyn(part_scatter_wide_kernel<false, EW, 4>, g2, PT_BLOCK, (size_t)PT_BLOCK * 4 * ebytes, s, p2); }
+            return launch_dyn(part_scatter_wide_kernel<false, EW, pw_items(EW)>, g2, PT_BLOCK, (size_t)PT_BLOCK * pw_items(EW) * ebytes, s, p2);
+        })));
     }
-    if (ring1) route_note("hash_partitions:rings", "%d x %d partitions: (key, value) entries through LDS rings, whole 256-byte blocks out", np1, np2);
+    VNM_HIP(hipGetLastError());
+    return hash_check_overflow(b, p.ring2 || p.ring2_512, s);
+}
 
-    const ulonglong2* fin_e = e1;
-    const uint32_t* fin_c = c1;
-    int64_t fin_cap = cap1, nfinal = np1;
-    int fin_regions = grid1;
-    ulonglong2* e2 = nullptr;
-    uint32_t* c2 = nullptr;
-    if (levels == 2) {
-        // worst case: every row survived and spread evenly; 25 % slack + constant
-        const int64_t per_pg = (int64_t)grid1 * rows_per_wg / np1 / split2;
-        const int64_t cap2 = per_pg / np2 + (int64_t)((double)(per_pg / np2) * std::max(0.25, slack)) + 256;
-        e2 = (ulonglong2*)pool.take((size_t)np1 * np2 * split2 * cap2 * ebytes);
-        c2 = (uint32_t*)pool.take((size_t)np1 * np2 * split2 * 4);
-        if (!e2 || !c2) return 1;
-        PartArgs p2{};
-        p2.in_entries = e1; p2.in_counts = c1; p2.in_cap = cap1; p2.in_regions = grid1; p2.in_split = split2;
-        p2.out_entries = e2; p2.out_counts = c2; p2.out_cap = cap2;
-        p2.nparts = np2; p2.shift = 15; p2.flags = flags;  // hash bits [23:15] (pass 1 used [31:24])
-        p2.debug = p1.debug;
-        p2.spill = spill; p2.spill_cap = spill_cap;
-        p2.nval = h->plan.n_cols;
-        p2.has_vmask = a.part_vmask;
-        {
-            KernelTimer timer("agg_part_scatter2", s);
-            const int g2 = np1 * p2.in_split;
-            if (ring2) VNM_TRY(launch_dyn(pring_scatter_kernel<false, 2, 16, false>, g2, PT_BLOCK, pring_lds(np2), s, p2, pring_cap(np2)));
-            else if (ring2_512) VNM_TRY(launch_dyn(pring_scatter_kernel<false, 1, 8, false>, g2, PT_BLOCK, (size_t)512 * 16 * 16, s, p2, 16));
-            else if (!wide) part_scatter_kernel<false><<<g2, PT_BLOCK, 0, s>>>(p2);
-            else VNM_TRY((pick_int<1, 7>(E, [&](auto e) {   // (one- and two-word entries: 8 items per lane only where the level has many sub-partitions)
-                constexpr int EW = decltype(e)::value;
-                if constexpr (EW <= 2) { if (np2 < 128) return launch_dyn(part_scatter_wide_kernel<false, EW, 4>, g2, PT_BLOCK, (size_t)PT_BLOCK * 4 * ebytes, s, p2); }
-                return launch_dyn(part_scatter_wide_kernel<false, EW, pw_items(EW)>, g2, PT_BLOCK, (size_t)PT_BLOCK * pw_items(EW) * ebytes, s, p2);
-            })));
-        }
-        VNM_HIP(hipGetLastError());
-        {
-            int ov = overflowed();
-            if (ov > 0 && (ring2 || ring2_512)) {
-                h->pring_off = true;
-                route_note("hash_partitions:rings_failed", "level 2: a region overflowed or a sub-tile needed too many rounds: the tile-sorting scatter takes the batch and every later one");
-                pool.done(e1); pool.done(c1); pool.done(e2); pool.done(c2); pool.done(flags); pool.done(spill);
-                return partitioned_aggregate(h, a, nrows, s, spill_out, n_spill_out);
-            }
-            if (ov) return ov < 0 ? set_error("aggregate: partition pass failed") : 2;
-        }
-        fin_e = e2; fin_c = c2; fin_cap = cap2; nfinal = (int64_t)np1 * np2; fin_regions = p2.in_split;
-    }
-
-    // few final partitions cannot fill the chip with one workgroup each: split them and merge through the
-    // HBM table (only legal while the table holds nothing else, so a failed attempt can simply be dropped)
-    int splits = 1;
-    if (nfinal < (int64_t)cus * 4) {
-        splits = (int)std::min<int64_t>(256, ((int64_t)cus * 8 + nfinal - 1) / nfinal);
-        if (splits > fin_regions) splits = fin_regions;
-    }
-    // Merging straight into the HBM table is only legal while the table holds nothing else (a failed attempt is then
-    // simply dropped).  With groups already in the table -- every batch of a stream after the first -- the split
-    // workgroups write their PARTIAL groups (a key may appear once per split) into a dense run instead, which is folded
-    // into the table like any other run: no flush storms for streamed input with 2.4 K ... 900 K groups (ADVICE r01).
-    const bool to_table = splits > 1 && !(h->have_table || h->have_run);
-    const bool dup_run = splits > 1 && !to_table;
+// Stage 4: how the final pass writes -- after the scatters, because it goes by what the handle holds NOW.
+void hash_plan_final(const vnm_agg* h, int64_t nrows, HashPlan& p) {
+    const int cus = device_info().num_cus;
+    // few final partitions cannot fill the chip with one workgroup each: split them and merge through the HBM table
+    p.splits = p.nfin < (int64_t)cus * 4 ? std::min((int)std::min<int64_t>(256, ((int64_t)cus * 8 + p.nfin - 1) / p.nfin), p.fin_regions) : 1;
+    // ... which is only legal while the table holds nothing else (a failed attempt is then simply dropped).  With groups already in
+    // the table -- every batch of a stream after the first -- the split workgroups write their PARTIAL groups (a key may appear once
+    // per split) into a dense run instead, which is folded into the table like any other run: no flush storms for streamed input
+    // with 2.4 K ... 900 K groups (ADVICE r01).
+    p.to_table = p.splits > 1 && !(h->have_table || h->have_run);
+    p.dup_run = p.splits > 1 && !p.to_table;
     // dense output sized from the hint (guarded in the kernel)
-    const int64_t dstride = to_table ? 2 : std::min<int64_t>(nrows, (h->hint * 2 + (1 << 20)) * (dup_run ? splits : 1)) + 2;
-    uint64_t* rk = (uint64_t*)pool.take((size_t)dstride * 8 * 2);
-    uint64_t* ra = (uint64_t*)pool.take((size_t)dstride * 8 * h->plan.n_words);
-    if (!rk || !ra) return 1;
-    unsigned long long* dir = nullptr;
-    if (!to_table && !dup_run) {   // the partition directory only describes runs with ONE workgroup per partition
-        dir = (unsigned long long*)pool.take((size_t)nfinal * 16);
-        if (!dir) return 1;
-    }
+    p.dstride = p.to_table ? 2 : std::min<int64_t>(nrows, (h->hint * 2 + (1 << 20)) * (p.dup_run ? p.splits : 1)) + 2;
+}
+
+// Stage 5: the final pass (takes the run and its directory), one LDS hash table per (share of a) partition.
+int hash_final(vnm_agg* h, const AggArgs& a, int64_t nrows, const HashPlan& p, HashBuffers& b, hipStream_t s) {
+    const int cus = device_info().num_cus;
+    b.take(b.rk, (size_t)p.dstride * 8 * 2); b.take(b.ra, (size_t)p.dstride * 8 * h->plan.n_words);
+    if (!b.rk || !b.ra) return 1;
+    if (!p.to_table && !p.dup_run) b.take(b.dir, (size_t)p.nfin * 16);   // the partition directory only describes runs with ONE workgroup per partition
+    if (!p.to_table && !p.dup_run && !b.dir) return 1;
     PartAggArgs pa{};
-    pa.dir = dir;
-    pa.splits = splits;
-    pa.to_table = to_table;
-    if (to_table) {
+    pa.dir = b.dir; pa.splits = p.splits; pa.to_table = p.to_table;
+    if (p.to_table) {
         VNM_TRY(ensure_table(h, nrows, s));
         // every resident workgroup may pass the room check and then insert a full LDS table at once
-        const int64_t g3max = std::min<int64_t>(nfinal * splits, (int64_t)cus * 4);
+        const int64_t g3max = std::min<int64_t>(p.nfin * p.splits, (int64_t)cus * 4);
         const uint64_t want = pow2_at_least(std::max<uint64_t>((uint64_t)h->hint * 4 + 8192, (uint64_t)(g3max * PA_SLOTS * 2)));
         if (h->g.cap < want) VNM_TRY(table_grow(h, want, s));
         pa.g = h->g;
         pa.table_limit = (int64_t)(h->g.cap * 8 / 10) - g3max * PA_SLOTS;
     }
-    pa.entries = fin_e; pa.counts = fin_c; pa.cap = fin_cap; pa.regions = fin_regions; pa.nfinal = nfinal;
+    const bool two = p.levels == 2;   // the last level's regions
+    pa.entries = two ? b.e2 : b.e1; pa.counts = two ? b.c2 : b.c1; pa.cap = two ? p.cap2 : p.cap1; pa.regions = p.fin_regions; pa.nfinal = p.nfin;
     pa.w_rows = a.hot_w_rows; pa.w_valid = a.hot_w_valid; pa.w_sum = a.hot_w_sum; pa.n_words = h->plan.n_words;
-    pa.w_lo = a.hot_comp && a.hot_w_sum >= 0 ? a.hot_w_sum + 1 : -1;
-    pa.comp = a.hot_comp;
-    pa.dkey = rk; pa.dacc = ra; pa.dstride = dstride; pa.flags = flags;
-    {
-        KernelTimer timer("agg_part_final", s);
-        if (a.part_generic) {
-            pa.n_ops = h->plan.n_ops;
-            pa.vtype = a.part_vtype;
-            for (int o = 0; o < h->plan.n_ops; o++) pa.ops[o] = h->plan.ops[o];
-            for (int w = 0; w < h->plan.n_words; w++) pa.merge[w] = h->plan.merge[w];
-            const size_t lds_bytes = (size_t)(pa_slots + 1) * 8 * (1 + h->plan.n_words);
-            pa.slots = pa_slots;
-            pa.ent_words = E;
-            pa.wide = wide;
-            pa.has_vmask = a.part_vmask;
-            for (int c = 0; c < 6; c++) pa.vtypes[c] = a.part_vtypes[c];
-            pa.nval = h->plan.n_cols;
-            pa.w_rows_g = -1;
-            pa.use_table = getenv("VNM_AGG_NO_PART_TABLE") == nullptr;
-            for (int c = 0; c < 6; c++) pa.wpack[c] = ~0ULL;
-            for (int o = 0; o < h->plan.n_ops && pa.use_table; o++) {
-                const AccOp& op = h->plan.ops[o];
-                if (op.kind == A_COUNT_ROWS) { if (pa.w_rows_g >= 0) pa.use_table = 0; pa.w_rows_g = op.word; continue; }
-                const int c = op.col < 0 ? 0 : op.col;
-                if (c > 5 || op.kind < 0 || op.kind > A_MAX || op.word >= 63 || ((pa.wpack[c] >> (6 * op.kind)) & 63ULL) != 63) { pa.use_table = 0; break; }
-                pa.wpack[c] = (pa.wpack[c] & ~(63ULL << (6 * op.kind))) | ((unsigned long long)op.word << (6 * op.kind));
-            }
-            VNM_TRY((pick_int<1, 7>(E, [&](auto e) {
-                return pick_bool(pa.use_table != 0, [&](auto t) { return launch_part_final(part_agg_generic_kernel<decltype(e)::value, decltype(t)::value>, nfinal * splits, lds_bytes, s, pa); });
-            })));
-        } else VNM_TRY(launch_part_final(part_agg_kernel, nfinal * splits, 0, s, pa));
+    pa.w_lo = a.hot_comp && a.hot_w_sum >= 0 ? a.hot_w_sum + 1 : -1; pa.comp = a.hot_comp;
+    pa.dkey = b.rk; pa.dacc = b.ra; pa.dstride = p.dstride; pa.flags = b.flags;
+    KernelTimer timer("agg_part_final", s);
+    if (!a.part_generic) return launch_part_final(part_agg_kernel, p.nfin * p.splits, 0, s, pa);
+    pa.n_ops = h->plan.n_ops; pa.nval = h->plan.n_cols; pa.vtype = a.part_vtype; pa.has_vmask = a.part_vmask;
+    pa.slots = p.pa_slots; pa.ent_words = p.E; pa.wide = p.wide;
+    for (int o = 0; o < h->plan.n_ops; o++) pa.ops[o] = h->plan.ops[o];
+    for (int w = 0; w < h->plan.n_words; w++) pa.merge[w] = h->plan.merge[w];
+    for (int c = 0; c < 6; c++) pa.vtypes[c] = a.part_vtypes[c];
+    const size_t lds_bytes = (size_t)(p.pa_slots + 1) * 8 * (1 + h->plan.n_words);
+    pa.w_rows_g = -1;
+    pa.use_table = getenv("VNM_AGG_NO_PART_TABLE") == nullptr;
+    // 6 bits per AccKind and column: the word its op accumulates in, 63 = none (dgen_program: ONE column, LDS places, COUNT(*) first)
+    for (int c = 0; c < 6; c++) pa.wpack[c] = ~0ULL;
+    for (int o = 0; o < h->plan.n_ops && pa.use_table; o++) {
+        const AccOp& op = h->plan.ops[o];
+        if (op.kind == A_COUNT_ROWS) { if (pa.w_rows_g >= 0) pa.use_table = 0; pa.w_rows_g = op.word; continue; }
+        const int c = op.col < 0 ? 0 : op.col;
+        if (c > 5 || op.kind < 0 || op.kind > A_MAX || op.word >= 63 || ((pa.wpack[c] >> (6 * op.kind)) & 63ULL) != 63) { pa.use_table = 0; break; }
+        pa.wpack[c] = (pa.wpack[c] & ~(63ULL << (6 * op.kind))) | ((unsigned long long)op.word << (6 * op.kind));
     }
-    VNM_HIP(hipGetLastError());
-    unsigned long long fl[3];
-    VNM_HIP(hipMemcpyAsync(fl, flags, 24, hipMemcpyDeviceToHost, s));
-    VNM_HIP(hipStreamSynchronize(s));
-    pool.done(e1); pool.done(c1); pool.done(e2); pool.done(c2); pool.done(flags);
-    if (fl[0]) {  // more groups than hinted / spill buffer full: use the general path for this batch
-        if (to_table) { table_free(&h->g); h->have_table = false; }  // drop the partial merge
-        return 3;  // only the final pass fails this way: the hint was too small, more partitions would do
-    }
-    if (spill_out) {
-        if (fl[2]) { pool.keep(spill); *spill_out = spill; *n_spill_out = (int64_t)fl[2]; }   // the caller owns it now
-        else { *spill_out = nullptr; *n_spill_out = 0; }
-    }
-    if (to_table) return 0;  // the groups already live in the HBM table
-    pool.keep(rk); pool.keep(ra); pool.keep(dir);   // the run belongs to the handle
-    h->run_key = rk; h->run_acc = ra; h->run_stride = dstride; h->run_n = (int64_t)fl[1];
-    h->run_dir = dir; h->run_nfin = dir ? nfinal : 0;
-    h->have_run = true;
-    if (dup_run) {   // keys repeat inside this run: it must never be handed out as a result, fold it into the table now
-        if (merge_run_into_table(h, s)) return 1;
-    }
-    return 0;
+    return pick_int<1, 7>(p.E, [&](auto e) {
+        return pick_bool(pa.use_table != 0, [&](auto t) { return launch_part_final(part_agg_generic_kernel<decltype(e)::value, decltype(t)::value>, p.nfin * p.splits, lds_bytes, s, pa); });
+    });
 }
 
+// Stage 6.  0 = done, 3 = more groups than hinted / spill buffer full (only the final pass fails so: more partitions would do).
+int hash_hand_over(vnm_agg* h, const HashPlan& p, HashBuffers& b, hipStream_t s, ulonglong2** spill_out, int64_t* n_spill_out) {
+    VNM_HIP(hipGetLastError());
+    unsigned long long fl[3]; VNM_TRY(read_flags(fl, b.flags, s));
+    b.release_regions();
+    if (fl[0] && p.to_table) { table_free(&h->g); h->have_table = false; }  // drop the partial merge
+    if (fl[0]) return 3;   // use the general path for this batch
+    if (spill_out) {
+        if (fl[2]) { b.pool.keep(b.spill); *spill_out = b.spill; *n_spill_out = (int64_t)fl[2]; }   // the caller owns it now
+        else { *spill_out = nullptr; *n_spill_out = 0; }
+    }
+    if (p.to_table) return 0;  // the groups already live in the HBM table
+    b.pool.keep(b.rk); b.pool.keep(b.ra); b.pool.keep(b.dir);
+    adopt_run(h, b.rk, b.ra, p.dstride, (int64_t)fl[1], b.dir, b.dir ? p.nfin : 0);
+    // keys repeat inside a dup_run: it must never be handed out as a result, fold it into the table now
+    return p.dup_run && merge_run_into_table(h, s) ? 1 : 0;
+}
+
+// The driver.  returns 0 = done (run stored), 2 = not applicable / overflowed (caller uses the general path), 3 = hint too small, 1 = error
+// spill_out / n_spill_out (optional): entries that did not fit their partition region (heavy keys); the caller
+// aggregates them with agg_hot_kernel<FROM_ENT> and owns the buffer.  Without them a full region fails the attempt.
+int partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_t s, ulonglong2** spill_out = nullptr, int64_t* n_spill_out = nullptr) {
+    HashPlan p{};
+    VNM_TRY(plan_hash_partitions(h, a, nrows, spill_out != nullptr, &p));
+    HashBuffers b;
+    // a level's rings failed (a full region, a heavy key): the same batch once more without them, the blocks back in the pool first
+    auto redo = [&](const char* level) {
+        h->pring_off = true;
+        route_note("hash_partitions:rings_failed", "%sa region overflowed or a sub-tile needed too many rounds: the tile-sorting scatter takes the batch and every later one", level);
+        b.free_all();
+        return partitioned_aggregate(h, a, nrows, s, spill_out, n_spill_out);
+    };
+    int rc = hash_scatter1(h, a, nrows, p, b, s);
+    if (rc) return rc == ATTEMPT_REDO ? redo("") : rc;
+    if (p.ring1) route_note("hash_partitions:rings", "%d x %d partitions: (key, value) entries through LDS rings, whole 256-byte blocks out", p.np1, p.np2);
+    if (p.levels == 2) {
+        rc = hash_scatter2(h, a, p, b, s);
+        if (rc) return rc == ATTEMPT_REDO ? redo("level 2: ") : rc;
+    }
+    hash_plan_final(h, nrows, p);
+    VNM_TRY(hash_final(h, a, nrows, p, b, s));
+    return hash_hand_over(h, p, b, s, spill_out, n_spill_out);
+}
 
 // ---- dense-key partitioned path: host side (kernels in vnm_agg_dense.inc) ------------------------------------
 // Sample the key range of the first large batch and derive the code map.  dense_state = 1 when the (widened) range fits
@@ -483,129 +515,116 @@ bool dgen_program(const vnm_agg* h, const AggArgs& a, DGenArgs* g) {
 inline int dgen_slot_bytes(const DGenArgs& g) { return 8 * g.n_lds + 4; }
 
 int upload_segs(vnm_agg* h, int64_t tile, const VSeg** dev, int* nseg, int64_t* ntiles, PoolScope& pool, hipStream_t s);
-// Ranges of at most 2^13 codes: one scan with the whole table in LDS.  Same return convention as the partitioned variant.
-int dense_scan_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_t s, ulonglong2** spill_out, int64_t* n_spill_out, bool generic = false,
-                         uint64_t** nspill_out = nullptr, int64_t* n_nspill_out = nullptr) {
-    const int cus = device_info().num_cus;
-    if (h->dmap.bits != DP_TBITS_MAX) return 2;
-    const int block = 1024;
+// ---- ranges of at most 2^13 codes: one scan with the whole table in LDS, no scatter ----------------------------------------------
+// dense_scan_generic: any program dgen_program can express, a run of its own; dense_scan_stream: the hot program, into the stream's table.
+// Same return convention as the partitioned variant.  Their code map: the plain code, no Fibonacci mix; false = not a small range.
+inline bool dense_scan_map(const vnm_agg* h, DenseMap* map) { *map = h->dmap; map->mul = 1; map->mul_inv = 1; return h->dmap.bits == DP_TBITS_MAX; }
+// the largest table (<= 2^13 slots) that fits 144 KB of LDS must hold the sampled range (2: it does not), centred in a smaller one
+int plan_scan_generic(const vnm_agg* h, DGenArgs* g) {
+    int tb = DP_TBITS_MAX;
+    while (tb > 9 && ((size_t)dgen_slot_bytes(*g) << tb) > 144 * 1024) tb--;
+    const uint64_t need = h->dense_rhi - h->dense_rlo;
+    if (need >= (1ULL << tb)) return 2;
+    if (tb != DP_TBITS_MAX) {
+        const uint64_t extra = ((1ULL << tb) - 1) - need;
+        g->map.lo_u = h->dense_rlo > extra / 2 ? h->dense_rlo - extra / 2 : 0;
+        g->map.bits = tb;
+        g->map.mask = (uint32_t)((1ULL << tb) - 1);
+    }
+    g->tbits = tb;
+    return 0;
+}
+
+// (nspill_out / n_nspill_out: keys of NULL-value rows, a nullable value column; without them such a column is not taken)
+int dense_scan_generic(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_t s, ulonglong2** spill_out, int64_t* n_spill_out, uint64_t** nspill_out, int64_t* n_nspill_out) {
+    DenseMap map;
+    if (!dense_scan_map(h, &map)) return 2;
     if (nspill_out) { *nspill_out = nullptr; *n_nspill_out = 0; }
-    if (generic) {
-        DGenArgs g{};
-        if (!dgen_program(h, a, &g)) return 2;
-        const bool vn = g.has_val && a.cols[0].validity != nullptr;   // nullable value column
-        if (vn && !nspill_out) return 2;
-        // the largest table (<= 2^13 slots) that fits 144 KB of LDS must hold the sampled range
-        int tb = DP_TBITS_MAX;
-        while (tb > 9 && ((size_t)dgen_slot_bytes(g) << tb) > 144 * 1024) tb--;
-        const uint64_t need = h->dense_rhi - h->dense_rlo;
-        if (need >= (1ULL << tb)) return 2;
-        const int slots = 1 << tb;
-        const size_t lds = (size_t)slots * dgen_slot_bytes(g);
-        const int per_cu = lds <= 72 * 1024 ? 2 : 1;
-        const int grid = (int)std::min<int64_t>((int64_t)cus * per_cu, std::max<int64_t>(1, (nrows / 2 + block - 1) / block));
-        PoolScope pool;
-        unsigned long long* flags = (unsigned long long*)pool.take(64);
-        uint64_t* pw = (uint64_t*)pool.take(std::max<size_t>(8, (size_t)grid * g.n_lds * slots * 8));
-        uint32_t* pc = (uint32_t*)pool.take((size_t)grid * slots * 4);
-        const int64_t spill_cap = nrows / 2 + (1 << 20);
-        ulonglong2* spill = (ulonglong2*)pool.take((size_t)spill_cap * 16);
-        const int64_t nspill_cap = vn ? nrows / 4 + (1 << 20) : 0;
-        uint64_t* nspill = vn ? (uint64_t*)pool.take((size_t)nspill_cap * 8) : nullptr;
-        const int64_t dstride = slots + 2;
-        uint64_t* rk = (uint64_t*)pool.take((size_t)dstride * 8 * 2);
-        uint64_t* ra = (uint64_t*)pool.take((size_t)dstride * 8 * std::max(1, h->plan.n_words));
-        if (!flags || !pw || !pc || !spill || !rk || !ra || (vn && !nspill)) return 1;
-        VNM_HIP(hipMemsetAsync(flags, 0, 64, s));
-        g.map = h->dmap; g.map.mul = 1; g.map.mul_inv = 1;
-        if (tb != DP_TBITS_MAX) {   // a smaller table: centre the sampled range in it
-            const uint64_t extra = ((1ULL << tb) - 1) - need;
-            g.map.lo_u = h->dense_rlo > extra / 2 ? h->dense_rlo - extra / 2 : 0;
-            g.map.bits = tb;
-            g.map.mask = (uint32_t)((1ULL << tb) - 1);
-        }
-        g.tbits = tb;
-        g.kp = (const uint64_t*)a.keys[0].values + a.keys[0].offset;
-        g.vp = g.has_val ? (const double*)a.cols[0].values + a.cols[0].offset : nullptr;
-        g.pp = h->pred_set ? (const double*)a.pred.values + a.pred.offset : nullptr;
-        g.has_pred = h->pred_set; g.pred_is_v = a.hot_pred_is_v; g.op = a.p.op; g.thr = a.p.dval;
-        g.nrows = nrows;
-        g.spill = spill; g.spill_cap = spill_cap;
-        if (vn) { g.vvalid = a.cols[0].validity; g.voff = a.cols[0].offset; g.nspill = nspill; g.nspill_cap = nspill_cap; }
-        g.dkey = rk; g.dacc = ra; g.dstride = dstride; g.flags = flags;
-        g.nfinal = 1; g.splits = grid; g.part_w = pw; g.part_cnt = pc;
-        {
-            KernelTimer timer("agg_scan", s);
-            if (vn) {
-                VNM_HIP(hipFuncSetAttribute((const void*)dgen_scan_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                dgen_scan_kernel<true, true><<<grid, block, lds, s>>>(g);
-            } else if (g.has_val) {
-                VNM_HIP(hipFuncSetAttribute((const void*)dgen_scan_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                dgen_scan_kernel<true><<<grid, block, lds, s>>>(g);
-            } else {
-                VNM_HIP(hipFuncSetAttribute((const void*)dgen_scan_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                dgen_scan_kernel<false><<<grid, block, lds, s>>>(g);
-            }
-            dgen_merge_kernel<<<std::max(1, slots / 512), 512, 0, s>>>(g);
-        }
-        VNM_HIP(hipGetLastError());
-        unsigned long long fl[4];
-        VNM_HIP(hipMemcpyAsync(fl, flags, 32, hipMemcpyDeviceToHost, s));
-        VNM_HIP(hipStreamSynchronize(s));
-        if (fl[0]) return 2;
-        if (fl[2]) { pool.keep(spill); *spill_out = spill; *n_spill_out = (int64_t)fl[2]; }
-        else { *spill_out = nullptr; *n_spill_out = 0; }
-        if (vn && fl[3]) { pool.keep(nspill); *nspill_out = nspill; *n_nspill_out = (int64_t)fl[3]; }
-        if ((int64_t)(fl[2] + fl[3]) > nrows / 16) h->dense_state = -1;
-        pool.keep(rk); pool.keep(ra);
-        h->run_key = rk; h->run_acc = ra; h->run_stride = dstride; h->run_n = (int64_t)fl[1];
-        h->run_dir = nullptr; h->run_nfin = 0;
-        h->have_run = true;
-        return 0;
+    DGenArgs g{};
+    if (!dgen_program(h, a, &g)) return 2;
+    const bool vn = g.has_val && a.cols[0].validity != nullptr;   // nullable value column
+    if (vn && !nspill_out) return 2;
+    g.map = map;
+    VNM_TRY(plan_scan_generic(h, &g));
+    const int block = 1024, slots = 1 << g.tbits;
+    const size_t lds = (size_t)slots * dgen_slot_bytes(g);
+    const int grid = (int)std::min<int64_t>((int64_t)device_info().num_cus * (lds <= 72 * 1024 ? 2 : 1), std::max<int64_t>(1, (nrows / 2 + block - 1) / block));
+    const int64_t spill_cap = nrows / 2 + (1 << 20), nspill_cap = vn ? nrows / 4 + (1 << 20) : 0, dstride = slots + 2;
+    AttemptBlocks b;
+    unsigned long long* flags; uint64_t *pw, *rk, *ra, *nspill = nullptr; uint32_t* pc; ulonglong2* spill;
+    b.take(flags, 64); b.take(pw, std::max<size_t>(8, (size_t)grid * g.n_lds * slots * 8)); b.take(pc, (size_t)grid * slots * 4);
+    b.take(spill, (size_t)spill_cap * 16); if (vn) b.take(nspill, (size_t)nspill_cap * 8);
+    b.take(rk, (size_t)dstride * 8 * 2); b.take(ra, (size_t)dstride * 8 * std::max(1, h->plan.n_words));
+    if (!flags || !pw || !pc || !spill || !rk || !ra || (vn && !nspill)) return 1;
+    VNM_HIP(hipMemsetAsync(flags, 0, 64, s));
+    g.kp = (const uint64_t*)a.keys[0].values + a.keys[0].offset;
+    g.vp = g.has_val ? (const double*)a.cols[0].values + a.cols[0].offset : nullptr;
+    fill_pred(g, h, a);
+    g.nrows = nrows; g.spill = spill; g.spill_cap = spill_cap;
+    if (vn) { g.vvalid = a.cols[0].validity; g.voff = a.cols[0].offset; g.nspill = nspill; g.nspill_cap = nspill_cap; }
+    g.dkey = rk; g.dacc = ra; g.dstride = dstride; g.flags = flags;
+    g.nfinal = 1; g.splits = grid; g.part_w = pw; g.part_cnt = pc;
+    {
+        KernelTimer timer("agg_scan", s);
+        VNM_TRY(pick_bool(g.has_val != 0, [&](auto hv) {
+            if constexpr (decltype(hv)::value) { if (vn) return launch_dyn(dgen_scan_kernel<true, true>, grid, block, lds, s, g); }
+            return launch_dyn(dgen_scan_kernel<decltype(hv)::value>, grid, block, lds, s, g);
+        }));
+        dgen_merge_kernel<<<std::max(1, slots / 512), 512, 0, s>>>(g);
     }
-    const int tb = DP_TBITS_MAX;
-    const int slots = 1 << tb;
-    const int grid = (int)std::min<int64_t>((int64_t)cus, std::max<int64_t>(1, (nrows / 2 + block - 1) / block));
-    // The batch's per-workgroup tables are added into the table of the STREAM (h->scan_pending, dscan_accumulate_kernel); the groups
-    // are written when something else needs them (flush_scan_pending).  59 x 2^24-row batches, G = 1000: 17.1 -> 5.5 ms per 1e9 rows.
-    DenseMap map = h->dmap;
-    map.mul = 1; map.mul_inv = 1;
+    VNM_HIP(hipGetLastError());
+    unsigned long long fl[4]; VNM_TRY(read_flags(fl, flags, s));
+    if (fl[0]) return 2;
+    if (fl[2]) { b.pool.keep(spill); *spill_out = spill; *n_spill_out = (int64_t)fl[2]; }
+    else { *spill_out = nullptr; *n_spill_out = 0; }
+    if (vn && fl[3]) { b.pool.keep(nspill); *nspill_out = nspill; *n_nspill_out = (int64_t)fl[3]; }
+    if ((int64_t)(fl[2] + fl[3]) > nrows / 16) h->dense_state = -1;
+    b.pool.keep(rk); b.pool.keep(ra);
+    adopt_run(h, rk, ra, dstride, (int64_t)fl[1]);
+    return 0;
+}
+
+// The table a stream of small-range batches accumulates in, empty (h->scan_pending).
+int scan_pending_create(vnm_agg* h, const DenseMap& map, const AggArgs& a, hipStream_t s) {
+    const int cus = device_info().num_cus, slots = 1 << DP_TBITS_MAX;
+    std::unique_ptr<DScanPending> sp(new DScanPending());
+    sp->slots = slots; sp->df.map = map;
+    sp->df.w_rows = a.hot_w_rows; sp->df.w_valid = a.hot_w_valid; sp->df.w_sum = a.hot_w_sum;
+    sp->df.w_lo = a.hot_comp && a.hot_w_sum >= 0 ? a.hot_w_sum + 1 : -1;
+    sp->t.sum = (double*)pool_alloc((size_t)slots * 8); sp->t.lo = (double*)pool_alloc((size_t)slots * 8);
+    sp->t.cnt = (unsigned long long*)pool_alloc((size_t)slots * 8);
+    sp->part_sum = (uint64_t*)pool_alloc((size_t)cus * slots * 8);
+    sp->part_lo = (float*)pool_alloc((size_t)cus * slots * 4); sp->part_cnt = (uint32_t*)pool_alloc((size_t)cus * slots * 4);
+    sp->flags = (unsigned long long*)pool_alloc(64);
+    if (!sp->t.sum || !sp->t.lo || !sp->t.cnt || !sp->part_sum || !sp->part_lo || !sp->part_cnt || !sp->flags) return 1;
+    fill_u64_kernel<<<(slots + 255) / 256, 256, 0, s>>>((uint64_t*)sp->t.sum, F64_NEG_ZERO, (int64_t)slots);   // (sums start at -0.0: merge_init)
+    if (hipGetLastError() != hipSuccess || hipMemsetAsync(sp->t.lo, 0, (size_t)slots * 8, s) != hipSuccess ||
+        hipMemsetAsync(sp->t.cnt, 0, (size_t)slots * 8, s) != hipSuccess) return set_error("aggregate: memset of the stream table failed");
+    h->scan_pending = sp.release();
+    return 0;
+}
+
+// The batch's per-workgroup tables are added into the table of the STREAM (h->scan_pending, dscan_accumulate_kernel); the groups
+// are written when something else needs them (flush_scan_pending).  59 x 2^24-row batches, G = 1000: 17.1 -> 5.5 ms per 1e9 rows.
+int dense_scan_stream(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_t s, ulonglong2** spill_out, int64_t* n_spill_out) {
+    DenseMap map;
+    if (!dense_scan_map(h, &map)) return 2;
+    const int block = 1024, slots = 1 << DP_TBITS_MAX;   // always the 2^13-slot table, one workgroup per CU
+    const int grid = (int)std::min<int64_t>((int64_t)device_info().num_cus, std::max<int64_t>(1, (nrows / 2 + block - 1) / block));
     if (h->scan_pending && memcmp(&h->scan_pending->df.map, &map, sizeof(DenseMap)) != 0) VNM_TRY(flush_scan_pending(h, s));
-    const bool comp = a.hot_comp && a.hot_w_sum >= 0;
-    if (!h->scan_pending) {
-        DScanPending* sp = new DScanPending();
-        sp->slots = slots;
-        sp->df.map = map;
-        sp->df.w_rows = a.hot_w_rows; sp->df.w_valid = a.hot_w_valid; sp->df.w_sum = a.hot_w_sum;
-        sp->df.w_lo = comp ? a.hot_w_sum + 1 : -1;
-        sp->t.sum = (double*)pool_alloc((size_t)slots * 8);
-        sp->t.lo = (double*)pool_alloc((size_t)slots * 8);
-        sp->t.cnt = (unsigned long long*)pool_alloc((size_t)slots * 8);
-        sp->part_sum = (uint64_t*)pool_alloc((size_t)cus * slots * 8);
-        sp->part_lo = (float*)pool_alloc((size_t)cus * slots * 4);
-        sp->part_cnt = (uint32_t*)pool_alloc((size_t)cus * slots * 4);
-        sp->flags = (unsigned long long*)pool_alloc(64);
-        if (!sp->t.sum || !sp->t.lo || !sp->t.cnt || !sp->part_sum || !sp->part_lo || !sp->part_cnt || !sp->flags) { delete sp; return 1; }
-        fill_u64_kernel<<<(slots + 255) / 256, 256, 0, s>>>((uint64_t*)sp->t.sum, F64_NEG_ZERO, (int64_t)slots);   // (sums start at -0.0: merge_init)
-        if (hipGetLastError() != hipSuccess || hipMemsetAsync(sp->t.lo, 0, (size_t)slots * 8, s) != hipSuccess ||
-            hipMemsetAsync(sp->t.cnt, 0, (size_t)slots * 8, s) != hipSuccess) { delete sp; return set_error("aggregate: memset of the stream table failed"); }
-        h->scan_pending = sp;
-    }
+    if (!h->scan_pending) VNM_TRY(scan_pending_create(h, map, a, s));
     DScanPending* sp = h->scan_pending;
     const int64_t spill_cap = nrows / 2 + (1 << 20);
     ulonglong2* spill = (ulonglong2*)pool_alloc((size_t)spill_cap * 16);
     if (!spill) return 1;
     PoolSlotGuard<ulonglong2> spill_guard(&spill);
     VNM_HIP(hipMemsetAsync(sp->flags, 0, 64, s));
-    DScanArgs d{};
-    d.map = map;
+    DScanArgs d{}; d.map = map;
     d.kp = (const uint64_t*)a.keys[0].values + a.keys[0].offset;
     d.vp = (const double*)a.cols[0].values + a.cols[0].offset;
     d.has_expr = a.has_expr; d.expr = a.expr;
-    d.pp = h->pred_set ? (const double*)a.pred.values + a.pred.offset : nullptr;
-    d.has_pred = h->pred_set; d.pred_is_v = a.hot_pred_is_v; d.op = a.p.op; d.thr = a.p.dval;
-    d.nrows = nrows;
-    d.comp = comp;
+    fill_pred(d, h, a);
+    d.nrows = nrows; d.comp = a.hot_comp && a.hot_w_sum >= 0;
     d.part_sum = sp->part_sum; d.part_lo = sp->part_lo; d.part_cnt = sp->part_cnt;
     d.flags = sp->flags; d.spill = spill; d.spill_cap = spill_cap;
     PoolScope seg_pool;
@@ -618,8 +637,7 @@ int dense_scan_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_
         KernelTimer timer("agg_scan", s);
         dscan_kernel<DP_TBITS_MAX><<<grid, block, 0, s>>>(d);
         VNM_HIP(hipGetLastError());
-        VNM_HIP(hipMemcpyAsync(fl, sp->flags, 24, hipMemcpyDeviceToHost, s));
-        VNM_HIP(hipStreamSynchronize(s));
+        VNM_TRY(read_flags(fl, sp->flags, s));
         if (fl[0]) return 2;   // spill buffer full or a compensation term beyond float range: the batch goes another way, the stream's table is untouched
         // (segments: keys outside the sampled range would have to go through the scan as entries of their own while the segment table is
         // in force -- rare enough to send the batches another way instead, before anything has been added to the stream's table)
@@ -708,26 +726,16 @@ int upload_segs(vnm_agg* h, int64_t tile, const VSeg** dev, int* nseg, int64_t* 
     return 0;
 }
 
-// Runs the deferred final pass of the dense path.  DF_RUN: the pending state becomes the handle's run (and is released);
-// DF_COLS: `cols` names the output columns (capacity pending->dstride), *n_out = groups written, the pending entries STAY (a later
-// finish() can still produce the partial state); DF_TABLE: the tables go to pending->table (rc 2: compensation terms out of the
-// float range -- the caller uses another exchange).
-int complete_pending(vnm_agg* h, hipStream_t s, int out = DF_RUN, const DFinalArgs* cols = nullptr, int64_t* n_out = nullptr) {
-    DensePending* pd = h->pending;
-    if (!pd) return 0;
-    if (out == DF_RUN && h->have_run) VNM_TRY(merge_run_into_table(h, s));   // (a run of another path: it has to make room)
-    DFinalArgs df = pd->df;
-    PoolScope pool;
-    uint64_t* rk = nullptr; uint64_t* ra = nullptr;
+// ---- the deferred final pass of the dense path, stage by stage (complete_pending below is the driver) -------------------------
+// Stage 1: where the groups go (DF_RUN: a run of `pool`'s blocks, df.dkey / df.dacc), its capacity, a fresh device copy of the sets.
+int pending_bind_output(const vnm_agg* h, DensePending* pd, int out, const DFinalArgs* cols, DFinalArgs& df, PoolScope& pool, hipStream_t s) {
     if (out == DF_RUN) {
-        rk = (uint64_t*)pool.take((size_t)pd->dstride * 8 * 2);
-        ra = (uint64_t*)pool.take((size_t)pd->dstride * 8 * h->plan.n_words);
-        if (!rk || !ra) return 1;
-        df.dkey = rk; df.dacc = ra;
+        df.dkey = (uint64_t*)pool.take((size_t)pd->dstride * 8 * 2);
+        df.dacc = (uint64_t*)pool.take((size_t)pd->dstride * 8 * h->plan.n_words);
+        if (!df.dkey || !df.dacc) return 1;
     } else if (out == DF_COLS) {
-        df.n_out = cols->n_out;
+        df.n_out = cols->n_out; df.pack_n = cols->pack_n;
         for (int c = 0; c < cols->n_out; c++) { df.out_kind[c] = cols->out_kind[c]; df.out_ptr[c] = cols->out_ptr[c]; df.key_field[c] = cols->key_field[c]; }
-        df.pack_n = cols->pack_n;
         for (int j = 0; j < cols->pack_n; j++) { df.pack_shift[j] = cols->pack_shift[j]; df.pack_bits[j] = cols->pack_bits[j]; df.pack_lo[j] = cols->pack_lo[j]; }
         if (cols->has_side) { df.has_side = 1; df.side = cols->side; df.side_bloom = cols->side_bloom; df.side_bloom_mask = cols->side_bloom_mask; df.side_found = cols->side_found; }
     } else {
@@ -741,78 +749,91 @@ int complete_pending(vnm_agg* h, hipStream_t s, int out = DF_RUN, const DFinalAr
     if (!pd->dsets) return 1;
     VNM_HIP(hipMemcpyAsync(pd->dsets, pd->sets.data(), pd->sets.size() * sizeof(DSet), hipMemcpyHostToDevice, s));
     df.sets = pd->dsets; df.nsets = (int)pd->sets.size();
-    unsigned long long fl[5] = {0, 0, 0, 0, 0};
-    uint64_t* psum = nullptr; float* plo = nullptr; uint32_t* pcnt = nullptr;
-    if (pd->fsplits > 1 && df.has_side) return set_error("aggregate: side table with a split final pass (internal error)");
-    if (pd->fsplits > 1) {   // few final partitions: each is shared by `fsplits` workgroups (partial tables + dpart_merge_kernel)
-        const size_t cells = (size_t)pd->nfinal * pd->fsplits << pd->tb;
-        psum = (uint64_t*)pool.take(cells * 8); plo = (float*)pool.take(cells * 4); pcnt = (uint32_t*)pool.take(cells * 4);
-        if (!psum || !plo || !pcnt) return 1;
+    return 0;
+}
+
+// Stage 2, few final partitions: each is shared by `fsplits` workgroups (partial tables + dpart_merge_kernel).
+int pending_final_split(const DensePending* pd, int out, const DFinalArgs& df, PoolScope& pool, hipStream_t s) {
+    const size_t cells = (size_t)pd->nfinal * pd->fsplits << pd->tb;
+    DFinalArgs ds = df; ds.splits = pd->fsplits;
+    ds.part_sum = (uint64_t*)pool.take(cells * 8); ds.part_lo = (float*)pool.take(cells * 4); ds.part_cnt = (uint32_t*)pool.take(cells * 4);
+    if (!ds.part_sum || !ds.part_lo || !ds.part_cnt) return 1;
+    KernelTimer timer("agg_part_final", s);
+    const int g3 = (int)std::min<int64_t>(pd->nfinal * pd->fsplits, (int64_t)device_info().num_cus * 8);
+    pick_int<9, 13>(pd->tb >= 9 && pd->tb <= 12 ? pd->tb : 13, [&](auto tbc) {
+        constexpr int TB = decltype(tbc)::value, blk = TB == 13 ? 1024 : (TB == 12 ? VNM_DF12_BLOCK : 512);
+        dpart_final_kernel<uint16_t, TB, true><<<g3, blk, 0, s>>>(ds);
+        return 0;
+    });
+    if (out != DF_COLS) ds.n_out = 0;
+    dpart_merge_kernel<<<(int)(pd->nfinal << (pd->tb - 9)), 512, 0, s>>>(ds, pd->tb);
+    VNM_HIP(hipGetLastError());
+    return 0;
+}
+// Stage 2, second attempt: 64-bit compensation terms only fit 2^12-slot tables -- partitions of 2^13 slots in two halves (slot bit 12).
+int pending_final_halves(DFinalArgs& df, int out, hipStream_t s) {
+    df.sub_bits = 1;
+    for (int sub = 0; sub < 2; sub++) { df.sub = sub; VNM_TRY(launch_dense_final(df, 12, out, true, s)); }
+    return 0;
+}
+// Stage 2, the usual one (attempt 1: with 64-bit compensation terms): one workgroup per partition, then the side table's groups.
+int pending_final_plain(const DensePending* pd, int out, int attempt, const DFinalArgs& df, hipStream_t s) {
+    if (df.has_side) {
+        VNM_HIP(hipMemsetAsync(df.side_found, 0, (size_t)df.side.cap + 2, s));
+        VNM_HIP(hipMemsetAsync(df.flags + 4, 0, 8, s));
     }
-    for (int attempt = 0; attempt < 2; attempt++) {
-        VNM_HIP(hipMemsetAsync(df.flags, 0, 16, s));   // [0] failure, [1] dense count ([2]: the scatter passes' spill count, consumed)
-        if (attempt == 0 && pd->fsplits > 1) {
-            DFinalArgs ds = df;
-            ds.splits = pd->fsplits; ds.part_sum = psum; ds.part_lo = plo; ds.part_cnt = pcnt;
-            const int cus = device_info().num_cus;
-            KernelTimer timer("agg_part_final", s);
-            const int g3 = (int)std::min<int64_t>(pd->nfinal * pd->fsplits, (int64_t)cus * 8);
-            if (pd->tb == 9) dpart_final_kernel<uint16_t, 9, true><<<g3, 512, 0, s>>>(ds);
-            else if (pd->tb == 10) dpart_final_kernel<uint16_t, 10, true><<<g3, 512, 0, s>>>(ds);
-            else if (pd->tb == 11) dpart_final_kernel<uint16_t, 11, true><<<g3, 512, 0, s>>>(ds);
-            else if (pd->tb == 12) dpart_final_kernel<uint16_t, 12, true><<<g3, VNM_DF12_BLOCK, 0, s>>>(ds);
-            else dpart_final_kernel<uint16_t, 13, true><<<g3, 1024, 0, s>>>(ds);
-            if (out != DF_COLS) ds.n_out = 0;
-            dpart_merge_kernel<<<(int)(pd->nfinal << (pd->tb - 9)), 512, 0, s>>>(ds, pd->tb);
-            VNM_HIP(hipGetLastError());
-        } else if (attempt == 1 && pd->tb == 13 && df.fx_q == 0.0) {
-            // 64-bit compensation terms only fit 2^12-slot tables: every partition in two halves (slot bit 12 = 0, then 1)
-            df.sub_bits = 1;
-            for (int sub = 0; sub < 2; sub++) { df.sub = sub; VNM_TRY(launch_dense_final(df, 12, out, true, s)); }
-        } else {
-            if (df.has_side) {
-                VNM_HIP(hipMemsetAsync(df.side_found, 0, (size_t)df.side.cap + 2, s));
-                VNM_HIP(hipMemsetAsync(df.flags + 4, 0, 8, s));
-            }
-            // every add of the pass proved exact by the scatter passes (exact_track): {sum, count} slots, non-returning atomics
-            // (VNM_DF_EXACT: 0 = never, 2 = assume it without proof -- measurements only)
-            const int xmode = (int)env_i64("VNM_DF_EXACT", 1);
-            const bool exact = attempt == 0 && df.w_sum >= 0 && df.w_lo >= 0 && !df.sub_bits && (xmode == 2 || (xmode == 1 && pd->exact_ok()));
-            if (exact) route_note("dense:exact_adds", "2^%d-slot tables without compensation words: %lld rows, values below 2^%d with lowest bits >= 2^%d",
-                                  pd->tb, (long long)pd->rows, (int)pd->x_exp - 1022, (int)(0xFFFFu - pd->x_inv) - 1075);
-            VNM_TRY(launch_dense_final(df, pd->tb, out, attempt == 1, s, exact, pd->sets.size() == 1 ? &pd->sets[0] : nullptr));
-            if (df.has_side) {
-                KernelTimer timer("agg_side_append", s);
-                dside_append_kernel<<<(int)std::min<int64_t>(((int64_t)df.side.cap + 2 + 255) / 256, (int64_t)device_info().num_cus * 8), 256, 0, s>>>(df, 0);
-                dside_append_kernel<<<1, 256, 0, s>>>(df, 1);
-                VNM_HIP(hipGetLastError());
-            }
-        }
-        VNM_HIP(hipMemcpyAsync(fl, df.flags, 40, hipMemcpyDeviceToHost, s));
-        VNM_HIP(hipStreamSynchronize(s));
-        if (!fl[0]) break;
-        if (out == DF_TABLE) return 2;
-        if (attempt == 1) return set_error("aggregate: dense final pass failed (internal error)");
-    }
-    if (getenv("VNM_AGG_TRACE")) fprintf(stderr, "[agg] dense final (deferred, %zu batch%s): mode %d -> groups %llu\n", pd->sets.size(),
-                                         pd->sets.size() == 1 ? "" : "es", out, fl[1]);
-    if (n_out) *n_out = (int64_t)fl[1];
-    if (out == DF_COLS && cols->null_pos) *cols->null_pos = df.has_side ? (int64_t)fl[4] : 0;
-    if (out == DF_RUN) {
-        pool.keep(rk); pool.keep(ra);
-        h->run_key = rk; h->run_acc = ra; h->run_stride = pd->dstride; h->run_n = (int64_t)fl[1];
-        h->run_dir = nullptr; h->run_nfin = 0;
-        h->have_run = true;
-        delete pd;
-        h->pending = nullptr;
+    // every add of the pass proved exact by the scatter passes (exact_track): {sum, count} slots, non-returning atomics
+    // (VNM_DF_EXACT: 0 = never, 2 = assume it without proof -- measurements only)
+    const int xmode = (int)env_i64("VNM_DF_EXACT", 1);
+    const bool exact = attempt == 0 && df.w_sum >= 0 && df.w_lo >= 0 && !df.sub_bits && (xmode == 2 || (xmode == 1 && pd->exact_ok()));
+    if (exact) route_note("dense:exact_adds", "2^%d-slot tables without compensation words: %lld rows, values below 2^%d with lowest bits >= 2^%d", pd->tb, (long long)pd->rows, (int)pd->x_exp - 1022, (int)(0xFFFFu - pd->x_inv) - 1075);
+    VNM_TRY(launch_dense_final(df, pd->tb, out, attempt == 1, s, exact, pd->sets.size() == 1 ? &pd->sets[0] : nullptr));
+    if (df.has_side) {
+        KernelTimer timer("agg_side_append", s);
+        dside_append_kernel<<<(int)std::min<int64_t>(((int64_t)df.side.cap + 2 + 255) / 256, (int64_t)device_info().num_cus * 8), 256, 0, s>>>(df, 0);
+        dside_append_kernel<<<1, 256, 0, s>>>(df, 1);
+        VNM_HIP(hipGetLastError());
     }
     return 0;
 }
 
+// Runs the deferred final pass of the dense path.  DF_RUN: the pending state becomes the handle's run (and is released);
+// DF_COLS: `cols` names the output columns (capacity pending->dstride), *n_out = groups written, the pending entries STAY (a later
+// finish() can still produce the partial state); DF_TABLE: the tables go to pending->table (rc 2: compensation terms out of the
+// float range -- the caller uses another exchange).
+int complete_pending(vnm_agg* h, hipStream_t s, int out = DF_RUN, const DFinalArgs* cols = nullptr, int64_t* n_out = nullptr) {
+    DensePending* pd = h->pending;
+    if (!pd) return 0;
+    if (out == DF_RUN && h->have_run) VNM_TRY(merge_run_into_table(h, s));   // (a run of another path: it has to make room)
+    DFinalArgs df = pd->df;
+    PoolScope pool;
+    VNM_TRY(pending_bind_output(h, pd, out, cols, df, pool, s));
+    if (pd->fsplits > 1 && df.has_side) return set_error("aggregate: side table with a split final pass (internal error)");
+    unsigned long long fl[5] = {0, 0, 0, 0, 0};
+    for (int attempt = 0; attempt < 2; attempt++) {   // (the second: compensation terms beyond the float range)
+        VNM_HIP(hipMemsetAsync(df.flags, 0, 16, s));   // [0] failure, [1] dense count ([2]: the scatter passes' spill count, consumed)
+        if (attempt == 0 && pd->fsplits > 1) VNM_TRY(pending_final_split(pd, out, df, pool, s));
+        else if (attempt == 1 && pd->tb == 13 && df.fx_q == 0.0) VNM_TRY(pending_final_halves(df, out, s));
+        else VNM_TRY(pending_final_plain(pd, out, attempt, df, s));
+        VNM_TRY(read_flags(fl, df.flags, s));
+        if (!fl[0]) break;
+        if (out == DF_TABLE) return 2;
+        if (attempt == 1) return set_error("aggregate: dense final pass failed (internal error)");
+    }
+    if (getenv("VNM_AGG_TRACE")) fprintf(stderr, "[agg] dense final (deferred, %zu batch%s): mode %d -> groups %llu\n", pd->sets.size(), pd->sets.size() == 1 ? "" : "es", out, fl[1]);
+    if (n_out) *n_out = (int64_t)fl[1];
+    if (out == DF_COLS && cols->null_pos) *cols->null_pos = df.has_side ? (int64_t)fl[4] : 0;
+    if (out == DF_RUN) {
+        pool.keep(df.dkey); pool.keep(df.dacc);
+        adopt_run(h, df.dkey, df.dacc, pd->dstride, (int64_t)fl[1]);
+        delete pd; h->pending = nullptr;
+    }
+    return 0;
+}
 
 // ---- the dense-key partitioned route, stage by stage (dense_partitioned_aggregate below is the driver) ---------------------
 // What one attempt does with a batch: the form of its entries and the whole geometry of the passes.  Filled by plan_dense_entries
-// and plan_dense_geometry, which make no HIP call and leave the handle alone; read-only afterwards.
+// and plan_dense_geometry -- or, the geometry alone, by plan_dense_two -- which make no HIP call and leave the handle alone; read-only afterwards.
 struct DensePlan {
     bool generic, has_val;
     bool vn, vn_lists;       // nullable value column; ... whose NULL rows may end up in a list of their own (nspill), not vn_fold
@@ -834,11 +855,10 @@ struct DensePlan {
     bool c16_1;              // pass-1 remainders fit 16 bits when they are the final slots
     int pmajor;              // VNM_DENSE_PRODUCER_MAJOR
     int64_t spill_cap, nspill_cap, dstride;
-    int rcap1, rcap2;        // entries per ring of the ring scatter (0 = the tile-sorting kernel takes the level)
+    int rcap1, rcap2;        // entries per ring of the ring scatter (0 = the tile-sorting kernel takes the level; two values: never 0)
     bool ring_limit;
     int ring_pairs1, ring_pairs2;   // pairs of rows per lane and sub-tile, at most
 };
-constexpr int DENSE_REDO = 4;   // a stage's answer: free everything, then the same batch once more (the handle says what changes)
 
 // Stage 2a: is the route applicable, and with which form of entries?  0, or 2 = not applicable.
 int plan_dense_entries(const vnm_agg* h, const AggArgs& a, bool generic, const DGenArgs& g, bool vn_fold, bool null_lists, DensePlan* p) {
@@ -1055,19 +1075,15 @@ int plan_dense_geometry(const vnm_agg* h, const AggArgs& a, int64_t nrows, const
     return 0;
 }
 
-// Stage 3 owns every pool block of the attempt: whatever has not been keep()-ed -- handed to the caller, the handle's run or the
-// pending pass -- goes back on every return path.
-struct DenseBuffers {
-    PoolScope pool;
+// Stage 3 owns every pool block of the attempt (AttemptBlocks), these by name:
+struct DenseBuffers : AttemptBlocks {
     unsigned long long* flags = nullptr;   // [0..3] status words, [6] exact-add statistics, [7] fixed-point misfit, [8..12] the NULL-key rows of this attempt (nullable key)
     double* v1 = nullptr; void* c1 = nullptr; uint32_t* n1 = nullptr;    // regions of level 1: values / words, code remainders, counts
     double* v2 = nullptr; void* c2 = nullptr; uint32_t* n2 = nullptr;    // ... of level 2
+    double* w1 = nullptr; double* w2 = nullptr;                          // the second value of two-value entries (dense_two_aggregate)
     ulonglong2* spill = nullptr;           // entries without a place: the caller's on success
     uint64_t* nspill = nullptr;            // keys of NULL-value rows without a place: the caller's on success
     uint64_t* rk = nullptr; uint64_t* ra = nullptr;                      // the run a final pass of this call writes
-    template <class T> void take(T*& p, size_t bytes) { p = (T*)pool.take(bytes); }
-    // before the batch is tried again: the retry finds the blocks in the pool
-    void free_all() { while (pool.n > 0) pool.done(pool.blocks[pool.n - 1]); }
 };
 
 int dense_allocate(const DensePlan& p, DenseBuffers& b, hipStream_t s) {
@@ -1140,8 +1156,7 @@ int dense_scatter1(vnm_agg* h, const AggArgs& a, int64_t nrows, const DensePlan&
     d1.kp = (const uint64_t*)a.keys[0].values + a.keys[0].offset;
     d1.vp = p.has_val ? (const double*)a.cols[0].values + a.cols[0].offset : nullptr;
     d1.has_expr = a.has_expr; d1.expr = a.expr;
-    d1.pp = h->pred_set ? (const double*)a.pred.values + a.pred.offset : nullptr;
-    d1.has_pred = h->pred_set; d1.pred_is_v = a.hot_pred_is_v; d1.op = a.p.op; d1.thr = a.p.dval;
+    fill_pred(d1, h, a);
     d1.nrows = nrows;
     d1.out_vals = b.v1; d1.out_codes = b.c1; d1.out_counts = b.n1; d1.out_cap = p.cap1;
     d1.nparts = p.np1; d1.out_bits = h->dmap.bits - p.p1;
@@ -1220,9 +1235,7 @@ int dense_final_count8(vnm_agg* h, const DensePlan& p, const DenseBuffers& b, DG
         }
         VNM_HIP(hipGetLastError());
         if (cb == 16) break;
-        unsigned long long f6[6];
-        VNM_HIP(hipMemcpyAsync(f6, b.flags, sizeof(f6), hipMemcpyDeviceToHost, s));
-        VNM_HIP(hipStreamSynchronize(s));
+        unsigned long long f6[6]; VNM_TRY(read_flags(f6, b.flags, s));
         if (!(f6[0] && f6[5])) break;
         cb = 16;
         h->count_cb = 16;
@@ -1271,13 +1284,11 @@ int dense_final_split(const DensePlan& p, DenseBuffers& b, DFinalArgs& df, hipSt
 
 // Stage 6, the usual one: the final pass is DEFERRED -- what it should write depends on what comes next (complete_pending), and the
 // batches of a stream share ONE final pass.  The scatter passes have to be known good first; then the entries join the pending pass
-// of the handle.  0 = done, 2 = the scatter failed, DENSE_REDO = a fixed-point misfit (32-bit words out of both levels -> out of the last only -> 8-byte words -> float64 entries).
+// of the handle.  0 = done, 2 = the scatter failed, ATTEMPT_REDO = a fixed-point misfit (32-bit words out of both levels -> out of the last only -> 8-byte words -> float64 entries).
 int dense_defer_final(vnm_agg* h, const AggArgs& a, int64_t nrows, const DensePlan& p, DenseBuffers& b, const DSet& fin, DFinalArgs& df, hipStream_t s,
                       ulonglong2** spill_out, int64_t* n_spill_out) {
     const DenseMap& mp = h->dmap;
-    unsigned long long fl0[8];
-    VNM_HIP(hipMemcpyAsync(fl0, b.flags, 64, hipMemcpyDeviceToHost, s));
-    VNM_HIP(hipStreamSynchronize(s));
+    unsigned long long fl0[8]; VNM_TRY(read_flags(fl0, b.flags, s));
     route_note(h->kn_valid ? "dense:nullable_key" : (h->segs_active ? "dense:stream_segments" : (p.vn ? "dense:nullable_value" : (p.levels == 1 && p.p1 == 5 && p.tb <= 10 ? "dense:32_partitions" :
                (p.fsplits > 1 ? "dense:split_final" : (p.levels == 2 ? "dense:two_levels" : "dense:one_level"))))),
                "2^%d codes, 2^%d-slot final tables, p1 %d p2 %d, final pass deferred%s: %s", mp.bits, p.tb, p.p1, p.p2, p.vn ? ", nullable value" : "", fl0[0] || (p.fx && fl0[7]) ? "scatter FAILED (the batch goes another way)" : "ok");
@@ -1287,18 +1298,18 @@ int dense_defer_final(vnm_agg* h, const AggArgs& a, int64_t nrows, const DensePl
     if (p.fx && fl0[7] == 2) {   // every value fits the words of the last level, one is outside the first level's window: that level alone goes back to 8-byte words, for this batch and every later one
         h->fx_narrow1_off = true;
         route_note("dense:fixed_point_misfit", "a value outside the first level's window, 2^%d * [%d, %d + 2^%d): the batch is redone with 8-byte words out of that level", p.fx_qe, p.fx_wbase, p.fx_wbase, p.fx_wbits);
-        return DENSE_REDO;
+        return ATTEMPT_REDO;
     }
     if (p.fx && fl0[7]) {   // a value that is not m * 2^qe with |m| < 2^31: float64 entries for this batch and every later one
         if (h->fx_narrow) {   // (outside the 18 bits of the narrow words: 64-bit words with six more bits below the quantum and 13 more above)
             h->fx_narrow = false;
             h->fx_qe = std::max(h->fx_qe - 6, -1000);
             route_note("dense:fixed_point_misfit", "a value outside 2^%d * [-2^18, 2^18): the batch is redone with 64-bit entry words", h->fx_qe + 6);
-            return DENSE_REDO;
+            return ATTEMPT_REDO;
         }
         h->fx_state = -1;
         route_note("dense:fixed_point_misfit", "a value outside 2^%d * [-2^31, 2^31): the batch is redone with float64 entries", h->fx_qe);
-        return DENSE_REDO;
+        return ATTEMPT_REDO;
     }
     if (fl0[0]) return 2;
     if (p.fx) route_note("dense:fixed_point", "%s entry words, quantum 2^%d", p.w32 ? (p.levels == 1 ? "4-byte" : (p.narrow1 ? "4-byte, then 4-byte" : "8-byte, then 4-byte")) : "8-byte", p.fx_qe);
@@ -1339,13 +1350,11 @@ int dense_defer_final(vnm_agg* h, const AggArgs& a, int64_t nrows, const DensePl
 }
 
 // Stage 7 (the passes that wrote a run of their own): read the flags, hand the run to the handle and the lists to the caller.
-// 0 = done, 2 = failed (the batch goes another way), DENSE_REDO = byte counters overflowed (two scatter levels take the batch).
+// 0 = done, 2 = failed (the batch goes another way), ATTEMPT_REDO = byte counters overflowed (two scatter levels take the batch).
 int dense_hand_over(vnm_agg* h, const AggArgs& a, int64_t nrows, const DensePlan& p, DenseBuffers& b, hipStream_t s, ulonglong2** spill_out, int64_t* n_spill_out,
                     uint64_t** nspill_out, int64_t* n_nspill_out) {
     VNM_HIP(hipGetLastError());
-    unsigned long long fl[4];
-    VNM_HIP(hipMemcpyAsync(fl, b.flags, 32, hipMemcpyDeviceToHost, s));
-    VNM_HIP(hipStreamSynchronize(s));
+    unsigned long long fl[4]; VNM_TRY(read_flags(fl, b.flags, s));
     if (!fl[0]) {
         if (fold_null_rows(h, a, b.flags, s)) return 1;
         VNM_HIP(hipStreamSynchronize(s));   // (the fold reads the flags block, which goes back when this attempt's owner does)
@@ -1358,16 +1367,14 @@ int dense_hand_over(vnm_agg* h, const AggArgs& a, int64_t nrows, const DensePlan
     if (fl[0]) {  // spill buffer full, dense output too small, or a compensation term beyond float range
         if (!p.count8) return 2;
         h->count8_off = true;   // (a group of 256 rows or more, most likely: flags[5]) the two scatter levels take the batch, and every later one
-        return DENSE_REDO;
+        return ATTEMPT_REDO;
     }
     if (fl[2]) { b.pool.keep(b.spill); *spill_out = b.spill; *n_spill_out = (int64_t)fl[2]; }   // the caller owns the lists now
     else { *spill_out = nullptr; *n_spill_out = 0; }
     if (p.vn && fl[3]) { b.pool.keep(b.nspill); *nspill_out = b.nspill; *n_nspill_out = (int64_t)fl[3]; }
     if ((int64_t)(fl[2] + fl[3]) > nrows / 16) h->dense_state = -1;  // the sampled range does not describe the data: stop trying
     b.pool.keep(b.rk); b.pool.keep(b.ra);   // the run belongs to the handle
-    h->run_key = b.rk; h->run_acc = b.ra; h->run_stride = p.dstride; h->run_n = (int64_t)fl[1];
-    h->run_dir = nullptr; h->run_nfin = 0;
-    h->have_run = true;
+    adopt_run(h, b.rk, b.ra, p.dstride, (int64_t)fl[1]);
     return 0;
 }
 
@@ -1425,122 +1432,114 @@ int dense_partitioned_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hip
     else if (p.fsplits > 1 && own_run) VNM_TRY(dense_final_split(p, b, df, s));
     else if (env_i64("VNM_DENSE_DEFER", 1)) {
         const int rc = dense_defer_final(h, a, nrows, p, b, fin, df, s, spill_out, n_spill_out);
-        return rc == DENSE_REDO ? redo() : rc;
+        return rc == ATTEMPT_REDO ? redo() : rc;
     } else VNM_TRY(launch_dense_final(df, p.tb, DF_RUN, false, s));
     const int rc = dense_hand_over(h, a, nrows, p, b, s, spill_out, n_spill_out, nspill_out, n_nspill_out);
-    return rc == DENSE_REDO ? redo() : rc;
+    return rc == ATTEMPT_REDO ? redo() : rc;
 }
 
-
-// The dense-key path for TWO plain float64 input columns (round 4, VERDICT r03 #6): `SELECT k, sum(a), sum(b) [, avg, count ...]` used
+// ---- the dense-key path for TWO plain float64 input columns (round 4, VERDICT r03 #6): `SELECT k, sum(a), sum(b) [, avg, count ...]` used
 // to take the hash partitions' wide entries (24-byte entries through two tile-sorting levels and LDS hash tables: 24 ms per 5e8 rows
 // at G = 1e8).  Here the entry is (value 1, value 2, code remainder) -- 20 bytes after pass 1, 18 after pass 2 -- through the ring
 // scatter (dring_scatter_kernel<..., V2>: a second ring array, 32-48 entries per ring in 148 KB of LDS) and a direct-addressed
 // final pass with two compensated sums per slot (dpart_final2_kernel).  Ranges of 2^21 .. 2^27 codes; no spill buffer: an entry
 // without a place (a key outside the sampled range, a full region) fails the pass and the batch takes the hash partitions.
-// returns 0 = done (run stored), 2 = not applicable / failed, 1 = error
-int dense_two_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_t s) {
+// Its geometry, in the DensePlan fields of that name (no HIP call, the handle is left alone).  0, or 2 = not a range, a program or a fan-out it takes.
+int plan_dense_two(const vnm_agg* h, const AggArgs& a, int64_t nrows, DensePlan* p) {
     const int cus = device_info().num_cus;
-    const DenseMap& mp = h->dmap;
-    int tb = 11;
-    if (mp.bits - tb > 15) tb = 12;
-    const int pbits = mp.bits - tb;
+    const int bits = h->dmap.bits;
+    p->tb = bits - 11 > 15 ? 12 : 11;
+    const int pbits = bits - p->tb;
     if (pbits > 15 || pbits < 10 || a.has_expr) return 2;
-    const int p2 = std::min(8, (pbits + 1) / 2), p1 = pbits - p2;      // (pass 1 moves the 20-byte entries: at most 128 rings of them fit)
-    if (p1 > 7 || p1 < 5) return 2;
-    const int np1 = 1 << p1, np2 = 1 << p2;
-    const int64_t tile1 = PT_TILE;
-    const int grid1 = (int)std::min<int64_t>((int64_t)cus * 2, (nrows + tile1 - 1) / tile1);
-    int split2 = std::max(2, (grid1 + PT_MAX_REGIONS - 1) / PT_MAX_REGIONS);
-    split2 = std::max(split2, std::min(grid1, (cus * 2 + np1 - 1) / np1));
-    const int64_t tiles_per_wg = ((nrows + tile1 - 1) / tile1 + grid1 - 1) / grid1;
-    const int64_t rows_per_wg = tiles_per_wg * tile1;
-    int64_t cap1 = ((rows_per_wg / np1 + rows_per_wg / np1 / 5 + 512) + 15) & ~15LL;
-    if (((cap1 / 16) & 1) == 0) cap1 += 16;
-    const int64_t per_pg = (int64_t)grid1 * rows_per_wg / np1 / split2;
-    int64_t cap2 = ((per_pg / np2 + per_pg / np2 / 4 + 256) + 15) & ~15LL;
-    if (((cap2 / 16) & 1) == 0) cap2 += 16;
-    const int64_t nfinal = (int64_t)1 << pbits;
-    const int64_t dstride = std::min<int64_t>(h->dense_span, nrows) + 2;
-    PoolScope pool;
-    unsigned long long* flags = (unsigned long long*)pool.take(64);
-    double* v1 = (double*)pool.take((size_t)np1 * grid1 * cap1 * 8);
-    double* w1 = (double*)pool.take((size_t)np1 * grid1 * cap1 * 8);
-    uint32_t* c1 = (uint32_t*)pool.take((size_t)np1 * grid1 * cap1 * 4);
-    uint32_t* n1 = (uint32_t*)pool.take((size_t)np1 * grid1 * 4);
-    double* v2 = (double*)pool.take((size_t)np1 * np2 * split2 * cap2 * 8);
-    double* w2 = (double*)pool.take((size_t)np1 * np2 * split2 * cap2 * 8);
-    uint16_t* c2 = (uint16_t*)pool.take((size_t)np1 * np2 * split2 * cap2 * 2);
-    uint32_t* n2 = (uint32_t*)pool.take((size_t)np1 * np2 * split2 * 4);
-    uint64_t* rk = (uint64_t*)pool.take((size_t)dstride * 8 * 2);
-    uint64_t* ra = (uint64_t*)pool.take((size_t)dstride * 8 * h->plan.n_words);
-    if (!flags || !v1 || !w1 || !c1 || !n1 || !v2 || !w2 || !c2 || !n2 || !rk || !ra) return 1;
-    VNM_HIP(hipMemsetAsync(flags, 0, 64, s));
+    p->p2 = std::min(8, (pbits + 1) / 2); p->p1 = pbits - p->p2;      // (pass 1 moves the 20-byte entries: at most 128 rings of them fit)
+    if (p->p1 > 7 || p->p1 < 5) return 2;
+    const int np1 = p->np1 = 1 << p->p1, np2 = p->np2 = 1 << p->p2;
+    const int64_t tiles = (nrows + PT_TILE - 1) / PT_TILE;
+    const int grid1 = p->grid1 = (int)std::min<int64_t>((int64_t)cus * 2, tiles);
+    p->split2 = std::max(2, (grid1 + PT_MAX_REGIONS - 1) / PT_MAX_REGIONS);
+    p->split2 = std::max(p->split2, std::min(grid1, (cus * 2 + np1 - 1) / np1));
+    const int64_t rows_per_wg = (tiles + grid1 - 1) / grid1 * PT_TILE;
+    p->cap1 = ((rows_per_wg / np1 + rows_per_wg / np1 / 5 + 512) + 15) & ~15LL;
+    if (((p->cap1 / 16) & 1) == 0) p->cap1 += 16;
+    const int64_t per_pg = (int64_t)grid1 * rows_per_wg / np1 / p->split2;
+    p->cap2 = ((per_pg / np2 + per_pg / np2 / 4 + 256) + 15) & ~15LL;
+    if (((p->cap2 / 16) & 1) == 0) p->cap2 += 16;
+    p->nfinal = (int64_t)1 << pbits;
+    p->dstride = std::min<int64_t>(h->dense_span, nrows) + 2;
+    // the rings of both levels (20- and 18-byte entries) must hold two flush blocks each
     const int lds_budget = (int)env_i64("VNM_DENSE_RING_LDS2", 148) * 1024;
     auto ring_cap = [&](int np, int esize) { return std::min(80, lds_budget / (np * esize) / DR_FB * DR_FB); };
-    const int rcap1 = ring_cap(np1, 20), rcap2 = ring_cap(np2, 18);
-    if (rcap1 < 2 * DR_FB || rcap2 < 2 * DR_FB) return 2;
-    DPartArgs d1{};
-    d1.map = mp;
+    p->rcap1 = ring_cap(np1, 20); p->rcap2 = ring_cap(np2, 18);
+    return p->rcap1 < 2 * DR_FB || p->rcap2 < 2 * DR_FB ? 2 : 0;
+}
+
+// Both scatter levels: rows -> (value 1, value 2, code remainder) entries in np1, then np1 x np2 partitions.  Two-value entries (V2):
+// no round limit, no segments; two pairs of rows per lane where an even spread of the sub-tile fits one round.
+int dense_two_scatters(const vnm_agg* h, const AggArgs& a, int64_t nrows, const DensePlan& p, const DenseBuffers& b, hipStream_t s) {
+    DPartArgs d1{}, d2{};
+    d1.map = d2.map = h->dmap; d1.flags = d2.flags = b.flags;
     d1.kp = (const uint64_t*)a.keys[0].values + a.keys[0].offset;
     d1.vp = (const double*)a.cols[0].values + a.cols[0].offset;
     d1.vp2 = (const double*)a.cols[1].values + a.cols[1].offset;
-    d1.pp = h->pred_set ? (const double*)a.pred.values + a.pred.offset : nullptr;
-    d1.has_pred = h->pred_set; d1.pred_is_v = a.hot_pred_is_v; d1.op = a.p.op; d1.thr = a.p.dval;
-    d1.nrows = nrows;
-    d1.out_vals = v1; d1.out_vals2 = w1; d1.out_codes = c1; d1.out_counts = n1; d1.out_cap = cap1;
-    d1.nparts = np1; d1.out_bits = mp.bits - p1;
-    d1.nt_store = 1;
-    d1.ready_list = (int)env_i64("VNM_DENSE_READY_LIST", 1) & 1;
-    d1.flags = flags; d1.spill = nullptr; d1.spill_cap = 0;
-    {   // (two-value entries, V2: no round limit, no segments; two pairs of rows per lane where an even spread of the sub-tile fits one round)
+    fill_pred(d1, h, a);
+    d1.nrows = nrows; d1.nt_store = 1; d1.ready_list = (int)env_i64("VNM_DENSE_READY_LIST", 1) & 1;
+    d1.out_vals = b.v1; d1.out_vals2 = b.w1; d1.out_codes = b.c1; d1.out_counts = b.n1; d1.out_cap = p.cap1;
+    d1.nparts = p.np1; d1.out_bits = h->dmap.bits - p.p1;
+    {
         KernelTimer timer("agg_part_scatter1", s);
         VNM_TRY(pick_bool(h->pred_set && !a.hot_pred_is_v, [&](auto pv) {
-            return pick_bool(ring_one_round(2, np1, rcap1, false), [&](auto two) {
-                return launch_ring<true, uint32_t, true, decltype(two)::value ? 2 : 1, decltype(pv)::value, false, 0, false, false, true, false, false>(grid1, d1, rcap1, s);
+            return pick_bool(ring_one_round(2, p.np1, p.rcap1, false), [&](auto two) {
+                return launch_ring<true, uint32_t, true, decltype(two)::value ? 2 : 1, decltype(pv)::value, false, 0, false, false, true, false, false>(p.grid1, d1, p.rcap1, s);
             });
         }));
     }
     VNM_HIP(hipGetLastError());
-    DPartArgs d2{};
-    d2.map = mp;
-    d2.in_vals = v1; d2.in_vals2 = w1; d2.in_codes = c1; d2.in_counts = n1; d2.in_cap = cap1;
-    d2.in_regions = grid1; d2.in_split = split2; d2.in_bits = mp.bits - p1;
-    d2.in_pstride = grid1; d2.in_rstride = 1;
-    d2.out_vals = v2; d2.out_vals2 = w2; d2.out_codes = c2; d2.out_counts = n2; d2.out_cap = cap2;
-    d2.nparts = np2; d2.out_bits = tb;
-    d2.flags = flags; d2.spill = nullptr; d2.spill_cap = 0;
+    d2.in_vals = b.v1; d2.in_vals2 = b.w1; d2.in_codes = (const uint32_t*)b.c1; d2.in_counts = b.n1; d2.in_cap = p.cap1;
+    d2.in_regions = p.grid1; d2.in_split = p.split2; d2.in_bits = d1.out_bits; d2.in_pstride = p.grid1; d2.in_rstride = 1;
+    d2.out_vals = b.v2; d2.out_vals2 = b.w2; d2.out_codes = b.c2; d2.out_counts = b.n2; d2.out_cap = p.cap2;
+    d2.nparts = p.np2; d2.out_bits = p.tb;
     {
         KernelTimer timer("agg_part_scatter2", s);
-        VNM_TRY(pick_bool(ring_one_round(2, np2, rcap2, false), [&](auto two) {
-            return launch_ring<false, uint16_t, true, decltype(two)::value ? 2 : 1, false, false, 0, false, false, true, false, false>(np1 * split2, d2, rcap2, s);
+        VNM_TRY(pick_bool(ring_one_round(2, p.np2, p.rcap2, false), [&](auto two) {
+            return launch_ring<false, uint16_t, true, decltype(two)::value ? 2 : 1, false, false, 0, false, false, true, false, false>(p.np1 * p.split2, d2, p.rcap2, s);
         }));
     }
     VNM_HIP(hipGetLastError());
+    return 0;
+}
+
+// returns 0 = done (run stored), 2 = not applicable / failed, 1 = error
+int dense_two_aggregate(vnm_agg* h, const AggArgs& a, int64_t nrows, hipStream_t s) {
+    const int cus = device_info().num_cus;
+    DensePlan p{};
+    VNM_TRY(plan_dense_two(h, a, nrows, &p));
+    const size_t n1e = (size_t)p.np1 * p.grid1 * p.cap1, n2e = (size_t)p.np1 * p.np2 * p.split2 * p.cap2;   // entries of the levels' regions
+    DenseBuffers b;
+    b.take(b.flags, 64);
+    b.take(b.v1, n1e * 8); b.take(b.w1, n1e * 8); b.take(b.c1, n1e * 4); b.take(b.n1, (size_t)p.np1 * p.grid1 * 4);
+    b.take(b.v2, n2e * 8); b.take(b.w2, n2e * 8); b.take(b.c2, n2e * 2); b.take(b.n2, (size_t)p.np1 * p.np2 * p.split2 * 4);
+    b.take(b.rk, (size_t)p.dstride * 8 * 2); b.take(b.ra, (size_t)p.dstride * 8 * h->plan.n_words);
+    if (!b.flags || !b.v1 || !b.w1 || !b.c1 || !b.n1 || !b.v2 || !b.w2 || !b.c2 || !b.n2 || !b.rk || !b.ra) return 1;
+    VNM_HIP(hipMemsetAsync(b.flags, 0, 64, s));
+    VNM_TRY(dense_two_scatters(h, a, nrows, p, b, s));
     DFinalArgs df{};
-    df.map = mp;
-    df.vals = v2; df.vals2 = w2; df.codes = c2; df.counts = n2; df.cap = cap2; df.regions = split2; df.nfinal = nfinal;
-    df.pstride = split2; df.rstride = 1;
-    df.w_rows = a.hot_w[A_COUNT_ROWS];
+    df.map = h->dmap; df.nfinal = p.nfinal; df.w_rows = a.hot_w[A_COUNT_ROWS];
+    df.vals = b.v2; df.vals2 = b.w2; df.codes = b.c2; df.counts = b.n2; df.cap = p.cap2; df.regions = p.split2; df.pstride = p.split2; df.rstride = 1;
     df.w_valid = a.hot_w[A_COUNT_VALID]; df.w_sum = a.hot_w[A_SUM_F64]; df.w_lo = a.hot_comp && df.w_sum >= 0 ? df.w_sum + 1 : -1;
     df.w_valid2 = a.hot_w2[A_COUNT_VALID]; df.w_sum2 = a.hot_w2[A_SUM_F64]; df.w_lo2 = a.hot_comp && df.w_sum2 >= 0 ? df.w_sum2 + 1 : -1;
-    df.dkey = rk; df.dacc = ra; df.dstride = dstride; df.flags = flags;
+    df.dkey = b.rk; df.dacc = b.ra; df.dstride = p.dstride; df.flags = b.flags;
     {
         KernelTimer timer("agg_part_final", s);
-        if (tb == 11) dpart_final2_kernel<uint16_t, 11><<<(int)std::min<int64_t>(nfinal, (int64_t)cus * 2), 512, 0, s>>>(df);
-        else dpart_final2_kernel<uint16_t, 12><<<(int)std::min<int64_t>(nfinal, (int64_t)cus), 1024, 0, s>>>(df);
+        if (p.tb == 11) dpart_final2_kernel<uint16_t, 11><<<(int)std::min<int64_t>(p.nfinal, (int64_t)cus * 2), 512, 0, s>>>(df);
+        else dpart_final2_kernel<uint16_t, 12><<<(int)std::min<int64_t>(p.nfinal, (int64_t)cus), 1024, 0, s>>>(df);
     }
     VNM_HIP(hipGetLastError());
-    unsigned long long fl[2] = {0, 0};
-    VNM_HIP(hipMemcpyAsync(fl, flags, 16, hipMemcpyDeviceToHost, s));
-    VNM_HIP(hipStreamSynchronize(s));
+    unsigned long long fl[2] = {0, 0}; VNM_TRY(read_flags(fl, b.flags, s));
     if (getenv("VNM_AGG_TRACE"))
-        fprintf(stderr, "[agg] dense, two columns: bits %d tb %d p1 %d p2 %d rings %d / %d -> fail %llu groups %llu\n", mp.bits, tb, p1, p2, rcap1, rcap2, fl[0], fl[1]);
+        fprintf(stderr, "[agg] dense, two columns: bits %d tb %d p1 %d p2 %d rings %d / %d -> fail %llu groups %llu\n", h->dmap.bits, p.tb, p.p1, p.p2, p.rcap1, p.rcap2, fl[0], fl[1]);
     if (fl[0]) return 2;
-    pool.keep(rk); pool.keep(ra);
-    h->run_key = rk; h->run_acc = ra; h->run_stride = dstride; h->run_n = (int64_t)fl[1];
-    h->run_dir = nullptr; h->run_nfin = 0;
-    h->have_run = true;
+    b.pool.keep(b.rk); b.pool.keep(b.ra);
+    adopt_run(h, b.rk, b.ra, p.dstride, (int64_t)fl[1]);
     return 0;
 }
 
