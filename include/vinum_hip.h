@@ -519,6 +519,25 @@ int vnm_strdict_like(vnm_strdict* h, const uint8_t* pattern, int64_t pattern_len
  * vnm_strdict_ranks_device it reads counts back in between and returns when the ranks are written. */
 int vnm_strdict_translate(vnm_strdict* src, vnm_strdict* dst, int64_t id_begin, int32_t* out_dst_code_of_src_id, void* stream);
 int vnm_strdict_ranks_joint(vnm_strdict* a, vnm_strdict* b, int32_t* out_rank_of_id_a, int32_t* out_rank_of_id_b, void* stream);
+/* A dictionary-typed Arrow column (dictionary<intN, utf8 | large_utf8 | binary | large_binary>): the batch dictionary's indices ->
+ * codes of the running dictionary.  The caller runs the batch dictionary's VALUES through vnm_strdict_encode and uploads the result
+ * as code_of_index (n_values int32s on the DEVICE; -1 = a NULL value), so only n_values strings are hashed, not one per row.
+ * indices: the DEVICE view of the index buffer -- any of VNM_I8 ... VNM_U64, optional validity bitmap, Arrow offset, length.
+ * out_codes[i] = code_of_index[index[i]], or -1 when row i is NULL or its value is NULL (length int32s on the device).
+ * out_validity: NULL, or a device bitmap at bit offset 0, bit i = out_codes[i] >= 0, (length + 7) / 8 bytes, the bits past length
+ * in the last byte 0; every byte is written by exactly one lane (no atomics).
+ * The bounds test precedes the table load: an index outside [0, n_values) on a valid row is never used as an address; the row gets
+ * -1 and is counted.  With out_bad the call synchronises, stores the count there and, if it is not 0, returns non-zero with
+ * "dictionary index out of bounds" (what Arrow's validate(full=True) says of such an array).  out_bad == NULL: one kernel on
+ * `stream`, launched asynchronously; the caller accepts -1 for such rows.
+ * A lane takes 8 consecutive rows (one bitmap byte): 16-byte index loads when values + offset is 16-byte aligned (8-byte for the
+ * 1-byte types), element loads otherwise and in the last partial group; 16-byte code stores when out_codes is 16-byte aligned.
+ * The table is read through L2, one tile per workgroup, or -- up to 8192 values, when a workgroup's rows are at least 4 x the values --
+ * from a copy in LDS by a persistent grid (VNM_REMAP_LDS=0 / 1 pins the form; DESIGN.md section 4.9c has both measured).
+ * VNM_STRDICT_REMAP_TILE: rows per workgroup and step (a size the tests walk around). */
+#define VNM_STRDICT_REMAP_TILE 2048
+int vnm_strdict_remap_indices(const vnm_dcol* indices, const int32_t* code_of_index, int64_t n_values, int32_t* out_codes,
+                              uint8_t* out_validity, int64_t* out_bad, void* stream);
 
 /* ---- IN / NOT IN against a list of any length: the list as a device-resident set ---------------------------
  * replaces np.isin(x, values[, invert]) (vinum/core/expressions.py:39-40; the parser hands it ONE Literal holding the whole list,

@@ -310,6 +310,8 @@ def lower(node, index: Optional[Dict[int, str]] = None):
         return (op,) + tuple(args)
     if hasattr(node, "value"):                                 # Literal (vinum/parser/query.py:126-176)
         v = node.value
+        if isinstance(v, (str, bytes)):                        # a string literal is not a column name: `city = 'Berlin'`
+            return ("lit", v)
         return list(v) if isinstance(v, (list, tuple)) else v
     if hasattr(node, "get_column_name"):                       # Column (:179-233)
         return node.get_column_name()

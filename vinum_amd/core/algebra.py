@@ -7,7 +7,7 @@ from .. import expr as E
 from .. import get_batch_size, ops
 from ..device import is_supported
 from .base import DeviceRecordBatch, Operator
-from .lowering import lower_column_compares, lower_dictionary, project_lowered, used_columns  # noqa: F401 (see FilterOperator)
+from .lowering import lower_column_compares, lower_dictionary, project_lowered, used_columns, value_type_of  # noqa: F401 (see FilterOperator)
 
 
 class TableReaderOperator(Operator):
@@ -78,7 +78,7 @@ class FilterOperator(Operator):
                 pred = (E.cmp_name(op), col, ("lit", lit))
             else:
                 if batch.column(col).dictionary is not None:
-                    raise TypeError(f"cannot compare the {batch.column(col).dictionary.type} column {col!r} with {lit!r}: only a "
+                    raise TypeError(f"cannot compare the {value_type_of(batch.column(col).dictionary)} column {col!r} with {lit!r}: only a "
                                     "string / binary literal or another such column")
                 outs, k = ops.filter_cmp(batch.column(col), op, lit, cols)
                 return DeviceRecordBatch(dict(zip(names, outs)), k)

@@ -10,6 +10,11 @@ def _is_dict(x, columns) -> bool:
     return isinstance(x, str) and x in columns and columns[x].dictionary is not None
 
 
+def value_type_of(dictionary):
+    """what a dictionary's VALUES are: a dictionary-typed column (dictionary<int8, utf8>) is a utf8 column to every message and rule"""
+    return getattr(dictionary, "value_type", dictionary.type)
+
+
 def lower_like(expr, columns, extra=None):
     """LIKE / NOT LIKE (LikeFunction, vinum/core/functions.py:301-344) -> a lookup in a per-pattern table of the column's
     dictionary: ("like", col, ("lit", p)) becomes ("lookup", col, table) and ("not_like", ...) ("not", ("lookup", ...)), where
@@ -82,7 +87,7 @@ def lower_column_compares(expr, columns, extra=None):
                 if da is db:
                     return e if op in ("eq", "ne") else (op, rank_name(a), rank_name(b))
                 if not (getattr(da, "on_device", False) and getattr(db, "on_device", False)):
-                    raise NotImplementedError(f"no GPU lowering for comparing {a!r} ({da.type}) with {b!r} ({db.type}): only string "
+                    raise NotImplementedError(f"no GPU lowering for comparing {a!r} ({value_type_of(da)}) with {b!r} ({value_type_of(db)}): only string "
                                               "and binary columns keep their dictionaries on the device")
                 if op in ("eq", "ne"):
                     name = f"__codes_of_{b}_in_{a}"
@@ -95,14 +100,14 @@ def lower_column_compares(expr, columns, extra=None):
                 return (op, ("lookup_i32", a, na), ("lookup_i32", b, nb))
             for x, y in ((a, b), (b, a)):
                 if _is_dict(x, columns) and not E.is_str_lit(y):
-                    raise TypeError(f"cannot compare the {columns[x].dictionary.type} column {x!r} with {y!r}: only a string / "
+                    raise TypeError(f"cannot compare the {value_type_of(columns[x].dictionary)} column {x!r} with {y!r}: only a string / "
                                     "binary literal or another such column")
         elif e[0] in _ARITHMETIC:
             for x in e[1:]:
                 if _is_dict(x, columns):
-                    raise TypeError(f"{e[0]}() over the {columns[x].dictionary.type} column {x!r}: not a numeric operand")
+                    raise TypeError(f"{e[0]}() over the {value_type_of(columns[x].dictionary)} column {x!r}: not a numeric operand")
         elif e[0] in E.IN_OPS and _is_dict(e[1], columns) and not all(isinstance(v, (str, bytes)) or E.is_str_lit(v) for v in e[2]):
-            raise TypeError(f"{e[0].upper().replace('_', ' ')} over the {columns[e[1]].dictionary.type} column {e[1]!r} needs string / "
+            raise TypeError(f"{e[0].upper().replace('_', ' ')} over the {value_type_of(columns[e[1]].dictionary)} column {e[1]!r} needs string / "
                             f"binary literals, got {list(e[2])!r}")
         return None
     return E.rewrite(expr, f), extra

@@ -535,6 +535,101 @@ __global__ __launch_bounds__(256) void sd_like_kernel(LikeArgs a) {
     }
 }
 
+// ---- a dictionary-typed Arrow column: the batch dictionary's indices -> the running dictionary's codes ---------------------------
+// The batch's distinct VALUES went through the encode kernel above (n_values rows, not n): `table[j]` is the running code of value
+// j (-1: a NULL value).  A row is table[index[row]], or -1 when the row is NULL, its value is NULL or its index lies outside
+// [0, n_values) -- the bounds test comes before the load, so such an index is never an address.  One lane takes RM_ROWS = 8
+// consecutive rows: their indices in 16-byte loads (one 8-byte load for 1-byte indices) when the first one is aligned, element by
+// element otherwise and in the last, partial group; 8 codes = two 16-byte stores; 8 validity bits = ONE byte of the output bitmap,
+// which no other lane touches (no atomics, no byte shared between lanes, let alone waves).  HBM-bound: 1-8 index bytes in, 4 code
+// bytes out per row; the table is read through L2, or from a copy in LDS when it is small against the rows (see the launch).
+constexpr int RM_ROWS = 8;
+constexpr int RM_TILE = 256 * RM_ROWS;     // rows per workgroup and step
+constexpr int RM_LDS_VALUES = 8192;        // the LDS form: a table of up to this many codes is copied into LDS (32 KB) per workgroup
+
+struct RemapArgs {
+    const void* idx;           // element `first` belongs to row 0
+    const uint8_t* valid;      // bitmap, bit `first` belongs to row 0 (or null)
+    int64_t first, n, n_values, ntiles;
+    const int32_t* table;
+    int32_t* out;
+    uint8_t* out_valid;        // bitmap at bit offset 0 (or null)
+    unsigned long long* bad;   // valid rows with an index outside the table (null: not counted)
+    int vec_in, vec_out;       // the first index / out[0] is aligned for the wide loads / stores
+};
+
+template <typename T, bool LDS>
+__global__ __launch_bounds__(256) void sd_remap_kernel(RemapArgs a) {
+    __shared__ unsigned s_bad;
+    __shared__ int32_t s_table[LDS ? RM_LDS_VALUES : 1];
+    if (threadIdx.x == 0) s_bad = 0;
+    if constexpr (LDS)
+        for (int64_t i = threadIdx.x; i < a.n_values; i += 256) s_table[i] = a.table[i];
+    __syncthreads();
+    unsigned nbad = 0;
+    for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+        const int64_t row0 = (tile * 256 + threadIdx.x) * RM_ROWS;
+        if (row0 >= a.n) break;
+        const int cnt = a.n - row0 < RM_ROWS ? (int)(a.n - row0) : RM_ROWS;
+        const T* p = (const T*)a.idx + a.first + row0;
+        T v[RM_ROWS];
+        if (a.vec_in && cnt == RM_ROWS) {
+            asm volatile("" ::: "memory");   // (compiler fences around the wide accesses: p[0] / o[0] of the element path merged into them splits a 16-byte access)
+            if constexpr (sizeof(T) == 1) {
+                const uint2 q = *(const uint2*)p;
+                __builtin_memcpy(v, &q, sizeof(v));
+            } else {
+                uint4 q[sizeof(T) / 2];
+#pragma unroll
+                for (int j = 0; j < (int)(sizeof(T) / 2); j++) q[j] = ((const uint4*)p)[j];
+                __builtin_memcpy(v, q, sizeof(v));
+            }
+            asm volatile("" ::: "memory");
+        } else {
+#pragma unroll
+            for (int k = 0; k < RM_ROWS; k++) v[k] = k < cnt ? p[k] : (T)0;
+        }
+        unsigned vbits = 0xFFu;
+        if (a.valid) {   // bits first + row0 ... + 7: at most two bytes of the bitmap, the second only if it exists
+            const int64_t bit = a.first + row0, last_byte = (a.first + a.n - 1) >> 3;
+            const int sh = (int)(bit & 7);
+            vbits = (unsigned)a.valid[bit >> 3] >> sh;
+            if (sh && (bit >> 3) + 1 <= last_byte) vbits |= (unsigned)a.valid[(bit >> 3) + 1] << (8 - sh);
+        }
+        vbits &= (1u << cnt) - 1;
+        int32_t c[RM_ROWS];
+        unsigned obits = 0;
+#pragma unroll
+        for (int k = 0; k < RM_ROWS; k++) {
+            int32_t code = -1;
+            if ((vbits >> k) & 1) {
+                const uint64_t u = (uint64_t)v[k];            // (a negative index: sign-extended, far outside)
+                if (u < (uint64_t)a.n_values) code = LDS ? s_table[u] : a.table[u];
+                else nbad++;
+            }
+            c[k] = code;
+            obits |= (code >= 0 ? 1u : 0u) << k;
+        }
+        int32_t* o = a.out + row0;
+        if (a.vec_out && cnt == RM_ROWS) {
+            asm volatile("" ::: "memory");
+            ((int4*)o)[0] = make_int4(c[0], c[1], c[2], c[3]);
+            ((int4*)o)[1] = make_int4(c[4], c[5], c[6], c[7]);
+            asm volatile("" ::: "memory");
+        } else {
+#pragma unroll
+            for (int k = 0; k < RM_ROWS; k++)
+                if (k < cnt) o[k] = c[k];
+        }
+        if (a.out_valid) a.out_valid[row0 >> 3] = (uint8_t)obits;   // (bits past n stay 0: vbits was cut to cnt)
+    }
+    if (a.bad) {
+        if (nbad) atomicAdd(&s_bad, nbad);
+        __syncthreads();
+        if (threadIdx.x == 0 && s_bad) atomicAdd(a.bad, (unsigned long long)s_bad);
+    }
+}
+
 }  // namespace vnm
 
 using namespace vnm;
@@ -1027,6 +1122,74 @@ int vnm_strdict_like(vnm_strdict* h, const uint8_t* pattern, int64_t pattern_len
         sd_like_kernel<<<grid, 256, 0, s>>>(a);
     }
     VNM_HIP(hipGetLastError());
+    return 0;
+}
+
+static_assert(RM_TILE == VNM_STRDICT_REMAP_TILE, "the header documents the kernel's rows per workgroup");
+
+int vnm_strdict_remap_indices(const vnm_dcol* indices, const int32_t* code_of_index, int64_t n_values, int32_t* out_codes,
+                              uint8_t* out_validity, int64_t* out_bad, void* stream) {
+    VNM_TRY(ensure_init());
+    if (out_bad) *out_bad = 0;
+    if (!indices) return set_error("vnm_strdict_remap_indices: null argument");
+    const int64_t n = indices->length;
+    if (n <= 0) return 0;
+    if (!indices->values || !out_codes || (n_values > 0 && !code_of_index)) return set_error("vnm_strdict_remap_indices: null argument");
+    if (n_values < 0 || indices->offset < 0) return set_error("vnm_strdict_remap_indices: negative n_values or offset");
+    if (indices->type < VNM_I8 || indices->type > VNM_U64) return set_error("vnm_strdict_remap_indices: the indices must be of an integer type");
+    static const int width[8] = {1, 2, 4, 8, 1, 2, 4, 8};   // VNM_I8 ... VNM_U64
+    const int w = width[indices->type];
+    hipStream_t s = as_stream(stream);
+    PoolScope pool;
+    RemapArgs a{};
+    a.idx = indices->values; a.valid = (const uint8_t*)indices->validity;
+    a.first = indices->offset; a.n = n; a.n_values = n_values;
+    a.table = code_of_index;
+    a.out = out_codes; a.out_valid = out_validity;
+    a.vec_in = (((uintptr_t)indices->values + (uintptr_t)indices->offset * (uintptr_t)w) & (w == 1 ? 7 : 15)) == 0;
+    a.vec_out = ((uintptr_t)out_codes & 15) == 0;
+    if (out_bad) {
+        a.bad = (unsigned long long*)pool.take(8);
+        if (!a.bad) return 1;
+        VNM_HIP(hipMemsetAsync(a.bad, 0, 8, s));
+    }
+    const int64_t tiles = (n + RM_TILE - 1) / RM_TILE;
+    if (tiles > 0x7FFFFFFFLL) return set_error("vnm_strdict_remap_indices: too many rows for one launch");
+    a.ntiles = tiles;
+    // the global form: one tile per workgroup, the table through L2.  The LDS form: a persistent grid, every workgroup copies the table
+    // (up to 32 KB) into LDS once and takes several tiles -- taken when a workgroup's rows are at least 4x the values it copies
+    // (VNM_REMAP_LDS=0 / 1: never / whenever the table fits, the A / B switch of tools/dictcol_bench.py)
+    const char* sw = getenv("VNM_REMAP_LDS");
+    const int64_t lds_grid = std::min<int64_t>(tiles, (int64_t)device_info().num_cus * 8);
+    const int64_t rows_per_wg = (tiles + lds_grid - 1) / lds_grid * RM_TILE;
+    const bool lds = n_values > 0 && n_values <= RM_LDS_VALUES && (sw ? sw[0] == '1' : rows_per_wg >= 4 * n_values);
+    const dim3 grid((unsigned)(lds ? lds_grid : tiles));
+#define VNM_REMAP_LAUNCH(T)                                      \
+    do {                                                         \
+        if (lds) sd_remap_kernel<T, true><<<grid, 256, 0, s>>>(a); \
+        else sd_remap_kernel<T, false><<<grid, 256, 0, s>>>(a);    \
+    } while (0)
+    {
+        KernelTimer timer("strdict_remap_indices", s);
+        switch (indices->type) {
+            case VNM_I8: VNM_REMAP_LAUNCH(int8_t); break;
+            case VNM_I16: VNM_REMAP_LAUNCH(int16_t); break;
+            case VNM_I32: VNM_REMAP_LAUNCH(int32_t); break;
+            case VNM_I64: VNM_REMAP_LAUNCH(int64_t); break;
+            case VNM_U8: VNM_REMAP_LAUNCH(uint8_t); break;
+            case VNM_U16: VNM_REMAP_LAUNCH(uint16_t); break;
+            case VNM_U32: VNM_REMAP_LAUNCH(uint32_t); break;
+            default: VNM_REMAP_LAUNCH(uint64_t); break;
+        }
+    }
+#undef VNM_REMAP_LAUNCH
+    VNM_HIP(hipGetLastError());
+    if (!out_bad) return 0;
+    unsigned long long bad = 0;
+    VNM_HIP(hipMemcpyAsync(&bad, a.bad, 8, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));
+    *out_bad = (int64_t)bad;
+    if (bad) return set_error("vnm_strdict_remap_indices: dictionary index out of bounds (%llu row(s) of %lld, %lld value(s))", bad, (long long)n, (long long)n_values);
     return 0;
 }
 

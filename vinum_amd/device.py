@@ -114,11 +114,17 @@ class DeviceColumn:
 
     # -- constructors -------------------------------------------------------------------------------
     @staticmethod
-    def from_arrow(arr, dictionary=None) -> "DeviceColumn":
+    def from_arrow(arr, dictionary=None, stage=None) -> "DeviceColumn":
+        """stage (optional, array -> DeviceColumn): how a dictionary-typed column's index buffer reaches HBM (io sources pass the
+        pinned ring)"""
         if isinstance(arr, pa.ChunkedArray):
             arr = arr.combine_chunks() if arr.num_chunks != 1 else arr.chunk(0)
         if dictionary is not None:                    # non-numeric column: stage its int32 codes
-            col = DeviceColumn.from_arrow(dictionary.encode(arr))
+            # (a dictionary-typed column's codes are made on the device, KeyDictionary.encode_to_device: no host copy to stage)
+            to_device = getattr(dictionary, "encode_to_device", None)
+            col = to_device(arr, stage=stage) if to_device is not None else None
+            if col is None:
+                col = DeviceColumn.from_arrow(dictionary.encode(arr))
             col.dictionary = dictionary
             return col
         vt, _ = physical_type(arr.type)

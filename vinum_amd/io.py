@@ -294,7 +294,8 @@ class _ArrowBatchSource:
                 from .vinum_lib import KeyDictionary
                 if n not in self._dicts:
                     self._dicts[n] = KeyDictionary(arr.type)
-                cols[n] = DeviceColumn.from_arrow(arr, dictionary=self._dicts[n])
+                # (a dictionary-typed column -- read_dictionary=[...] -- stages its index buffer through the pinned ring as well)
+                cols[n] = DeviceColumn.from_arrow(arr, dictionary=self._dicts[n], stage=lambda a: _stage_arrow_column(a, a.type))
         return DeviceRecordBatch(cols, b.num_rows)
 
     def read_next_batch(self) -> pa.RecordBatch:

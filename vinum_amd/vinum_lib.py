@@ -153,6 +153,7 @@ class _StringMinMax:
         self._cls, self._groupby = op_cls, list(groupby_cols)
         self._funcs = list(funcs)                       # AggFuncDefs (MIN / MAX over non-numeric columns)
         self._partials = []
+        self._types = {}                                # result column -> the dictionary type of its input column
 
     def _aggregate(self, key_arrays, rank_arrays, names_of):
         """one numeric operator over (keys, int32 rank columns): MIN / MAX per function"""
@@ -171,7 +172,7 @@ class _StringMinMax:
         if isinstance(column, pa.ChunkedArray):
             column = column.combine_chunks()
         t = column.type
-        if len(column) and (pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t)):
+        if len(column) and device_value_type(t) is not None:       # (a dictionary-typed column too: its indices are remapped on the device)
             # the batch's dictionary from the device (vnm_strdict_encode, a fresh handle: every value of the batch is new to it);
             # the host sorts the DISTINCT values and turns codes into ranks (one gather)
             # ... and ranks them there too (round 5, vnm_strdict_ranks_device: the distinct values sorted byte-wise by the multi-key radix
@@ -179,7 +180,7 @@ class _StringMinMax:
             from .device import DeviceBuffer
             kd = KeyDictionary(t)
             codes = kd.encode(column)
-            d = pa.concat_arrays(kd._chunks) if kd._chunks else pa.array([], type=t)
+            d = pa.concat_arrays(kd._chunks) if kd._chunks else pa.array([], type=kd.value_type)
             c = codes.fill_null(0).to_numpy(zero_copy_only=False).astype(np.int64)
             mask = ~codes.is_valid().to_numpy(zero_copy_only=False) if codes.null_count else None
             if not len(d):
@@ -216,6 +217,10 @@ class _StringMinMax:
                 rank_name[c] = f"__vnm_rank{len(rank_name)}"
                 ranks[rank_name[c]], dicts[c] = self._ranks(batch.column(batch.schema.names.index(c)))
             names_of.append(rank_name[c])
+        for i, f in enumerate(self._funcs):
+            t = batch.schema.field(f.column_name).type
+            if pa.types.is_dictionary(t):
+                self._types[f"s{i}"] = t
         res = self._aggregate(key_arrays, ranks, names_of)
         nk = len(self._groupby)
         cand = [dicts[f.column_name].take(res.column(nk + i)) for i, f in enumerate(self._funcs)]     # NULL rank -> NULL string
@@ -279,11 +284,11 @@ class _HashAggregateBase:
             t = schema.field(c).type
             if f.func == AggFuncType.COUNT:
                 self._stand_in.add(c)
-            elif f.func in (AggFuncType.MIN, AggFuncType.MAX) and (pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t)
-                                                                  or pa.types.is_large_binary(t)):
+            elif f.func in (AggFuncType.MIN, AggFuncType.MAX) and device_value_type(t) is not None:
                 # round 6: vnm_agg_op_* take such columns themselves (one growing device dictionary per column, candidates per group
-                # in HBM); the shim's own route stays reachable for A / B runs
-                if os.environ.get("VNM_STRING_MINMAX_IN_SHIM"):
+                # in HBM); the shim's own route stays reachable for A / B runs -- and is the route of a DICTIONARY-TYPED column, whose
+                # `dictionary` child vnm_agg_op_* do not read
+                if os.environ.get("VNM_STRING_MINMAX_IN_SHIM") or pa.types.is_dictionary(t):
                     str_funcs.append(f)
                 else:
                     self._abi_str.add(c)
@@ -397,6 +402,9 @@ class _HashAggregateBase:
         if not hasattr(self, "_pending"):            # no batch at all: nothing to line up (the numeric result is what there is)
             return res
         smm = self._strmm.result()
+        if self._strmm._types:       # a dictionary-typed input's MIN / MAX comes back in its type (the candidates travel as plain values)
+            smm = pa.RecordBatch.from_arrays([c.cast(self._strmm._types[n]) if n in self._strmm._types else c
+                                              for n, c in zip(smm.schema.names, smm.columns)], names=smm.schema.names)
         o_num, o_str = _canonical_order(res, self._groupby), _canonical_order(smm, self._groupby)
         if len(o_num) != len(o_str):
             raise RuntimeError(f"aggregate: the numeric result holds {len(o_num)} groups, the string MIN / MAX result {len(o_str)} (internal error)")
@@ -458,6 +466,20 @@ class OneGroupAggregate(_HashAggregateBase):
         super().__init__([], [], agg_funcs)
 
 
+def _is_string_like(t) -> bool:
+    return pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t)
+
+
+def device_value_type(t):
+    """The type of the values the DEVICE dictionary holds for a column of type `t`: `t` itself for utf8 / large_utf8 / binary /
+    large_binary, the value type of a dictionary<intN, one of those four>; None for every other type (the host route)."""
+    if _is_string_like(t):
+        return t
+    if pa.types.is_dictionary(t) and _is_string_like(t.value_type):
+        return t.value_type
+    return None
+
+
 class KeyDictionary:
     """Running dictionary of one non-numeric group-by column: value -> int32 code.
 
@@ -469,13 +491,33 @@ class KeyDictionary:
     offsets and bytes cross PCIe once, one kernel hashes every row and finds or inserts it in the dictionary table; only the
     values a batch ADDS come back, and this object keeps them to decode the result's key column).  The host route it replaces
     (Arrow's `dictionary_encode` + a NumPy merge of the batch's dictionary into the running one) ran at 7-17 M rows/s, 1.5 M
-    rows/s at 5e6 distinct values.  Other types (bool, decimal, date64 ...: a handful of values or fixed width) keep it."""
+    rows/s at 5e6 distinct values.  Other types (bool, decimal, date64 ...: a handful of values or fixed width) keep it.
+
+    A DICTIONARY-TYPED column -- dictionary<intN, utf8 | large_utf8 | binary | large_binary>: a pandas categorical, a Parquet
+    column read with read_dictionary, an IPC stream of another engine -- takes the device route too, and cheaper: the batch
+    dictionary's VALUES go through vnm_strdict_encode (n_values strings hashed, not one per row), the indices cross PCIe at
+    their native 1-8 bytes per row and vnm_strdict_remap_indices gathers table[index] on the device (encode_to_device).  A batch
+    whose dictionary is the very buffers of the batch before (an IPC stream repeats its dictionary this way) reuses the table;
+    `values_encodes` counts the encodes of batch dictionaries.  A batch dictionary may hold duplicates (both indices get one
+    code) and values no row uses (they enter the running dictionary and are harmless).  `type` stays the column's type and is
+    what decode() returns -- value type, index type and `ordered` flag: decoded to the value type, then cast, so the output's
+    dictionary need not equal any input's, and a result with more distinct values than the index type can number surfaces
+    Arrow's cast error ("Integer value 128 not in range").  Everything that reasons about the VALUES -- LIKE's utf8 rule,
+    literals, the offsets' width -- uses `value_type`.  A dictionary type over any other value type (numbers, decimals, nested)
+    keeps the host route."""
 
     def __init__(self, arrow_type: pa.DataType):
         self.type = arrow_type
         self.values = pa.array([], type=arrow_type)     # host route: the dictionary in order of first appearance
-        self._device = (pa.types.is_string(arrow_type) or pa.types.is_large_string(arrow_type) or pa.types.is_binary(arrow_type)
-                        or pa.types.is_large_binary(arrow_type))
+        dev_type = device_value_type(arrow_type)
+        self._device = dev_type is not None
+        self.value_type = dev_type if dev_type is not None else arrow_type    # what the device dictionary's values are
+        self._dict_typed = self._device and pa.types.is_dictionary(arrow_type)
+        self._batch_dict = None    # dictionary-typed input: the previous batch's dictionary (kept alive: its addresses are compared) ...
+        self._batch_table = None   # ... its codes in HBM (DeviceBuffer of int32, -1 = a NULL value) and whether any is NULL
+        self._batch_table_nulls = False
+        self.values_encodes = 0    # batch dictionaries run through vnm_strdict_encode (a repeated one is not)
+        self.remap_launches = 0    # vnm_strdict_remap_indices calls
         self._h = None
         self._chunks = []          # device route: the values each batch added ...
         self._pos = None           # ... and id -> position in their concatenation (-1: an id never handed out)
@@ -490,8 +532,8 @@ class KeyDictionary:
 
     @property
     def on_device(self) -> bool:
-        """True for the four string / binary types, whose dictionary lives in HBM (vnm_strdict); the host-route dictionaries
-        (bool, decimal, date64 ...) have no device tables"""
+        """True for the four string / binary types and the dictionary types over them, whose dictionary lives in HBM
+        (vnm_strdict); the host-route dictionaries (bool, decimal, date64 ...) have no device tables"""
         return self._device
 
     def __del__(self):
@@ -519,14 +561,14 @@ class KeyDictionary:
         L.check(lib.vnm_strdict_last_new(self._h, ctypes.byref(n_new), ctypes.byref(new_bytes)))
         if not n_new.value:
             return
-        wide = pa.types.is_large_string(self.type) or pa.types.is_large_binary(self.type)
+        wide = pa.types.is_large_string(self.value_type) or pa.types.is_large_binary(self.value_type)
         ids = np.empty(n_new.value, np.int32)
         lens = np.empty(n_new.value, np.int32)
         data = np.empty(max(new_bytes.value, 1), np.uint8)
         L.check(lib.vnm_strdict_fetch_new(self._h, ids.ctypes.data, lens.ctypes.data, data.ctypes.data))
         offs = np.zeros(n_new.value + 1, np.int64 if wide else np.int32)
         np.cumsum(lens, out=offs[1:])
-        self._chunks.append(pa.Array.from_buffers(self.type, n_new.value, [None, pa.py_buffer(offs), pa.py_buffer(data[:new_bytes.value])]))
+        self._chunks.append(pa.Array.from_buffers(self.value_type, n_new.value, [None, pa.py_buffer(offs), pa.py_buffer(data[:new_bytes.value])]))
         top = int(lib.vnm_strdict_ids(self._h))
         if self._pos is None or len(self._pos) < top:
             grown = np.full(max(top, 2 * (len(self._pos) if self._pos is not None else 0)), -1, np.int64)
@@ -536,11 +578,12 @@ class KeyDictionary:
         self._pos[ids] = self._n_values + np.arange(n_new.value, dtype=np.int64)
         self._n_values += n_new.value
 
-    def _encode_device(self, column: pa.Array) -> pa.Array:
+    def _encode_values(self, column: pa.Array):
+        """a utf8 / binary array of the value type through vnm_strdict_encode: its codes as a NumPy int32 array, -1 for NULL"""
         import numpy as np
         lib = L.lib()
         n = len(column)
-        wide = pa.types.is_large_string(self.type) or pa.types.is_large_binary(self.type)
+        wide = pa.types.is_large_string(self.value_type) or pa.types.is_large_binary(self.value_type)
         vbuf, obuf, dbuf = column.buffers()
         codes = np.empty(max(n, 1), np.int32)
         L.check(lib.vnm_strdict_encode(self.handle(), obuf.address if obuf is not None else None, 1 if wide else 0,
@@ -548,15 +591,76 @@ class KeyDictionary:
                                        vbuf.address if (vbuf is not None and column.null_count) else None,
                                        column.offset, n, codes.ctypes.data, None, None, None))
         self.absorb_new()
-        codes = codes[:n]
+        return codes[:n]
+
+    def _encode_device(self, column: pa.Array) -> pa.Array:
+        codes = self._encode_values(column)
         mask = (codes < 0) if column.null_count else None
         return pa.array(codes, type=pa.int32(), mask=mask)
+
+    @staticmethod
+    def _same_buffers(a: pa.Array, b: pa.Array) -> bool:
+        """two arrays over the very same memory (type, offset, length, every buffer's address and size)"""
+        if a is b:
+            return True
+        if a.type != b.type or len(a) != len(b) or a.offset != b.offset:
+            return False
+        ba, bb = a.buffers(), b.buffers()
+        return len(ba) == len(bb) and all((x is None) == (y is None) and (x is None or (x.address == y.address and x.size == y.size))
+                                          for x, y in zip(ba, bb))
+
+    def encode_to_device(self, column, stage=None):
+        """A DICTIONARY-TYPED column -> the DeviceColumn of its running codes, without a host copy of the codes (None for any
+        other input: the caller encodes on the host route of encode()):
+          1. the batch dictionary's values through the device encode (skipped when they are the previous batch's buffers): int32
+             codes, -1 for a NULL value -- the table, uploaded once per batch dictionary;
+          2. the index buffer staged at its native width (`stage`: array -> DeviceColumn; io sources pass the pinned ring,
+             default DeviceColumn.from_arrow);
+          3. vnm_strdict_remap_indices: codes = table[index], -1 and a cleared validity bit for a NULL row or a NULL value; an
+             index outside the batch dictionary raises "dictionary index out of bounds"."""
+        import numpy as np
+        from .device import DeviceBuffer, DeviceColumn
+        if not self._dict_typed:
+            return None
+        if isinstance(column, pa.ChunkedArray):
+            column = column.combine_chunks() if column.num_chunks != 1 else column.chunk(0)
+        if not isinstance(column, pa.DictionaryArray):
+            return None
+        n = len(column)
+        if n == 0:
+            return DeviceColumn(DeviceBuffer(0), None, 0, 0, pa.int32(), dictionary=self)
+        values = column.dictionary
+        if values.type != self.value_type:
+            values = values.cast(self.value_type)
+        if self._batch_dict is None or not self._same_buffers(values, self._batch_dict):
+            table = self._encode_values(values) if len(values) else np.zeros(0, np.int32)
+            self.values_encodes += 1
+            self._batch_dict, self._batch_table = values, DeviceBuffer.from_host(table)
+            self._batch_table_nulls = bool((table < 0).any())
+        idx = column.indices                           # (the column's validity, offset and length with the integer type)
+        icol = stage(idx) if stage is not None else DeviceColumn.from_arrow(idx)
+        d = icol.dcol()
+        codes = DeviceBuffer(n * 4)
+        validity = DeviceBuffer((n + 7) >> 3) if (idx.null_count or self._batch_table_nulls) else None
+        bad = ctypes.c_int64(0)
+        L.check(L.lib().vnm_strdict_remap_indices(ctypes.byref(d), self._batch_table.ptr, len(values), codes.ptr,
+                                                 validity.ptr if validity is not None else None, ctypes.byref(bad), None))
+        self.remap_launches += 1
+        return DeviceColumn(codes, validity, 0, n, pa.int32(), dictionary=self)
 
     def encode(self, column) -> pa.Array:
         import numpy as np
         import pyarrow.compute as pc
         if isinstance(column, pa.ChunkedArray):
             column = column.combine_chunks()
+        if self._dict_typed and not len(column):
+            return pa.array([], type=pa.int32())
+        if self._dict_typed:
+            dev = self.encode_to_device(column)
+            if dev is None:
+                raise TypeError(f"KeyDictionary({self.type}).encode: a {column.type} column")
+            codes = dev.to_numpy()
+            return pa.array(codes, type=pa.int32(), mask=(codes < 0) if dev.validity_ptr else None)
         if self._device and len(column):
             return self._encode_device(column)
         enc = column.dictionary_encode()
@@ -581,7 +685,7 @@ class KeyDictionary:
         vals = self.values_by_code()
         if not len(vals):
             return None
-        i = pc.index(vals, pa.scalar(value, type=self.type)).as_py()
+        i = pc.index(vals, pa.scalar(value, type=self.value_type)).as_py()
         return None if i < 0 else int(i)
 
     def rank_bounds(self, value):
@@ -592,7 +696,7 @@ class KeyDictionary:
         vals = self.values_by_code()
         if not len(vals):
             return 0, 0
-        lit = pa.scalar(value, type=self.type)
+        lit = pa.scalar(value, type=self.value_type)
         less = int(pc.sum(pc.less(vals, lit)).as_py() or 0)
         return less, 0 if self.code_of(value) is None else 1
 
@@ -627,9 +731,9 @@ class KeyDictionary:
         what it holds), so a stream of batches matches each distinct value once per pattern."""
         from . import ops
         from .device import DeviceBuffer, DeviceColumn
-        t = self.type
+        t = self.value_type                                              # (a dictionary-typed column: what its values are)
         if not (pa.types.is_string(t) or pa.types.is_large_string(t)):
-            raise TypeError(f"LIKE needs a string column, not {t}")    # (the reference's re.match raises on bytes / numbers)
+            raise TypeError(f"LIKE needs a string column, not {self.type}")    # (the reference's re.match raises on bytes / numbers)
         ops.like_tokens(pattern)                                         # (NotImplementedError for a regex metacharacter)
         lib = L.lib()
         top = int(lib.vnm_strdict_ids(self._h)) if self._h is not None else 0
@@ -656,7 +760,7 @@ class KeyDictionary:
 
     def _pair_check(self, other, what):
         if not (self._device and getattr(other, "on_device", False)):
-            raise NotImplementedError(f"no GPU lowering for {what} of a {self.type} and a {other.type} dictionary: the device "
+            raise NotImplementedError(f"no GPU lowering for {what} of a {self.value_type} and a {getattr(other, 'value_type', other.type)} dictionary: the device "
                                       "dictionaries are the string and binary types")
 
     @staticmethod
@@ -734,7 +838,7 @@ class KeyDictionary:
             cached = getattr(self, "_by_code_cache", None)
             if cached is not None and cached[0] == stamp:
                 return cached[1]
-            values = pa.concat_arrays(self._chunks) if self._chunks else pa.array([], type=self.type)
+            values = pa.concat_arrays(self._chunks) if self._chunks else pa.array([], type=self.value_type)
             pos = self._pos[:top] if self._pos is not None else np.zeros(0, np.int64)
             out = values.take(pa.array(np.where(pos < 0, 0, pos), type=pa.int64(), mask=(pos < 0) if (pos < 0).any() else None))
             self._by_code_cache = (stamp, out)
@@ -742,9 +846,17 @@ class KeyDictionary:
         return self.values
 
     def decode(self, codes: pa.Array) -> pa.Array:
-        if self._device and self._h is not None:
+        """codes -> values of the column's type.  A dictionary-typed column comes back with ITS type (value type, index type,
+        `ordered`): decoded to the value type, then cast -- the output's dictionary is built by that cast and need not equal any
+        input dictionary; more distinct values than the index type can number surface Arrow's cast error."""
+        if self._dict_typed:
+            return self._decode_values(codes).cast(self.type)
+        return self._decode_values(codes)
+
+    def _decode_values(self, codes: pa.Array) -> pa.Array:
+        if self._device and (self._h is not None or self._pos is not None):
             import numpy as np
-            values = pa.concat_arrays(self._chunks) if self._chunks else pa.array([], type=self.type)
+            values = pa.concat_arrays(self._chunks) if self._chunks else pa.array([], type=self.value_type)
             c = codes.fill_null(0).to_numpy(zero_copy_only=False).astype(np.int64)
             pos = self._pos[c] if self._pos is not None and len(c) else np.zeros(len(c), np.int64)
             null = ~codes.is_valid().to_numpy(zero_copy_only=False) if codes.null_count else np.zeros(len(c), bool)
