@@ -519,6 +519,28 @@ int vnm_strdict_like(vnm_strdict* h, const uint8_t* pattern, int64_t pattern_len
  * vnm_strdict_ranks_device it reads counts back in between and returns when the ranks are written. */
 int vnm_strdict_translate(vnm_strdict* src, vnm_strdict* dst, int64_t id_begin, int32_t* out_dst_code_of_src_id, void* stream);
 int vnm_strdict_ranks_joint(vnm_strdict* a, vnm_strdict* b, int32_t* out_rank_of_id_a, int32_t* out_rank_of_id_b, void* stream);
+/* upper() / lower() (UpperStringFunction / LowerStringFunction, vinum/core/functions.py:279-298: pc.utf8_upper / pc.utf8_lower, one
+ * code point -> one code point, no context) as a function of the dictionary's VALUES: dst is the dictionary DERIVED from src under
+ * the map, a row then costs one lookup of its code.
+ * vnm_strdict_map_codepoints: for every id of src in [id_begin, vnm_strdict_ids(src)) the value's bytes are decoded as UTF-8, each
+ * code point found in map_from (n_map entries, strictly ascending, at most 2048) is replaced by the map_to entry at the same
+ * position, the result is encoded and found or inserted in dst; out_dst_code_of_src_id[id] = dst's code of it (a DEVICE array of
+ * vnm_strdict_ids(src) int32s; only that range is written).  -2: the id was never handed out, or its value is malformed (-1 stays
+ * the NULL code).  Two values with one image get one code.  src is only read; afterwards vnm_strdict_last_new / _fetch_new on dst
+ * return the values it added, as after an encode.  A table kept across batches is extended with id_begin = the id count it covers;
+ * growth of dst invalidates nothing as long as dst grows through this call alone.  The map is checked and uploaded on the first
+ * call with a dst handle and kept; a later call with another map is refused, so is a map_from that is not strictly ascending and a
+ * pair whose image needs more than twice the bytes of its source (a value's room in the scratch buffer is twice its length; the
+ * Unicode case maps stay inside: ASCII maps into ASCII, the longest growth is 2 -> 3 bytes).
+ * Malformed means structurally broken, what Arrow refuses: a continuation byte where a lead byte is due, a lead byte without all
+ * its continuation bytes inside the value (the bytes of the NEXT value are never read), 0xF8..0xFF.  Overlong forms, surrogates and
+ * values past U+10FFFF are not looked for (Arrow is lax about them too): a code point outside the map is copied as it stands.
+ * Such a value is counted and not inserted.  out_invalid != NULL: the count is stored there and a non-zero count returns non-zero
+ * with "Invalid UTF8 sequence in input" -- the well-formed values are in dst and in the table all the same.  out_invalid == NULL:
+ * malformed values just get -2.  Either way the call goes through dst's encode, which reads counts back: it returns when the
+ * table is written. */
+int vnm_strdict_map_codepoints(vnm_strdict* src, vnm_strdict* dst, const int32_t* map_from, const int32_t* map_to, int64_t n_map,
+                               int64_t id_begin, int32_t* out_dst_code_of_src_id, int64_t* out_invalid, void* stream);
 /* A dictionary-typed Arrow column (dictionary<intN, utf8 | large_utf8 | binary | large_binary>): the batch dictionary's indices ->
  * codes of the running dictionary.  The caller runs the batch dictionary's VALUES through vnm_strdict_encode and uploads the result
  * as code_of_index (n_values int32s on the DEVICE; -1 = a NULL value), so only n_values strings are hashed, not one per row.

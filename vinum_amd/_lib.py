@@ -130,6 +130,7 @@ PROTOTYPES = {
     "vnm_strdict_last_new": (c_int, [c_void, c_void, c_void]),
     "vnm_strdict_translate": (c_int, [c_void, c_void, c_i64, c_void, c_void]),
     "vnm_strdict_ranks_joint": (c_int, [c_void, c_void, c_void, c_void, c_void]),
+    "vnm_strdict_map_codepoints": (c_int, [c_void, c_void, c_void, c_void, c_i64, c_i64, c_void, c_void, c_void]),
     "vnm_strdict_remap_indices": (c_int, [c_void, c_void, c_i64, c_void, c_void, c_void, c_void]),
     "vnm_like_compile": (c_int, [c_void, c_i64, c_void, c_void]),
     "vnm_strdict_like": (c_int, [c_void, c_void, c_i64, c_int, c_i64, c_void, c_void]),

@@ -171,8 +171,30 @@ class LikeFunction(VectorizedExpression):
         super().__init__(arguments, is_numpy_func=True)
         self.invert = invert
 
-# the numeric part of _default_functions_registry, with the same callables (math constants: the lambdas themselves)
+
+
+class AbstractStringFunction(VectorizedExpression):
+    """Shape of functions.py:196-247: built as Cls(arguments), `_function` is None, the work lives in `_expr_kernel`."""
+
+    def __init__(self, arguments: Iterable, shared_id: Optional[str] = None):
+        super().__init__(arguments)
+
+
+class UpperStringFunction(AbstractStringFunction):
+    """functions.py:279-287: pc.utf8_upper over the argument (cast to string first, :219-221)."""
+
+
+class LowerStringFunction(AbstractStringFunction):
+    """functions.py:290-297: pc.utf8_lower."""
+
+
+_CASE_SPEC = {"UpperStringFunction": "upper", "LowerStringFunction": "lower"}
+
+# the numeric part of _default_functions_registry, with the same callables (math constants: the lambdas themselves), and the two
+# string functions that run on the device
 FUNCTIONS_REGISTRY = {
+    "upper": (UpperStringFunction, FunctionType.CLASS),
+    "lower": (LowerStringFunction, FunctionType.CLASS),
     "to_bool": (BoolCastFunction, FunctionType.CLASS),
     "to_float": (FloatCastFunction, FunctionType.CLASS),
     "to_int": (IntCastFunction, FunctionType.CLASS),
@@ -231,7 +253,9 @@ def vectorize(expr, registry=None, classes=None, functions=None, like_cls=None):
             return Lt(args[0])
         if op in ("like", "not_like"):                           # planner.py:189-193
             return like_cls(tuple(build(a) for a in args), op == "not_like")
-        if op == "fn" and (args[0].lower() in _AGG_NAMES or not _is_builtin(args[0].lower(), functions)):
+        # (the "fn" spelling of upper / lower builds what it always built, an AggregateFunction node -- the planner resolves that
+        #  spelling by the operand's type, planner._case_by_type; the operator node ("upper", x) builds the function's class)
+        if op == "fn" and (args[0].lower() in _AGG_NAMES or args[0].lower() in _CASE_SPEC.values() or not _is_builtin(args[0].lower(), functions)):
             arg = build(args[1]) if len(args) > 1 else None
             return AF(args[0], arg) if arg is not None else AF(args[0])
         if op == "fn" or op in FUNCTIONS_REGISTRY:
@@ -290,13 +314,18 @@ def lower(node, index: Optional[Dict[int, str]] = None):
         if fn is None and cast in _CAST_SPEC and type(node).__name__ in ("BoolCastFunction", "FloatCastFunction", "IntCastFunction"):
             args = [lower(a, index) for a in node.arguments]   # AbstractCastFunction (functions.py:148-162)
             return (_CAST_SPEC[cast],) + tuple(args)
+        # UpperStringFunction / LowerStringFunction (functions.py:279-298), by QUALIFIED name: the class the reference (or this
+        # module) defines under that name at module level -- some other class whose __name__ was set to it is not that function
+        if fn is None and type(node).__qualname__ in _CASE_SPEC and len(tuple(node.arguments)) == 1:
+            return (_CASE_SPEC[type(node).__qualname__], lower(tuple(node.arguments)[0], index))
         if fn is not None and id(fn) not in index and id(fn) in _UFUNC_SPEC:
             return (_UFUNC_SPEC[id(fn)],) + tuple(lower(a, index) for a in node.arguments)
         if fn is None or id(fn) not in index:
             raise NotImplementedError(f"no GPU lowering for {fn if fn is not None else type(node).__name__!r}: the numeric "
                                       "operators and the built-ins abs, sqrt, sin, cos, tan, log, log2, log10, power, pi, e, "
-                                      "to_int, to_float, to_bool and LIKE / NOT LIKE against a string literal run on the "
-                                      "GPU; UDFs, string and datetime functions and other np.* functions do not")
+                                      "to_int, to_float, to_bool, upper / lower of a string column and LIKE / NOT LIKE against "
+                                      "a string literal run on the GPU; UDFs, concat, to_str, the datetime functions and other "
+                                      "np.* functions do not")
         sql = index[id(fn)]
         args = [lower(a, index) for a in node.arguments]
         if sql.startswith("fn:"):

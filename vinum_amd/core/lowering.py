@@ -1,5 +1,5 @@
 """What a dictionary-coded column (strings, binaries: int32 codes of the column's own running dictionary in HBM) needs before an
-expression over it is a numeric program: three rewrites of vinum_amd.expr trees (lower_dictionary runs them in order) and the one
+expression over it is a numeric program: four rewrites of vinum_amd.expr trees (lower_dictionary runs them in order) and the one
 path on which the operators evaluate lowered expressions (project_lowered, used_columns).  `columns` is a batch's name ->
 DeviceColumn; every rewrite returns (expression, extra), `extra` holding the tables, rank and mask columns the result reads by name."""
 from .. import expr as E
@@ -13,6 +13,49 @@ def _is_dict(x, columns) -> bool:
 def value_type_of(dictionary):
     """what a dictionary's VALUES are: a dictionary-typed column (dictionary<int8, utf8>) is a utf8 column to every message and rule"""
     return getattr(dictionary, "value_type", dictionary.type)
+
+
+CASE_FNS = ("upper", "lower")
+
+
+def with_derived(columns, extra):
+    """`columns` plus the dictionary-coded columns a lowering has put into `extra` (lower_case_functions: upper(city) is a column)"""
+    derived = {n: c for n, c in extra.items() if getattr(c, "dictionary", None) is not None}
+    return {**columns, **derived} if derived else columns
+
+
+def lower_case_functions(expr, columns, extra=None):
+    """upper(x) / lower(x) (UpperStringFunction / LowerStringFunction, vinum/core/functions.py:279-298: pc.utf8_upper / utf8_lower)
+    over a dictionary-coded string column, or over another such function: the node becomes the NAME of a derived column added to
+    `extra` -- the int32 codes of the DERIVED dictionary (KeyDictionary.mapped_column: each distinct value mapped once on the
+    device, a row one lookup), the operand's validity, `.dictionary` the derived dictionary.  To every later step and operator it
+    is an ordinary string column.  A node that occurs several times under one `extra` is materialised once.  A numeric column
+    raises TypeError (the reference would print the numbers as text: not restated), a literal or any other expression
+    NotImplementedError; a binary column TypeError and a host-route dictionary NotImplementedError (KeyDictionary.mapped)."""
+    extra = {} if extra is None else extra
+
+    def f(e):
+        if e[0] not in CASE_FNS:
+            return None
+        if len(e) != 2:
+            raise NotImplementedError(f"no GPU lowering for {e[0]}() with {len(e) - 1} operand(s)")
+        x = e[1]
+        if isinstance(x, tuple) and x and x[0] in CASE_FNS:
+            x = f(x)
+        cols = with_derived(columns, extra)
+        if not isinstance(x, str) or x not in cols:
+            raise NotImplementedError(f"no GPU lowering for {e[0]}() over {x!r}: the operand must be a string column or upper() / lower() of one")
+        c = cols[x]
+        if c.dictionary is None:
+            raise TypeError(f"{e[0]}() needs a string column, {x!r} is {c.arrow_type}")
+        mapped_column = getattr(c.dictionary, "mapped_column", None)
+        if mapped_column is None:         # a dictionary object that cannot map: the node stays, and is refused where it is compiled
+            return e
+        name = f"__{e[0]}_{x}"
+        if name not in extra:
+            extra[name] = mapped_column(e[0], c)
+        return name
+    return E.rewrite(expr, f), extra
 
 
 def lower_like(expr, columns, extra=None):
@@ -149,8 +192,11 @@ def lower_literal_compares(expr, columns, extra=None):
 
 
 def lower_dictionary(expr, columns, extra=None):
-    """The three lowerings in their order: LIKE, then the column pairs -- which refuse a numeric operand, so they run before the
-    literals turn into codes and ranks -- then the literals; the last two only act where a dictionary-coded column is read at all."""
+    """The four lowerings in their order: upper() / lower() -- whose results are string columns to the other three --, LIKE, then
+    the column pairs -- which refuse a numeric operand, so they run before the literals turn into codes and ranks -- then the
+    literals; the last two only act where a dictionary-coded column is read at all."""
+    expr, extra = lower_case_functions(expr, columns, extra)
+    columns = with_derived(columns, extra)
     expr, extra = lower_like(expr, columns, extra)
     if any(_is_dict(c, columns) for c in E.columns_of(expr)):
         expr, extra = lower_column_compares(expr, columns, extra)
@@ -164,8 +210,11 @@ def used_columns(exprs, columns, extra):
 
 
 def project_lowered(exprs, columns, length, scalar_length=None):
-    """ops.project_many of `exprs` lowered into one shared `extra`; scalar_length: the length when none of them reads a column"""
+    """ops.project_many of `exprs` lowered into one shared `extra`; scalar_length: the length when none of them reads a column.
+    An expression that lowers to a column of `extra` -- upper(city): the derived column -- is that column, no program runs."""
     extra = {}
     exprs = [lower_dictionary(e, columns, extra)[0] for e in exprs]
-    used = used_columns(exprs, columns, extra)
-    return ops.project_many(exprs, used, length=length if used or scalar_length is None else scalar_length)
+    computed = [e for e in exprs if not (isinstance(e, str) and e in extra)]
+    used = used_columns(computed, columns, extra)
+    res = iter(ops.project_many(computed, used, length=length if used or scalar_length is None else scalar_length) if computed else [])
+    return [extra[e] if (isinstance(e, str) and e in extra) else next(res) for e in exprs]

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "vnm_common.hpp"
+#include "vnm_strcase.hpp"
 
 namespace vnm {
 
@@ -630,6 +631,81 @@ __global__ __launch_bounds__(256) void sd_remap_kernel(RemapArgs a) {
     }
 }
 
+// ---- upper() / lower() over the dictionary's values (UpperStringFunction / LowerStringFunction, vinum/core/functions.py:279-298) -----
+// pc.utf8_upper / utf8_lower map code point -> code point without context, so a function of the VALUE alone: one lane per id of
+// `src` decodes its value, substitutes every code point found in a sorted table (map_from -> map_to, ~1500 pairs, a copy in LDS per
+// workgroup), encodes the image into a scratch buffer and the (start, length) spans go through the encode kernel above into `dst`.
+// No scan: a code point's image is at most twice as long as the code point (the host refuses a map where it is not), so value `id`
+// owns the 2 * length bytes at twice its heap offset relative to the first heap byte of this call's ids.
+//   * 8 source bytes per step while they are all < 0x80 and the map keeps ASCII inside ASCII: eight lookups in a 128-byte LDS
+//     table, one 8-byte store -- the code point table is not touched;
+//   * any other code point: lead byte -> length, the length is held against the END OF THE VALUE before a continuation byte is
+//     read (a lead byte at the end of a value never pulls in its neighbour's bytes), continuation bytes must be 10xxxxxx; a stray
+//     continuation byte and 0xF8..0xFF are no lead bytes.  Such a value is counted, gets no span (validity bit 0) and is not inserted;
+//   * the search is a branch-free lower bound over the LDS copy (one compare + select per power of two);
+//   * every store is held against the value's room first, whatever the table says.
+// A wave takes 64 consecutive ids, so its ballot IS the 8 bytes of the validity bitmap the encode kernel reads for them.
+constexpr int MC_MAX_MAP = 2048;   // pairs a workgroup holds in LDS (16 KB); the two Unicode case maps have ~1500
+
+struct SdMapArgs {
+    const uint8_t* sheap;
+    const int64_t* s_off;
+    const int32_t* s_len;          // -1: an id never handed out
+    const int32_t* map;            // [n_map] from (ascending), [n_map] to, then 128 bytes: the image of every ASCII byte
+    int n_map, top_step;           // top_step: the largest power of two <= n_map (0: an empty map)
+    int ascii_closed;              // every ASCII code point maps inside ASCII: the 8-byte step may be taken
+    int64_t id_begin, id_end;
+    int64_t heap_base;             // no id >= id_begin lies below this heap offset
+    uint8_t* scratch;
+    int64_t scratch_bytes;
+    int64_t* starts;               // [id_end - id_begin] spans of the images in `scratch`
+    int32_t* lens;
+    unsigned long long* valid;     // bitmap, bit id - id_begin: the value exists and is well-formed
+    unsigned long long* counts;    // [0] malformed values  [1] values whose room lay outside the scratch buffer (internal error)
+};
+
+__global__ __launch_bounds__(256) void sd_map_kernel(SdMapArgs a) {
+    __shared__ int32_t s_from[MC_MAX_MAP], s_to[MC_MAX_MAP];
+    __shared__ uint8_t s_ascii[128];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < a.n_map; i += 256) { s_from[i] = a.map[i]; s_to[i] = a.map[a.n_map + i]; }
+    if (tid < 128) s_ascii[tid] = ((const uint8_t*)(a.map + 2 * (int64_t)a.n_map))[tid];
+    __syncthreads();
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t id0 = a.id_begin + (int64_t)blockIdx.x * 256; id0 < a.id_end; id0 += stride) {   // (uniform trips: every lane reaches the ballots)
+        const int64_t id = id0 + tid;
+        const int64_t len = id < a.id_end ? (int64_t)a.s_len[id] : -1;
+        const bool live = len >= 0;
+        bool ok = live, outside = false;
+        int64_t start = 0, o = 0;
+        if (live) {
+            const int64_t off = a.s_off[id];
+            const int64_t room = 2 * len;
+            start = 2 * (off - a.heap_base);
+            if (off < a.heap_base || start + room > a.scratch_bytes) { ok = false; outside = true; }
+            if (ok) {
+                o = mc_map_value(a.sheap + off, len, a.scratch + start, room, s_from, s_to, a.n_map, a.top_step, s_ascii, a.ascii_closed != 0);
+                ok = o >= 0;
+            }
+        }
+        if (id < a.id_end) { a.starts[id - a.id_begin] = ok ? start : 0; a.lens[id - a.id_begin] = ok ? (int32_t)o : 0; }
+        const unsigned long long good = __ballot(ok), bad = __ballot(live && !ok && !outside), out = __ballot(outside);
+        if ((tid & 63) == 0) {
+            const int64_t first = id0 + (tid & ~63);                        // the wave's first id
+            if (first < a.id_end) a.valid[(first - a.id_begin) >> 6] = good;
+            if (bad) atomicAdd(&a.counts[0], (unsigned long long)__popcll(bad));
+            if (out) atomicAdd(&a.counts[1], (unsigned long long)__popcll(out));
+        }
+    }
+}
+
+// after the encode: a row without a span came back as the NULL code -1; in a table indexed by id it is "no code", -2
+__global__ __launch_bounds__(256) void sd_map_absent_kernel(int32_t* codes, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
+        if (codes[i] < 0) codes[i] = -2;
+}
+
 }  // namespace vnm
 
 using namespace vnm;
@@ -651,6 +727,13 @@ struct vnm_strdict {
     int32_t* id_len = nullptr;
     int64_t id_cap = 0;
     std::map<std::string, std::pair<int32_t*, int>> like_patterns;   // pattern -> its tokens + bytes on the device, token count
+    // (ids, heap_used) after every encode that added values: an id >= marks[k].first lies at or above heap offset marks[k].second
+    // (ids are never handed out again and the heap only grows) -- where vnm_strdict_map_codepoints' scratch for [id_begin, ids) starts
+    std::vector<std::pair<int64_t, int64_t>> marks;
+    // as the DESTINATION of vnm_strdict_map_codepoints: the code point map this dictionary was derived with, uploaded once
+    int32_t* map_dev = nullptr;              // [n] from, [n] to, 128 bytes ASCII image
+    std::vector<int32_t> map_host;           // from + to, to recognise the map on the next call
+    int map_ascii_closed = 0;
 };
 
 // the id-indexed arrays cover every id handed out so far (ids come in chunks, so they grow even when no value is new)
@@ -686,6 +769,7 @@ void vnm_strdict_destroy(vnm_strdict* h) {
     pool_free(h->id_off);
     pool_free(h->id_len);
     for (auto& kv : h->like_patterns) pool_free(kv.second.first);
+    pool_free(h->map_dev);
     delete h;
 }
 
@@ -834,6 +918,7 @@ static int strdict_encode_device_impl(vnm_strdict* h, const vnm_dcol* offsets, c
     if (tot[1]) VNM_HIP(hipMemcpyAsync(h->new_bytes.data(), h->heap + h->heap_used, (size_t)tot[1], hipMemcpyDeviceToHost, s));
     VNM_HIP(hipStreamSynchronize(s));
     h->heap_used += (int64_t)tot[1];
+    h->marks.emplace_back(h->ids, h->heap_used);
     if (n_new) *n_new = (int64_t)fresh;
     if (new_bytes) *new_bytes = (int64_t)tot[1];
     return 0;
@@ -991,6 +1076,100 @@ int vnm_strdict_translate(vnm_strdict* src, vnm_strdict* dst, int64_t id_begin, 
         sd_translate_kernel<<<grid, 256, 0, s>>>(a);
     }
     VNM_HIP(hipGetLastError());
+    return 0;
+}
+
+static int utf8_width(int64_t cp) { return cp < 0x80 ? 1 : cp < 0x800 ? 2 : cp < 0x10000 ? 3 : 4; }
+
+// Every value of `src` with an id in [id_begin, vnm_strdict_ids(src)) mapped code point by code point (map_from -> map_to) and
+// found or inserted in `dst`: out_dst_code_of_src_id[id] = dst's code of the image, -2 for an id never handed out and for a
+// malformed value.  sd_map_kernel writes the images, strdict_encode_device_impl (the spans form) inserts them: afterwards dst's
+// new values are fetched as after any encode.  The encode reads counts back, so the call returns when the table is written.
+int vnm_strdict_map_codepoints(vnm_strdict* src, vnm_strdict* dst, const int32_t* map_from, const int32_t* map_to, int64_t n_map,
+                               int64_t id_begin, int32_t* out_dst_code_of_src_id, int64_t* out_invalid, void* stream) {
+    VNM_TRY(ensure_init());
+    if (out_invalid) *out_invalid = 0;
+    if (!src || !dst || !out_dst_code_of_src_id || (n_map > 0 && (!map_from || !map_to))) return set_error("vnm_strdict_map_codepoints: null argument");
+    if (src == dst) return set_error("vnm_strdict_map_codepoints: src and dst are one dictionary (src is only read, dst grows)");
+    if (src->failed || dst->failed) return set_error("vnm_strdict: an earlier encode failed half-way; the dictionary cannot be used any more (create a new one)");
+    if (id_begin < 0) return set_error("vnm_strdict_map_codepoints: id_begin < 0");
+    if (n_map < 0 || n_map > MC_MAX_MAP) return set_error("vnm_strdict_map_codepoints: a map of %lld pairs (0..%d are held)", (long long)n_map, MC_MAX_MAP);
+    // ---- the map: checked on the host, uploaded once per dst handle
+    if (!dst->map_dev) {
+        int closed = 1;
+        for (int64_t i = 0; i < n_map; i++) {
+            const int64_t f = map_from[i], t = map_to[i];
+            if (f < 0 || f > 0x10FFFF || t < 0 || t > 0x10FFFF) return set_error("vnm_strdict_map_codepoints: pair %lld (U+%04llX -> U+%04llX) is no code point", (long long)i, (long long)f, (long long)t);
+            if (i > 0 && map_from[i - 1] >= f) return set_error("vnm_strdict_map_codepoints: map_from must be strictly ascending (entry %lld: U+%04llX after U+%04llX)", (long long)i, (long long)f, (long long)map_from[i - 1]);
+            if (utf8_width(t) > 2 * utf8_width(f))
+                return set_error("vnm_strdict_map_codepoints: U+%04llX (%d byte) -> U+%04llX (%d bytes): an image may be at most twice as long as its source, the room a value has",
+                                 (long long)f, utf8_width(f), (long long)t, utf8_width(t));
+            if (f < 0x80 && t >= 0x80) closed = 0;
+        }
+        std::vector<int32_t> blob((size_t)n_map * 2 + 32, 0);
+        if (n_map) { memcpy(blob.data(), map_from, (size_t)n_map * 4); memcpy(blob.data() + n_map, map_to, (size_t)n_map * 4); }
+        uint8_t* ascii = (uint8_t*)(blob.data() + 2 * n_map);
+        for (int b = 0; b < 128; b++) ascii[b] = (uint8_t)b;
+        if (closed)
+            for (int64_t i = 0; i < n_map && map_from[i] < 0x80; i++) ascii[map_from[i]] = (uint8_t)map_to[i];
+        int32_t* dev = (int32_t*)pool_alloc(blob.size() * 4);
+        if (!dev) return 1;
+        if (hipMemcpy(dev, blob.data(), blob.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { pool_free(dev); return set_error("vnm_strdict_map_codepoints: map upload failed"); }
+        dst->map_dev = dev;
+        dst->map_host.assign(blob.begin(), blob.begin() + 2 * n_map);
+        dst->map_ascii_closed = closed;
+    } else if ((int64_t)dst->map_host.size() != 2 * n_map || (n_map && (memcmp(dst->map_host.data(), map_from, (size_t)n_map * 4) ||
+                                                                        memcmp(dst->map_host.data() + n_map, map_to, (size_t)n_map * 4)))) {
+        return set_error("vnm_strdict_map_codepoints: dst was derived with another map");
+    }
+    dst->new_ids.clear(); dst->new_lens.clear(); dst->new_bytes.clear();
+    const int64_t n = src->ids - id_begin;
+    if (n <= 0) return 0;
+    hipStream_t s = as_stream(stream);
+    int64_t heap_base = 0;
+    for (const auto& m : src->marks)
+        if (m.first <= id_begin) heap_base = m.second;
+    PoolScope pool;
+    SdMapArgs a{};
+    a.sheap = src->heap; a.s_off = src->id_off; a.s_len = src->id_len;
+    a.map = dst->map_dev; a.n_map = (int)n_map; a.ascii_closed = dst->map_ascii_closed;
+    for (int p = 1; p <= a.n_map; p <<= 1) a.top_step = p;
+    a.id_begin = id_begin; a.id_end = src->ids;
+    a.heap_base = heap_base;
+    a.scratch_bytes = 2 * (src->heap_used - heap_base);
+    const int64_t words = (n + 63) / 64;
+    a.scratch = (uint8_t*)pool.take((size_t)std::max<int64_t>(a.scratch_bytes, 8));
+    a.starts = (int64_t*)pool.take((size_t)n * 8);
+    a.lens = (int32_t*)pool.take((size_t)n * 4);
+    a.valid = (unsigned long long*)pool.take((size_t)words * 8);
+    a.counts = (unsigned long long*)pool.take(16);
+    if (!a.scratch || !a.starts || !a.lens || !a.valid || !a.counts) return 1;
+    VNM_HIP(hipMemsetAsync(a.counts, 0, 16, s));
+    const int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)device_info().num_cus * 8);
+    {
+        KernelTimer timer("strdict_map_codepoints", s);
+        sd_map_kernel<<<grid, 256, 0, s>>>(a);
+    }
+    VNM_HIP(hipGetLastError());
+    vnm_dcol offs{};
+    offs.values = (void*)a.starts; offs.type = VNM_I64; offs.offset = 0; offs.length = n + 1;
+    int32_t* out = out_dst_code_of_src_id + id_begin;
+    const int rc = strdict_encode_device_impl(dst, &offs, a.lens, (const uint8_t*)a.valid, 0, a.scratch, 0, out, nullptr, nullptr, stream);
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        if (dst->d.slot) dst->failed = true;
+        return rc;
+    }
+    sd_map_absent_kernel<<<(int)std::min<int64_t>((n + 255) / 256, (int64_t)device_info().num_cus * 8), 256, 0, s>>>(out, n);
+    VNM_HIP(hipGetLastError());
+    unsigned long long counts[2] = {0, 0};
+    VNM_HIP(hipMemcpyAsync(counts, a.counts, 16, hipMemcpyDeviceToHost, s));
+    VNM_HIP(hipStreamSynchronize(s));     // (the scratch goes back to the pool with this scope)
+    if (counts[1]) return set_error("vnm_strdict_map_codepoints: %llu value(s) lay outside the scratch buffer (internal error)", counts[1]);
+    if (out_invalid) {
+        *out_invalid = (int64_t)counts[0];
+        if (counts[0]) return set_error("Invalid UTF8 sequence in input (%llu of %lld dictionary value(s))", counts[0], (long long)n);
+    }
     return 0;
 }
 

@@ -11,8 +11,8 @@ A query is a dict (see tests/golden/planner_cases.py):
     order_by   [expr]            sort_order ["ASC" | "DESC"]   limit int | None   offset int
     expr := the prefix tuples of vinum_amd.expr (the one definition of the node forms), with ("fn", name, arg...) for the
             aggregate functions count_star / count / sum / avg / min / max and the numeric built-in scalar functions
-            (SCALAR_FN_NAMES: abs, sqrt, sin, ..., to_int, pi, e and their np. spellings), which are per-row expressions
-            wherever they appear, like any operator; LIKE / NOT LIKE against a utf8 / large_utf8 column (planner.py:189-193)
+            (SCALAR_FN_NAMES: abs, sqrt, sin, ..., to_int, pi, e and their np. spellings) and upper / lower of a string
+            column, which are per-row expressions wherever they appear, like any operator; LIKE / NOT LIKE against a utf8 / large_utf8 column (planner.py:189-193)
             may stand in WHERE, HAVING, the SELECT list (a uint8 mask) and aggregate arguments alike.
 
 What the planner does with the aggregate part mirrors planner.py:380-469:
@@ -39,6 +39,8 @@ SCALAR_FN_NAMES = {n: n for n in ("abs", "sqrt", "cos", "sin", "tan", "power", "
                                   "to_bool", "pi", "e")}
 SCALAR_FN_NAMES.update({"np." + n: n for n in ("sqrt", "cos", "sin", "tan", "power", "log", "log2", "log10", "abs")})
 SCALAR_FN_NAMES["np.absolute"] = "abs"
+# the string built-ins that run on the device: a function of the column's dictionary (core.lowering.lower_case_functions)
+SCALAR_FN_NAMES.update({"upper": "upper", "lower": "lower"})
 
 
 def _t(e):
@@ -51,6 +53,18 @@ def _t(e):
             return tuple([SCALAR_FN_NAMES[e[1].lower()]] + [_t(x) for x in e[2:]])
         return tuple([e[0]] + [_t(x) for x in e[1:]])
     return e
+
+
+def _case_by_type(e, schema):
+    """upper(x) / lower(x) are the string built-ins where x can be a string.  Over a NUMERIC column of a table -- whose schema is
+    known at plan time -- the name is no function of this planner, and the query is refused as one with any unknown function is
+    ("unknown aggregate function 'upper'"; the reference would print the numbers as text, which is not restated).  Without a schema
+    (a file source, the adapter) the lowering raises TypeError for such an operand when the batch arrives (core.lowering)."""
+    for n in E.nodes(e) if e is not None else ():
+        if isinstance(n, tuple) and n and n[0] in ("upper", "lower") and len(n) == 2 and isinstance(n[1], str) and n[1] in schema.names:
+            t = schema.field(n[1]).type
+            if pa.types.is_integer(t) or pa.types.is_floating(t) or pa.types.is_temporal(t):
+                raise ValueError(f"unknown aggregate function {n[0]!r}: upper() / lower() take a string column, {n[1]!r} is {t}")
 
 
 def _is_fn(e) -> bool:
@@ -105,6 +119,9 @@ def plan_query(query: Dict, source, expected_groups: int = 0) -> Plan:
     limit, offset = query.get("limit"), query.get("offset") or 0
     distinct = bool(query.get("distinct"))
     steps = []
+    if isinstance(source, pa.Table):
+        for e in select + group_by + order_by + [where, having]:
+            _case_by_type(e, source.schema)
 
     # ---- column pruning (planner.py:346-371): only what the query touches is staged into HBM
     used: List[str] = []

@@ -527,6 +527,9 @@ class KeyDictionary:
         self.like_ids_matched = 0
         self._translate = {}       # id(other dictionary) -> [weakref, device table, capacity, ids it covers, own / other's value count]
         self._joint = {}           # id(other dictionary) -> [weakref, (own, other's value count), own / other's rank table, id counts]
+        self._mapped = {}          # "upper" | "lower" -> [derived dictionary, device table code -> derived code, capacity, ids it covers, own value count]
+        self.map_launches = 0      # vnm_strdict_map_codepoints calls and the ids they mapped, over both functions
+        self.map_ids_mapped = 0
         self.translate_builds = 0  # vnm_strdict_translate / vnm_strdict_ranks_joint calls this dictionary made (pair tables)
         self.joint_rank_builds = 0
 
@@ -825,6 +828,72 @@ class KeyDictionary:
             self.joint_rank_builds += 1
             entry = self._joint[id(other)] = [self._pair_ref(self._joint, other), stamp, mine, theirs, ids]
         return (DeviceColumn(entry[2], None, 0, entry[4][0], pa.int32()), DeviceColumn(entry[3], None, 0, entry[4][1], pa.int32()))
+
+    def mapped(self, fn: str):
+        """upper() / lower() of this dictionary (`fn`: "upper" | "lower"; pc.utf8_upper / pc.utf8_lower, functions.py:279-298):
+        (the DERIVED dictionary, an int32 DeviceColumn `code here -> code there`, one entry per id handed out here; -2 for an id
+        never handed out).  The function depends on the value alone, so each distinct value is mapped ONCE, on the device
+        (vnm_strdict_map_codepoints with the code point table of vinum_amd.strcase), and found or inserted in the derived
+        dictionary; a row then costs one lookup of its code (mapped_column).  One derived dictionary per (dictionary, function),
+        the same object for the life of this one -- an AggregateOperator keeps the one of its first batch -- extended with the ids
+        handed out since the last call; a batch that brought no new value launches nothing (`map_launches`, `map_ids_mapped`).
+        The derived dictionary is a full KeyDictionary of type string, whatever this one's is (the reference casts to string
+        first, functions.py:219-221): it absorbs its new values, so it decodes, ranks, matches LIKE, pairs with other dictionaries
+        and maps again (upper(lower(c))).  A binary / large_binary dictionary raises TypeError (Arrow has no such kernel), a
+        host-route dictionary NotImplementedError; a structurally malformed UTF-8 value raises ValueError("Invalid UTF8 sequence in
+        input") from the call that first maps it -- whether or not a row holding it survives the query's filter."""
+        from . import strcase
+        from .device import DeviceBuffer, DeviceColumn
+        if fn not in strcase.CASE_FNS:
+            raise ValueError(f"no case map {fn!r}: one of {strcase.CASE_FNS}")
+        if not self._device:
+            raise NotImplementedError(f"no GPU lowering for {fn}() over a {self.type} column: only string columns keep their dictionaries on the device")
+        t = self.value_type
+        if not (pa.types.is_string(t) or pa.types.is_large_string(t)):
+            raise TypeError(f"{fn}() needs a string column, not {self.type}")      # (pc.utf8_upper has no kernel for binary)
+        lib = L.lib()
+        top = self._id_count()
+        entry = self._mapped.get(fn)
+        if entry is None:
+            entry = self._mapped[fn] = [KeyDictionary(pa.string()), DeviceBuffer(max(top, 1) * 4), max(top, 1), 0, -1]
+        derived, buf, cap, covered, mine = entry
+        # by VALUES, as translate_table: the id counter moves by whole chunks on every encode, only a new value is work
+        if top > covered and mine != self._n_values:
+            if top > cap:
+                cap = max(top, 2 * cap)
+                grown = DeviceBuffer(cap * 4)
+                if covered:
+                    L.check(lib.vnm_memcpy_d2d(grown.ptr, buf.ptr, covered * 4, None))
+                buf = grown
+            map_from, map_to = strcase.case_table(fn)
+            invalid = ctypes.c_int64(0)
+            rc = lib.vnm_strdict_map_codepoints(self.handle(), derived.handle(), map_from.ctypes.data, map_to.ctypes.data, len(map_from),
+                                                covered, buf.ptr, ctypes.byref(invalid), None)
+            self.map_launches += 1
+            self.map_ids_mapped += top - covered
+            entry[1:3] = [buf, cap]
+            message = L.last_error() if rc != 0 else None
+            if derived._h is not None:
+                derived.absorb_new()        # (also after a malformed value: the well-formed ones are in the derived dictionary)
+            if rc != 0:                     # (nothing is recorded as covered: the next call maps these ids, and raises, again)
+                if invalid.value:
+                    raise ValueError("Invalid UTF8 sequence in input")
+                raise L.VinumHipError(message)
+            entry[3:] = [top, self._n_values]
+        return entry[0], DeviceColumn(entry[1], None, 0, entry[3], pa.int32())
+
+    def mapped_column(self, fn: str, codes_col):
+        """upper(column) / lower(column) over a column of THIS dictionary's codes: the int32 DeviceColumn of the derived
+        dictionary's codes -- table[code] per row, one gather (NULL stays NULL: same validity) -- with `.dictionary` the derived
+        dictionary, so every operator takes it as the string column it is."""
+        from .device import DeviceBuffer, DeviceColumn
+        derived, table = self.mapped(fn)
+        n = codes_col.length
+        off = codes_col.offset if codes_col._validity is not None else 0      # (one Arrow offset serves values and bitmap)
+        out = DeviceBuffer(max(off + n, 1) * 4)
+        if n:
+            L.check(L.lib().vnm_strdict_codes_to_ranks(codes_col.values_ptr + codes_col.offset * 4, table.values_ptr, n, out.ptr + off * 4, None))
+        return DeviceColumn(out, codes_col._validity, off, n, pa.int32(), keep=(table, codes_col), dictionary=derived)
 
     def values_by_code(self) -> pa.Array:
         """The dictionary as an array indexed by CODE (a code the device never handed out: NULL) -- what the ranks exchange to build
