@@ -18,7 +18,7 @@ import numpy as np
 import pyarrow as pa
 
 from vinum_amd import _lib as L
-from vinum_amd import planner, vinum_lib
+from vinum_amd import keydict, planner, vinum_lib
 from vinum_amd.device import DeviceBuffer, physical_type
 
 n = int(float(sys.argv[1])) if len(sys.argv) > 1 else 100_000_000
@@ -39,12 +39,12 @@ def timed(query, table, reps=3):
 class host_route:
     """dictionary types lose the device route inside: KeyDictionary takes Arrow dictionary_encode + index_in for them"""
 
-    def __enter__(self):
-        self._was = vinum_lib.device_value_type
-        vinum_lib.device_value_type = lambda t: None if pa.types.is_dictionary(t) else self._was(t)
+    def __enter__(self):        # (in both modules that look the function up: KeyDictionary's own and the aggregates')
+        self._was = keydict.device_value_type
+        keydict.device_value_type = vinum_lib.device_value_type = lambda t: None if pa.types.is_dictionary(t) else self._was(t)
 
     def __exit__(self, *exc):
-        vinum_lib.device_value_type = self._was
+        keydict.device_value_type = vinum_lib.device_value_type = self._was
 
 
 print(f"rows {n}", flush=True)

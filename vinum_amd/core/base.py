@@ -23,7 +23,7 @@ class DeviceRecordBatch:
         for i, n in enumerate(batch.schema.names):
             arr = batch.column(i)
             if dictionaries is not None and not is_supported(arr.type):
-                from ..vinum_lib import KeyDictionary
+                from ..keydict import KeyDictionary
                 if n not in dictionaries:
                     dictionaries[n] = KeyDictionary(arr.type)
                 cols[n] = DeviceColumn.from_arrow(arr, dictionary=dictionaries[n])

@@ -99,7 +99,7 @@ class DeviceBuffer:
 class DeviceColumn:
     def __init__(self, values, validity, offset, length, arrow_type, keep=None, dictionary=None):
         """values / validity: DeviceBuffer, raw int pointer, or None (validity).
-        dictionary: a vinum_lib.KeyDictionary when the column holds the int32 CODES of a non-numeric column (strings,
+        dictionary: a keydict.KeyDictionary when the column holds the int32 CODES of a non-numeric column (strings,
         bools, decimals: dictionary-encoded on ingest); to_arrow() then returns the decoded values."""
         self._values, self._validity = values, validity
         self.offset, self.length, self.arrow_type = int(offset), int(length), arrow_type

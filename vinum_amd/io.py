@@ -162,7 +162,7 @@ class GpuCsvReader:
         return None
 
     def _dictionary(self, name: str):
-        from .vinum_lib import KeyDictionary
+        from .keydict import KeyDictionary
         if name not in self._dicts:
             t = self.schema.field(name).type
             self._dicts[name] = KeyDictionary(t)
@@ -291,7 +291,7 @@ class _ArrowBatchSource:
             if is_supported(arr.type):
                 cols[n] = _stage_arrow_column(arr, arr.type)
             else:
-                from .vinum_lib import KeyDictionary
+                from .keydict import KeyDictionary
                 if n not in self._dicts:
                     self._dicts[n] = KeyDictionary(arr.type)
                 # (a dictionary-typed column -- read_dictionary=[...] -- stages its index buffer through the pinned ring as well)

@@ -1,0 +1,484 @@
+"""KeyDictionary: the running dictionary of one non-numeric column (value -> int32 code) and the device tables derived from it,
+one entry per dictionary id: LIKE matches, translations into and joint ranks with another dictionary, upper() / lower() maps.
+Importable without the shared library, like vinum_lib (which re-exports KeyDictionary and device_value_type)."""
+import ctypes
+from dataclasses import dataclass
+
+import numpy as np
+import pyarrow as pa
+
+from . import _lib as L
+
+
+def _is_string_like(t) -> bool:
+    return pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t)
+
+
+def device_value_type(t):
+    """The type of the values the DEVICE dictionary holds for a column of type `t`: `t` itself for utf8 / large_utf8 / binary /
+    large_binary, the value type of a dictionary<intN, one of those four>; None for every other type (the host route)."""
+    if _is_string_like(t):
+        return t
+    if pa.types.is_dictionary(t) and _is_string_like(t.value_type):
+        return t.value_type
+    return None
+
+
+class _IdTable:
+    """A device table with one entry of `itemsize` bytes per dictionary id.  Entries [0, covered) are filled; the table grows by
+    doubling and keeps them.  Its owner fills [covered, top) and advances `covered` -- when, is the owner's rule."""
+
+    def __init__(self, top: int, itemsize: int):
+        from .device import DeviceBuffer
+        self.cap, self.covered, self.itemsize = max(top, 1), 0, itemsize
+        self.buf = DeviceBuffer(self.cap * itemsize)
+
+    def reserve(self, top: int) -> None:
+        from .device import DeviceBuffer
+        if top <= self.cap:
+            return
+        self.cap = max(top, 2 * self.cap)
+        grown = DeviceBuffer(self.cap * self.itemsize)
+        if self.covered:
+            L.check(L.lib().vnm_memcpy_d2d(grown.ptr, self.buf.ptr, self.covered * self.itemsize, None))
+        self.buf = grown
+
+    def column(self, arrow_type):
+        from .device import DeviceColumn
+        return DeviceColumn(self.buf, None, 0, self.covered, arrow_type)
+
+
+@dataclass
+class _Translation:               # KeyDictionary._translate[id(other)]
+    ref: object                   # weak reference to `other`
+    table: _IdTable               # int32: code here -> code in `other`, -2 where it holds none
+    mine: int = -1                # own / other's value count at the last call
+    theirs: int = -1
+
+
+@dataclass
+class _JointRanks:                # KeyDictionary._joint[id(other)]
+    ref: object                   # weak reference to `other`
+    stamp: tuple                  # (own, other's value count) the tables were built at
+    mine: object                  # DeviceBuffers of int32 ranks: own / other's table ...
+    theirs: object
+    ids: tuple                    # ... and their lengths, (own, other's id count)
+
+
+@dataclass
+class _CaseMap:                   # KeyDictionary._mapped["upper" | "lower"]
+    derived: "KeyDictionary"
+    table: _IdTable               # int32: code here -> code in `derived`, -2 for an id never handed out
+    mine: int = -1                # own value count when the table last advanced
+
+
+class KeyDictionary:
+    """Running dictionary of one non-numeric group-by column: value -> int32 code.
+
+    The reference keys its generic map on arrow::Scalar vectors (generic_hash_aggregate.h:10-45): hash + Equals per row.
+    Here every batch is encoded once on ingest and the GPU groups by 4-byte codes with the numeric machinery (NULL stays
+    NULL: its own group, as in the reference where a NULL scalar equals a NULL scalar).
+
+    utf8 / large_utf8 / binary / large_binary columns are encoded ON THE DEVICE (`vnm_strdict_encode`, csrc/vnm_strdict.hip:
+    offsets and bytes cross PCIe once, one kernel hashes every row and finds or inserts it in the dictionary table; only the
+    values a batch ADDS come back, and this object keeps them to decode the result's key column).  Other types (bool, decimal,
+    date64 ...: a handful of values or fixed width) keep the host route: Arrow's `dictionary_encode` + a NumPy merge.
+
+    A DICTIONARY-TYPED column -- dictionary<intN, utf8 | large_utf8 | binary | large_binary> -- takes the device route too
+    (DESIGN.md 4.9c): the batch dictionary's VALUES go through vnm_strdict_encode, the indices through vnm_strdict_remap_indices
+    (encode_to_device).  `type` stays the column's type and is what decode() returns (decoded to the value type, then cast);
+    everything that reasons about the VALUES -- LIKE's utf8 rule, literals, the offsets' width -- uses `value_type`.  A
+    dictionary type over any other value type (numbers, decimals, nested) keeps the host route.
+
+    The derived device tables (like_table, translate_table, joint_rank_tables, mapped) are cached here.  The ID count
+    (`_id_count()`) sizes a table and moves by whole chunks on every encode; the VALUE count (`_n_values`) moves only when a
+    value is new, and only that is work.  Each method states its rule; DESIGN.md 4.9 has all four side by side."""
+
+    def __init__(self, arrow_type: pa.DataType):
+        self.type = arrow_type
+        self.values = pa.array([], type=arrow_type)     # host route: the dictionary in order of first appearance
+        dev_type = device_value_type(arrow_type)
+        self._device = dev_type is not None
+        self.value_type = dev_type if dev_type is not None else arrow_type    # what the device dictionary's values are
+        self._dict_typed = self._device and pa.types.is_dictionary(arrow_type)
+        self._batch_dict = None    # dictionary-typed input: the previous batch's dictionary (kept alive: its addresses are compared) ...
+        self._batch_table, self._batch_table_nulls = None, False   # ... its codes in HBM (DeviceBuffer of int32, -1 = a NULL value); is any NULL
+        self.values_encodes = self.remap_launches = 0    # batch dictionaries encoded (a repeated one is not), vnm_strdict_remap_indices calls
+        self._h = None
+        self._chunks = []          # device route: the values each batch added ...
+        self._pos = None           # ... and id -> position in their concatenation (-1: an id never handed out)
+        self._n_values = 0
+        self._by_code_cache = None  # ((id count, chunk count), values_by_code() at that stamp)
+        self._like = {}            # LIKE pattern -> _IdTable of uint8 (like_table)
+        self.like_launches = self.like_ids_matched = 0       # vnm_strdict_like calls and the ids they matched, over every pattern
+        self._translate = {}       # id(other dictionary) -> _Translation
+        self._joint = {}           # id(other dictionary) -> _JointRanks
+        self._mapped = {}          # "upper" | "lower" -> _CaseMap
+        self.map_launches = self.map_ids_mapped = 0          # vnm_strdict_map_codepoints calls and the ids they mapped, over both functions
+        self.translate_builds = self.joint_rank_builds = 0   # vnm_strdict_translate / vnm_strdict_ranks_joint calls this dictionary made
+
+    @property
+    def on_device(self) -> bool:
+        """True for the four string / binary types and the dictionary types over them, whose dictionary lives in HBM
+        (vnm_strdict); the host-route dictionaries (bool, decimal, date64 ...) have no device tables"""
+        return self._device
+
+    @property
+    def _wide(self) -> bool:
+        return pa.types.is_large_string(self.value_type) or pa.types.is_large_binary(self.value_type)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                L.lib().vnm_strdict_destroy(h)
+            except Exception:
+                pass
+
+    def handle(self):
+        """the device dictionary (vnm_strdict*) behind a utf8 / binary column, created on first use"""
+        if self._h is None:
+            self._h = L.lib().vnm_strdict_create()
+            if not self._h:
+                raise RuntimeError(L.last_error())
+        return self._h
+
+    def _id_count(self) -> int:
+        return int(L.lib().vnm_strdict_ids(self._h)) if self._h is not None else 0
+
+    def _values_in_order(self) -> pa.Array:
+        """the device route's values in order of first appearance: what `_pos` indexes"""
+        return pa.concat_arrays(self._chunks) if self._chunks else pa.array([], type=self.value_type)
+
+    def absorb_new(self):
+        """after an encode through this dictionary's handle (vnm_strdict_encode here, vnm_csv_parse_block_ex in io.py): fetch the values
+        it added -- the host copy of the dictionary is the concatenation of these"""
+        lib = L.lib()
+        n_new, new_bytes = ctypes.c_int64(0), ctypes.c_int64(0)
+        L.check(lib.vnm_strdict_last_new(self._h, ctypes.byref(n_new), ctypes.byref(new_bytes)))
+        n = n_new.value
+        if not n:
+            return
+        ids, lens, data = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(max(new_bytes.value, 1), np.uint8)
+        L.check(lib.vnm_strdict_fetch_new(self._h, ids.ctypes.data, lens.ctypes.data, data.ctypes.data))
+        offs = np.zeros(n + 1, np.int64 if self._wide else np.int32)
+        np.cumsum(lens, out=offs[1:])
+        self._chunks.append(pa.Array.from_buffers(self.value_type, n, [None, pa.py_buffer(offs), pa.py_buffer(data[:new_bytes.value])]))
+        top, old = self._id_count(), self._pos if self._pos is not None else np.zeros(0, np.int64)
+        if len(old) < top:
+            self._pos = np.full(max(top, 2 * len(old)), -1, np.int64)
+            self._pos[:len(old)] = old
+        self._pos[ids] = self._n_values + np.arange(n, dtype=np.int64)
+        self._n_values += n
+
+    def _encode_values(self, column: pa.Array):
+        """a utf8 / binary array of the value type through vnm_strdict_encode: its codes as a NumPy int32 array, -1 for NULL"""
+        n = len(column)
+        vbuf, obuf, dbuf = column.buffers()
+        codes = np.empty(max(n, 1), np.int32)
+        L.check(L.lib().vnm_strdict_encode(self.handle(), obuf.address if obuf is not None else None, 1 if self._wide else 0,
+                                           dbuf.address if dbuf is not None and dbuf.size else None,
+                                           vbuf.address if (vbuf is not None and column.null_count) else None,
+                                           column.offset, n, codes.ctypes.data, None, None, None))
+        self.absorb_new()
+        return codes[:n]
+
+    @staticmethod
+    def _same_buffers(a: pa.Array, b: pa.Array) -> bool:
+        """two arrays over the very same memory (type, offset, length, every buffer's address and size)"""
+        if a is b:
+            return True
+        if a.type != b.type or len(a) != len(b) or a.offset != b.offset:
+            return False
+        ba, bb = a.buffers(), b.buffers()
+        return len(ba) == len(bb) and all((x is None) == (y is None) and (x is None or (x.address == y.address and x.size == y.size))
+                                          for x, y in zip(ba, bb))
+
+    def encode_to_device(self, column, stage=None):
+        """A DICTIONARY-TYPED column -> the DeviceColumn of its running codes, without a host copy of the codes (None for any
+        other input: the caller encodes on the host route of encode()).  (1) The batch dictionary's values through the device
+        encode, skipped when they are the previous batch's buffers: int32 codes, -1 for a NULL value -- the table; (2) the index
+        buffer staged at its native width (`stage`: array -> DeviceColumn, default DeviceColumn.from_arrow; io sources pass the
+        pinned ring); (3) vnm_strdict_remap_indices: codes = table[index], -1 and a cleared validity bit for a NULL row or a NULL
+        value; an index outside the batch dictionary raises "dictionary index out of bounds"."""
+        from .device import DeviceBuffer, DeviceColumn
+        if not self._dict_typed:
+            return None
+        if isinstance(column, pa.ChunkedArray):
+            column = column.combine_chunks() if column.num_chunks != 1 else column.chunk(0)
+        if not isinstance(column, pa.DictionaryArray):
+            return None
+        n = len(column)
+        if n == 0:
+            return DeviceColumn(DeviceBuffer(0), None, 0, 0, pa.int32(), dictionary=self)
+        values = column.dictionary
+        if values.type != self.value_type:
+            values = values.cast(self.value_type)
+        if self._batch_dict is None or not self._same_buffers(values, self._batch_dict):
+            table = self._encode_values(values) if len(values) else np.zeros(0, np.int32)
+            self.values_encodes += 1
+            self._batch_dict, self._batch_table = values, DeviceBuffer.from_host(table)
+            self._batch_table_nulls = bool((table < 0).any())
+        idx = column.indices                           # (the column's validity, offset and length with the integer type)
+        icol = stage(idx) if stage is not None else DeviceColumn.from_arrow(idx)
+        d = icol.dcol()
+        codes = DeviceBuffer(n * 4)
+        validity = DeviceBuffer((n + 7) >> 3) if (idx.null_count or self._batch_table_nulls) else None
+        bad = ctypes.c_int64(0)
+        L.check(L.lib().vnm_strdict_remap_indices(ctypes.byref(d), self._batch_table.ptr, len(values), codes.ptr,
+                                                 validity.ptr if validity is not None else None, ctypes.byref(bad), None))
+        self.remap_launches += 1
+        return DeviceColumn(codes, validity, 0, n, pa.int32(), dictionary=self)
+
+    def encode(self, column) -> pa.Array:
+        import pyarrow.compute as pc
+        if isinstance(column, pa.ChunkedArray):
+            column = column.combine_chunks()
+        if self._dict_typed and not len(column):
+            return pa.array([], type=pa.int32())
+        if self._dict_typed:
+            dev = self.encode_to_device(column)
+            if dev is None:
+                raise TypeError(f"KeyDictionary({self.type}).encode: a {column.type} column")
+            codes = dev.to_numpy()
+            return pa.array(codes, type=pa.int32(), mask=(codes < 0) if dev.validity_ptr else None)
+        if self._device and len(column):
+            codes = self._encode_values(column)
+            return pa.array(codes, type=pa.int32(), mask=(codes < 0) if column.null_count else None)
+        enc = column.dictionary_encode()
+        local = enc.dictionary
+        pos = pc.index_in(local, value_set=self.values) if len(self.values) else pa.nulls(len(local), pa.int32())
+        known = pos.is_valid().to_numpy(zero_copy_only=False)
+        mapping = pos.fill_null(0).to_numpy(zero_copy_only=False).astype(np.int32)
+        n_new = int((~known).sum())
+        if n_new:
+            mapping[~known] = len(self.values) + np.arange(n_new, dtype=np.int32)
+            fresh = local.filter(pa.array(~known))
+            self.values = pa.concat_arrays([self.values, fresh]) if len(self.values) else fresh
+        idx = enc.indices
+        codes = mapping[idx.fill_null(0).to_numpy(zero_copy_only=False).astype(np.int64)] if len(local) else np.zeros(len(idx), np.int32)
+        mask = ~idx.is_valid().to_numpy(zero_copy_only=False) if idx.null_count else None
+        return pa.array(codes, type=pa.int32(), mask=mask)
+
+    def code_of(self, value):
+        """The code of `value` in this dictionary, or None (predicates on a dictionary-coded column: `city = 'Berlin'` is a
+        comparison of int32 codes in HBM)."""
+        import pyarrow.compute as pc
+        vals = self.values_by_code()
+        if not len(vals):
+            return None
+        i = pc.index(vals, pa.scalar(value, type=self.value_type)).as_py()
+        return None if i < 0 else int(i)
+
+    def rank_bounds(self, value):
+        """(number of dictionary values < value, 1 if value is in the dictionary else 0): with r = rank_column's rank of a row,
+        v < value <=> r < less, v <= value <=> r < less + present, v > value <=> r >= less + present, v >= value <=> r >= less
+        (byte-wise order, as Arrow compares utf8 / binary)."""
+        import pyarrow.compute as pc
+        vals = self.values_by_code()
+        if not len(vals):
+            return 0, 0
+        lit = pa.scalar(value, type=self.value_type)
+        less = int(pc.sum(pc.less(vals, lit)).as_py() or 0)
+        return less, 0 if self.code_of(value) is None else 1
+
+    @staticmethod
+    def _gather(codes_col, table_ptr, keep, dictionary=None):
+        """table[code] per row (vnm_strdict_codes_to_ranks): a fresh int32 DeviceColumn with the codes' validity; `keep` owns the table"""
+        from .device import DeviceBuffer, DeviceColumn
+        n = codes_col.length
+        off = codes_col.offset if codes_col._validity is not None else 0      # (one Arrow offset serves values and bitmap)
+        out = DeviceBuffer(max(off + n, 1) * 4)
+        if n:
+            L.check(L.lib().vnm_strdict_codes_to_ranks(codes_col.values_ptr + codes_col.offset * 4, table_ptr, n, out.ptr + off * 4, None))
+        return DeviceColumn(out, codes_col._validity, off, n, pa.int32(), keep=(keep, codes_col), dictionary=dictionary)
+
+    def _device_ranks(self):
+        """DeviceBuffer of int32: id -> rank of its value in byte-wise order, as Arrow's SortIndices compares (an id never handed out: unspecified)"""
+        from .device import DeviceBuffer
+        rank_of = DeviceBuffer(max(self._id_count(), 1) * 4)
+        L.check(L.lib().vnm_strdict_ranks_device(self._h, rank_of.ptr, None))
+        return rank_of
+
+    def ranked_values(self):
+        """A device-route dictionary's (rank of id: host int32, one entry per id, unspecified for an id never handed out; the
+        values in rank order).  A dictionary without values launches nothing and ranks its ids 0."""
+        values, top = self._values_in_order(), self._id_count()
+        if not len(values):
+            return np.zeros(max(top, 1), np.int32), values
+        rank_of_id = self._device_ranks().to_host(np.int32, top)
+        live = np.nonzero(self._pos[:top] >= 0)[0]
+        by_rank = np.empty(len(values), np.int64)
+        by_rank[rank_of_id[live]] = self._pos[live]             # rank -> position in `values`
+        return rank_of_id, values.take(pa.array(by_rank))
+
+    def rank_column(self, codes_col):
+        """ORDER BY a dictionary-coded column: the rows' order-preserving RANKS as an int32 DeviceColumn (NULL stays NULL).  utf8 /
+        binary dictionaries are ranked on the device (_device_ranks), the small host-route ones (decimals, date64 ...) by Arrow."""
+        from .device import DeviceBuffer
+        if self._device and self._h is not None:
+            rank_of = self._device_ranks()
+        else:
+            import pyarrow.compute as pc
+            order = pc.sort_indices(self.values).to_numpy(zero_copy_only=False) if len(self.values) else np.zeros(0, np.int64)
+            r = np.zeros(max(len(self.values), 1), np.int32)
+            r[order] = np.arange(len(order), dtype=np.int32)
+            rank_of = DeviceBuffer.from_host(r)
+        return self._gather(codes_col, rank_of.ptr, rank_of)
+
+    def like_table(self, pattern: str):
+        """`column LIKE pattern` for every value of this dictionary: a device uint8 DeviceColumn, entry = 1 when the value with
+        that code matches (vnm_strdict_like: the reference's regex restated, functions.py:301-344; trailing NULs dropped for utf8,
+        whose values reach the reference as a NumPy 'U' array).  Its length is the number of ids handed out so far.  Cached per
+        pattern: a call matches only the ids handed out since the last one, so a stream matches each distinct value once per pattern."""
+        from . import ops
+        t = self.value_type                                              # (a dictionary-typed column: what its values are)
+        if not (pa.types.is_string(t) or pa.types.is_large_string(t)):
+            raise TypeError(f"LIKE needs a string column, not {self.type}")    # (the reference's re.match raises on bytes / numbers)
+        ops.like_tokens(pattern)                                         # (NotImplementedError for a regex metacharacter)
+        top = self._id_count()
+        table = self._like.get(pattern)
+        if table is None:
+            table = self._like[pattern] = _IdTable(top, 1)
+        if top > table.covered:
+            table.reserve(top)
+            raw = pattern.encode("utf-8")
+            L.check(L.lib().vnm_strdict_like(self._h, raw, len(raw), L.LIKE_STRIP_NUL if pa.types.is_string(t) else 0, table.covered,
+                                             table.buf.ptr, None))
+            self.like_launches += 1
+            self.like_ids_matched += top - table.covered
+            table.covered = top
+        return table.column(pa.uint8())
+
+    def _pair_check(self, other, what):
+        if not (self._device and getattr(other, "on_device", False)):
+            raise NotImplementedError(f"no GPU lowering for {what} of a {self.value_type} and a {getattr(other, 'value_type', other.type)} dictionary: the device "
+                                      "dictionaries are the string and binary types")
+
+    @staticmethod
+    def _pair_ref(cache, other):
+        """A weak reference to `other` that drops `other`'s entry (and its device tables) from `cache` when `other` dies."""
+        import weakref
+        key = id(other)
+
+        def drop(ref):
+            entry = cache.get(key)
+            if entry is not None and entry.ref is ref:
+                del cache[key]
+        return weakref.ref(other, drop)
+
+    def translate_table(self, other):
+        """This dictionary's codes in terms of `other`'s: an int32 DeviceColumn with one entry per id handed out here, the code
+        `other` holds for the same BYTES, or -2 where it holds none (vnm_strdict_translate; bytes compared exactly, whatever mix
+        of utf8 / large_utf8 / binary / large_binary the two are).  `a = b` over two dictionary-coded columns then is
+        code_a == table[code_b].  Cached per pair; work only when a dictionary GREW by values: while `other` has not, only the ids
+        handed out here since are looked up; once it has, an absent value may be present now and the whole table is built again."""
+        self._pair_check(other, "a translation")
+        top = self._id_count()
+        entry = self._translate.get(id(other))
+        if entry is None or entry.ref() is not other:
+            entry = self._translate[id(other)] = _Translation(self._pair_ref(self._translate, other), _IdTable(top, 4))
+        table = entry.table
+        if entry.theirs != other._n_values:
+            table.covered = 0
+        if (table.covered == 0 or entry.mine != self._n_values) and top > table.covered:
+            table.reserve(top)
+            L.check(L.lib().vnm_strdict_translate(self.handle(), other.handle(), table.covered, table.buf.ptr, None))
+            self.translate_builds += 1
+            table.covered = top
+        entry.mine, entry.theirs = self._n_values, other._n_values
+        return table.column(pa.int32())
+
+    def joint_rank_tables(self, other):
+        """(own table, other's table): int32 DeviceColumns, one entry per id, the dense rank of the value in the ascending byte
+        order of the UNION of both dictionaries (vnm_strdict_ranks_joint: the order of rank_column; equal bytes share a rank), so
+        `a < b` over two dictionary-coded columns is table_a[code_a] < table_b[code_b].  Cached per pair and rebuilt in full when
+        either grows (by values, as translate_table)."""
+        from .device import DeviceBuffer, DeviceColumn
+        self._pair_check(other, "joint ranks")
+        lib = L.lib()
+        stamp = (self._n_values, other._n_values)
+        entry = self._joint.get(id(other))
+        if entry is None or entry.ref() is not other or entry.stamp != stamp:
+            ids = (self._id_count(), other._id_count())
+            mine, theirs = (DeviceBuffer(max(n, 1) * 4) for n in ids)
+            for buf in (mine, theirs):
+                L.check(lib.vnm_memset(buf.ptr, 0xFF, buf.nbytes))           # (ids never handed out: -1, no row holds them)
+            L.check(lib.vnm_strdict_ranks_joint(self.handle(), other.handle(), mine.ptr, theirs.ptr, None))
+            self.joint_rank_builds += 1
+            entry = self._joint[id(other)] = _JointRanks(self._pair_ref(self._joint, other), stamp, mine, theirs, ids)
+        return (DeviceColumn(entry.mine, None, 0, entry.ids[0], pa.int32()), DeviceColumn(entry.theirs, None, 0, entry.ids[1], pa.int32()))
+
+    def mapped(self, fn: str):
+        """upper() / lower() of this dictionary (`fn`: "upper" | "lower"; pc.utf8_upper / pc.utf8_lower, functions.py:279-298):
+        (the DERIVED dictionary, an int32 DeviceColumn `code here -> code there`, one entry per id handed out here; -2 for an id
+        never handed out).  The function depends on the value alone, so each distinct value is mapped ONCE, on the device
+        (vnm_strdict_map_codepoints with the code point table of vinum_amd.strcase), and found or inserted in the derived
+        dictionary; a row then costs one lookup of its code (mapped_column).  One derived dictionary per (dictionary, function),
+        the same object for the life of this one, extended with the ids handed out since the last call; a batch that brought no
+        new value launches nothing (`map_launches`, `map_ids_mapped`).  It is a full KeyDictionary of type string, whatever this
+        one's is (the reference casts first, functions.py:219-221), and absorbs its new values: it decodes, ranks, matches LIKE,
+        pairs and maps again.  A binary dictionary raises TypeError (Arrow has no such kernel), a host-route one
+        NotImplementedError, a structurally malformed UTF-8 value ValueError("Invalid UTF8 sequence in input") from every call
+        that has to map it -- whether or not a row holding it survives the query's filter."""
+        from . import strcase
+        if fn not in strcase.CASE_FNS:
+            raise ValueError(f"no case map {fn!r}: one of {strcase.CASE_FNS}")
+        if not self._device:
+            raise NotImplementedError(f"no GPU lowering for {fn}() over a {self.type} column: only string columns keep their dictionaries on the device")
+        t = self.value_type
+        if not (pa.types.is_string(t) or pa.types.is_large_string(t)):
+            raise TypeError(f"{fn}() needs a string column, not {self.type}")      # (pc.utf8_upper has no kernel for binary)
+        top = self._id_count()
+        entry = self._mapped.get(fn)
+        if entry is None:
+            entry = self._mapped[fn] = _CaseMap(KeyDictionary(pa.string()), _IdTable(top, 4))
+        derived, table = entry.derived, entry.table
+        if top > table.covered and entry.mine != self._n_values:       # (by values, as translate_table: only a new value is work)
+            table.reserve(top)
+            map_from, map_to = strcase.case_table(fn)
+            invalid = ctypes.c_int64(0)
+            rc = L.lib().vnm_strdict_map_codepoints(self.handle(), derived.handle(), map_from.ctypes.data, map_to.ctypes.data, len(map_from),
+                                                    table.covered, table.buf.ptr, ctypes.byref(invalid), None)
+            self.map_launches += 1
+            self.map_ids_mapped += top - table.covered
+            message = L.last_error() if rc != 0 else None
+            if derived._h is not None:
+                derived.absorb_new()        # (also after a malformed value: the well-formed ones are in the derived dictionary)
+            if rc != 0:                     # (nothing is recorded as covered: the next call maps these ids, and raises, again)
+                raise ValueError("Invalid UTF8 sequence in input") if invalid.value else L.VinumHipError(message)
+            table.covered, entry.mine = top, self._n_values
+        return derived, table.column(pa.int32())
+
+    def mapped_column(self, fn: str, codes_col):
+        """upper(column) / lower(column) over a column of THIS dictionary's codes: the derived dictionary's codes, table[code] per
+        row (NULL stays NULL), with `.dictionary` the derived dictionary, so every operator takes it as the string column it is."""
+        derived, table = self.mapped(fn)
+        return self._gather(codes_col, table.values_ptr, table, dictionary=derived)
+
+    def values_by_code(self) -> pa.Array:
+        """The dictionary as an array indexed by CODE (a code the device never handed out: NULL) -- what the ranks exchange to build
+        one dictionary before partial groups keyed by these codes can travel (distributed.union_dictionary)."""
+        if self._device and self._h is not None:
+            # (cached until the dictionary grows: a predicate asks once per batch and literal, the concat + take is O(distinct values))
+            stamp = (self._id_count(), len(self._chunks))
+            if self._by_code_cache is None or self._by_code_cache[0] != stamp:
+                pos = self._pos[:stamp[0]] if self._pos is not None else np.zeros(0, np.int64)
+                out = self._values_in_order().take(pa.array(np.where(pos < 0, 0, pos), type=pa.int64(), mask=(pos < 0) if (pos < 0).any() else None))
+                self._by_code_cache = (stamp, out)
+            return self._by_code_cache[1]
+        return self.values
+
+    def decode(self, codes: pa.Array) -> pa.Array:
+        """codes -> values of the column's type.  A dictionary-typed column comes back with ITS type (value type, index type,
+        `ordered`): decoded to the value type, then cast; more distinct values than the index type numbers surface Arrow's cast error."""
+        if self._device and (self._h is not None or self._pos is not None):
+            c = codes.fill_null(0).to_numpy(zero_copy_only=False).astype(np.int64)
+            pos = self._pos[c] if self._pos is not None and len(c) else np.zeros(len(c), np.int64)
+            null = ~codes.is_valid().to_numpy(zero_copy_only=False) if codes.null_count else np.zeros(len(c), bool)
+            if ((pos < 0) & ~null).any():
+                raise RuntimeError("KeyDictionary.decode: a code that was never handed out (internal error)")
+            values = self._values_in_order().take(pa.array(np.where(null, 0, pos), type=pa.int64(), mask=null if null.any() else None))
+        else:
+            values = self.values.take(codes)
+        return values.cast(self.type) if self._dict_typed else values

@@ -22,6 +22,7 @@ import os
 import pyarrow as pa
 
 from . import _lib as L
+from .keydict import KeyDictionary, device_value_type
 
 
 class AggFuncType(enum.IntEnum):
@@ -133,7 +134,6 @@ def _canonical_order(batch: pa.RecordBatch, key_names):
 
 def _abi_generic_key(t) -> bool:
     """non-numeric key types vnm_agg_op_* encode below the C ABI (vnm_arrow.cpp: GenKey)"""
-    import os
     if os.environ.get("VNM_GENERIC_BELOW_ABI", "1") == "0":
         return False
     return (pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t) or
@@ -173,39 +173,24 @@ class _StringMinMax:
             column = column.combine_chunks()
         t = column.type
         if len(column) and device_value_type(t) is not None:       # (a dictionary-typed column too: its indices are remapped on the device)
-            # the batch's dictionary from the device (vnm_strdict_encode, a fresh handle: every value of the batch is new to it);
-            # the host sorts the DISTINCT values and turns codes into ranks (one gather)
-            # ... and ranks them there too (round 5, vnm_strdict_ranks_device: the distinct values sorted byte-wise by the multi-key radix
-            # sort over their 8-byte chunks); the host only gathers rank[code] and lines the dictionary up by rank
-            from .device import DeviceBuffer
+            # the batch's dictionary from the device (vnm_strdict_encode, a fresh handle: every value of the batch is new to it),
+            # ranked there too (KeyDictionary.ranked_values); the host only gathers rank[code] (a NULL row: entry 0, masked)
             kd = KeyDictionary(t)
             codes = kd.encode(column)
-            d = pa.concat_arrays(kd._chunks) if kd._chunks else pa.array([], type=kd.value_type)
-            c = codes.fill_null(0).to_numpy(zero_copy_only=False).astype(np.int64)
-            mask = ~codes.is_valid().to_numpy(zero_copy_only=False) if codes.null_count else None
-            if not len(d):
-                return pa.array(np.zeros(len(c), np.int32), type=pa.int32(), mask=mask), d
-            top = int(L.lib().vnm_strdict_ids(kd._h))
-            dev = DeviceBuffer(max(top, 1) * 4)
-            L.check(L.lib().vnm_strdict_ranks_device(kd._h, dev.ptr, None))
-            rank_of_id = dev.to_host(np.int32, top)               # (ids never handed out: garbage, never looked at)
-            live = np.nonzero(kd._pos[:top] >= 0)[0]
-            by_rank = np.empty(len(d), np.int64)
-            by_rank[rank_of_id[live]] = kd._pos[live]              # rank -> position in `d`
-            return pa.array(rank_of_id[c], type=pa.int32(), mask=mask), d.take(pa.array(by_rank))
-        enc = column.dictionary_encode()
-        d = enc.dictionary
-        if pa.types.is_string(d.type) or pa.types.is_large_string(d.type):
-            d_sort = d.cast(pa.large_binary() if pa.types.is_large_string(d.type) else pa.binary())   # byte-wise, as string_view's operator<
+            rank_of, by_rank = kd.ranked_values()
         else:
+            enc = column.dictionary_encode()
+            codes, d = enc.indices, enc.dictionary
             d_sort = d
-        order = pc.sort_indices(d_sort).to_numpy(zero_copy_only=False)
-        rank_of = np.empty(len(d), np.int32)
-        rank_of[order] = np.arange(len(d), dtype=np.int32)
-        idx = enc.indices
-        ranks = rank_of[idx.fill_null(0).to_numpy(zero_copy_only=False).astype(np.int64)] if len(d) else np.zeros(len(idx), np.int32)
-        mask = ~idx.is_valid().to_numpy(zero_copy_only=False) if idx.null_count else None
-        return pa.array(ranks, type=pa.int32(), mask=mask), d.take(pa.array(order))
+            if pa.types.is_string(d.type) or pa.types.is_large_string(d.type):
+                d_sort = d.cast(pa.large_binary() if pa.types.is_large_string(d.type) else pa.binary())   # byte-wise, as string_view's operator<
+            order = pc.sort_indices(d_sort).to_numpy(zero_copy_only=False)
+            rank_of = np.zeros(max(len(d), 1), np.int32)          # (an empty dictionary: every row is NULL and gathers entry 0)
+            rank_of[order] = np.arange(len(d), dtype=np.int32)
+            by_rank = d.take(pa.array(order))
+        c = codes.fill_null(0).to_numpy(zero_copy_only=False).astype(np.int64)
+        mask = ~codes.is_valid().to_numpy(zero_copy_only=False) if codes.null_count else None
+        return pa.array(rank_of[c], type=pa.int32(), mask=mask), by_rank
 
     def next(self, key_arrays, batch: pa.RecordBatch) -> None:
         # (the rank columns get names of their own: the aggregated column may be a group-by column as well, and a batch with two
@@ -464,475 +449,6 @@ class OneGroupAggregate(_HashAggregateBase):
 
     def __init__(self, agg_funcs):
         super().__init__([], [], agg_funcs)
-
-
-def _is_string_like(t) -> bool:
-    return pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t)
-
-
-def device_value_type(t):
-    """The type of the values the DEVICE dictionary holds for a column of type `t`: `t` itself for utf8 / large_utf8 / binary /
-    large_binary, the value type of a dictionary<intN, one of those four>; None for every other type (the host route)."""
-    if _is_string_like(t):
-        return t
-    if pa.types.is_dictionary(t) and _is_string_like(t.value_type):
-        return t.value_type
-    return None
-
-
-class KeyDictionary:
-    """Running dictionary of one non-numeric group-by column: value -> int32 code.
-
-    The reference keys its generic map on arrow::Scalar vectors (generic_hash_aggregate.h:10-45): hash + Equals per row.
-    Here every batch is encoded once on ingest and the GPU groups by 4-byte codes with the numeric machinery (NULL stays
-    NULL: its own group, as in the reference where a NULL scalar equals a NULL scalar).
-
-    utf8 / large_utf8 / binary / large_binary columns are encoded ON THE DEVICE (`vnm_strdict_encode`, csrc/vnm_strdict.hip:
-    offsets and bytes cross PCIe once, one kernel hashes every row and finds or inserts it in the dictionary table; only the
-    values a batch ADDS come back, and this object keeps them to decode the result's key column).  The host route it replaces
-    (Arrow's `dictionary_encode` + a NumPy merge of the batch's dictionary into the running one) ran at 7-17 M rows/s, 1.5 M
-    rows/s at 5e6 distinct values.  Other types (bool, decimal, date64 ...: a handful of values or fixed width) keep it.
-
-    A DICTIONARY-TYPED column -- dictionary<intN, utf8 | large_utf8 | binary | large_binary>: a pandas categorical, a Parquet
-    column read with read_dictionary, an IPC stream of another engine -- takes the device route too, and cheaper: the batch
-    dictionary's VALUES go through vnm_strdict_encode (n_values strings hashed, not one per row), the indices cross PCIe at
-    their native 1-8 bytes per row and vnm_strdict_remap_indices gathers table[index] on the device (encode_to_device).  A batch
-    whose dictionary is the very buffers of the batch before (an IPC stream repeats its dictionary this way) reuses the table;
-    `values_encodes` counts the encodes of batch dictionaries.  A batch dictionary may hold duplicates (both indices get one
-    code) and values no row uses (they enter the running dictionary and are harmless).  `type` stays the column's type and is
-    what decode() returns -- value type, index type and `ordered` flag: decoded to the value type, then cast, so the output's
-    dictionary need not equal any input's, and a result with more distinct values than the index type can number surfaces
-    Arrow's cast error ("Integer value 128 not in range").  Everything that reasons about the VALUES -- LIKE's utf8 rule,
-    literals, the offsets' width -- uses `value_type`.  A dictionary type over any other value type (numbers, decimals, nested)
-    keeps the host route."""
-
-    def __init__(self, arrow_type: pa.DataType):
-        self.type = arrow_type
-        self.values = pa.array([], type=arrow_type)     # host route: the dictionary in order of first appearance
-        dev_type = device_value_type(arrow_type)
-        self._device = dev_type is not None
-        self.value_type = dev_type if dev_type is not None else arrow_type    # what the device dictionary's values are
-        self._dict_typed = self._device and pa.types.is_dictionary(arrow_type)
-        self._batch_dict = None    # dictionary-typed input: the previous batch's dictionary (kept alive: its addresses are compared) ...
-        self._batch_table = None   # ... its codes in HBM (DeviceBuffer of int32, -1 = a NULL value) and whether any is NULL
-        self._batch_table_nulls = False
-        self.values_encodes = 0    # batch dictionaries run through vnm_strdict_encode (a repeated one is not)
-        self.remap_launches = 0    # vnm_strdict_remap_indices calls
-        self._h = None
-        self._chunks = []          # device route: the values each batch added ...
-        self._pos = None           # ... and id -> position in their concatenation (-1: an id never handed out)
-        self._n_values = 0
-        self._like = {}            # LIKE pattern -> [device table, capacity, ids it covers] (like_table)
-        self.like_launches = 0     # vnm_strdict_like calls and the ids they matched, over every pattern
-        self.like_ids_matched = 0
-        self._translate = {}       # id(other dictionary) -> [weakref, device table, capacity, ids it covers, own / other's value count]
-        self._joint = {}           # id(other dictionary) -> [weakref, (own, other's value count), own / other's rank table, id counts]
-        self._mapped = {}          # "upper" | "lower" -> [derived dictionary, device table code -> derived code, capacity, ids it covers, own value count]
-        self.map_launches = 0      # vnm_strdict_map_codepoints calls and the ids they mapped, over both functions
-        self.map_ids_mapped = 0
-        self.translate_builds = 0  # vnm_strdict_translate / vnm_strdict_ranks_joint calls this dictionary made (pair tables)
-        self.joint_rank_builds = 0
-
-    @property
-    def on_device(self) -> bool:
-        """True for the four string / binary types and the dictionary types over them, whose dictionary lives in HBM
-        (vnm_strdict); the host-route dictionaries (bool, decimal, date64 ...) have no device tables"""
-        return self._device
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                L.lib().vnm_strdict_destroy(h)
-            except Exception:
-                pass
-
-    def handle(self):
-        """the device dictionary (vnm_strdict*) behind a utf8 / binary column, created on first use"""
-        if self._h is None:
-            self._h = L.lib().vnm_strdict_create()
-            if not self._h:
-                raise RuntimeError(L.last_error())
-        return self._h
-
-    def absorb_new(self):
-        """after an encode through this dictionary's handle (vnm_strdict_encode here, vnm_csv_parse_block_ex in io.py): fetch the values
-        it added -- the host copy of the dictionary is the concatenation of these"""
-        import numpy as np
-        lib = L.lib()
-        n_new, new_bytes = ctypes.c_int64(0), ctypes.c_int64(0)
-        L.check(lib.vnm_strdict_last_new(self._h, ctypes.byref(n_new), ctypes.byref(new_bytes)))
-        if not n_new.value:
-            return
-        wide = pa.types.is_large_string(self.value_type) or pa.types.is_large_binary(self.value_type)
-        ids = np.empty(n_new.value, np.int32)
-        lens = np.empty(n_new.value, np.int32)
-        data = np.empty(max(new_bytes.value, 1), np.uint8)
-        L.check(lib.vnm_strdict_fetch_new(self._h, ids.ctypes.data, lens.ctypes.data, data.ctypes.data))
-        offs = np.zeros(n_new.value + 1, np.int64 if wide else np.int32)
-        np.cumsum(lens, out=offs[1:])
-        self._chunks.append(pa.Array.from_buffers(self.value_type, n_new.value, [None, pa.py_buffer(offs), pa.py_buffer(data[:new_bytes.value])]))
-        top = int(lib.vnm_strdict_ids(self._h))
-        if self._pos is None or len(self._pos) < top:
-            grown = np.full(max(top, 2 * (len(self._pos) if self._pos is not None else 0)), -1, np.int64)
-            if self._pos is not None:
-                grown[:len(self._pos)] = self._pos
-            self._pos = grown
-        self._pos[ids] = self._n_values + np.arange(n_new.value, dtype=np.int64)
-        self._n_values += n_new.value
-
-    def _encode_values(self, column: pa.Array):
-        """a utf8 / binary array of the value type through vnm_strdict_encode: its codes as a NumPy int32 array, -1 for NULL"""
-        import numpy as np
-        lib = L.lib()
-        n = len(column)
-        wide = pa.types.is_large_string(self.value_type) or pa.types.is_large_binary(self.value_type)
-        vbuf, obuf, dbuf = column.buffers()
-        codes = np.empty(max(n, 1), np.int32)
-        L.check(lib.vnm_strdict_encode(self.handle(), obuf.address if obuf is not None else None, 1 if wide else 0,
-                                       dbuf.address if dbuf is not None and dbuf.size else None,
-                                       vbuf.address if (vbuf is not None and column.null_count) else None,
-                                       column.offset, n, codes.ctypes.data, None, None, None))
-        self.absorb_new()
-        return codes[:n]
-
-    def _encode_device(self, column: pa.Array) -> pa.Array:
-        codes = self._encode_values(column)
-        mask = (codes < 0) if column.null_count else None
-        return pa.array(codes, type=pa.int32(), mask=mask)
-
-    @staticmethod
-    def _same_buffers(a: pa.Array, b: pa.Array) -> bool:
-        """two arrays over the very same memory (type, offset, length, every buffer's address and size)"""
-        if a is b:
-            return True
-        if a.type != b.type or len(a) != len(b) or a.offset != b.offset:
-            return False
-        ba, bb = a.buffers(), b.buffers()
-        return len(ba) == len(bb) and all((x is None) == (y is None) and (x is None or (x.address == y.address and x.size == y.size))
-                                          for x, y in zip(ba, bb))
-
-    def encode_to_device(self, column, stage=None):
-        """A DICTIONARY-TYPED column -> the DeviceColumn of its running codes, without a host copy of the codes (None for any
-        other input: the caller encodes on the host route of encode()):
-          1. the batch dictionary's values through the device encode (skipped when they are the previous batch's buffers): int32
-             codes, -1 for a NULL value -- the table, uploaded once per batch dictionary;
-          2. the index buffer staged at its native width (`stage`: array -> DeviceColumn; io sources pass the pinned ring,
-             default DeviceColumn.from_arrow);
-          3. vnm_strdict_remap_indices: codes = table[index], -1 and a cleared validity bit for a NULL row or a NULL value; an
-             index outside the batch dictionary raises "dictionary index out of bounds"."""
-        import numpy as np
-        from .device import DeviceBuffer, DeviceColumn
-        if not self._dict_typed:
-            return None
-        if isinstance(column, pa.ChunkedArray):
-            column = column.combine_chunks() if column.num_chunks != 1 else column.chunk(0)
-        if not isinstance(column, pa.DictionaryArray):
-            return None
-        n = len(column)
-        if n == 0:
-            return DeviceColumn(DeviceBuffer(0), None, 0, 0, pa.int32(), dictionary=self)
-        values = column.dictionary
-        if values.type != self.value_type:
-            values = values.cast(self.value_type)
-        if self._batch_dict is None or not self._same_buffers(values, self._batch_dict):
-            table = self._encode_values(values) if len(values) else np.zeros(0, np.int32)
-            self.values_encodes += 1
-            self._batch_dict, self._batch_table = values, DeviceBuffer.from_host(table)
-            self._batch_table_nulls = bool((table < 0).any())
-        idx = column.indices                           # (the column's validity, offset and length with the integer type)
-        icol = stage(idx) if stage is not None else DeviceColumn.from_arrow(idx)
-        d = icol.dcol()
-        codes = DeviceBuffer(n * 4)
-        validity = DeviceBuffer((n + 7) >> 3) if (idx.null_count or self._batch_table_nulls) else None
-        bad = ctypes.c_int64(0)
-        L.check(L.lib().vnm_strdict_remap_indices(ctypes.byref(d), self._batch_table.ptr, len(values), codes.ptr,
-                                                 validity.ptr if validity is not None else None, ctypes.byref(bad), None))
-        self.remap_launches += 1
-        return DeviceColumn(codes, validity, 0, n, pa.int32(), dictionary=self)
-
-    def encode(self, column) -> pa.Array:
-        import numpy as np
-        import pyarrow.compute as pc
-        if isinstance(column, pa.ChunkedArray):
-            column = column.combine_chunks()
-        if self._dict_typed and not len(column):
-            return pa.array([], type=pa.int32())
-        if self._dict_typed:
-            dev = self.encode_to_device(column)
-            if dev is None:
-                raise TypeError(f"KeyDictionary({self.type}).encode: a {column.type} column")
-            codes = dev.to_numpy()
-            return pa.array(codes, type=pa.int32(), mask=(codes < 0) if dev.validity_ptr else None)
-        if self._device and len(column):
-            return self._encode_device(column)
-        enc = column.dictionary_encode()
-        local = enc.dictionary
-        pos = pc.index_in(local, value_set=self.values) if len(self.values) else pa.nulls(len(local), pa.int32())
-        known = pos.is_valid().to_numpy(zero_copy_only=False)
-        mapping = pos.fill_null(0).to_numpy(zero_copy_only=False).astype(np.int32)
-        n_new = int((~known).sum())
-        if n_new:
-            mapping[~known] = len(self.values) + np.arange(n_new, dtype=np.int32)
-            fresh = local.filter(pa.array(~known))
-            self.values = pa.concat_arrays([self.values, fresh]) if len(self.values) else fresh
-        idx = enc.indices
-        codes = mapping[idx.fill_null(0).to_numpy(zero_copy_only=False).astype(np.int64)] if len(local) else np.zeros(len(idx), np.int32)
-        mask = ~idx.is_valid().to_numpy(zero_copy_only=False) if idx.null_count else None
-        return pa.array(codes, type=pa.int32(), mask=mask)
-
-    def code_of(self, value):
-        """The code of `value` in this dictionary, or None (predicates on a dictionary-coded column: `city = 'Berlin'` is a
-        comparison of int32 codes in HBM)."""
-        import pyarrow.compute as pc
-        vals = self.values_by_code()
-        if not len(vals):
-            return None
-        i = pc.index(vals, pa.scalar(value, type=self.value_type)).as_py()
-        return None if i < 0 else int(i)
-
-    def rank_bounds(self, value):
-        """(number of dictionary values < value, 1 if value is in the dictionary else 0): with r = rank_column's rank of a row,
-        v < value <=> r < less, v <= value <=> r < less + present, v > value <=> r >= less + present, v >= value <=> r >= less
-        (byte-wise order, as Arrow compares utf8 / binary)."""
-        import pyarrow.compute as pc
-        vals = self.values_by_code()
-        if not len(vals):
-            return 0, 0
-        lit = pa.scalar(value, type=self.value_type)
-        less = int(pc.sum(pc.less(vals, lit)).as_py() or 0)
-        return less, 0 if self.code_of(value) is None else 1
-
-    def rank_column(self, codes_col):
-        """ORDER BY a dictionary-coded column: the rows' order-preserving RANKS as an int32 DeviceColumn (same validity as the
-        codes: NULL stays NULL).  utf8 / binary dictionaries are ranked on the device (vnm_strdict_ranks_device: the distinct values
-        sorted byte-wise, as Arrow's SortIndices compares them); the small host-route dictionaries (decimals, date64 ...) by Arrow."""
-        import numpy as np
-        from .device import DeviceBuffer, DeviceColumn
-        lib = L.lib()
-        n = codes_col.length
-        if self._device and self._h is not None:
-            top = max(int(lib.vnm_strdict_ids(self._h)), 1)
-            rank_of = DeviceBuffer(top * 4)
-            L.check(lib.vnm_strdict_ranks_device(self._h, rank_of.ptr, None))
-        else:
-            import pyarrow.compute as pc
-            order = pc.sort_indices(self.values).to_numpy(zero_copy_only=False) if len(self.values) else np.zeros(0, np.int64)
-            r = np.zeros(max(len(self.values), 1), np.int32)
-            r[order] = np.arange(len(order), dtype=np.int32)
-            rank_of = DeviceBuffer.from_host(r)
-        off = codes_col.offset if codes_col._validity is not None else 0      # (one Arrow offset serves values and bitmap)
-        out = DeviceBuffer(max(off + n, 1) * 4)
-        L.check(lib.vnm_strdict_codes_to_ranks(codes_col.values_ptr + codes_col.offset * 4, rank_of.ptr, n, out.ptr + off * 4, None))
-        return DeviceColumn(out, codes_col._validity, off, n, pa.int32(), keep=(rank_of, codes_col))
-
-    def like_table(self, pattern: str):
-        """`column LIKE pattern` for every value of this dictionary: a device uint8 DeviceColumn, entry = 1 when the value with
-        that code matches (vnm_strdict_like: the reference's regex restated, functions.py:301-344; trailing NULs dropped for utf8,
-        whose values reach the reference as a NumPy 'U' array).  Its length is the number of ids handed out so far.  Cached per
-        pattern: a later call matches only the ids the dictionary has handed out since (the table grows by doubling and keeps
-        what it holds), so a stream of batches matches each distinct value once per pattern."""
-        from . import ops
-        from .device import DeviceBuffer, DeviceColumn
-        t = self.value_type                                              # (a dictionary-typed column: what its values are)
-        if not (pa.types.is_string(t) or pa.types.is_large_string(t)):
-            raise TypeError(f"LIKE needs a string column, not {self.type}")    # (the reference's re.match raises on bytes / numbers)
-        ops.like_tokens(pattern)                                         # (NotImplementedError for a regex metacharacter)
-        lib = L.lib()
-        top = int(lib.vnm_strdict_ids(self._h)) if self._h is not None else 0
-        entry = self._like.get(pattern)
-        if entry is None:
-            entry = self._like[pattern] = [DeviceBuffer(max(top, 1)), max(top, 1), 0]
-        buf, cap, covered = entry
-        if top > covered:
-            if top > cap:
-                cap = max(top, 2 * cap)
-                grown = DeviceBuffer(cap)
-                L.check(lib.vnm_memcpy_d2d(grown.ptr, buf.ptr, covered, None))
-                buf = grown
-            raw = pattern.encode("utf-8")
-            L.check(lib.vnm_strdict_like(self._h, raw, len(raw), L.LIKE_STRIP_NUL if pa.types.is_string(t) else 0, covered,
-                                         buf.ptr, None))
-            self.like_launches += 1
-            self.like_ids_matched += top - covered
-            entry[:] = [buf, cap, top]
-        return DeviceColumn(buf, None, 0, entry[2], pa.uint8())
-
-    def _id_count(self) -> int:
-        return int(L.lib().vnm_strdict_ids(self._h)) if self._h is not None else 0
-
-    def _pair_check(self, other, what):
-        if not (self._device and getattr(other, "on_device", False)):
-            raise NotImplementedError(f"no GPU lowering for {what} of a {self.value_type} and a {getattr(other, 'value_type', other.type)} dictionary: the device "
-                                      "dictionaries are the string and binary types")
-
-    @staticmethod
-    def _pair_ref(cache, other):
-        """A weak reference to `other` that drops `other`'s entry (and its device tables) from `cache` when `other` dies."""
-        import weakref
-        key = id(other)
-
-        def drop(ref):
-            entry = cache.get(key)
-            if entry is not None and entry[0] is ref:
-                del cache[key]
-        return weakref.ref(other, drop)
-
-    def translate_table(self, other):
-        """This dictionary's codes in terms of `other`'s: an int32 DeviceColumn with one entry per id handed out here, the code
-        `other` holds for the same BYTES, or -2 where it holds none (vnm_strdict_translate; bytes compared exactly, whatever mix
-        of utf8 / large_utf8 / binary / large_binary the two are).  `a = b` over two dictionary-coded columns then is
-        code_a == table[code_b].  Cached per pair and rebuilt only when a dictionary GREW -- by values: the id counter moves by
-        whole chunks on every encode, so the id counts size the table and the value counts say whether anything is new.  While
-        `other` has not grown only the ids handed out here since the last call are looked up; once it has, an absent value may
-        have become present and the whole table is built again."""
-        from .device import DeviceBuffer, DeviceColumn
-        self._pair_check(other, "a translation")
-        lib = L.lib()
-        top = self._id_count()
-        entry = self._translate.get(id(other))
-        if entry is None or entry[0]() is not other:
-            entry = self._translate[id(other)] = [self._pair_ref(self._translate, other), DeviceBuffer(max(top, 1) * 4), max(top, 1), 0, -1, -1]
-        _, buf, cap, covered, mine, theirs = entry
-        if theirs != other._n_values:
-            covered = 0
-        if (covered == 0 or mine != self._n_values) and top > covered:
-            if top > cap:
-                cap = max(top, 2 * cap)
-                grown = DeviceBuffer(cap * 4)
-                if covered:
-                    L.check(lib.vnm_memcpy_d2d(grown.ptr, buf.ptr, covered * 4, None))
-                buf = grown
-            L.check(lib.vnm_strdict_translate(self.handle(), other.handle(), covered, buf.ptr, None))
-            self.translate_builds += 1
-            covered = top
-        entry[1:] = [buf, cap, covered, self._n_values, other._n_values]
-        return DeviceColumn(buf, None, 0, covered, pa.int32())
-
-    def joint_rank_tables(self, other):
-        """(own table, other's table): int32 DeviceColumns, one entry per id, the dense rank of the value in the ascending byte
-        order of the UNION of both dictionaries (vnm_strdict_ranks_joint: the order of rank_column; equal bytes share a rank), so
-        `a < b` over two dictionary-coded columns is table_a[code_a] < table_b[code_b].  Cached per pair until either grows (by
-        values, as translate_table)."""
-        from .device import DeviceBuffer, DeviceColumn
-        self._pair_check(other, "joint ranks")
-        lib = L.lib()
-        stamp = (self._n_values, other._n_values)
-        entry = self._joint.get(id(other))
-        if entry is None or entry[0]() is not other or entry[1] != stamp:
-            ids = (self._id_count(), other._id_count())
-            mine, theirs = DeviceBuffer(max(ids[0], 1) * 4), DeviceBuffer(max(ids[1], 1) * 4)
-            L.check(lib.vnm_memset(mine.ptr, 0xFF, max(ids[0], 1) * 4))      # (ids never handed out: no row holds them)
-            L.check(lib.vnm_memset(theirs.ptr, 0xFF, max(ids[1], 1) * 4))
-            L.check(lib.vnm_strdict_ranks_joint(self.handle(), other.handle(), mine.ptr, theirs.ptr, None))
-            self.joint_rank_builds += 1
-            entry = self._joint[id(other)] = [self._pair_ref(self._joint, other), stamp, mine, theirs, ids]
-        return (DeviceColumn(entry[2], None, 0, entry[4][0], pa.int32()), DeviceColumn(entry[3], None, 0, entry[4][1], pa.int32()))
-
-    def mapped(self, fn: str):
-        """upper() / lower() of this dictionary (`fn`: "upper" | "lower"; pc.utf8_upper / pc.utf8_lower, functions.py:279-298):
-        (the DERIVED dictionary, an int32 DeviceColumn `code here -> code there`, one entry per id handed out here; -2 for an id
-        never handed out).  The function depends on the value alone, so each distinct value is mapped ONCE, on the device
-        (vnm_strdict_map_codepoints with the code point table of vinum_amd.strcase), and found or inserted in the derived
-        dictionary; a row then costs one lookup of its code (mapped_column).  One derived dictionary per (dictionary, function),
-        the same object for the life of this one -- an AggregateOperator keeps the one of its first batch -- extended with the ids
-        handed out since the last call; a batch that brought no new value launches nothing (`map_launches`, `map_ids_mapped`).
-        The derived dictionary is a full KeyDictionary of type string, whatever this one's is (the reference casts to string
-        first, functions.py:219-221): it absorbs its new values, so it decodes, ranks, matches LIKE, pairs with other dictionaries
-        and maps again (upper(lower(c))).  A binary / large_binary dictionary raises TypeError (Arrow has no such kernel), a
-        host-route dictionary NotImplementedError; a structurally malformed UTF-8 value raises ValueError("Invalid UTF8 sequence in
-        input") from the call that first maps it -- whether or not a row holding it survives the query's filter."""
-        from . import strcase
-        from .device import DeviceBuffer, DeviceColumn
-        if fn not in strcase.CASE_FNS:
-            raise ValueError(f"no case map {fn!r}: one of {strcase.CASE_FNS}")
-        if not self._device:
-            raise NotImplementedError(f"no GPU lowering for {fn}() over a {self.type} column: only string columns keep their dictionaries on the device")
-        t = self.value_type
-        if not (pa.types.is_string(t) or pa.types.is_large_string(t)):
-            raise TypeError(f"{fn}() needs a string column, not {self.type}")      # (pc.utf8_upper has no kernel for binary)
-        lib = L.lib()
-        top = self._id_count()
-        entry = self._mapped.get(fn)
-        if entry is None:
-            entry = self._mapped[fn] = [KeyDictionary(pa.string()), DeviceBuffer(max(top, 1) * 4), max(top, 1), 0, -1]
-        derived, buf, cap, covered, mine = entry
-        # by VALUES, as translate_table: the id counter moves by whole chunks on every encode, only a new value is work
-        if top > covered and mine != self._n_values:
-            if top > cap:
-                cap = max(top, 2 * cap)
-                grown = DeviceBuffer(cap * 4)
-                if covered:
-                    L.check(lib.vnm_memcpy_d2d(grown.ptr, buf.ptr, covered * 4, None))
-                buf = grown
-            map_from, map_to = strcase.case_table(fn)
-            invalid = ctypes.c_int64(0)
-            rc = lib.vnm_strdict_map_codepoints(self.handle(), derived.handle(), map_from.ctypes.data, map_to.ctypes.data, len(map_from),
-                                                covered, buf.ptr, ctypes.byref(invalid), None)
-            self.map_launches += 1
-            self.map_ids_mapped += top - covered
-            entry[1:3] = [buf, cap]
-            message = L.last_error() if rc != 0 else None
-            if derived._h is not None:
-                derived.absorb_new()        # (also after a malformed value: the well-formed ones are in the derived dictionary)
-            if rc != 0:                     # (nothing is recorded as covered: the next call maps these ids, and raises, again)
-                if invalid.value:
-                    raise ValueError("Invalid UTF8 sequence in input")
-                raise L.VinumHipError(message)
-            entry[3:] = [top, self._n_values]
-        return entry[0], DeviceColumn(entry[1], None, 0, entry[3], pa.int32())
-
-    def mapped_column(self, fn: str, codes_col):
-        """upper(column) / lower(column) over a column of THIS dictionary's codes: the int32 DeviceColumn of the derived
-        dictionary's codes -- table[code] per row, one gather (NULL stays NULL: same validity) -- with `.dictionary` the derived
-        dictionary, so every operator takes it as the string column it is."""
-        from .device import DeviceBuffer, DeviceColumn
-        derived, table = self.mapped(fn)
-        n = codes_col.length
-        off = codes_col.offset if codes_col._validity is not None else 0      # (one Arrow offset serves values and bitmap)
-        out = DeviceBuffer(max(off + n, 1) * 4)
-        if n:
-            L.check(L.lib().vnm_strdict_codes_to_ranks(codes_col.values_ptr + codes_col.offset * 4, table.values_ptr, n, out.ptr + off * 4, None))
-        return DeviceColumn(out, codes_col._validity, off, n, pa.int32(), keep=(table, codes_col), dictionary=derived)
-
-    def values_by_code(self) -> pa.Array:
-        """The dictionary as an array indexed by CODE (a code the device never handed out: NULL) -- what the ranks exchange to build
-        one dictionary before partial groups keyed by these codes can travel (distributed.union_dictionary)."""
-        import numpy as np
-        if self._device and self._h is not None:
-            # (cached until the dictionary grows: a predicate on a dictionary column asks once per batch and literal -- ADVICE r05 --, and
-            #  the concat + take is O(distinct values))
-            top = int(L.lib().vnm_strdict_ids(self._h))
-            stamp = (top, len(self._chunks))
-            cached = getattr(self, "_by_code_cache", None)
-            if cached is not None and cached[0] == stamp:
-                return cached[1]
-            values = pa.concat_arrays(self._chunks) if self._chunks else pa.array([], type=self.value_type)
-            pos = self._pos[:top] if self._pos is not None else np.zeros(0, np.int64)
-            out = values.take(pa.array(np.where(pos < 0, 0, pos), type=pa.int64(), mask=(pos < 0) if (pos < 0).any() else None))
-            self._by_code_cache = (stamp, out)
-            return out
-        return self.values
-
-    def decode(self, codes: pa.Array) -> pa.Array:
-        """codes -> values of the column's type.  A dictionary-typed column comes back with ITS type (value type, index type,
-        `ordered`): decoded to the value type, then cast -- the output's dictionary is built by that cast and need not equal any
-        input dictionary; more distinct values than the index type can number surface Arrow's cast error."""
-        if self._dict_typed:
-            return self._decode_values(codes).cast(self.type)
-        return self._decode_values(codes)
-
-    def _decode_values(self, codes: pa.Array) -> pa.Array:
-        if self._device and (self._h is not None or self._pos is not None):
-            import numpy as np
-            values = pa.concat_arrays(self._chunks) if self._chunks else pa.array([], type=self.value_type)
-            c = codes.fill_null(0).to_numpy(zero_copy_only=False).astype(np.int64)
-            pos = self._pos[c] if self._pos is not None and len(c) else np.zeros(len(c), np.int64)
-            null = ~codes.is_valid().to_numpy(zero_copy_only=False) if codes.null_count else np.zeros(len(c), bool)
-            if ((pos < 0) & ~null).any():
-                raise RuntimeError("KeyDictionary.decode: a code that was never handed out (internal error)")
-            return values.take(pa.array(np.where(null, 0, pos), type=pa.int64(), mask=null if null.any() else None))
-        return self.values.take(codes)
 
 
 class GenericHashAggregate:
