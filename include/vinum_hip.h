@@ -365,7 +365,14 @@ vnm_agg_op* vnm_agg_op_create(int kind, int n_groupby, const char** groupby_cols
                               const char** in_cols, const char** out_cols);
 /* Consumes both.  The first batch fixes the layout: the columns the operator reads are found there by name, and every later
  * batch must hold each of them at the same position, with the same name and format (otherwise: "the batch schema changed").
- * Columns nobody reads may be of any type. */
+ * Columns nobody reads may be of any type.
+ * A child with a `dictionary` is never read as its indices.  dictionary<intN, utf8 | large_utf8 | binary | large_binary> is taken as
+ * group key, under COUNT and under MIN / MAX: per batch the dictionary's VALUES go through the operator's device dictionary, the
+ * native-width indices through vnm_strdict_remap_indices (route note keys:dictionary_child); a row is NULL when its index or its
+ * value is (one NULL group; COUNT counts neither); result() hands key and MIN / MAX columns back in the dictionary type, ordered
+ * flag kept, with a dictionary of exactly the values the groups use (vnm_dict_take_compact; more of them than the index type
+ * names fails with Arrow's "These dictionaries cannot be combined. ...").  Later batches must repeat the value format too.  Any
+ * other dictionary type as key, or any dictionary type under SUM / AVG, gets the error of an unsupported column type. */
 int vnm_agg_op_next(vnm_agg_op* h, struct ArrowArray* batch, struct ArrowSchema* schema);
 /* Every batch of an Arrow C stream, as one vnm_agg_op_next each (consumes and releases the stream).  The reference's pipeline
  * hands over 10 000-row batches (vinum/__init__.py:52, table_batch_reader.cpp:5-16); crossing the language boundary once per
@@ -416,6 +423,13 @@ typedef struct vnm_sort_op vnm_sort_op;
 vnm_sort_op* vnm_sort_op_create(int n, const char** cols, const int* orders);
 int vnm_sort_op_next(vnm_sort_op* h, struct ArrowArray* batch, struct ArrowSchema* schema);
 int vnm_sort_op_next_stream(vnm_sort_op* h, struct ArrowArrayStream* stream);   /* as vnm_agg_op_next_stream */
+/* Column types: numeric / temporal, utf8 / large_utf8 / binary / large_binary, decimal128, boolean (payload only), and
+ * dictionary<intN, utf8 | large_utf8 | binary | large_binary> as key or payload: the batch dictionaries' values go through one
+ * device dictionary per column, the native-width indices through vnm_strdict_remap_indices, a key orders by the values' ranks (a
+ * row that is NULL by index or by value last in both directions), and the column leaves in its own dictionary type -- indices of
+ * the input's width, the ordered flag kept, a dictionary of exactly the values the produced rows use (vnm_dict_take_compact; more
+ * of them than the index type holds fails with Arrow's "These dictionaries cannot be combined. ...").  A dictionary over any
+ * other value type: "has a type the GPU path does not handle". */
 int vnm_sort_op_sorted(vnm_sort_op* h, int64_t limit, struct ArrowArray* out, struct ArrowSchema* out_schema);
 void vnm_sort_op_destroy(vnm_sort_op* h);
 
@@ -560,6 +574,30 @@ int vnm_strdict_map_codepoints(vnm_strdict* src, vnm_strdict* dst, const int32_t
 #define VNM_STRDICT_REMAP_TILE 2048
 int vnm_strdict_remap_indices(const vnm_dcol* indices, const int32_t* code_of_index, int64_t n_values, int32_t* out_codes,
                               uint8_t* out_validity, int64_t* out_bad, void* stream);
+/* The way back: running codes -> a compact dictionary column of the input's index type (what Sort hands out for a dictionary-typed
+ * column).  Ids are handed out in chunks and a LIMIT uses only some of them, so the codes are not dense.
+ * With c_i = codes[rows ? rows[i] : i] (codes: int32s on the DEVICE; rows: n int64 row numbers on the device, NULL = identity):
+ *   an id is USED if some c_i equals it; out_used_ids (device, room for min(n, n_ids) int32s) receives the used ids in ascending
+ *   order and *out_n_used their count;
+ *   out_indices[i] (device, n values of index_type: VNM_I8 ... VNM_U64) = the position of c_i in out_used_ids, 0 where c_i < 0;
+ *   out_validity: NULL, or a device bitmap at bit offset 0, bit i = c_i >= 0, (n + 7) / 8 bytes, the bits past n in the last byte
+ *   0; every byte is written by exactly one lane (no atomics); *out_null_count (may be NULL) = the cleared bits among the n.
+ * The two counts are HOST memory, written after the call's own synchronisation of `stream`.
+ * n_ids bounds the codes (vnm_strdict_ids): the bounds test precedes every table access, so a code >= n_ids on a row that is read
+ * is never used as an address; such rows are counted and the call returns non-zero with "code out of bounds (K row(s) ...)".
+ * If *out_n_used exceeds the largest value of index_type the call returns non-zero with Arrow's own words for the same data
+ * (pa.concat_arrays): "These dictionaries cannot be combined.  The unified dictionary requires a larger index type."; nothing is
+ * promised about the output buffers then.
+ * Three passes: mark (plain one-byte stores into a zeroed n_ids-byte table), scan (exclusive, over the table), gather (a lane takes
+ * 8 consecutive rows = one bitmap byte; 16-byte code loads when rows == NULL and codes is 16-byte aligned; 8 / 16-byte index
+ * stores when out_indices is 16-byte aligned (8 for the 1-byte types), element stores otherwise and in the last partial group).
+ * The scan's table is read through L2, one tile per workgroup, or -- up to VNM_DICT_COMPACT_LDS_IDS ids, when a workgroup's rows are
+ * at least 4 x n_ids -- from a copy in LDS by a persistent grid (VNM_DICT_COMPACT_LDS=0 / 1 pins the form).
+ * VNM_DICT_COMPACT_TILE: rows per workgroup and step of the gather, ids per workgroup of the scan (sizes the tests walk around). */
+#define VNM_DICT_COMPACT_TILE 2048
+#define VNM_DICT_COMPACT_LDS_IDS 8192
+int vnm_dict_take_compact(const int32_t* codes, const int64_t* rows, int64_t n, int64_t n_ids, int index_type, void* out_indices,
+                          uint8_t* out_validity, int64_t* out_null_count, int32_t* out_used_ids, int64_t* out_n_used, void* stream);
 
 /* ---- IN / NOT IN against a list of any length: the list as a device-resident set ---------------------------
  * replaces np.isin(x, values[, invert]) (vinum/core/expressions.py:39-40; the parser hands it ONE Literal holding the whole list,

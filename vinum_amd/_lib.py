@@ -42,6 +42,7 @@ EQ, NE, GT, GE, LT, LE = range(6)
 LIKE_STRIP_NUL = 1                                       # vnm_strdict_like flags
 LIKE_TOK_LIT, LIKE_TOK_ANY, LIKE_TOK_STAR = 0, 1, 2     # vnm_like_compile token kinds
 STRDICT_REMAP_TILE = 2048                                # vnm_strdict_remap_indices: rows per workgroup
+DICT_COMPACT_TILE, DICT_COMPACT_LDS_IDS = 2048, 8192    # vnm_dict_take_compact: rows per workgroup, the largest table of the LDS form
 IN_DOM_I64, IN_DOM_U64, IN_DOM_F64 = range(3)           # vnm_in_set compare domains
 IN_ROUTES = ("in_set:bitmap_lds", "in_set:bitmap_global", "in_set:sorted_lds", "in_set:sorted_global")   # enum vnm_in_route
 MASK_U8 = 100
@@ -132,6 +133,7 @@ PROTOTYPES = {
     "vnm_strdict_ranks_joint": (c_int, [c_void, c_void, c_void, c_void, c_void]),
     "vnm_strdict_map_codepoints": (c_int, [c_void, c_void, c_void, c_void, c_i64, c_i64, c_void, c_void, c_void]),
     "vnm_strdict_remap_indices": (c_int, [c_void, c_void, c_i64, c_void, c_void, c_void, c_void]),
+    "vnm_dict_take_compact": (c_int, [c_void, c_void, c_i64, c_i64, c_int, c_void, c_void, c_void, c_void, c_void, c_void]),
     "vnm_like_compile": (c_int, [c_void, c_i64, c_void, c_void]),
     "vnm_strdict_like": (c_int, [c_void, c_void, c_i64, c_int, c_i64, c_void, c_void]),
     "vnm_in_set_create": (c_int, [c_int, c_void, c_i64, c_void]),

@@ -55,6 +55,10 @@ void release_schema(struct ArrowSchema* s) {
         }
     }
     free(s->children);
+    if (s->dictionary) {
+        if (s->dictionary->release) s->dictionary->release(s->dictionary);
+        free(s->dictionary);
+    }
     free((void*)s->format);
     free((void*)s->name);
     s->release = nullptr;
@@ -69,6 +73,10 @@ void release_array(struct ArrowArray* a) {
         }
     }
     free(a->children);
+    if (a->dictionary) {
+        if (a->dictionary->release) a->dictionary->release(a->dictionary);
+        free(a->dictionary);
+    }
     for (int64_t i = 0; i < a->n_buffers; i++) free((void*)a->buffers[i]);
     free(a->buffers);
     a->release = nullptr;
@@ -256,14 +264,50 @@ struct GenKey {
     std::vector<std::string> by_id;       // id -> bytes (ids are handed out in chunks: not dense)
     std::map<std::pair<uint64_t, uint64_t>, int32_t> dec_id;      // GK_DEC: (low, high) words -> code
     std::vector<std::pair<uint64_t, uint64_t>> dec_val;
+    // GK_STR over a dictionary-typed column (dictionary<intN, string-like>): the batch dictionaries' VALUES are encoded, the indices
+    // remapped on the device (stage_dict_codes); the result leaves in the dictionary type (make_dict_key_array)
+    bool dict_typed = false;
+    int index_type = -1;           // VNM_I8 ... VNM_U64
+    std::string value_format;      // u / U / z / Z
+    bool ordered = false;          // ARROW_FLAG_DICTIONARY_ORDERED
     ~GenKey() { if (dict) vnm_strdict_destroy(dict); }
 };
+static bool is_string_format(const std::string& f) { return f == "u" || f == "U" || f == "z" || f == "Z"; }
+// an integer index format over a string-like value format?  (the one dictionary type the device route takes)
+static bool is_string_dictionary(const struct ArrowSchema* s) {
+    return s->dictionary && s->format && strlen(s->format) == 1 && strchr("cCsSiIlL", s->format[0]) && s->dictionary->format &&
+           is_string_format(s->dictionary->format);
+}
 static int generic_kind(const std::string& f, bool* wide) {
     *wide = f == "U" || f == "Z";
     if (f == "u" || f == "U" || f == "z" || f == "Z") return GK_STR;
     if (f == "b") return GK_BOOL;
     if (f.rfind("d:", 0) == 0 && (f.find(",128") != std::string::npos || std::count(f.begin(), f.end(), ',') == 1)) return GK_DEC;
     return GK_NUM;
+}
+// how a non-numeric column travels, from its SCHEMA: a child with a dictionary is never judged by its index format alone (GK_NUM here
+// means "not taken": a dictionary over anything but strings / binaries)
+static void describe_generic(const struct ArrowSchema* s, GenKey* g) {
+    if (!s->dictionary) { g->kind = generic_kind(s->format ? s->format : "", &g->wide); return; }
+    g->kind = GK_NUM;
+    if (!is_string_dictionary(s)) return;
+    g->kind = GK_STR;
+    g->dict_typed = true;
+    g->value_format = s->dictionary->format;
+    g->wide = g->value_format == "U" || g->value_format == "Z";
+    g->ordered = (s->flags & 1) != 0;
+    switch (s->format[0]) {
+        case 'c': g->index_type = VNM_I8; break;   case 'C': g->index_type = VNM_U8; break;
+        case 's': g->index_type = VNM_I16; break;  case 'S': g->index_type = VNM_U16; break;
+        case 'i': g->index_type = VNM_I32; break;  case 'I': g->index_type = VNM_U32; break;
+        case 'l': g->index_type = VNM_I64; break;  default: g->index_type = VNM_U64; break;
+    }
+}
+// what a later batch's child must repeat: the format, and the value format of a dictionary-typed child
+static std::string schema_signature(const struct ArrowSchema* s) {
+    std::string sig = s->format ? s->format : "";
+    if (s->dictionary) { sig += "|"; sig += s->dictionary->format ? s->dictionary->format : ""; sig += (s->flags & 1) ? "|ordered" : ""; }
+    return sig;
 }
 struct ColChunk { const struct ArrowArray* col; int64_t off, len; };   // rows [off, off + len) of a child array
 static const uint8_t* chunk_validity(const ColChunk& c) { return (c.col->null_count != 0 && c.col->n_buffers > 0) ? (const uint8_t*)c.col->buffers[0] : nullptr; }
@@ -282,8 +326,109 @@ static std::vector<uint8_t> joined_validity(const std::vector<ColChunk>& chunks,
     }
     return bits;
 }
+// the values the last vnm_strdict_encode added -> by_id
+static int genkey_fetch_new(GenKey& g, int64_t n_new, int64_t new_bytes) {
+    if (n_new <= 0) return 0;
+    std::vector<int32_t> ids((size_t)n_new), lens((size_t)n_new);
+    std::vector<uint8_t> bytes((size_t)(new_bytes ? new_bytes : 1));
+    VNM_TRY(vnm_strdict_fetch_new(g.dict, ids.data(), lens.data(), bytes.data()));
+    size_t o = 0;
+    for (int64_t i = 0; i < n_new; i++) {
+        if ((size_t)ids[(size_t)i] >= g.by_id.size()) g.by_id.resize((size_t)ids[(size_t)i] + 1);
+        g.by_id[(size_t)ids[(size_t)i]].assign((const char*)bytes.data() + o, (size_t)lens[(size_t)i]);
+        o += (size_t)lens[(size_t)i];
+    }
+    return 0;
+}
+// bit i = codes[i] >= 0; one lane per byte of the bitmap (the bits past n in the last byte 0)
+__global__ void codes_valid_bits_kernel(const int32_t* codes, int64_t n, uint8_t* bits) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b * 8 >= n) return;
+    unsigned v = 0;
+    for (int k = 0; k < 8; k++)
+        if (b * 8 + k < n && codes[b * 8 + k] >= 0) v |= 1u << k;
+    bits[b] = (uint8_t)v;
+}
+// A dictionary-typed key / COUNT / MIN / MAX column -> int32 codes of the operator's device dictionary, validity = codes >= 0 (a row
+// is NULL by index or by value).  Per chunk the D VALUES of its dictionary are encoded from their host buffers (own offset, length,
+// validity; a NULL value: table entry -1) unless the chunk repeats the previous chunk's dictionary buffers -- judged inside one call
+// only, while every chunk is alive --, the code_of_index table is uploaded, and the native-width indices, joined through the pinned
+// ring, are remapped on the device.  No per-row host loop, no string bytes per row over PCIe.
+static int stage_dict_codes(GenKey& g, const std::vector<ColChunk>& chunks, int64_t total, vnm_dcol* out) {
+    const int w = type_width(g.index_type);
+    const size_t t1 = (size_t)(total ? total : 1);
+    PoolScope pool;
+    void* didx = pool.take(t1 * w);
+    int32_t* codes = (int32_t*)pool.take(t1 * 4);
+    uint8_t* vbits = (uint8_t*)pool.take((size_t)(total + 7) / 8 + 8);
+    if (!didx || !codes || !vbits) return 1;
+    std::vector<const void*> srcs;
+    std::vector<size_t> sizes;
+    for (auto& c : chunks) {
+        if (!c.len) continue;
+        if (!c.col->dictionary || c.col->dictionary->n_buffers < 3 || c.col->n_buffers < 2 || !c.col->buffers[1]) return set_error("a dictionary-typed column without its dictionary or indices");
+        srcs.push_back((const uint8_t*)c.col->buffers[1] + (size_t)c.off * w);
+        sizes.push_back((size_t)c.len * w);
+    }
+    if (!srcs.empty()) VNM_TRY(stage_chunks(didx, srcs.data(), sizes.data(), srcs.size(), nullptr));
+    const std::vector<uint8_t> bits = joined_validity(chunks, total);
+    uint8_t* dbits = nullptr;
+    if (!bits.empty()) {
+        dbits = (uint8_t*)pool.take((size_t)(total + 7) / 8 + 8);
+        if (!dbits) return 1;
+        VNM_HIP(hipMemcpyAsync(dbits, bits.data(), (size_t)(total + 7) / 8, hipMemcpyHostToDevice, nullptr));
+    }
+    VNM_HIP(hipStreamSynchronize(nullptr));
+    int32_t* table = nullptr;
+    int64_t table_cap = 0, row = 0, values = 0, skipped = 0;
+    const struct ArrowArray* prev = nullptr;
+    for (auto& c : chunks) {
+        if (!c.len) continue;
+        const struct ArrowArray* dv = c.col->dictionary;
+        const int64_t D = dv->length;
+        const bool same = prev && prev->buffers[0] == dv->buffers[0] && prev->buffers[1] == dv->buffers[1] && prev->buffers[2] == dv->buffers[2] &&
+                          prev->offset == dv->offset && prev->length == dv->length;
+        if (same) skipped++;
+        else {
+            std::vector<int32_t> code_of((size_t)(D ? D : 1), -1);
+            if (D > 0) {
+                int64_t n_new = 0, new_bytes = 0;
+                const uint8_t* valid = dv->null_count != 0 ? (const uint8_t*)dv->buffers[0] : nullptr;
+                VNM_TRY(vnm_strdict_encode(g.dict, dv->buffers[1], g.wide ? 1 : 0, (const uint8_t*)dv->buffers[2], valid, dv->offset, D,
+                                           code_of.data(), &n_new, &new_bytes, nullptr));
+                VNM_TRY(genkey_fetch_new(g, n_new, new_bytes));
+            }
+            if (D > table_cap) {
+                pool.done(table);
+                table_cap = std::max<int64_t>(D, 2 * table_cap);
+                table = (int32_t*)pool.take((size_t)table_cap * 4);
+                if (!table) return 1;
+            }
+            if (D > 0) VNM_HIP(hipMemcpy(table, code_of.data(), (size_t)D * 4, hipMemcpyHostToDevice));
+            values += D;
+            prev = dv;
+        }
+        vnm_dcol view{};
+        view.values = didx; view.validity = dbits; view.offset = row; view.length = c.len; view.type = g.index_type;
+        int64_t bad = 0;
+        VNM_TRY(vnm_strdict_remap_indices(&view, table, D, codes + row, nullptr, &bad, nullptr));
+        row += c.len;
+    }
+    if (total > 0) {
+        const int64_t nb = (total + 7) / 8;
+        codes_valid_bits_kernel<<<dim3((unsigned)((nb + 255) / 256)), 256, 0, nullptr>>>(codes, total, vbits);
+        VNM_HIP(hipGetLastError());
+    }
+    VNM_HIP(hipStreamSynchronize(nullptr));
+    route_note("keys:dictionary_child", "rows=%lld values_encoded=%lld dictionaries_skipped=%lld", (long long)total, (long long)values, (long long)skipped);
+    memset(out, 0, sizeof(*out));
+    out->values = codes; out->validity = vbits; out->type = VNM_I32; out->length = total;
+    pool.keep(codes); pool.keep(vbits);
+    return 0;
+}
 // a non-numeric key column -> int32 codes in HBM
 static int stage_generic_key(GenKey& g, const std::vector<ColChunk>& chunks, int64_t total, vnm_dcol* out) {
+    if (g.dict_typed) return stage_dict_codes(g, chunks, total, out);
     std::vector<int32_t> codes((size_t)(total ? total : 1), -1);
     int64_t pos = 0;
     for (auto& c : chunks) {
@@ -293,17 +438,7 @@ static int stage_generic_key(GenKey& g, const std::vector<ColChunk>& chunks, int
         if (g.kind == GK_STR) {
             int64_t n_new = 0, new_bytes = 0;
             VNM_TRY(vnm_strdict_encode(g.dict, c.col->buffers[1], g.wide ? 1 : 0, (const uint8_t*)c.col->buffers[2], valid, c.off, c.len, codes.data() + pos, &n_new, &new_bytes, nullptr));
-            if (n_new > 0) {
-                std::vector<int32_t> ids((size_t)n_new), lens((size_t)n_new);
-                std::vector<uint8_t> bytes((size_t)(new_bytes ? new_bytes : 1));
-                VNM_TRY(vnm_strdict_fetch_new(g.dict, ids.data(), lens.data(), bytes.data()));
-                size_t o = 0;
-                for (int64_t i = 0; i < n_new; i++) {
-                    if ((size_t)ids[(size_t)i] >= g.by_id.size()) g.by_id.resize((size_t)ids[(size_t)i] + 1);
-                    g.by_id[(size_t)ids[(size_t)i]].assign((const char*)bytes.data() + o, (size_t)lens[(size_t)i]);
-                    o += (size_t)lens[(size_t)i];
-                }
-            }
+            VNM_TRY(genkey_fetch_new(g, n_new, new_bytes));
         } else if (g.kind == GK_BOOL) {
             const uint8_t* v = (const uint8_t*)c.col->buffers[1];
             for (int64_t i = 0; i < c.len; i++) if (is_valid(i)) codes[(size_t)(pos + i)] = (v[(c.off + i) >> 3] >> ((c.off + i) & 7)) & 1;
@@ -382,6 +517,46 @@ static void make_generic_key_array(struct ArrowArray* a, const GenKey& g, int64_
         if (valid_bytes[i] && codes[i] >= 0 && (size_t)codes[i] < g.dec_val.size()) { v[2 * i] = g.dec_val[(size_t)codes[i]].first; v[2 * i + 1] = g.dec_val[(size_t)codes[i]].second; }
     a->buffers[1] = v;
 }
+// The groups' codes of a dictionary-typed column (host: int32 values + validity bytes) -> a dictionary-typed Arrow array: indices of the
+// input's width into a dictionary of exactly the values the groups use (vnm_dict_take_compact over the codes, rows = NULL); the NULL
+// group stays NULL.
+static int make_dict_key_array(struct ArrowArray* a, const GenKey& g, int64_t n, const int32_t* codes, const uint8_t* valid_bytes) {
+    const size_t n1 = (size_t)(n ? n : 1);
+    const int w = type_width(g.index_type);
+    const int64_t n_ids = vnm_strdict_ids(g.dict);
+    std::vector<int32_t> hc(n1, -1);
+    for (int64_t i = 0; i < n; i++) if (valid_bytes[i]) hc[(size_t)i] = codes[i];
+    PoolScope pool;
+    int32_t* dcodes = (int32_t*)pool.take(n1 * 4);
+    void* dind = pool.take(n1 * w);
+    uint8_t* dvalid = (uint8_t*)pool.take((size_t)(n + 7) / 8 + 8);
+    int32_t* dused = (int32_t*)pool.take((size_t)std::max<int64_t>(std::min(n, n_ids), 1) * 4);
+    if (!dcodes || !dind || !dvalid || !dused) return 1;
+    VNM_HIP(hipMemcpy(dcodes, hc.data(), n1 * 4, hipMemcpyHostToDevice));
+    int64_t nulls = 0, n_used = 0;
+    VNM_TRY(vnm_dict_take_compact(dcodes, nullptr, n, n_ids, g.index_type, dind, dvalid, &nulls, dused, &n_used, nullptr));
+    std::vector<int32_t> used((size_t)(n_used ? n_used : 1));
+    if (n_used) VNM_HIP(hipMemcpy(used.data(), dused, (size_t)n_used * 4, hipMemcpyDeviceToHost));
+    VNM_TRY(make_primitive_from_device(a, n, w, dind, dvalid, nulls));
+    a->dictionary = (struct ArrowArray*)calloc(1, sizeof(struct ArrowArray));
+    const std::vector<uint8_t> all_valid((size_t)(n_used ? n_used : 1), 1);
+    make_generic_key_array(a->dictionary, g, n_used, used.data(), all_valid.data());   // (GK_STR: the values as a plain array of the value type)
+    return 0;
+}
+// a non-numeric result column (group key, string MIN / MAX) of the type it came in with
+static int make_key_column(struct ArrowArray* a, const GenKey& g, int64_t n, const int32_t* codes, const uint8_t* valid_bytes) {
+    if (g.dict_typed) return make_dict_key_array(a, g, n, codes, valid_bytes);
+    make_generic_key_array(a, g, n, codes, valid_bytes);
+    return 0;
+}
+// ... and its schema: the dictionary child and the ordered flag of a dictionary-typed column
+static void make_key_schema(struct ArrowSchema* s, const GenKey& g, const std::string& format, const std::string& name) {
+    make_schema(s, format, name, 0);
+    if (!g.dict_typed) return;
+    s->dictionary = (struct ArrowSchema*)calloc(1, sizeof(struct ArrowSchema));
+    make_schema(s->dictionary, g.value_format, "", 0);
+    if (g.ordered) s->flags |= 1;   // ARROW_FLAG_DICTIONARY_ORDERED
+}
 
 // ---- MIN / MAX over utf8 / large_utf8 / binary / large_binary columns below the C ABI -------------------------------------------------
 // StringMinMaxFunc (agg_funcs.h:219-261): NULLs skipped, a group of NULLs only gives NULL, values compared byte-wise.  The device
@@ -421,6 +596,10 @@ struct vnm_agg_op {
     int kind;
     std::vector<std::unique_ptr<GenKey>> gkeys;   // per group-by column: how a non-numeric key travels (GK_NUM: as it is)
     std::vector<char> standin;                    // per function: COUNT over a non-numeric column (int8 stand-in with its validity)
+    // per function: COUNT over a dictionary-typed string column counts its CODES (valid by index and by value); the dictionary is
+    // the key's when the column is a key too, one of count_dicts otherwise
+    std::vector<GenKey*> count_gk;
+    std::vector<std::unique_ptr<GenKey>> count_dicts;
     std::vector<std::string> groupby, agg_cols, in_cols, out_cols;
     std::vector<int> funcs;
     vnm_agg* dev = nullptr;
@@ -443,7 +622,7 @@ struct vnm_agg_op {
 static int agg_op_init(vnm_agg_op* h, const struct ArrowSchema* sch) {
     // a failed earlier attempt (unknown column, unsupported type) must not leave half-filled index vectors behind
     h->key_idx.clear(); h->key_t.clear(); h->in_idx.clear(); h->in_t.clear(); h->aggcol_key.clear(); h->gkeys.clear(); h->standin.clear();
-    h->strcols.clear(); h->strfns.clear(); h->dev_of.clear();
+    h->strcols.clear(); h->strfns.clear(); h->dev_of.clear(); h->count_gk.clear(); h->count_dicts.clear();
     for (auto& c : h->cands) c.drop();
     h->cands.clear(); h->cand_rows = 0; h->cand_floor = 0;
     if (h->dev) { vnm_agg_destroy(h->dev); h->dev = nullptr; }
@@ -453,9 +632,10 @@ static int agg_op_init(vnm_agg_op* h, const struct ArrowSchema* sch) {
         if (i < 0) return set_error("Column not found: %s", c.c_str());
         h->key_idx.push_back(i);
         h->key_t.push_back(parse_format(sch->children[i]->format));
+        if (sch->children[i]->dictionary) h->key_t.back().type = -1;   // (never a plain intN column: its indices mean nothing across batches)
         std::unique_ptr<GenKey> g(new GenKey());
         if (h->key_t.back().type < 0) {   // a non-numeric key: its codes travel (the column keeps its format for the result)
-            g->kind = generic_kind(h->key_t.back().format, &g->wide);
+            describe_generic(sch->children[i], g.get());
             if (g->kind == GK_NUM || h->kind == VNM_ONE_GROUP) return set_error("Unsupported data type for aggregation column.");
             if (g->kind == GK_STR && !(g->dict = vnm_strdict_create())) return 1;
             h->key_t.back().type = VNM_I32;
@@ -473,6 +653,7 @@ static int agg_op_init(vnm_agg_op* h, const struct ArrowSchema* sch) {
     for (auto& t : h->key_t) ktypes.push_back(t.type);
     for (size_t i = 0; i < h->funcs.size(); i++) {
         h->standin.push_back(0);
+        h->count_gk.push_back(nullptr);
         h->dev_of.push_back((int)dfuncs.size());
         if (h->funcs[i] == VNM_COUNT_STAR || h->in_cols[i].empty()) {
             h->in_idx.push_back(-1);
@@ -483,16 +664,19 @@ static int agg_op_init(vnm_agg_op* h, const struct ArrowSchema* sch) {
         int ci = find_child(sch, h->in_cols[i]);
         if (ci < 0) return set_error("Column not found: %s", h->in_cols[i].c_str());
         ColType t = parse_format(sch->children[ci]->format);
+        GenKey how;                          // a dictionary-typed child is judged by its values, never read as its indices
+        describe_generic(sch->children[ci], &how);
+        if (sch->children[ci]->dictionary) t.type = -1;
         h->in_idx.push_back(ci);
         h->in_t.push_back(t);
-        bool wide_str = false;
-        if (t.type < 0 && (h->funcs[i] == VNM_MIN || h->funcs[i] == VNM_MAX) && generic_kind(t.format, &wide_str) == GK_STR) {
+        if (t.type < 0 && (h->funcs[i] == VNM_MIN || h->funcs[i] == VNM_MAX) && how.kind == GK_STR) {
             // MIN / MAX of strings / binaries: not a function of the device operator (strmm_* below)
             int col = -1;
             for (size_t q = 0; q < h->strcols.size(); q++) if (h->strcols[q]->child == ci) col = (int)q;
             if (col < 0) {
                 std::unique_ptr<StrCol> sc(new StrCol());
-                sc->child = ci; sc->dict.kind = GK_STR; sc->dict.wide = wide_str;
+                sc->child = ci;
+                describe_generic(sch->children[ci], &sc->dict);
                 if (!(sc->dict.dict = vnm_strdict_create())) return 1;
                 col = (int)h->strcols.size();
                 h->strcols.push_back(std::move(sc));
@@ -508,6 +692,22 @@ static int agg_op_init(vnm_agg_op* h, const struct ArrowSchema* sch) {
                 case VNM_SUM: return set_error("Column data type is not supported by sum().");
                 default: return set_error("Column data type is not supported by avg().");
             }
+        }
+        if (t.type < 0 && how.dict_typed) {   // COUNT over a dictionary-typed string column: its codes, NULL where the row OR its value is
+            GenKey* g = nullptr;
+            for (size_t j = 0; j < h->key_idx.size(); j++) if (h->key_idx[j] == ci) g = h->gkeys[j].get();
+            for (size_t q = 0; !g && q < i; q++) if (h->count_gk[q] && h->in_idx[q] == ci) g = h->count_gk[q];
+            if (!g) {
+                std::unique_ptr<GenKey> own(new GenKey());
+                describe_generic(sch->children[ci], own.get());
+                if (!(own->dict = vnm_strdict_create())) return 1;
+                g = own.get();
+                h->count_dicts.push_back(std::move(own));
+            }
+            h->count_gk.back() = g;
+            h->in_t.back().type = VNM_I32;
+            dfuncs.push_back(h->funcs[i]); itypes.push_back(VNM_I32); iflags.push_back(0); ids.push_back(1000000 + ci);
+            continue;
         }
         if (t.type < 0) {   // COUNT over a non-numeric column: an int8 stand-in with the column's validity (its own column id: the same
                             // column may also be a key, which travels as codes)
@@ -782,10 +982,10 @@ static int strmm_join(vnm_agg_op* h, int64_t n, std::vector<std::vector<int32_t>
     }
     return 0;
 }
-static void strmm_column(vnm_agg_op* h, int f, int64_t n, const std::vector<int32_t>& ids, struct ArrowArray* out) {
+static int strmm_column(vnm_agg_op* h, int f, int64_t n, const std::vector<int32_t>& ids, struct ArrowArray* out) {
     std::vector<uint8_t> vb((size_t)(n ? n : 1));
     for (int64_t r = 0; r < n; r++) vb[(size_t)r] = ids[(size_t)r] >= 0;
-    make_generic_key_array(out, h->strcols[(size_t)h->strfns[(size_t)f].col]->dict, n, ids.data(), vb.data());
+    return make_key_column(out, h->strcols[(size_t)h->strfns[(size_t)f].col]->dict, n, ids.data(), vb.data());
 }
 
 extern "C" {
@@ -818,7 +1018,7 @@ static int agg_op_flush(vnm_agg_op* h) {
     };
     for (size_t j = 0; !rc && j < h->key_idx.size(); j++) rc = get(h->key_idx[j], h->key_t[j], &keys[j], h->gkeys[j].get());
     for (size_t i = 0; !rc && i < h->funcs.size(); i++)
-        if (h->dev_of[i] >= 0 && h->in_idx[i] >= 0) rc = get(h->in_idx[i], h->in_t[i], &inputs[(size_t)h->dev_of[i]], nullptr, h->standin[i] != 0);
+        if (h->dev_of[i] >= 0 && h->in_idx[i] >= 0) rc = get(h->in_idx[i], h->in_t[i], &inputs[(size_t)h->dev_of[i]], h->count_gk[i], h->standin[i] != 0);
     if (!rc && total > 0) rc = vnm_agg_next_device(h->dev, total, keys.data(), inputs.data(), nullptr, nullptr);
     if (hipStreamSynchronize(nullptr) != hipSuccess && !rc) rc = set_error("vnm_agg_op_next: stream synchronisation failed");
     if (!rc) rc = strmm_batch(h, total, keys, chunks_of);
@@ -846,7 +1046,7 @@ int vnm_agg_op_next(vnm_agg_op* h, struct ArrowArray* batch, struct ArrowSchema*
         if (!rc) {
             h->formats.clear(); h->names.clear();
             for (int64_t c = 0; c < ib.sch.n_children; c++) {
-                h->formats.push_back(ib.sch.children[c]->format ? ib.sch.children[c]->format : "");
+                h->formats.push_back(schema_signature(ib.sch.children[c]));
                 h->names.push_back(ib.sch.children[c]->name ? ib.sch.children[c]->name : "");
             }
         }
@@ -854,7 +1054,7 @@ int vnm_agg_op_next(vnm_agg_op* h, struct ArrowArray* batch, struct ArrowSchema*
         // the columns the operator reads must be where -- and what, under the same name -- they were in the first batch (a
         // column of the same type in another layout would otherwise be read in their place)
         auto same = [&](int ci) { return ci < (int)ib.sch.n_children && ci < (int)h->formats.size() && ib.sch.children[ci]->format &&
-                                         h->formats[(size_t)ci] == ib.sch.children[ci]->format && ib.sch.children[ci]->name &&
+                                         h->formats[(size_t)ci] == schema_signature(ib.sch.children[ci]) && ib.sch.children[ci]->name &&
                                          h->names[(size_t)ci] == ib.sch.children[ci]->name; };
         for (size_t j = 0; !rc && j < h->key_idx.size(); j++) if (!same(h->key_idx[j])) rc = set_error("vnm_agg_op_next: the batch schema changed");
         for (size_t i = 0; !rc && i < h->funcs.size(); i++) if (h->in_idx[i] >= 0 && !same(h->in_idx[i])) rc = set_error("vnm_agg_op_next: the batch schema changed");
@@ -889,7 +1089,7 @@ int vnm_agg_op_next(vnm_agg_op* h, struct ArrowArray* batch, struct ArrowSchema*
     };
     for (size_t j = 0; !rc && j < h->key_idx.size(); j++) rc = get(h->key_idx[j], h->key_t[j], &keys[j], h->gkeys[j].get());
     for (size_t i = 0; !rc && i < h->funcs.size(); i++)
-        if (h->dev_of[i] >= 0 && h->in_idx[i] >= 0) rc = get(h->in_idx[i], h->in_t[i], &inputs[(size_t)h->dev_of[i]], nullptr, h->standin[i] != 0);
+        if (h->dev_of[i] >= 0 && h->in_idx[i] >= 0) rc = get(h->in_idx[i], h->in_t[i], &inputs[(size_t)h->dev_of[i]], h->count_gk[i], h->standin[i] != 0);
     if (!rc) rc = vnm_agg_next_device(h->dev, ib.arr.length, keys.data(), inputs.data(), nullptr, (void*)s);
     if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error("vnm_agg_op_next: stream synchronisation failed");
     if (!rc) rc = strmm_batch(h, ib.arr.length, keys, [&](int ci) { return std::vector<ColChunk>{ColChunk{ib.arr.children[ci], ib.arr.children[ci]->offset + ib.arr.offset, ib.arr.length}}; });
@@ -940,17 +1140,17 @@ int vnm_agg_op_result(vnm_agg_op* h, struct ArrowArray* out, struct ArrowSchema*
                 if (!rc && nulls && hipMemcpy(bm.data(), db, (size_t)((n + 7) / 8), hipMemcpyDeviceToHost) != hipSuccess) rc = set_error("result: device to host copy failed");
                 if (!rc) {
                     if (nulls) for (int64_t r = 0; r < n; r++) vb[(size_t)r] = (bm[(size_t)(r >> 3)] >> (r & 7)) & 1;
-                    make_generic_key_array(out->children[col], *h->gkeys[j], n, codes.data(), vb.data());
+                    rc = make_key_column(out->children[col], *h->gkeys[j], n, codes.data(), vb.data());
                 }
             } else if (!rc) rc = make_primitive_from_device(out->children[col], n, type_width(t.type), dv, db, nulls);
-            make_schema(out_schema->children[col], t.format, h->agg_cols[a], 0);
+            make_key_schema(out_schema->children[col], *h->gkeys[j], t.format, h->agg_cols[a]);
         }
         for (size_t i = 0; !rc && i < h->funcs.size(); i++, col++) {
             int kind = 0;
             int64_t nulls = 0;
             if (strfn_of[i] >= 0) {
-                strmm_column(h, strfn_of[i], n, str_ids[(size_t)strfn_of[i]], out->children[col]);
-                make_schema(out_schema->children[col], h->in_t[i].format, h->out_cols[i], 0);
+                rc = strmm_column(h, strfn_of[i], n, str_ids[(size_t)strfn_of[i]], out->children[col]);
+                make_key_schema(out_schema->children[col], h->strcols[(size_t)h->strfns[(size_t)strfn_of[i]].col]->dict, h->in_t[i].format, h->out_cols[i]);
                 continue;
             }
             rc = vnm_agg_result_func_device(h->dev, h->dev_of[i], dv, db, &kind, &nulls, nullptr);
@@ -990,8 +1190,8 @@ int vnm_agg_op_result(vnm_agg_op* h, struct ArrowArray* out, struct ArrowSchema*
         if (h->gkeys[j]->kind != GK_NUM) {
             std::vector<int32_t> codes((size_t)(n ? n : 1));
             for (int64_t r = 0; r < n; r++) codes[(size_t)r] = (int32_t)vals[(size_t)r];
-            make_generic_key_array(out->children[col], *h->gkeys[j], n, codes.data(), valid.data());
-            make_schema(out_schema->children[col], t.format, h->agg_cols[a], 0);
+            VNM_TRY(make_key_column(out->children[col], *h->gkeys[j], n, codes.data(), valid.data()));
+            make_key_schema(out_schema->children[col], *h->gkeys[j], t.format, h->agg_cols[a]);
             continue;
         }
         std::vector<uint8_t> narrow((size_t)(n ? n : 1) * w);
@@ -1002,8 +1202,8 @@ int vnm_agg_op_result(vnm_agg_op* h, struct ArrowArray* out, struct ArrowSchema*
     for (size_t i = 0; i < h->funcs.size(); i++, col++) {
         int kind = 0;
         if (strfn_of[i] >= 0) {
-            strmm_column(h, strfn_of[i], n, str_ids[(size_t)strfn_of[i]], out->children[col]);
-            make_schema(out_schema->children[col], h->in_t[i].format, h->out_cols[i], 0);
+            VNM_TRY(strmm_column(h, strfn_of[i], n, str_ids[(size_t)strfn_of[i]], out->children[col]));
+            make_key_schema(out_schema->children[col], h->strcols[(size_t)h->strfns[(size_t)strfn_of[i]].col]->dict, h->in_t[i].format, h->out_cols[i]);
             continue;
         }
         VNM_TRY(vnm_agg_result_func(h->dev, h->dev_of[i], cells.data(), valid.data(), &kind));
@@ -1045,17 +1245,30 @@ int vnm_agg_op_result(vnm_agg_op* h, struct ArrowArray* out, struct ArrowSchema*
 // sort operator
 // =========================================================================================================
 // ---- column kinds of a table under Sort (vnm_sort_op_sorted) ---------------------------------------------------------------------
-enum { SC_NUM = 0, SC_VAR = 1, SC_BOOL = 2, SC_DEC = 3 };
+enum { SC_NUM = 0, SC_VAR = 1, SC_BOOL = 2, SC_DEC = 3, SC_DICT = 4 };
 struct SortColInfo {
     int kind = -1;
-    ColType t;
-    bool wide = false;      // large_utf8 / large_binary: 64-bit offsets
+    ColType t;              // SC_DICT: the index type
+    bool wide = false;      // large_utf8 / large_binary: 64-bit offsets (SC_DICT: of the values)
     std::string format;
+    std::string value_format;   // SC_DICT: u / U / z / Z
+    bool ordered = false;       // SC_DICT: ARROW_FLAG_DICTIONARY_ORDERED
 };
 
-static SortColInfo classify_sort_col(const char* f) {
+static SortColInfo classify_sort_col(const struct ArrowSchema* s) {
     SortColInfo c;
+    const char* f = s->format;
     c.format = f ? f : "";
+    if (s->dictionary) {    // dictionary<intN, string-like>; any other value type stays kind -1 (never read as its indices)
+        c.value_format = s->dictionary->format ? s->dictionary->format : "";
+        const ColType it = parse_format(f);
+        if (is_string_dictionary(s)) {
+            c.kind = SC_DICT; c.t = it;
+            c.wide = c.value_format == "U" || c.value_format == "Z";
+            c.ordered = (s->flags & 1) != 0;
+        }
+        return c;
+    }
     c.t = parse_format(f);
     if (c.t.type >= 0) { c.kind = SC_NUM; return c; }
     if (c.format == "u" || c.format == "z") { c.kind = SC_VAR; return c; }
@@ -1075,12 +1288,97 @@ struct DevSortCol {
     uint8_t* bits = nullptr;     // SC_BOOL: the values, bit i = row i
     void* fixed = nullptr;       // SC_DEC: 16-byte values
     uint8_t* validity = nullptr; // bitmap, bit i = row i (null: no NULLs); SC_NUM keeps its own in `num`
+    // SC_DICT: the rows' codes in one dictionary that grows with the batches (-1: NULL by index or by value; `validity` = codes >= 0)
+    int32_t* codes = nullptr;
+    vnm_strdict* dict = nullptr;
+    // the values the encodes added, laid end to end in the order they came back (value k: id, bytes [val_off[k], val_off[k + 1]));
+    // nothing is indexed by id until the result's dictionary asks for the ids it uses (an id-indexed table of strings is one cache
+    // miss per value)
+    std::vector<int32_t> val_ids;
+    std::vector<int64_t> val_off{0};
+    std::vector<uint8_t> val_bytes;
+    int64_t values_encoded = 0, dicts_skipped = 0;  // for the route note
     void free_all() {
         vnm_free_column(&num);
-        pool_free(offs); pool_free(data); pool_free(bits); pool_free(fixed); pool_free(validity);
-        offs = nullptr; data = nullptr; bits = nullptr; fixed = nullptr; validity = nullptr;
+        pool_free(offs); pool_free(data); pool_free(bits); pool_free(fixed); pool_free(validity); pool_free(codes);
+        offs = nullptr; data = nullptr; bits = nullptr; fixed = nullptr; validity = nullptr; codes = nullptr;
+        if (dict) vnm_strdict_destroy(dict);
+        dict = nullptr;
     }
 };
+
+// the values the last vnm_strdict_encode added, appended to the column's value list
+static int fetch_new_values(DevSortCol* d, int64_t n_new, int64_t new_bytes) {
+    if (n_new <= 0) return 0;
+    const size_t k0 = d->val_ids.size(), b0 = d->val_bytes.size();
+    std::vector<int32_t> lens((size_t)n_new);
+    d->val_ids.resize(k0 + (size_t)n_new);
+    d->val_bytes.resize(b0 + (size_t)new_bytes + 1);     // (+ 1: never a null pointer for the fetch; cut below)
+    VNM_TRY(vnm_strdict_fetch_new(d->dict, d->val_ids.data() + k0, lens.data(), d->val_bytes.data() + b0));
+    d->val_bytes.resize(b0 + (size_t)new_bytes);
+    for (int64_t i = 0; i < n_new; i++) d->val_off.push_back(d->val_off.back() + lens[(size_t)i]);
+    return 0;
+}
+
+// A dictionary-typed column of all batches -> int32 codes of ONE device dictionary: per batch the D VALUES of its dictionary are
+// encoded (host buffers, their own offset / length / validity; a NULL value: table entry -1) unless the batch repeats the previous
+// batch's dictionary buffers, the code_of_index table is uploaded, and the native-width indices -- joined through the pinned ring
+// like any numeric column -- are remapped on the device into the joined codes at the batch's row offset.  Nothing per row on the
+// host, no string bytes per row over PCIe.
+static int stage_dict_col(const std::vector<std::unique_ptr<ImportedBatch>>& batches, int ci, const SortColInfo& info, int64_t total, DevSortCol* d) {
+    d->dict = vnm_strdict_create();
+    if (!d->dict) return 1;
+    VNM_TRY(stage_children(batches, ci, info.t, total, &d->num));
+    d->codes = (int32_t*)pool_alloc((size_t)(total ? total : 1) * 4);
+    d->validity = (uint8_t*)pool_alloc((size_t)(total + 7) / 8 + 8);
+    if (!d->codes || !d->validity) return 1;
+    PoolScope pool;
+    int32_t* table = nullptr;
+    int64_t table_cap = 0, row = 0;
+    const struct ArrowArray* prev = nullptr;
+    for (auto& b : batches) {
+        const int64_t len = b->arr.length;
+        if (!len) continue;
+        const struct ArrowArray* dv = b->arr.children[ci]->dictionary;
+        if (!dv || dv->n_buffers < 3) return set_error("Sort: a dictionary-typed column without its dictionary");
+        const int64_t D = dv->length;
+        const bool same = prev && prev->buffers[0] == dv->buffers[0] && prev->buffers[1] == dv->buffers[1] && prev->buffers[2] == dv->buffers[2] &&
+                          prev->offset == dv->offset && prev->length == dv->length;
+        if (same) d->dicts_skipped++;
+        else {
+            std::vector<int32_t> code_of((size_t)(D ? D : 1), -1);
+            if (D > 0) {
+                int64_t n_new = 0, new_bytes = 0;
+                const uint8_t* valid = dv->null_count != 0 ? (const uint8_t*)dv->buffers[0] : nullptr;
+                VNM_TRY(vnm_strdict_encode(d->dict, dv->buffers[1], info.wide ? 1 : 0, (const uint8_t*)dv->buffers[2], valid, dv->offset, D,
+                                           code_of.data(), &n_new, &new_bytes, nullptr));
+                VNM_TRY(fetch_new_values(d, n_new, new_bytes));
+            }
+            if (D > table_cap) {
+                pool.done(table);
+                table_cap = std::max<int64_t>(D, 2 * table_cap);
+                table = (int32_t*)pool.take((size_t)table_cap * 4);
+                if (!table) return 1;
+            }
+            if (D > 0) VNM_HIP(hipMemcpy(table, code_of.data(), (size_t)D * 4, hipMemcpyHostToDevice));
+            d->values_encoded += D;
+            prev = dv;
+        }
+        vnm_dcol view = d->num;
+        view.offset = row; view.length = len;
+        int64_t bad = 0;
+        VNM_TRY(vnm_strdict_remap_indices(&view, table, D, d->codes + row, nullptr, &bad, nullptr));
+        row += len;
+    }
+    vnm_free_column(&d->num);
+    if (total > 0) {
+        const int64_t nb = (total + 7) / 8;
+        codes_valid_bits_kernel<<<dim3((unsigned)((nb + 255) / 256)), 256, 0, nullptr>>>(d->codes, total, d->validity);
+        VNM_HIP(hipGetLastError());
+        VNM_HIP(hipStreamSynchronize(nullptr));
+    }
+    return 0;
+}
 
 // the validity bits of child `ci` of every batch laid end to end -> one device bitmap (null when the column has no NULLs)
 static int stage_validity(const std::vector<std::unique_ptr<ImportedBatch>>& batches, int ci, int64_t total, uint8_t** out) {
@@ -1107,6 +1405,7 @@ static int stage_validity(const std::vector<std::unique_ptr<ImportedBatch>>& bat
 
 static int stage_sort_col(const std::vector<std::unique_ptr<ImportedBatch>>& batches, int ci, const SortColInfo& info, int64_t total, DevSortCol* d) {
     if (info.kind == SC_NUM) return stage_children(batches, ci, info.t, total, &d->num);
+    if (info.kind == SC_DICT) return stage_dict_col(batches, ci, info, total, d);
     VNM_TRY(stage_validity(batches, ci, total, &d->validity));
     if (info.kind == SC_VAR) {
         std::vector<int64_t> offs((size_t)total + 1, 0);
@@ -1181,6 +1480,49 @@ static uint8_t* pack_bits(const uint8_t* bytes, int64_t n, int64_t* zeros) {
     return bm;
 }
 
+// the values of ids[0 .. n) (ascending) -> a utf8 / binary (wide: large_) array without NULLs: the dictionary of a result column
+static int make_string_array(struct ArrowArray* a, bool wide, const DevSortCol& d, int64_t n_ids, const int32_t* ids, int64_t n) {
+    // where each wanted id lies in the value list: the wanted ids' slots in a table by id (4 bytes per id, written in ascending
+    // order), then one pass over the list
+    std::vector<int64_t> at_of((size_t)(n ? n : 1), -1);
+    if (n > 0) {
+        std::vector<int32_t> slot_of_id((size_t)(n_ids > 0 ? n_ids : 1), -1);
+        for (int64_t i = 0; i < n; i++) {
+            if (ids[i] < 0 || ids[i] >= n_ids) return set_error("a result dictionary names id %d of %lld (internal error)", ids[i], (long long)n_ids);
+            slot_of_id[(size_t)ids[i]] = (int32_t)i;
+        }
+        for (size_t k = 0; k < d.val_ids.size(); k++) {
+            const int32_t id = d.val_ids[k];
+            if (id >= 0 && id < n_ids && slot_of_id[(size_t)id] >= 0) at_of[(size_t)slot_of_id[(size_t)id]] = (int64_t)k;
+        }
+    }
+    size_t bytes = 0;
+    for (int64_t i = 0; i < n; i++) {
+        if (at_of[(size_t)i] < 0) return set_error("a result dictionary names id %d, which no encode handed over (internal error)", ids[i]);
+        bytes += (size_t)(d.val_off[(size_t)at_of[(size_t)i] + 1] - d.val_off[(size_t)at_of[(size_t)i]]);
+    }
+    if (!wide && bytes > 0x7FFFFFFFULL) return set_error("a result dictionary holds more than 2 GiB of bytes (use the large type)");
+    memset(a, 0, sizeof(*a));
+    a->length = n;
+    a->release = release_array;
+    a->n_buffers = 3;
+    a->buffers = (const void**)calloc(3, sizeof(void*));
+    uint8_t* data = (uint8_t*)malloc(bytes ? bytes : 1);
+    int32_t* o32 = wide ? nullptr : (int32_t*)malloc((size_t)(n + 1) * 4);
+    int64_t* o64 = wide ? (int64_t*)malloc((size_t)(n + 1) * 8) : nullptr;
+    size_t at = 0;
+    for (int64_t i = 0; i < n; i++) {
+        if (wide) o64[i] = (int64_t)at; else o32[i] = (int32_t)at;
+        const int64_t from = d.val_off[(size_t)at_of[(size_t)i]], len = d.val_off[(size_t)at_of[(size_t)i] + 1] - from;
+        memcpy(data + at, d.val_bytes.data() + from, (size_t)len);
+        at += (size_t)len;
+    }
+    if (wide) o64[n] = (int64_t)at; else o32[n] = (int32_t)at;
+    a->buffers[1] = wide ? (void*)o64 : (void*)o32;
+    a->buffers[2] = data;
+    return 0;
+}
+
 // rows `idx` of a staged column -> a freshly allocated Arrow array (host buffers)
 static int take_sort_col(const DevSortCol& d, const SortColInfo& info, const int64_t* idx, int64_t n, struct ArrowArray* out) {
     const size_t n1 = (size_t)(n ? n : 1);
@@ -1198,6 +1540,23 @@ static int take_sort_col(const DevSortCol& d, const SortColInfo& info, const int
         }
         make_primitive(out, n, w, hv.data(), d.num.validity ? hb.data() : nullptr);
         return 0;
+    }
+    if (info.kind == SC_DICT) {
+        // indices of the input's width into a dictionary of exactly the values these n rows use, in id order
+        const int w = type_width(info.t.type);
+        const int64_t n_ids = vnm_strdict_ids(d.dict);
+        PoolScope pool;
+        void* dind = pool.take(n1 * w);
+        uint8_t* dvalid = (uint8_t*)pool.take((size_t)(n + 7) / 8 + 8);
+        int32_t* dused = (int32_t*)pool.take((size_t)std::max<int64_t>(std::min(n, n_ids), 1) * 4);
+        if (!dind || !dvalid || !dused) return 1;
+        int64_t nulls = 0, n_used = 0;
+        VNM_TRY(vnm_dict_take_compact(d.codes, idx, n, n_ids, info.t.type, dind, dvalid, &nulls, dused, &n_used, nullptr));
+        std::vector<int32_t> used((size_t)(n_used ? n_used : 1));
+        if (n_used) VNM_HIP(hipMemcpy(used.data(), dused, (size_t)n_used * 4, hipMemcpyDeviceToHost));
+        VNM_TRY(make_primitive_from_device(out, n, w, dind, dvalid, nulls));
+        out->dictionary = (struct ArrowArray*)calloc(1, sizeof(struct ArrowArray));
+        return make_string_array(out->dictionary, info.wide, d, n_ids, used.data(), n_used);
     }
     PoolScope pool;
     std::vector<uint8_t> hvalid;
@@ -1320,6 +1679,10 @@ int vnm_sort_op_next_stream(vnm_sort_op* h, struct ArrowArrayStream* stream) {
 //                          values, vnm_strdict_ranks_device) as an int32 key column -- NULL stays NULL (last in both directions),
 //                          equal values share a rank, so the stable sort keeps them in row order like SortIndices;
 //                          PAYLOAD: gathered on the device (lengths -> prefix sums -> bytes, vnm_take_varwidth)
+//   dictionary<intN, one of the four above>
+//                          the batch dictionaries' VALUES through one device dictionary, the indices remapped to its codes on the
+//                          device (stage_dict_col); KEY: the codes' ranks, as above; leaves in its own type, the dictionary compacted
+//                          to the values the produced rows use (vnm_dict_take_compact) -- DESIGN.md section 4.9e
 //   decimal128             KEY: (high int64, low uint64) as two keys; PAYLOAD: 16-byte gather
 //   boolean                PAYLOAD: bit gather; as a KEY it raises like the reference (vinum/core/algebra.py:191-201)
 int vnm_sort_op_sorted(vnm_sort_op* h, int64_t limit, struct ArrowArray* out, struct ArrowSchema* out_schema) {
@@ -1330,13 +1693,20 @@ int vnm_sort_op_sorted(vnm_sort_op* h, int64_t limit, struct ArrowArray* out, st
     int64_t total = 0;
     for (auto& b : h->batches) {
         if (b->sch.n_children != ncols) return set_error("Failed to create table from record batches.");
-        for (int64_t c = 0; c < ncols; c++)
-            if (strcmp(b->sch.children[c]->format, sch->children[c]->format) != 0) return set_error("Failed to create table from record batches.");
+        for (int64_t c = 0; c < ncols; c++) {
+            const struct ArrowSchema *x = b->sch.children[c], *y = sch->children[c];
+            if (strcmp(x->format, y->format) != 0 || !x->dictionary != !y->dictionary ||
+                (x->dictionary && (strcmp(x->dictionary->format, y->dictionary->format) != 0 || ((x->flags ^ y->flags) & 1))))   // (& 1: the ordered flag)
+                return set_error("Failed to create table from record batches.");
+        }
         total += b->arr.length;
     }
     std::vector<SortColInfo> info((size_t)ncols);
     for (int64_t c = 0; c < ncols; c++) {
-        info[c] = classify_sort_col(sch->children[c]->format);
+        info[c] = classify_sort_col(sch->children[c]);
+        if (info[c].kind < 0 && sch->children[c]->dictionary)
+            return set_error("Sort: column '%s' has a type the GPU path does not handle (format dictionary<%s, %s>)",
+                             sch->children[c]->name, sch->children[c]->format, sch->children[c]->dictionary->format);
         if (info[c].kind < 0) return set_error("Sort: column '%s' has a type the GPU path does not handle (format %s)",
                                                sch->children[c]->name, sch->children[c]->format);
     }
@@ -1364,6 +1734,16 @@ int vnm_sort_op_sorted(vnm_sort_op* h, int64_t limit, struct ArrowArray* out, st
             vnm_dcol kc{};
             kc.length = total; kc.validity = d.validity;
             if (info[c].kind == SC_NUM) { keys.push_back(d.num); orders.push_back(h->orders[k]); continue; }
+            if (info[c].kind == SC_DICT) {   // the codes are there already: ranks over the dictionary as SC_VAR takes them after its encode
+                int32_t* ranks = (int32_t*)scratch.take((size_t)total * 4);
+                int32_t* rank_of = (int32_t*)scratch.take((size_t)std::max<int64_t>(vnm_strdict_ids(d.dict), 1) * 4);
+                if (!ranks || !rank_of) { rc = 1; break; }
+                rc = vnm_strdict_ranks_device(d.dict, rank_of, nullptr);
+                if (!rc) rc = vnm_strdict_codes_to_ranks(d.codes, rank_of, total, ranks, nullptr);
+                kc.values = ranks; kc.type = VNM_I32;
+                keys.push_back(kc); orders.push_back(h->orders[k]);
+                continue;
+            }
             if (info[c].kind == SC_VAR) {
                 vnm_strdict* sd = vnm_strdict_create();
                 if (!sd) { rc = 1; break; }
@@ -1401,8 +1781,21 @@ int vnm_sort_op_sorted(vnm_sort_op* h, int64_t limit, struct ArrowArray* out, st
         for (int64_t c = 0; c < ncols && !rc; c++) {
             rc = take_sort_col(dev[c], info[c], idx, n_out, out->children[c]);
             if (!rc) make_schema(out_schema->children[c], info[c].format, sch->children[c]->name ? sch->children[c]->name : "", 0);
+            if (!rc && info[c].kind == SC_DICT) {
+                struct ArrowSchema* cs = out_schema->children[c];
+                cs->dictionary = (struct ArrowSchema*)calloc(1, sizeof(struct ArrowSchema));
+                make_schema(cs->dictionary, info[c].value_format, "", 0);
+                if (info[c].ordered) cs->flags |= 1;   // ARROW_FLAG_DICTIONARY_ORDERED
+            }
         }
         if (rc) { release_array(out); release_schema(out_schema); }
+    }
+    if (!rc) {
+        int64_t cols = 0, values = 0, skipped = 0;
+        for (int64_t c = 0; c < ncols; c++)
+            if (info[c].kind == SC_DICT) { cols++; values += dev[c].values_encoded; skipped += dev[c].dicts_skipped; }
+        if (cols) route_note("sort:dictionary_key_ranks", "rows=%lld columns=%lld values_encoded=%lld dictionaries_skipped=%lld",
+                             (long long)total, (long long)cols, (long long)values, (long long)skipped);
     }
     pool_free(idx);
     for (auto& d : dev) d.free_all();

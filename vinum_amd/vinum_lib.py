@@ -132,10 +132,17 @@ def _canonical_order(batch: pa.RecordBatch, key_names):
     return np.lexsort(keys[::-1])
 
 
+def _is_string_like(t) -> bool:
+    return pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t)
+
+
 def _abi_generic_key(t) -> bool:
-    """non-numeric key types vnm_agg_op_* encode below the C ABI (vnm_arrow.cpp: GenKey)"""
+    """non-numeric key types vnm_agg_op_* encode below the C ABI (vnm_arrow.cpp: GenKey); dictionary<intN, string-like> among them:
+    the library reads the `dictionary` child itself"""
     if os.environ.get("VNM_GENERIC_BELOW_ABI", "1") == "0":
         return False
+    if pa.types.is_dictionary(t):
+        return pa.types.is_integer(t.index_type) and _is_string_like(t.value_type)
     return (pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t) or
             pa.types.is_boolean(t) or (pa.types.is_decimal(t) and t.bit_width == 128))
 
@@ -267,13 +274,15 @@ class _HashAggregateBase:
             if not c or c not in schema.names or _is_numeric(schema.field(c).type):
                 continue
             t = schema.field(c).type
-            if f.func == AggFuncType.COUNT:
+            below_abi = _abi_generic_key(t) and pa.types.is_dictionary(t)
+            if f.func == AggFuncType.COUNT and below_abi:
+                self._abi_str.add(c)            # the library counts rows valid by index AND by value; an int8 stand-in knows only the index
+            elif f.func == AggFuncType.COUNT:
                 self._stand_in.add(c)
             elif f.func in (AggFuncType.MIN, AggFuncType.MAX) and device_value_type(t) is not None:
                 # round 6: vnm_agg_op_* take such columns themselves (one growing device dictionary per column, candidates per group
-                # in HBM); the shim's own route stays reachable for A / B runs -- and is the route of a DICTIONARY-TYPED column, whose
-                # `dictionary` child vnm_agg_op_* do not read
-                if os.environ.get("VNM_STRING_MINMAX_IN_SHIM") or pa.types.is_dictionary(t):
+                # in HBM), dictionary-typed ones included; the shim's own route stays reachable for A / B runs
+                if os.environ.get("VNM_STRING_MINMAX_IN_SHIM") or (pa.types.is_dictionary(t) and not below_abi):
                     str_funcs.append(f)
                 else:
                     self._abi_str.add(c)
@@ -336,7 +345,12 @@ class _HashAggregateBase:
         if not pending:
             return
         if self._stand_in or self._strmm is not None or len(pending) == 1:
-            # (stand-in / rank columns are built per batch: one joined batch, as before)
+            # (stand-in / rank columns are built per batch: one joined batch, as before -- unless a column is dictionary-typed: pyarrow
+            # cannot join batches whose dictionaries differ and hold a NULL, so those go one by one)
+            if any(pa.types.is_dictionary(f.type) for f in pending[0].schema):
+                for b in pending:
+                    self._send(b)
+                return
             joined = pa.Table.from_batches(pending).combine_chunks()
             for b in joined.to_batches():
                 self._send(b)
@@ -506,7 +520,10 @@ class GenericHashAggregate:
 
     def _flush(self) -> None:
         pending, self._pending, self._pending_rows = self._pending, [], 0
-        if pending:
+        if pending and not self._dicts:
+            for b in pending:            # nothing to encode here: the class underneath lets small batches cross the ABI as one stream
+                self._encode_and_send(b)
+        elif pending:
             for b in pa.Table.from_batches(pending).combine_chunks().to_batches():
                 self._encode_and_send(b)
 
@@ -540,7 +557,9 @@ class Sort:
     sort keys + Take of EVERY column of the table, any Arrow type.  All of it happens below the C ABI (vnm_sort_op_*), on the
     device: numeric / temporal keys and columns; string / binary KEYS as order-preserving ranks from the device string dictionary
     (NULL stays NULL and goes last in both directions, equal values share a rank, so the stable sort leaves ties in row order
-    like SortIndices); string / binary / boolean / decimal128 PAYLOAD gathered on the device; decimal128 keys as two key words.
+    like SortIndices); string / binary / boolean / decimal128 PAYLOAD gathered on the device; decimal128 keys as two key words;
+    a dictionary<intN, string / binary> KEY through the device dictionary, back in its own type with a compacted dictionary (the
+    library takes such payload as well; this class keeps a dictionary-typed column that is only payload, see next()).
     Boolean sort keys raise like the reference's SortOperator (vinum/core/algebra.py:191-201: Arrow 3.0 cannot sort them).
     A column of a type the library does not take (lists, structs, ...) that is NOT a sort key stays with this wrapper: an
     int64 row-id column rides along and the column is gathered with Arrow `take` by the sorted row ids."""
@@ -548,8 +567,9 @@ class Sort:
     @staticmethod
     def _below_the_abi(t) -> bool:
         from .device import is_supported
-        return (is_supported(t) or pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or
-                pa.types.is_large_binary(t) or pa.types.is_boolean(t) or (pa.types.is_decimal(t) and t.bit_width == 128))
+        if pa.types.is_dictionary(t):       # dictionary<intN, string-like>: key or payload (vnm_arrow.cpp: SC_DICT)
+            return pa.types.is_integer(t.index_type) and _is_string_like(t.value_type)
+        return (is_supported(t) or _is_string_like(t) or pa.types.is_boolean(t) or (pa.types.is_decimal(t) and t.bit_width == 128))
 
     def __init__(self, sort_cols, sort_order):
         self._cols, self._orders = list(sort_cols), [int(o) for o in sort_order]
@@ -572,7 +592,10 @@ class Sort:
         # default is 10 000 rows) are kept here and cross the boundary joined, as in the aggregates.
         if self._carried is None:
             self._schema_order = batch.schema.names
-            self._carried = [f.name for f in batch.schema if not self._below_the_abi(f.type)]
+            # (a dictionary-typed column that is only payload keeps riding here: Arrow `take` hands the input's dictionary back as
+            # it is, the library one compacted to the values the produced rows use)
+            self._carried = [f.name for f in batch.schema if not self._below_the_abi(f.type) or
+                             (pa.types.is_dictionary(f.type) and f.name not in self._cols)]
             for name in self._carried:
                 if name in self._cols:
                     raise RuntimeError(f"Failed to sort table. (ORDER BY a column of type {batch.schema.field(name).type})")
