@@ -542,3 +542,77 @@ def test_under_the_pool_guard(monkeypatch):
     finally:
         lib.vnm_pool_set_guard(0)
         lib.vnm_pool_guard_reset()
+
+
+# ---- 6. one reader of dictionary-typed columns under both operators; one batch routine under both batch paths ---------------------
+_BOTH_OPERATORS = """
+import json
+import pyarrow as pa
+from vinum_amd import _lib as L
+from tests.dictsort_util import sort_table
+from tests.test_gpu_dictsort import _raw_aggregate, _raw_sort
+batches, _ = sort_table(pa.string(), pa.int8())
+s = _raw_sort(batches, ["c"], [0])
+a = _raw_aggregate(L.SINGLE_NUMERICAL, ["c"], ["c"], [(L.COUNT_STAR, "", "n")], batches)
+print(json.dumps({"rows": sum(b.num_rows for b in batches), "sorted": s.column("c").cast(pa.string()).to_pylist(),
+                  "keys": a.column("c").cast(pa.string()).to_pylist(), "n": a.column("n").to_pylist()}))
+"""
+
+
+def test_both_operators_read_a_dictionary_column_the_same_way():
+    """The four batches of sort_table (misaligned lengths, a sliced first batch, a NULL value in every dictionary, the last batch
+    repeating its neighbour's dictionary buffers) once through vnm_sort_op_* and once through vnm_agg_op_* as the key of COUNT(*).
+    The aggregate's note is followed by the device operator's, so both notes are read from the trace of a fresh process
+    (VNM_AGG_TRACE is read once per process)."""
+    import json
+    import os
+    import re
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, "-c", _BOTH_OPERATORS], cwd=root, capture_output=True, text=True, timeout=300,
+                       env={**os.environ, "VNM_AGG_TRACE": "1"})
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads(p.stdout.strip().splitlines()[-1])
+    fields = lambda name: [dict(kv.split("=") for kv in line.split(": ", 1)[1].split())      # noqa: E731
+                           for line in p.stderr.splitlines() if re.match(r"\[route\] " + re.escape(name) + ":", line)]
+    sort_notes, agg_notes = fields("sort:dictionary_key_ranks"), fields("keys:dictionary_child")
+    assert len(sort_notes) == 1, p.stderr[-2000:]
+    assert len(agg_notes) == 1, p.stderr[-2000:]                      # four batches below the coalescing threshold: one flush
+    for f in ("rows", "values_encoded", "dictionaries_skipped"):
+        assert sort_notes[0][f] == agg_notes[0][f], (f, sort_notes, agg_notes)
+    assert agg_notes[0]["dictionaries_skipped"] == "1" and int(agg_notes[0]["rows"]) == out["rows"]
+    assert int(agg_notes[0]["values_encoded"]) > 0
+    assert len(out["keys"]) == len(set(out["keys"])) and None in out["keys"]
+    assert set(out["keys"]) == set(out["sorted"])
+    assert sum(out["n"]) == out["rows"] == len(out["sorted"])
+
+
+def test_a_large_batch_and_the_same_rows_in_small_batches_agree():
+    """2^20 + 3 rows, just over the coalescing threshold's default: as one batch they are staged straight from their own buffers
+    (vnm_agg_op_next's direct path), cut into 7 uneven batches they wait and go as one flush.  Same groups, bit for bit."""
+    from vinum_amd import _lib as L
+    n, off = (1 << 20) + 3, 5
+    rng = np.random.default_rng(77)
+    m = n + off
+    k = pa.array(rng.integers(-40, 40, m).astype(np.int64), mask=rng.random(m) < 0.03)
+    words = np.array([f"w{i:02d}é" for i in range(23)] + [""], dtype=object)
+    s = pa.array(words[rng.integers(0, len(words), m)], pa.string(), mask=rng.random(m) < 0.04)
+    v = pa.array(rng.standard_normal(m) * 1e3, mask=rng.random(m) < 0.05)
+    whole = pa.RecordBatch.from_arrays([k, s, v], names=["k", "s", "v"]).slice(off, n)
+    assert whole.num_rows == n and whole.column("v").offset == off
+    cuts = [0, 1, 100_003, 100_003, 377_777, 900_001, n - 7, n]         # (7 batches, one of them empty, all below 2^20 rows)
+    small = [whole.slice(a, b - a) for a, b in zip(cuts, cuts[1:])]
+    funcs = [(L.SUM, "v", "sum"), (L.COUNT, "v", "count"), (L.MIN, "v", "min"), (L.MAX, "v", "max")]
+    got = [_raw_aggregate(L.MULTI_NUMERICAL, ["k", "s"], ["k", "s"], funcs, bs) for bs in ([whole], small)]
+    assert got[0].schema == got[1].schema
+
+    def rows(r):
+        keys = list(zip(r.column("k").to_pylist(), r.column("s").to_pylist()))
+        cols = [np.asarray(r.column(c).to_numpy(zero_copy_only=False)).view(np.uint64 if c != "count" else np.int64).tolist() for c in ("sum", "min", "max", "count")]
+        assert all(r.column(c).null_count == 0 for c in ("sum", "min", "max", "count"))
+        return sorted(zip(keys, *cols), key=lambda x: (x[0][0] is None, x[0][0] or 0, x[0][1] is None, x[0][1] or ""))
+
+    a, b = rows(got[0]), rows(got[1])
+    assert len(a) == len({x[0] for x in a}) > 81 * 20 and any(x[0][0] is None for x in a) and any(x[0][1] is None for x in a)
+    assert a == b

@@ -137,7 +137,7 @@ def _is_string_like(t) -> bool:
 
 
 def _abi_generic_key(t) -> bool:
-    """non-numeric key types vnm_agg_op_* encode below the C ABI (vnm_arrow.cpp: GenKey); dictionary<intN, string-like> among them:
+    """non-numeric key types vnm_agg_op_* encode below the C ABI (vnm_agg_op.cpp: GenKey over vnm_arrow_host.hpp's ColDesc); dictionary<intN, string-like> among them:
     the library reads the `dictionary` child itself"""
     if os.environ.get("VNM_GENERIC_BELOW_ABI", "1") == "0":
         return False
@@ -567,7 +567,7 @@ class Sort:
     @staticmethod
     def _below_the_abi(t) -> bool:
         from .device import is_supported
-        if pa.types.is_dictionary(t):       # dictionary<intN, string-like>: key or payload (vnm_arrow.cpp: SC_DICT)
+        if pa.types.is_dictionary(t):       # dictionary<intN, string-like>: key or payload (vnm_sort_op.cpp over vnm_arrow.cpp: COL_DICT)
             return pa.types.is_integer(t.index_type) and _is_string_like(t.value_type)
         return (is_supported(t) or _is_string_like(t) or pa.types.is_boolean(t) or (pa.types.is_decimal(t) and t.bit_width == 128))
 
