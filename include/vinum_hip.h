@@ -451,6 +451,10 @@ typedef struct vnm_expr_ins {
     double imm_f;
     int64_t imm_i;
 } vnm_expr_ins;
+/* what one program may hold (vnm_project counts its implied final STORE as an instruction; vnm_agg_set_input_expr takes the same) */
+#define VNM_PROJECT_MAX_INS 64
+#define VNM_PROJECT_MAX_COLS 16
+#define VNM_PROJECT_MAX_OUT 16
 /* out_type (returned): the vnm_type of the result, values stored with that type's width (a buffer of length*8 bytes
  * always suffices), or VNM_MASK_U8 (predicate) with out_values = length bytes (BETWEEN / IN are compiled to AND / OR
  * chains by the caller). */

@@ -5,6 +5,7 @@ Exact functions (abs, sqrt, the casts, integer power, float16 sqrt) must match N
 the GPU -- neither is a value).  The transcendentals are checked against a correctly rounded reference (math.* in float64,
 rounded to the result type) within the OCML error bounds: float64 sin / cos / log / log2 / log10 <= 2 ULP, tan / pow
 <= 3 ULP; float32 <= 2 / <= 4 ULP; float16 <= 1 ULP.  Budget: a few seconds in total."""
+import ctypes
 import math
 
 import numpy as np
@@ -17,6 +18,7 @@ torch = pytest.importorskip("torch")
 if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
+from vinum_amd import _lib as L  # noqa: E402
 from vinum_amd import ops  # noqa: E402
 from vinum_amd import planner as P  # noqa: E402
 from vinum_amd.device import DeviceColumn  # noqa: E402
@@ -245,3 +247,111 @@ def test_issue_queries_through_the_planner():
     cnt = [int(((city == c) & (g == x)).sum()) for c, x in keys]
     assert got.column(2).to_pylist() == cnt
     assert got.column(3).to_pylist() == [float(tax[(city == c) & (g == x)].min()) for c, x in keys]
+
+
+# ---- every kernel instantiation by name, the programs beyond 64 KB of LDS, the power flag: one tile and a tail ---------------------
+PN = 1027            # one full tile of 1024 rows plus a three-row tail: the 16-byte path and the guarded path of push and store
+PRNG = np.random.default_rng(17)
+PX, PY = PRNG.standard_normal(PN + 1) * 10.0, PRNG.standard_normal(PN + 1) * 3.0
+PK = PRNG.integers(-1000, 1000, PN + 1)
+PCODES = PRNG.integers(-2, 10, PN + 1).astype(np.int32)           # negative codes and codes past both tables among them
+PCODE_NULL = PRNG.random(PN + 1) < 0.2
+TABLE_U8 = np.array([1, 0, 2, 0, 255], np.uint8)
+TABLE_I32 = np.array([5, -7, 0, 2 ** 31 - 1, -2 ** 31, 11, 3], np.int32)
+SPANS = ["project_kernel", "project_kernel_exact_fn", "project_kernel_math", "project_kernel_lookup", "project_kernel_lookup_i32"]
+
+
+@pytest.fixture(scope="module")
+def pdev():
+    d = {"x": DeviceColumn.from_numpy(PX), "y": DeviceColumn.from_numpy(PY), "k": DeviceColumn.from_numpy(PK),
+         "c": DeviceColumn.from_arrow(pa.array(PCODES, mask=PCODE_NULL))}
+    return d, {"t8": DeviceColumn.from_numpy(TABLE_U8), "t32": DeviceColumn.from_numpy(TABLE_I32)}
+
+
+def _prun(exprs, pdev, off):
+    """the rows [off, off + PN) of the row columns: Arrow offset 1 turns the 16-byte push off"""
+    rows, tables = pdev
+    names = {c for e in exprs for c in ops.columns_of(e)}
+    cols = {c: rows[c].slice(off, PN) if c in rows else tables[c] for c in names}
+    return [o.to_numpy() for o in ops.project_many(exprs, cols, length=PN)]
+
+
+def _span_counts():
+    out = {}
+    for name in SPANS:
+        ms, count = ctypes.c_double(0), ctypes.c_int64(0)
+        L.lib().vnm_profile_query(name.encode(), ctypes.byref(ms), ctypes.byref(count))
+        out[name] = count.value
+    return out
+
+
+@pytest.mark.parametrize("off", [0, 1])
+@pytest.mark.parametrize("lookup", [None, "lookup", "lookup_i32"])
+@pytest.mark.parametrize("fn", ["plain", "abs", "sin"])
+def test_each_instantiation_runs_under_its_own_name(pdev, fn, lookup, off):
+    x, y = PX[off:off + PN], PY[off:off + PN]
+    exprs = [{"plain": ("add", "x", "y"), "abs": ("abs", ("sub", "x", "y")), "sin": ("sin", "x")}[fn]]
+    if lookup:
+        exprs.append((lookup, "c", "t8" if lookup == "lookup" else "t32"))
+    name = {"lookup": "project_kernel_lookup", "lookup_i32": "project_kernel_lookup_i32"}.get(
+        lookup, {"plain": "project_kernel", "abs": "project_kernel_exact_fn", "sin": "project_kernel_math"}[fn])
+    L.lib().vnm_set_profiling(1)
+    try:
+        before = _span_counts()
+        got = _prun(exprs, pdev, off)
+        after = _span_counts()
+    finally:
+        L.lib().vnm_set_profiling(0)
+    assert after == {n: before[n] + (1 if n == name else 0) for n in SPANS}
+    if fn == "sin":
+        assert got[0].dtype == np.float64
+        ref = np.array([math.sin(v) for v in x])
+        assert _ulps(got[0], ref, np.float64).max() <= BOUND[np.dtype(np.float64)][None]
+    else:
+        _same_bits(got[0], x + y if fn == "plain" else np.absolute(x - y))
+    if lookup:
+        codes, null = PCODES[off:off + PN], PCODE_NULL[off:off + PN]
+        table = TABLE_U8 if lookup == "lookup" else TABLE_I32
+        hit = ~null & (codes >= 0) & (codes < len(table))
+        entry = table[np.where(hit, codes, 0)]
+        if lookup == "lookup":
+            assert got[1].dtype == np.uint8 and np.array_equal(got[1], (hit & (entry != 0)).astype(np.uint8))
+        else:
+            _same_bits(got[1], np.where(hit, entry.astype(np.float64), np.nan))
+
+
+def _right_nested(names, innermost=None):
+    e = innermost or names[-1]
+    for n in reversed(names[:-1]):
+        e = ("add", n, e)
+    return e
+
+
+@pytest.mark.parametrize("off", [0, 1])
+@pytest.mark.parametrize("depth,with_abs", [(10, False), (9, True), (12, False)])
+def test_deep_programs_beyond_64k_of_lds(pdev, depth, with_abs, off):
+    """a right-nested sum holds every operand on the stack at once: depth 10 (9 with a built-in, which stages the top through one
+    more level) is the first whose LDS passes 64 KB, 12 the deepest a program may be"""
+    names = [("x", "y", "k")[i % 3] for i in range(depth)]
+    (got,) = _prun([_right_nested(names, ("abs", names[-1]) if with_abs else None)], pdev, off)
+    arrays = {"x": PX[off:off + PN], "y": PY[off:off + PN], "k": PK[off:off + PN]}
+    want = np.absolute(arrays[names[-1]]) if with_abs else arrays[names[-1]]
+    for n in reversed(names[:-1]):
+        want = arrays[n] + want
+    _same_bits(got, want)
+
+
+@pytest.mark.parametrize("off", [0, 1])
+def test_integer_power_with_an_exponent_column(pdev, off):
+    rows, _ = pdev
+    base = PK[off:off + PN]
+    e = np.abs(PK) % 9
+    cols = {"k": rows["k"].slice(off, PN), "e": DeviceColumn.from_numpy(e).slice(off, PN)}
+    (got,) = ops.project_many([("power", "k", "e")], cols, length=PN)
+    _same_bits(got.to_numpy(), np.power(base, e[off:off + PN]))
+    e[off + PN - 2] = -1          # in the tail, past the full tile
+    cols["e"] = DeviceColumn.from_numpy(e).slice(off, PN)
+    with pytest.raises(ValueError, match="Integers to negative integer powers are not allowed."):
+        np.power(base, e[off:off + PN])
+    with pytest.raises(ValueError, match="Integers to negative integer powers are not allowed."):
+        ops.project_many([("power", "k", "e")], cols, length=PN)

@@ -45,6 +45,7 @@ STRDICT_REMAP_TILE = 2048                                # vnm_strdict_remap_ind
 DICT_COMPACT_TILE, DICT_COMPACT_LDS_IDS = 2048, 8192    # vnm_dict_take_compact: rows per workgroup, the largest table of the LDS form
 IN_DOM_I64, IN_DOM_U64, IN_DOM_F64 = range(3)           # vnm_in_set compare domains
 IN_ROUTES = ("in_set:bitmap_lds", "in_set:bitmap_global", "in_set:sorted_lds", "in_set:sorted_global")   # enum vnm_in_route
+PJ_MAX_INS, PJ_MAX_COLS, PJ_MAX_OUT = 64, 16, 16         # VNM_PROJECT_MAX_*: what one projection program may hold, its final STORE included
 MASK_U8 = 100
 OUT_F16 = 101
 OUT_U64, OUT_I64, OUT_F64, OUT_F32, OUT_DEC128, OUT_I32 = range(6)

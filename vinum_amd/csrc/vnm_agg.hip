@@ -1285,7 +1285,7 @@ int vnm_agg_set_input_expr(vnm_agg* h, int func_idx, int n_ins, const vnm_expr_i
     if (!h || !program) return set_error("vnm_agg_set_input_expr: null argument");
     if (func_idx < 0 || func_idx >= h->n_funcs || h->func_col[func_idx] < 0) return set_error("vnm_agg_set_input_expr: function %d has no input column", func_idx);
     if (h->expr_col >= 0 && h->expr_col != h->func_col[func_idx]) return set_error("vnm_agg_set_input_expr: one expression input per operator (project the others first)");
-    if (n_ins < 1 || n_ins > 64 || n_cols < 1 || n_cols > 16) return set_error("vnm_agg_set_input_expr: bad program size");
+    if (n_ins < 1 || n_ins > VNM_PROJECT_MAX_INS || n_cols < 1 || n_cols > VNM_PROJECT_MAX_COLS) return set_error("vnm_agg_set_input_expr: bad program size");
     if (h->c_in_types[func_idx] != VNM_F64 || h->widen_in[func_idx]) return set_error("vnm_agg_set_input_expr: declare the function's input type as float64 (the expression's result type)");
     h->expr_col = h->func_col[func_idx];
     h->expr_prog.assign(program, program + n_ins);

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/vinum_hip.h"
+#include "vnm_types.hpp"
 
 namespace vnm {
 
@@ -119,16 +120,7 @@ void route_note(const char* route, const char* reason_fmt = nullptr, ...);
 // ---------------------------------------------------------------------------------------------
 // device-side column access
 // ---------------------------------------------------------------------------------------------
-__host__ __device__ inline int type_width(int t) {
-    switch (t) {
-        case VNM_I8: case VNM_U8: return 1;
-        case VNM_I16: case VNM_U16: return 2;
-        case VNM_I32: case VNM_U32: case VNM_F32: return 4;
-        default: return 8;
-    }
-}
-__host__ __device__ inline bool type_is_float(int t) { return t == VNM_F32 || t == VNM_F64; }
-__host__ __device__ inline bool type_is_unsigned(int t) { return t >= VNM_U8 && t <= VNM_U64; }
+// (type_width, type_is_float, type_is_unsigned: vnm_types.hpp)
 
 // validity test, array_iterators.h:27-29: nulls_ptr && !GetBit(nulls_ptr, offset + i)
 __device__ __forceinline__ bool col_valid(const vnm_dcol& c, int64_t i) {

@@ -46,33 +46,17 @@
 // applies as it stands (compare False, `!=` True).  Programs with this opcode run the LK = 2 instantiation (both lookups); LK = 0 / 1
 // programs run the code they ran before.
 #include "vnm_common.hpp"
+#include "vnm_project_type.hpp"   // the limits, PIns and the host's program typer
 
 namespace vnm {
 
-constexpr int PJ_MAX_INS = 64;
-constexpr int PJ_MAX_COLS = 16;
-constexpr int PJ_MAX_OUT = 16;
-constexpr int PJ_STACK = 12;
 constexpr int PJ_BLOCK = 256;
-constexpr int PJ_NOP = -1;   // an instruction folded away by the host (unary operator on a literal)
 #ifndef VNM_PJ_R
 #define VNM_PJ_R 4
 #endif
 constexpr int PJ_R = VNM_PJ_R;                 // rows per lane per tile: one opcode decode serves PJ_R rows
 constexpr int PJ_TILE = PJ_BLOCK * PJ_R;
 static_assert(PJ_R % 2 == 0, "a lane owns pairs of adjacent rows");
-
-struct PIns {
-    int op;
-    int arg;
-    int is_f;    // result (or pushed value) is held as float64 bits
-    int cvt_a;   // convert operand a (deeper) to float64 first: 1 from int64, 2 from uint64
-    int cvt_b;   // ... operand b (top)
-    int nar;     // bring the result back into this vnm_type's range (-1: it already is)
-    int cmp;     // comparisons: 0 int64, 1 float64, 2 uint64, 3 a is uint64 / b signed, 4 a signed / b is uint64
-    double imm_f;
-    int64_t imm_i;
-};
 
 struct ProjArgs {
     int n_ins;
@@ -456,389 +440,83 @@ __global__ __launch_bounds__(PJ_BLOCK) void project_kernel(ProjArgs a) {
 
 using namespace vnm;
 
-// np.result_type of two column types (NumPy 2 / NEP 50; probed table in profiles/numpy_promotion_r02.txt)
-static int pj_promote(int a, int b) {
-    if (a == b) return a;
-    const bool fa = type_is_float(a), fb = type_is_float(b);
-    if (fa && fb) return VNM_F64;
-    if (fa || fb) {
-        const int f = fa ? a : b, i = fa ? b : a;
-        if (f == VNM_F64) return VNM_F64;
-        return type_width(i) <= 2 ? VNM_F32 : VNM_F64;
-    }
-    const bool ua = type_is_unsigned(a), ub = type_is_unsigned(b);
-    const int wa = type_width(a), wb = type_width(b);
-    if (ua == ub) return wa >= wb ? a : b;
-    const int u = ua ? a : b, sg = ua ? b : a;
-    if (type_width(u) < type_width(sg)) return sg;
-    switch (u) {
-        case VNM_U8: return VNM_I16;
-        case VNM_U16: return VNM_I32;
-        case VNM_U32: return VNM_I64;
-        default: return VNM_F64;   // uint64 with a signed type
-    }
-}
-constexpr int PJ_T_F16 = 13;   // host-side type id of a float16 value (after the bool mask and the weak literals)
-// the same with float16 values (results of sqrt / sin / ... over 8-bit integers): float16 survives 8-bit integers and
-// float16, float32 16-bit integers and float32, everything else goes to float64
-static int pj_promote_h(int a, int b) {
-    if (a != PJ_T_F16 && b != PJ_T_F16) return pj_promote(a, b);
-    const int o = a == PJ_T_F16 ? b : a;
-    if (o == PJ_T_F16) return PJ_T_F16;
-    if (type_is_float(o)) return o;
-    return type_width(o) == 1 ? PJ_T_F16 : type_width(o) == 2 ? VNM_F32 : VNM_F64;
-}
-static const char* pj_type_name(int t) {
-    static const char* n[] = {"int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64", "float32", "float64"};
-    return t >= 0 && t < 10 ? n[t] : "?";
-}
-static bool pj_int_fits(int t, int64_t v) {
-    switch (t) {
-        case VNM_I8: return v >= -128 && v <= 127;
-        case VNM_I16: return v >= -32768 && v <= 32767;
-        case VNM_I32: return v >= INT32_MIN && v <= INT32_MAX;
-        case VNM_U8: return v >= 0 && v <= 255;
-        case VNM_U16: return v >= 0 && v <= 65535;
-        case VNM_U32: return v >= 0 && v <= (int64_t)UINT32_MAX;
-        case VNM_U64: return v >= 0;
-        default: return true;
-    }
+// The nine instantiations, [lookup level][math level]: the entry's function is what gets the raised LDS limit AND what is launched;
+// its name is what the profile shows (the lookup level names a program before its math level does).
+using ProjectKernel = void (*)(ProjArgs);
+struct ProjectKernelEntry {
+    ProjectKernel fn;
+    const char* timer;
+};
+// Not needed for correctness: the table below would instantiate the same nine kernels by naming them.  Spelled out only to keep them in
+// the code object in the order they have always had (same code per kernel either way), so that its assembly compares equal line by
+// line with the one before the host side was split.
+template __global__ void vnm::project_kernel<2, 2>(ProjArgs); template __global__ void vnm::project_kernel<1, 2>(ProjArgs); template __global__ void vnm::project_kernel<0, 2>(ProjArgs);
+template __global__ void vnm::project_kernel<2, 1>(ProjArgs); template __global__ void vnm::project_kernel<1, 1>(ProjArgs); template __global__ void vnm::project_kernel<0, 1>(ProjArgs);
+template __global__ void vnm::project_kernel<2, 0>(ProjArgs); template __global__ void vnm::project_kernel<1, 0>(ProjArgs); template __global__ void vnm::project_kernel<0, 0>(ProjArgs);
+static const ProjectKernelEntry PJ_KERNELS[3][3] = {
+    {{project_kernel<0, 0>, "project_kernel"}, {project_kernel<1, 0>, "project_kernel_exact_fn"}, {project_kernel<2, 0>, "project_kernel_math"}},
+    {{project_kernel<0, 1>, "project_kernel_lookup"}, {project_kernel<1, 1>, "project_kernel_lookup"}, {project_kernel<2, 1>, "project_kernel_lookup"}},
+    {{project_kernel<0, 2>, "project_kernel_lookup_i32"}, {project_kernel<1, 2>, "project_kernel_lookup_i32"}, {project_kernel<2, 2>, "project_kernel_lookup_i32"}},
+};
+
+// ONE workgroup per tile: a workgroup loads, computes and stores with nothing of its own to overlap, so it is the
+// dispatcher that keeps the memory system busy (three expressions over 1e9 rows: 8 workgroups per CU looping over tiles
+// 11.15 ms, 32 per CU 10.2, 128 per CU 9.7, one per tile 9.27 = 5.2 TB/s)
+static int project_grid(int64_t length) {
+    const int64_t grid64 = getenv("VNM_PJ_GRID") ? (int64_t)device_info().num_cus * atoi(getenv("VNM_PJ_GRID")) : (int64_t)1 << 30;
+    const int64_t need = (length + PJ_TILE - 1) / PJ_TILE;
+    return (int)grid64 > need ? (int)need : (int)grid64;
 }
 
-// Abstract interpretation of the program (a type per stack slot: the ten numeric types with NumPy's promotion, "weak"
-// Python literals, bool masks), launch.  `single`: the program is one expression without a STORE; out index 0 is implied.
-static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, const vnm_dcol* cols, int64_t length,
-                        int n_out, void** out_values, int* out_types, bool single, void* stream) {
-    if (n_ins <= 0 || n_ins + (single ? 1 : 0) > PJ_MAX_INS)
-        return set_error("vnm_project: program must have 1..%d instructions", PJ_MAX_INS - (single ? 1 : 0));
-    if (n_cols < 0 || n_cols > PJ_MAX_COLS) return set_error("vnm_project: at most %d input columns", PJ_MAX_COLS);
-    if (n_out < 1 || n_out > PJ_MAX_OUT) return set_error("vnm_project: 1..%d outputs per call", PJ_MAX_OUT);
-    ProjArgs a{};
-    a.n_cols = n_cols;
-    a.length = length;
-    // the lookup tables of VNM_EX_LOOKUP_U8 / _I32 are columns of their own length (one entry per dictionary id); every other
-    // column is a row column of the batch
-    bool is_table[PJ_MAX_COLS] = {};
-    int table_type[PJ_MAX_COLS];
-    int lookup = 0;
-    for (int i = 0; i < n_ins; i++) {
-        if (program[i].op != VNM_EX_LOOKUP_U8 && program[i].op != VNM_EX_LOOKUP_I32) continue;
-        const int64_t t = program[i].imm_i;
-        const int want = program[i].op == VNM_EX_LOOKUP_U8 ? VNM_U8 : VNM_I32;
-        if (t < 0 || t >= n_cols) return set_error("vnm_project: lookup table index %lld out of range", (long long)t);
-        if (program[i].arg == t) return set_error("vnm_project: a lookup reads its codes from its own table");
-        if (is_table[t] && table_type[t] != want) return set_error("vnm_project: lookup table %lld is read as uint8 and as int32", (long long)t);
-        is_table[t] = true;
-        table_type[t] = want;
-        lookup = std::max(lookup, want == VNM_U8 ? 1 : 2);
-    }
-    for (int c = 0; c < n_cols; c++) {
-        if (cols[c].type < VNM_I8 || cols[c].type > VNM_F64) return set_error("vnm_project: column %d: unsupported type %d", c, cols[c].type);
-        if (is_table[c]) {
-            if (cols[c].type != table_type[c] || cols[c].validity || cols[c].offset < 0 || cols[c].length < 0)
-                return set_error("vnm_project: lookup table %d must be %s column without NULLs", c, table_type[c] == VNM_U8 ? "a uint8" : "an int32");
-        } else if (cols[c].length != length) return set_error("Select expressions have unequal sizes. This is not permitted.");
-        a.cols[c] = cols[c];
-    }
-    enum { T_B = 10, T_WI = 11, T_WF = 12 };   // 0..9 = vnm_type; bool mask; weak Python int / float literal
-    int ty[PJ_STACK];
-    int lit[PJ_STACK];   // the instruction that pushed a weak literal still unchanged on the stack (-1: none)
-    int sp = 0, depth = 1;
-    bool stored[PJ_MAX_OUT] = {};
-    const int total = n_ins + (single ? 1 : 0);
-    auto is_num = [&](int t) { return t != T_B; };
-    auto is_float_t = [&](int t) { return t == PJ_T_F16 || (t < 10 && type_is_float(t)); };
-    auto held_f = [&](int t) { return t == T_WF || is_float_t(t); };                        // held as float64 bits
-    auto cvt_of = [&](int t) { return held_f(t) ? 0 : (t == VNM_U64 ? 2 : 1); };           // how to turn the held word into a double
-    // a weak literal meets a float32 column: NumPy casts the scalar to float32 first
-    auto round_lit_f32 = [&](int slot) {
-        if (lit[slot] < 0) return;
-        PIns& p = a.ins[lit[slot]];
-        if (p.op == VNM_EX_CONST_I) { p.op = VNM_EX_CONST_F; p.imm_f = (double)(float)p.imm_i; p.is_f = 1; }
-        else p.imm_f = (double)(float)p.imm_f;
-    };
-    // ... a float16 value: the scalar is cast to float16 (npy_double_to_half: one rounding, straight from double)
-    auto round_lit_f16 = [&](int slot) {
-        if (lit[slot] < 0) return;
-        PIns& p = a.ins[lit[slot]];
-        if (p.op == VNM_EX_CONST_I) { p.op = VNM_EX_CONST_F; p.imm_f = (double)(_Float16)(double)p.imm_i; p.is_f = 1; }
-        else p.imm_f = (double)(_Float16)p.imm_f;
-    };
-    auto round_lit = [&](int slot, int t) {
-        if (t == VNM_F32) round_lit_f32(slot);
-        else if (t == PJ_T_F16) round_lit_f16(slot);
-    };
-    int cst[PJ_STACK];   // the CONST instruction that pushed the slot's value, weak or strong, still unchanged (-1: none)
-    int math = 0;   // the kernel instantiation: 1 exact built-ins / float16 values, 2 transcendentals or power
-    bool pow_check = false;
-    for (int i = 0; i < total; i++) {
-        vnm_expr_ins in;
-        if (i < n_ins) in = program[i];
-        else { in = vnm_expr_ins{}; in.op = VNM_EX_STORE; in.arg = 0; }
-        PIns& o = a.ins[i];
-        o.op = in.op;
-        o.arg = in.arg;
-        o.imm_f = in.imm_f;
-        o.imm_i = in.imm_i;
-        o.cvt_a = o.cvt_b = 0;
-        o.is_f = 0;
-        o.nar = -1;
-        o.cmp = 0;
-        switch (in.op) {
-            case VNM_EX_COL: {
-                if (in.arg < 0 || in.arg >= n_cols) return set_error("vnm_project: column index %d out of range", in.arg);
-                if (is_table[in.arg]) return set_error("vnm_project: column %d is a lookup table, not a row column", in.arg);
-                if (sp >= PJ_STACK) return set_error("vnm_project: expression too deep");
-                const int ct = cols[in.arg].type;
-                int t = ct;
-                if (cols[in.arg].validity != nullptr && !type_is_float(ct)) t = VNM_F64;   // NULL -> NaN needs a float (record_batch.py:112-118)
-                o.is_f = type_is_float(t);
-                lit[sp] = -1;
-                cst[sp] = -1;
-                ty[sp++] = t;
-                break;
-            }
-            case VNM_EX_CONST_F:
-            case VNM_EX_CONST_I:
-                if (sp >= PJ_STACK) return set_error("vnm_project: expression too deep");
-                o.is_f = in.op == VNM_EX_CONST_F;
-                // arg = 1: a STRONG constant (an element of the array np.isin builds from an IN list): int64 / float64
-                lit[sp] = in.arg == 1 ? -1 : i;
-                cst[sp] = i;
-                ty[sp++] = in.arg == 1 ? (o.is_f ? VNM_F64 : VNM_I64) : (o.is_f ? T_WF : T_WI);
-                o.arg = 0;
-                break;
-            case VNM_EX_LOOKUP_U8:
-            case VNM_EX_LOOKUP_I32:
-            case VNM_EX_IS_NULL:
-            case VNM_EX_IS_NOT_NULL:
-                if (in.arg < 0 || in.arg >= n_cols) return set_error("vnm_project: column index %d out of range", in.arg);
-                if (is_table[in.arg]) return set_error("vnm_project: column %d is a lookup table, not a row column", in.arg);
-                if ((in.op == VNM_EX_LOOKUP_U8 || in.op == VNM_EX_LOOKUP_I32) && cols[in.arg].type != VNM_I32)
-                    return set_error("vnm_project: a lookup reads int32 dictionary codes (column %d)", in.arg);
-                if (sp >= PJ_STACK) return set_error("vnm_project: expression too deep");
-                lit[sp] = -1;
-                cst[sp] = -1;
-                o.is_f = in.op == VNM_EX_LOOKUP_I32;                      // an int32 value that can be NULL: float64, NaN
-                ty[sp++] = in.op == VNM_EX_LOOKUP_I32 ? (int)VNM_F64 : (int)T_B;
-                break;
-            case VNM_EX_NEG:
-            case VNM_EX_BNOT: {
-                if (sp < 1) return set_error("vnm_project: malformed program (stack underflow)");
-                const int t = ty[sp - 1];
-                if (t == T_B) return set_error("vnm_project: arithmetic on a boolean mask is not supported");
-                if (in.op == VNM_EX_BNOT && held_f(t)) return set_error("ufunc 'invert' not supported for float inputs");
-                if (t >= T_WI && lit[sp - 1] >= 0) {
-                    // a Python literal: folded here.  `~5` stays a (weak) Python int; np.negative(5) RETURNS a NumPy scalar,
-                    // np.int64 / np.float64, which is a strong type from then on
-                    PIns& c = a.ins[lit[sp - 1]];
-                    if (in.op == VNM_EX_BNOT) c.imm_i = ~c.imm_i;
-                    else if (c.op == VNM_EX_CONST_I) { c.imm_i = (int64_t)(0 - (uint64_t)c.imm_i); ty[sp - 1] = VNM_I64; lit[sp - 1] = -1; }
-                    else { c.imm_f = -c.imm_f; ty[sp - 1] = VNM_F64; lit[sp - 1] = -1; }
-                    o.op = PJ_NOP;
-                    break;
-                }
-                o.is_f = held_f(t);
-                if (t < 10 && !type_is_float(t) && type_width(t) < 8) o.nar = t;
-                lit[sp - 1] = -1;
-                cst[sp - 1] = -1;
-                break;
-            }
-            case VNM_EX_ABS: case VNM_EX_SQRT: case VNM_EX_SIN: case VNM_EX_COS: case VNM_EX_TAN: case VNM_EX_LOG:
-            case VNM_EX_LOG2: case VNM_EX_LOG10: case VNM_EX_TO_F64: case VNM_EX_TO_I64: case VNM_EX_TO_BOOL: {
-                if (sp < 1) return set_error("vnm_project: malformed program (stack underflow)");
-                const bool cast = in.op >= VNM_EX_TO_F64;
-                const bool trans = !cast && in.op != VNM_EX_ABS && in.op != VNM_EX_SQRT;
-                math = std::max(math, trans ? 2 : 1);
-                int t = ty[sp - 1];
-                if (t == T_B && !cast) return set_error("vnm_project: arithmetic on a boolean mask is not supported");
-                if (t == T_WI) t = VNM_I64;    // a NumPy ufunc / np.array over a Python scalar: int64 / float64
-                if (t == T_WF) t = VNM_F64;
-                o.cvt_a = t == T_B ? 1 : cvt_of(t);
-                int rt;
-                if (in.op == VNM_EX_ABS) {
-                    rt = t;
-                    if (type_is_unsigned(t)) o.op = PJ_NOP;                     // the identity
-                    else if (!is_float_t(t) && type_width(t) < 8) o.nar = t;     // abs(int8 -128) == -128
-                } else if (in.op == VNM_EX_TO_F64) rt = VNM_F64;
-                else if (in.op == VNM_EX_TO_I64) rt = VNM_I64;
-                else if (in.op == VNM_EX_TO_BOOL) rt = T_B;
-                else {
-                    rt = is_float_t(t) ? t : type_width(t) == 1 ? PJ_T_F16 : type_width(t) == 2 ? VNM_F32 : VNM_F64;
-                    o.cmp = rt != VNM_F64 ? 1 : 0;                             // float32 arithmetic, NumPy's f / e loops
-                    if (rt == PJ_T_F16) o.nar = VNM_OUT_F16;
-                }
-                o.is_f = held_f(rt);
-                ty[sp - 1] = rt;
-                lit[sp - 1] = -1;
-                cst[sp - 1] = -1;
-                break;
-            }
-            case VNM_EX_NOT:
-                if (sp < 1) return set_error("vnm_project: malformed program (stack underflow)");
-                if (ty[sp - 1] != T_B) return set_error("NOT expects a boolean operand");
-                break;
-            case VNM_EX_AND:
-            case VNM_EX_OR:
-                if (sp < 2) return set_error("vnm_project: malformed program (stack underflow)");
-                if (ty[sp - 1] != T_B || ty[sp - 2] != T_B) return set_error("AND / OR expect boolean operands");
-                sp--;
-                break;
-            case VNM_EX_EQ: case VNM_EX_NE: case VNM_EX_GT: case VNM_EX_GE: case VNM_EX_LT: case VNM_EX_LE: {
-                if (sp < 2) return set_error("vnm_project: malformed program (stack underflow)");
-                const int tb = ty[sp - 1], ta = ty[sp - 2];
-                if (!is_num(ta) || !is_num(tb)) return set_error("vnm_project: comparing boolean masks is not supported");
-                // a float32 column against a Python literal compares in float32
-                if ((ta == VNM_F32 || ta == PJ_T_F16) && (tb == T_WI || tb == T_WF)) round_lit(sp - 1, ta);
-                if ((tb == VNM_F32 || tb == PJ_T_F16) && (ta == T_WI || ta == T_WF)) round_lit(sp - 2, tb);
-                const bool anyf = held_f(ta) || held_f(tb);
-                if (anyf) {  // NumPy compares in float64 as soon as one side is float (float32 values are exact float64s)
-                    o.cmp = 1;
-                    // the literal may just have become a float constant: ask the instruction, not the type
-                    const bool a_f = held_f(ta) || (lit[sp - 2] >= 0 && a.ins[lit[sp - 2]].op == VNM_EX_CONST_F);
-                    const bool b_f = held_f(tb) || (lit[sp - 1] >= 0 && a.ins[lit[sp - 1]].op == VNM_EX_CONST_F);
-                    o.cvt_a = a_f ? 0 : (ta == VNM_U64 ? 2 : 1);
-                    o.cvt_b = b_f ? 0 : (tb == VNM_U64 ? 2 : 1);
-                } else {     // integers compare exactly, int64 against uint64 included
-                    const bool ua = ta == VNM_U64, ub = tb == VNM_U64;
-                    const bool sa = ta == T_WI || (ta < 10 && !type_is_unsigned(ta)), sb = tb == T_WI || (tb < 10 && !type_is_unsigned(tb));
-                    o.cmp = (ua && ub) ? 2 : (ua && sb) ? 3 : (sa && ub) ? 4 : (ua || ub) ? 2 : 0;
-                }
-                o.arg = anyf ? 1 : 0;
-                sp--;
-                ty[sp - 1] = T_B;
-                lit[sp - 1] = -1;
-                cst[sp - 1] = -1;
-                break;
-            }
-            case VNM_EX_ADD: case VNM_EX_SUB: case VNM_EX_MUL: case VNM_EX_DIV: case VNM_EX_MOD:
-            case VNM_EX_BAND: case VNM_EX_BOR: case VNM_EX_BXOR: case VNM_EX_POW: {
-                if (sp < 2) return set_error("vnm_project: malformed program (stack underflow)");
-                const int tb = ty[sp - 1], ta = ty[sp - 2];
-                if (!is_num(ta) || !is_num(tb)) return set_error("vnm_project: arithmetic on a boolean mask is not supported");
-                const bool wa = ta == T_WI || ta == T_WF, wb = tb == T_WI || tb == T_WF;
-                int rt;
-                if (wa && wb) rt = (ta == T_WF || tb == T_WF) ? VNM_F64 : VNM_I64;       // Python scalars: default int64 / float64
-                else if (wa || wb) {
-                    const int w = wa ? ta : tb, t = wa ? tb : ta, wslot = wa ? sp - 2 : sp - 1;
-                    if (w == T_WI) {
-                        rt = t;                                                               // the literal takes the column's type
-                        // true division runs in float64 whatever the integer width: NumPy converts the literal to double, no range check
-                        if (in.op != VNM_EX_DIV && !is_float_t(t) && lit[wslot] >= 0 && !pj_int_fits(t, a.ins[lit[wslot]].imm_i))
-                            return set_error("OverflowError: Python integer %lld out of bounds for %s", (long long)a.ins[lit[wslot]].imm_i, pj_type_name(t));
-                        round_lit(wslot, t);
-                    } else {
-                        rt = (t == VNM_F32 || t == PJ_T_F16) ? t : VNM_F64;
-                        round_lit(wslot, t);
-                    }
-                } else rt = pj_promote_h(ta, tb);
-                const bool bitop = in.op >= VNM_EX_BAND && in.op <= VNM_EX_BXOR;
-                if (bitop && (is_float_t(rt) || held_f(ta) || held_f(tb))) return set_error("ufunc 'bitwise' not supported for float inputs");
-                if (in.op == VNM_EX_DIV && !is_float_t(rt)) rt = VNM_F64;
-                const bool rf = is_float_t(rt);
-                if (in.op == VNM_EX_POW) {
-                    math = 2;
-                    if (!rf) {
-                        // integer ** negative integer: NumPy's ValueError -- a constant exponent here, a column in the kernel
-                        if (cst[sp - 1] >= 0 && a.ins[cst[sp - 1]].op == VNM_EX_CONST_I && a.ins[cst[sp - 1]].imm_i < 0)
-                            return set_error("ValueError: Integers to negative integer powers are not allowed.");
-                        if (cst[sp - 1] < 0 && !type_is_unsigned(tb)) { o.arg = 1; pow_check = true; }
-                    } else if (rt != VNM_F64) o.cmp = 1;   // float32 arithmetic (float32 and float16 results)
-                }
-                o.is_f = rf;
-                if (rf) {
-                    const bool a_f = held_f(ta) || (lit[sp - 2] >= 0 && a.ins[lit[sp - 2]].op == VNM_EX_CONST_F);
-                    const bool b_f = held_f(tb) || (lit[sp - 1] >= 0 && a.ins[lit[sp - 1]].op == VNM_EX_CONST_F);
-                    o.cvt_a = a_f ? 0 : (ta == VNM_U64 ? 2 : 1);
-                    o.cvt_b = b_f ? 0 : (tb == VNM_U64 ? 2 : 1);
-                }
-                if (rt == VNM_F32 || (!rf && type_width(rt) < 8)) o.nar = rt;
-                if (rt == PJ_T_F16) { o.nar = VNM_OUT_F16; math = std::max(math, 1); }
-                if (rt == VNM_U64 && in.op == VNM_EX_MOD) o.cmp = 2;   // unsigned modulo
-                sp--;
-                ty[sp - 1] = rt;
-                lit[sp - 1] = -1;
-                cst[sp - 1] = -1;
-                break;
-            }
-            case VNM_EX_STORE: {
-                if (single && i < n_ins) return set_error("vnm_project: VNM_EX_STORE belongs to vnm_project_multi programs");
-                if (sp < 1) return set_error("vnm_project: malformed program (stack underflow)");
-                if (in.arg < 0 || in.arg >= n_out) return set_error("vnm_project: output index %d out of range", in.arg);
-                if (stored[in.arg]) return set_error("vnm_project: output %d stored twice", in.arg);
-                stored[in.arg] = true;
-                int t = ty[sp - 1];
-                if (t == T_WI) t = VNM_I64;            // np.repeat(5, n) -> int64, np.repeat(5.0, n) -> float64 (algebra.py:77-87)
-                if (t == T_WF) t = VNM_F64;
-                if (t == PJ_T_F16) t = VNM_OUT_F16;
-                a.out[in.arg] = out_values[in.arg];
-                a.out_is_mask[in.arg] = t == T_B;
-                a.out_type[in.arg] = t == T_B ? VNM_U8 : t;
-                if (out_types) out_types[in.arg] = t == T_B ? VNM_MASK_U8 : t;
-                sp--;
-                break;
-            }
-            default: return set_error("vnm_project: unknown opcode %d", in.op);
-        }
-        if (sp > depth) depth = sp;
-    }
-    if (sp != 0) return set_error("vnm_project: malformed program (final stack depth %d)", sp + (single ? 1 : 0));
-    for (int k = 0; k < n_out; k++)
-        if (!stored[k]) return set_error("vnm_project: output %d is never stored", k);
-    a.n_ins = total;
-    // typing needs no device: a zero-length call type-checks a program (result types, NumPy's errors) on any host
-    if (length <= 0) return 0;
-    VNM_TRY(ensure_init());
-    if (pow_check && math != 2) return set_error("vnm_project: internal error (power outside the MATH kernel)");
+static int project_launch(ProjArgs& a, const PjTyped& t, hipStream_t s) {
+    const ProjectKernelEntry& k = PJ_KERNELS[t.lookup][t.math];
     // depth - 1 levels below the register top; MATH programs stage the top through one more level
-    const size_t lds = (size_t)(math ? depth : (depth > 1 ? depth - 1 : 1)) * PJ_R * PJ_BLOCK * 8;
-    // ONE workgroup per tile: a workgroup loads, computes and stores with nothing of its own to overlap, so it is the
-    // dispatcher that keeps the memory system busy (three expressions over 1e9 rows: 8 workgroups per CU looping over tiles
-    // 11.15 ms, 32 per CU 10.2, 128 per CU 9.7, one per tile 9.27 = 5.2 TB/s)
-    int64_t grid64 = getenv("VNM_PJ_GRID") ? (int64_t)device_info().num_cus * atoi(getenv("VNM_PJ_GRID")) : (int64_t)1 << 30;
-    int grid = (int)grid64;
-    int64_t need = (length + PJ_TILE - 1) / PJ_TILE;
-    if (grid > need) grid = (int)need;
-    const void* kern = lookup == 2 ? (math == 2 ? (const void*)project_kernel<2, 2> : math == 1 ? (const void*)project_kernel<1, 2> : (const void*)project_kernel<0, 2>)
-                     : lookup ? (math == 2 ? (const void*)project_kernel<2, 1> : math == 1 ? (const void*)project_kernel<1, 1> : (const void*)project_kernel<0, 1>)
-                              : (math == 2 ? (const void*)project_kernel<2, 0> : math == 1 ? (const void*)project_kernel<1, 0> : (const void*)project_kernel<0, 0>);
+    const size_t lds = (size_t)(t.math ? t.depth : (t.depth > 1 ? t.depth - 1 : 1)) * PJ_R * PJ_BLOCK * 8;
+    const int grid = project_grid(a.length);
     if (lds > 64 * 1024)   // depth >= 10: beyond the default dynamic LDS limit
-        VNM_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipStream_t s = as_stream(stream);
+        VNM_HIP(hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     PoolScope scope;
-    if (pow_check) {   // an integer power with a signed exponent column: the kernel reports a negative exponent
+    if (t.pow_check) {   // an integer power with a signed exponent column: the kernel reports a negative exponent
         a.neg_pow = (int*)scope.take(sizeof(int));
         if (!a.neg_pow) return 1;
         VNM_HIP(hipMemsetAsync(a.neg_pow, 0, sizeof(int), s));
     }
-    if (lookup == 2) {
-        KernelTimer timer("project_kernel_lookup_i32", s);
-        if (math == 2) project_kernel<2, 2><<<grid, PJ_BLOCK, lds, s>>>(a);
-        else if (math == 1) project_kernel<1, 2><<<grid, PJ_BLOCK, lds, s>>>(a);
-        else project_kernel<0, 2><<<grid, PJ_BLOCK, lds, s>>>(a);
-    } else if (lookup) {
-        KernelTimer timer("project_kernel_lookup", s);
-        if (math == 2) project_kernel<2, 1><<<grid, PJ_BLOCK, lds, s>>>(a);
-        else if (math == 1) project_kernel<1, 1><<<grid, PJ_BLOCK, lds, s>>>(a);
-        else project_kernel<0, 1><<<grid, PJ_BLOCK, lds, s>>>(a);
-    } else if (math == 2) {
-        KernelTimer timer("project_kernel_math", s);
-        project_kernel<2, 0><<<grid, PJ_BLOCK, lds, s>>>(a);
-    } else if (math == 1) {
-        KernelTimer timer("project_kernel_exact_fn", s);
-        project_kernel<1, 0><<<grid, PJ_BLOCK, lds, s>>>(a);
-    } else {
-        KernelTimer timer("project_kernel", s);
-        project_kernel<0, 0><<<grid, PJ_BLOCK, lds, s>>>(a);
+    {
+        KernelTimer timer(k.timer, s);
+        k.fn<<<grid, PJ_BLOCK, lds, s>>>(a);
     }
     VNM_HIP(hipGetLastError());
-    if (pow_check) {
+    if (t.pow_check) {
         int neg = 0;
         VNM_HIP(hipMemcpyAsync(&neg, a.neg_pow, sizeof(int), hipMemcpyDeviceToHost, s));
         VNM_HIP(hipStreamSynchronize(s));
         if (neg) return set_error("ValueError: Integers to negative integer powers are not allowed.");
     }
     return 0;
+}
+
+// Type the program (vnm_project_type.hpp), then launch the instantiation its lookup and math levels name.  `single`: the program is
+// one expression without a STORE; out index 0 is implied.
+static int project_impl(int n_ins, const vnm_expr_ins* program, int n_cols, const vnm_dcol* cols, int64_t length,
+                        int n_out, void** out_values, int* out_types, bool single, void* stream) {
+    PjTyped typed;
+    const std::string err = pj_type_program(n_ins, program, n_cols, cols, length, n_out, single, typed);
+    if (!err.empty()) return set_error("%s", err.c_str());
+    if (out_types) std::copy(typed.out_types, typed.out_types + n_out, out_types);
+    // typing needs no device: a zero-length call type-checks a program (result types, NumPy's errors) on any host
+    if (length <= 0) return 0;
+    VNM_TRY(ensure_init());
+    if (typed.pow_check && typed.math != 2) return set_error("vnm_project: internal error (power outside the MATH kernel)");
+    ProjArgs a{};
+    a.n_ins = typed.n_ins;
+    a.n_cols = n_cols;
+    a.length = length;
+    std::copy(typed.ins, typed.ins + typed.n_ins, a.ins);
+    std::copy(cols, cols + n_cols, a.cols);
+    std::copy(out_values, out_values + n_out, a.out);
+    memcpy(a.out_is_mask, typed.out_is_mask, sizeof(a.out_is_mask));
+    memcpy(a.out_type, typed.out_type, sizeof(a.out_type));
+    return project_launch(a, typed, as_stream(stream));
 }
 
 extern "C" {

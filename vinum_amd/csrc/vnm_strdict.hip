@@ -13,7 +13,7 @@
 //   * ids come from per-workgroup chunks of a global counter (an LDS atomic inside the claim; holes < 2x);
 //   * the table grows by rehash between launches (workgroups resume from progress[]); ids and heap offsets survive.
 // The host side keeps the dictionary's values (it receives only the NEW values of each batch: ids, lengths, bytes) and maps
-// the result's codes back (vinum_amd/vinum_lib.py::KeyDictionary).
+// the result's codes back (vinum_amd/keydict.py::KeyDictionary).
 #include <algorithm>
 #include <cstring>
 #include <map>

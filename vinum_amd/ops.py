@@ -604,7 +604,7 @@ def project_many(exprs, columns: dict, length=None, stream=None):
     exprs = [lower_in_sets(e, columns, length, stream, extra)[0] for e in exprs]
     if extra:
         columns = {**columns, **extra}
-    # pack expressions into programs that respect the kernel limits (64 instructions, 16 columns, 16 outputs)
+    # pack expressions into programs that respect the kernel limits (L.PJ_MAX_*: instructions, columns, outputs)
     chunks, cur, cur_cols, cur_ins = [], [], [], 0
     for k, e in enumerate(exprs):
         tmp = []
@@ -612,7 +612,7 @@ def project_many(exprs, columns: dict, length=None, stream=None):
         _emit_expr(e, {n: 0 for n in ecols}, tmp)
         n_ins = len(tmp) + 1
         merged = cur_cols + [c for c in ecols if c not in cur_cols]
-        if cur and (cur_ins + n_ins > 64 or len(merged) > 16 or len(cur) >= 16):
+        if cur and (cur_ins + n_ins > L.PJ_MAX_INS or len(merged) > L.PJ_MAX_COLS or len(cur) >= L.PJ_MAX_OUT):
             chunks.append((cur, cur_cols))
             cur, cur_ins, merged = [], 0, list(ecols)
         cur.append(k)
@@ -639,7 +639,7 @@ def project_many(exprs, columns: dict, length=None, stream=None):
 
 
 # ---- IN / NOT IN lists as device-resident sets (vnm_inset.hip) -----------------------------------
-PJ_MAX_INS = 64          # vnm_project.hip: instructions per program, the final STORE included
+PJ_MAX_INS = L.PJ_MAX_INS          # instructions per program, the final STORE included
 _IN_SET_CACHE_SIZE = 32
 
 
