@@ -559,6 +559,49 @@ int vnm_strdict_ranks_joint(vnm_strdict* a, vnm_strdict* b, int32_t* out_rank_of
  * table is written. */
 int vnm_strdict_map_codepoints(vnm_strdict* src, vnm_strdict* dst, const int32_t* map_from, const int32_t* map_to, int64_t n_map,
                                int64_t id_begin, int32_t* out_dst_code_of_src_id, int64_t* out_invalid, void* stream);
+/* concat() / || (ConcatFunction, vinum/core/functions.py:250-276: every operand through np.array(., dtype='U'), folded left with
+ * np.char.add).  An operand contributes its bytes without TRAILING 0x00 bytes (leading and embedded ones stay); a NULL contributes
+ * the four bytes "None"; the result is never NULL.  The work is on bytes: malformed UTF-8 is concatenated as it stands.
+ *
+ * vnm_strdict_concat_affix -- one column and literals, a function of the value: for every id of src in [id_begin,
+ * vnm_strdict_ids(src)) the image prefix + rstrip_nul(value) + suffix is written into scratch spans and found or inserted in dst
+ * through dst's span encode (the one insert path); out_dst_code_of_src_id[id] = dst's code of it (a DEVICE array of
+ * vnm_strdict_ids(src) int32s, only that range is written; -2: the id was never handed out).  The image of NULL, prefix + "None" +
+ * suffix, is inserted by the same call and its code stored in *out_null_code (host).  Two values with one image ("a\0" and "a") get
+ * one code.  src is only read; afterwards vnm_strdict_last_new / _fetch_new on dst return the values it added.  A table kept across
+ * batches is extended with id_begin = the id count it covers.  dst remembers the prefix and suffix of its first call and refuses
+ * others.  The call goes through dst's encode, which reads counts back: it returns when the table is written.
+ *
+ * vnm_strdict_gather_codes -- the row pass of that form: out_codes[i] = table[codes[i]], and null_code where row i is NULL by its
+ * validity bit (bit validity_offset + i; validity may be NULL) or by code -1.  A code at or past n_ids gets -2 and is never an
+ * address.  No validity comes out.  codes points at row 0.  One kernel on `stream`, launched asynchronously. */
+int vnm_strdict_concat_affix(vnm_strdict* src, vnm_strdict* dst, const uint8_t* prefix, int64_t prefix_len, const uint8_t* suffix, int64_t suffix_len,
+                             int64_t id_begin, int32_t* out_dst_code_of_src_id, int32_t* out_null_code, void* stream);
+int vnm_strdict_gather_codes(const int32_t* codes, const uint8_t* validity, int64_t validity_offset, const int32_t* table, int64_t n_ids, int64_t n,
+                             int32_t null_code, int32_t* out_codes, void* stream);
+/* vnm_strpair -- two columns, concat(a, sep, b): a persistent open-addressing table on the device, one per (pair of dictionaries,
+ * prefix, sep, suffix), that lives across batches so a pair keeps its code.  A slot holds the 64-bit key (uint32)(code_a + 1) << 32 |
+ * (uint32)(code_b + 1) -- NULL is code -1 or a cleared validity bit of the operand's column -- and the pair's int32 code in dst.
+ * vnm_strpair_create takes the literal in front of a and the one behind b (either may be empty).
+ * vnm_strpair_concat(h, a, b, dst, sep, sep_len, codes_a, codes_b, length, out_codes, stream): codes_a / codes_b are int32 DEVICE
+ * columns of `length` rows (values, validity or NULL, Arrow offset) holding codes of a / b; out_codes[i] (DEVICE, `length` int32s) =
+ * dst's code of prefix + value_a + sep + value_b + suffix of row i.  Passes: find (4 rows per lane, 16-byte loads where the three
+ * pointers are aligned; probe, CAS(EMPTY -> key); no lane waits for another; the probe walk is bounded by 1024 slots and by the capacity; the
+ * CAS winner appends its slot to a new-pairs list); on overflow -- past 70 % fill or the bound -- the table grows x4, a rehash kernel
+ * re-inserts key and code, the find pass runs again (counted in `rehashes`); concat (one lane per NEW pair: exact length first,
+ * every store held against it, the spans through dst's encode, the codes into the new slots); gather (in place).  String bytes are
+ * touched once per distinct pair.  a and b may be one dictionary; dst must be neither.  a, b are only read and may have grown since
+ * the last call.  A separator other than the first call's is refused; so is a code outside [-1, vnm_strdict_ids).  Returns when
+ * out_codes is written; vnm_strdict_last_new / _fetch_new on dst return the values the call added.
+ * The initial slot count is $VNM_STRPAIR_SLOTS rounded up to a power of two (default 65536, at least 16).
+ * vnm_strpair_stats: out6 = {calls with length > 0, pairs concatenated (= distinct pairs seen), rehashes, slots, occupied slots,
+ * occupied slots WITHOUT a code (0 after every call that returned 0)}. */
+typedef struct vnm_strpair vnm_strpair;
+vnm_strpair* vnm_strpair_create(const uint8_t* prefix, int64_t prefix_len, const uint8_t* suffix, int64_t suffix_len);
+void vnm_strpair_destroy(vnm_strpair* h);
+int vnm_strpair_concat(vnm_strpair* h, vnm_strdict* a, vnm_strdict* b, vnm_strdict* dst, const uint8_t* sep, int64_t sep_len, const vnm_dcol* codes_a,
+                       const vnm_dcol* codes_b, int64_t length, int32_t* out_codes, void* stream);
+int vnm_strpair_stats(vnm_strpair* h, int64_t* out6, void* stream);
 /* A dictionary-typed Arrow column (dictionary<intN, utf8 | large_utf8 | binary | large_binary>): the batch dictionary's indices ->
  * codes of the running dictionary.  The caller runs the batch dictionary's VALUES through vnm_strdict_encode and uploads the result
  * as code_of_index (n_values int32s on the DEVICE; -1 = a NULL value), so only n_values strings are hashed, not one per row.

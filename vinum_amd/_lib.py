@@ -133,6 +133,12 @@ PROTOTYPES = {
     "vnm_strdict_translate": (c_int, [c_void, c_void, c_i64, c_void, c_void]),
     "vnm_strdict_ranks_joint": (c_int, [c_void, c_void, c_void, c_void, c_void]),
     "vnm_strdict_map_codepoints": (c_int, [c_void, c_void, c_void, c_void, c_i64, c_i64, c_void, c_void, c_void]),
+    "vnm_strdict_concat_affix": (c_int, [c_void, c_void, c_void, c_i64, c_void, c_i64, c_i64, c_void, c_void, c_void]),
+    "vnm_strdict_gather_codes": (c_int, [c_void, c_void, c_i64, c_void, c_i64, c_i64, ctypes.c_int32, c_void, c_void]),
+    "vnm_strpair_create": (c_void, [c_void, c_i64, c_void, c_i64]),
+    "vnm_strpair_destroy": (None, [c_void]),
+    "vnm_strpair_concat": (c_int, [c_void, c_void, c_void, c_void, c_void, c_i64, c_void, c_void, c_i64, c_void, c_void]),
+    "vnm_strpair_stats": (c_int, [c_void, c_void, c_void]),
     "vnm_strdict_remap_indices": (c_int, [c_void, c_void, c_i64, c_void, c_void, c_void, c_void]),
     "vnm_dict_take_compact": (c_int, [c_void, c_void, c_i64, c_i64, c_int, c_void, c_void, c_void, c_void, c_void, c_void]),
     "vnm_like_compile": (c_int, [c_void, c_i64, c_void, c_void]),

@@ -49,6 +49,7 @@ class SQLExpression(enum.Enum):   # vinum/parser/query.py:17-59 (the members the
     AND = enum.auto(); BETWEEN = enum.auto(); NOT_BETWEEN = enum.auto(); IN = enum.auto(); NOT_IN = enum.auto()
     NOT = enum.auto(); OR = enum.auto(); IS_NULL = enum.auto(); IS_NOT_NULL = enum.auto()
     FUNCTION = enum.auto()
+    CONCAT = enum.auto()              # `a || b` (parser.py:81)
 
 
 class FunctionType(enum.Enum):    # vinum/core/functions.py:347-350
@@ -188,13 +189,24 @@ class LowerStringFunction(AbstractStringFunction):
     """functions.py:290-297: pc.utf8_lower."""
 
 
-_CASE_SPEC = {"UpperStringFunction": "upper", "LowerStringFunction": "lower"}
+class ConcatFunction(AbstractStringFunction):
+    """functions.py:250-276: every argument through np.array(., dtype='U'), folded left with np.char.add -- built as
+    Cls(arguments) with the callable and both dispatch flags set."""
 
-# the numeric part of _default_functions_registry, with the same callables (math constants: the lambdas themselves), and the two
+    def __init__(self, arguments: Iterable) -> None:
+        VectorizedExpression.__init__(self, arguments, function=np.char.add, is_numpy_func=True, is_binary_func=True)
+
+
+_CASE_SPEC = {"UpperStringFunction": "upper", "LowerStringFunction": "lower"}
+_STRING_FN_NAMES = ("upper", "lower", "concat")       # their "fn" spelling builds what it always built; the operator node builds the class
+EXPRESSION_FUNCTIONS[SQLExpression.CONCAT] = (ConcatFunction, FunctionType.CLASS)       # expressions.py:51
+
+# the numeric part of _default_functions_registry, with the same callables (math constants: the lambdas themselves), and the three
 # string functions that run on the device
 FUNCTIONS_REGISTRY = {
     "upper": (UpperStringFunction, FunctionType.CLASS),
     "lower": (LowerStringFunction, FunctionType.CLASS),
+    "concat": (ConcatFunction, FunctionType.CLASS),
     "to_bool": (BoolCastFunction, FunctionType.CLASS),
     "to_float": (FloatCastFunction, FunctionType.CLASS),
     "to_int": (IntCastFunction, FunctionType.CLASS),
@@ -219,7 +231,7 @@ _SPEC_TO_SQL = {"add": "ADDITION", "sub": "SUBTRACTION", "mul": "MULTIPLICATION"
                 "eq": "EQUALS", "ne": "NOT_EQUALS", "gt": "GREATER_THAN", "ge": "GREATER_THAN_OR_EQUAL", "lt": "LESS_THAN",
                 "le": "LESS_THAN_OR_EQUAL", "and": "AND", "or": "OR", "not": "NOT", "is_null": "IS_NULL",
                 "is_not_null": "IS_NOT_NULL", "in": "IN", "not_in": "NOT_IN", "between": "BETWEEN",
-                "not_between": "NOT_BETWEEN"}
+                "not_between": "NOT_BETWEEN", "concat": "CONCAT"}
 _SQL_TO_SPEC = {v: k for k, v in _SPEC_TO_SQL.items()}
 
 
@@ -253,9 +265,12 @@ def vectorize(expr, registry=None, classes=None, functions=None, like_cls=None):
             return Lt(args[0])
         if op in ("like", "not_like"):                           # planner.py:189-193
             return like_cls(tuple(build(a) for a in args), op == "not_like")
+        if op == "||":                                           # parser.py:81: SQLExpression.CONCAT, a CLASS entry of the expression registry
+            cls, _ = registry[SQL[_SPEC_TO_SQL["concat"]]]
+            return cls([build(a) for a in args])                 # planner.py:129-131: Cls(arguments)
         # (the "fn" spelling of upper / lower builds what it always built, an AggregateFunction node -- the planner resolves that
         #  spelling by the operand's type, planner._case_by_type; the operator node ("upper", x) builds the function's class)
-        if op == "fn" and (args[0].lower() in _AGG_NAMES or args[0].lower() in _CASE_SPEC.values() or not _is_builtin(args[0].lower(), functions)):
+        if op == "fn" and (args[0].lower() in _AGG_NAMES or args[0].lower() in _STRING_FN_NAMES or not _is_builtin(args[0].lower(), functions)):
             arg = build(args[1]) if len(args) > 1 else None
             return AF(args[0], arg) if arg is not None else AF(args[0])
         if op == "fn" or op in FUNCTIONS_REGISTRY:
@@ -318,13 +333,18 @@ def lower(node, index: Optional[Dict[int, str]] = None):
         # module) defines under that name at module level -- some other class whose __name__ was set to it is not that function
         if fn is None and type(node).__qualname__ in _CASE_SPEC and len(tuple(node.arguments)) == 1:
             return (_CASE_SPEC[type(node).__qualname__], lower(tuple(node.arguments)[0], index))
+        # ConcatFunction (functions.py:250-276; `concat(...)` and `a || b` both build it), by qualified name AND by its shape: it
+        # carries a callable (np.char.add) and folds as a binary function.  A VectorizedExpression that merely holds np.char.add is
+        # not that function.
+        if type(node).__qualname__ == "ConcatFunction" and fn is not None and getattr(node, "_is_binary_func", False) and len(tuple(node.arguments)) >= 1:
+            return ("concat",) + tuple(lower(a, index) for a in node.arguments)
         if fn is not None and id(fn) not in index and id(fn) in _UFUNC_SPEC:
             return (_UFUNC_SPEC[id(fn)],) + tuple(lower(a, index) for a in node.arguments)
         if fn is None or id(fn) not in index:
             raise NotImplementedError(f"no GPU lowering for {fn if fn is not None else type(node).__name__!r}: the numeric "
                                       "operators and the built-ins abs, sqrt, sin, cos, tan, log, log2, log10, power, pi, e, "
-                                      "to_int, to_float, to_bool, upper / lower of a string column and LIKE / NOT LIKE against "
-                                      "a string literal run on the GPU; UDFs, concat, to_str, the datetime functions and other "
+                                      "to_int, to_float, to_bool, upper / lower / concat of string columns and LIKE / NOT LIKE "
+                                      "against a string literal run on the GPU; UDFs, to_str, the datetime functions and other "
                                       "np.* functions do not")
         sql = index[id(fn)]
         args = [lower(a, index) for a in node.arguments]

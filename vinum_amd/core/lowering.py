@@ -16,6 +16,7 @@ def value_type_of(dictionary):
 
 
 CASE_FNS = ("upper", "lower")
+STRING_FNS = CASE_FNS + ("concat",)
 
 
 def with_derived(columns, extra):
@@ -24,30 +25,53 @@ def with_derived(columns, extra):
     return {**columns, **derived} if derived else columns
 
 
+def concat_literal(x):
+    """the bytes a literal operand of concat() contributes (ConcatFunction, functions.py:250-276: np.array(str(x), dtype='U')): a
+    string literal without its trailing NULs, a number as str(number); None for anything that is no literal"""
+    if E.is_str_lit(x):
+        v = x[1]
+        return (v.encode("utf-8") if isinstance(v, str) else bytes(v)).rstrip(b"\x00")
+    if isinstance(x, (bool, int, float)):
+        return str(x).encode("utf-8")
+    return None
+
+
 def lower_case_functions(expr, columns, extra=None):
-    """upper(x) / lower(x) (UpperStringFunction / LowerStringFunction, vinum/core/functions.py:279-298: pc.utf8_upper / utf8_lower)
-    over a dictionary-coded string column, or over another such function: the node becomes the NAME of a derived column added to
-    `extra` -- the int32 codes of the DERIVED dictionary (KeyDictionary.mapped_column: each distinct value mapped once on the
-    device, a row one lookup), the operand's validity, `.dictionary` the derived dictionary.  To every later step and operator it
-    is an ordinary string column.  A node that occurs several times under one `extra` is materialised once.  A numeric column
-    raises TypeError (the reference would print the numbers as text: not restated), a literal or any other expression
-    NotImplementedError; a binary column TypeError and a host-route dictionary NotImplementedError (KeyDictionary.mapped)."""
+    """The one pass over the string-function nodes, in any nesting: upper(x) / lower(x) (UpperStringFunction / LowerStringFunction,
+    vinum/core/functions.py:279-298: pc.utf8_upper / utf8_lower) and concat(x, ...) (ConcatFunction, :250-276) over dictionary-coded
+    string columns, literals and other such nodes.  A node becomes the NAME of a derived column added to `extra` -- the int32 codes
+    of a DERIVED dictionary, `.dictionary` that dictionary -- and is to every later step and operator an ordinary string column.  A
+    node that occurs several times under one `extra` is materialised once.
+      * upper / lower: KeyDictionary.mapped_column -- each distinct value mapped once on the device, a row one lookup, the
+        operand's validity.
+      * concat: adjacent literals merge here (a number is str(number), a string literal loses its trailing NULs).  One column with
+        literals is a function of the value (KeyDictionary.affixed_column: prefix + value + suffix once per distinct value, a row
+        one lookup).  Two columns are a function of the row's PAIR of codes (KeyDictionary.pair_column: a persistent device pair
+        table, the bytes written once per distinct pair); three or more fold left as the reference does, the first step's derived
+        dictionary being the second step's left one, the literal in front of the first column and the one behind the last going
+        into the first / last step's byte writer.  The result has no validity: a NULL operand is "None".
+    A numeric or temporal column raises TypeError naming it (the reference would print the numbers as text: not restated), a
+    concat() of literals alone and any other operand expression NotImplementedError; a binary column TypeError and a host-route
+    dictionary NotImplementedError (KeyDictionary.mapped / affixed / paired)."""
     extra = {} if extra is None else extra
 
-    def f(e):
-        if e[0] not in CASE_FNS:
-            return None
-        if len(e) != 2:
-            raise NotImplementedError(f"no GPU lowering for {e[0]}() with {len(e) - 1} operand(s)")
-        x = e[1]
-        if isinstance(x, tuple) and x and x[0] in CASE_FNS:
+    def operand(fn, x):
+        """the name of the string column `x` stands for, its column; None where its dictionary cannot do this (a stub): the node stays"""
+        if isinstance(x, tuple) and x and x[0] in STRING_FNS:
             x = f(x)
         cols = with_derived(columns, extra)
         if not isinstance(x, str) or x not in cols:
-            raise NotImplementedError(f"no GPU lowering for {e[0]}() over {x!r}: the operand must be a string column or upper() / lower() of one")
+            raise NotImplementedError(f"no GPU lowering for {fn}() over {x!r}: the operand must be a string column or upper() / lower()" +
+                                      (" / concat() of one, or a literal" if fn == "concat" else " of one"))
         c = cols[x]
         if c.dictionary is None:
-            raise TypeError(f"{e[0]}() needs a string column, {x!r} is {c.arrow_type}")
+            raise TypeError(f"{fn}() needs a string column, {x!r} is {c.arrow_type}")
+        return x, c
+
+    def case_fn(e):
+        if len(e) != 2:
+            raise NotImplementedError(f"no GPU lowering for {e[0]}() with {len(e) - 1} operand(s)")
+        x, c = operand(e[0], e[1])
         mapped_column = getattr(c.dictionary, "mapped_column", None)
         if mapped_column is None:         # a dictionary object that cannot map: the node stays, and is refused where it is compiled
             return e
@@ -55,6 +79,51 @@ def lower_case_functions(expr, columns, extra=None):
         if name not in extra:
             extra[name] = mapped_column(e[0], c)
         return name
+
+    def concat(e):
+        parts = []                         # bytes (merged literals) and (name, column) in operand order
+        for x in e[1:]:
+            lit = concat_literal(x)
+            if lit is None:
+                parts.append(operand("concat", x))
+            elif parts and isinstance(parts[-1], bytes):
+                parts[-1] += lit
+            else:
+                parts.append(lit)
+        cols = [p for p in parts if not isinstance(p, bytes)]
+        if not cols:
+            raise NotImplementedError(f"no GPU lowering for concat() of literals alone ({list(e[1:])!r}): there is no per-row work")
+        if any(getattr(c.dictionary, "affixed_column", None) is None or getattr(c.dictionary, "pair_column", None) is None for _, c in cols):
+            return e                       # (a dictionary object that cannot concatenate: refused where the node is compiled)
+        lits, at = [b""], 0                # lits[k]: the literal in front of column k; lits[len(cols)]: the one behind the last
+        for p in parts:
+            if isinstance(p, bytes):
+                lits[at] = p
+            else:
+                at += 1
+                lits.append(b"")
+        label = lambda b: repr(b.decode("utf-8", "replace"))
+        (name, col) = cols[0]
+        if len(cols) == 1:
+            out = f"__concat({label(lits[0])},{name},{label(lits[1])})"
+            if out not in extra:
+                extra[out] = col.dictionary.affixed_column(lits[0], lits[1], col)
+            return out
+        for k in range(1, len(cols)):       # the left fold: (((a . b) . c) . d)
+            rname, rcol = cols[k]
+            prefix, suffix = lits[0] if k == 1 else b"", lits[len(cols)] if k == len(cols) - 1 else b""
+            out = f"__concat({label(prefix)},{name},{label(lits[k])},{rname},{label(suffix)})"
+            if out not in extra:
+                extra[out] = col.dictionary.pair_column(rcol.dictionary, prefix, lits[k], suffix, col, rcol)
+            name, col = out, extra[out]
+        return name
+
+    def f(e):
+        if e[0] in CASE_FNS:
+            return case_fn(e)
+        if e[0] == "concat":
+            return concat(e)
+        return None
     return E.rewrite(expr, f), extra
 
 
@@ -192,7 +261,7 @@ def lower_literal_compares(expr, columns, extra=None):
 
 
 def lower_dictionary(expr, columns, extra=None):
-    """The four lowerings in their order: upper() / lower() -- whose results are string columns to the other three --, LIKE, then
+    """The four lowerings in their order: upper() / lower() / concat() -- whose results are string columns to the other three --, LIKE, then
     the column pairs -- which refuse a numeric operand, so they run before the literals turn into codes and ranks -- then the
     literals; the last two only act where a dictionary-coded column is read at all."""
     expr, extra = lower_case_functions(expr, columns, extra)

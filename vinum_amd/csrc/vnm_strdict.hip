@@ -734,6 +734,10 @@ struct vnm_strdict {
     int32_t* map_dev = nullptr;              // [n] from, [n] to, 128 bytes ASCII image
     std::vector<int32_t> map_host;           // from + to, to recognise the map on the next call
     int map_ascii_closed = 0;
+    // as the DESTINATION of vnm_strdict_concat_affix: prefix | suffix this dictionary was derived with, uploaded once
+    uint8_t* affix_dev = nullptr;
+    std::string affix_host;
+    int64_t affix_pre = -1;
 };
 
 // the id-indexed arrays cover every id handed out so far (ids come in chunks, so they grow even when no value is new)
@@ -770,6 +774,7 @@ void vnm_strdict_destroy(vnm_strdict* h) {
     pool_free(h->id_len);
     for (auto& kv : h->like_patterns) pool_free(kv.second.first);
     pool_free(h->map_dev);
+    pool_free(h->affix_dev);
     delete h;
 }
 
@@ -1373,3 +1378,5 @@ int vnm_strdict_remap_indices(const vnm_dcol* indices, const int32_t* code_of_in
 }
 
 }  // extern "C"
+
+#include "vnm_strconcat.inc"

@@ -1,5 +1,6 @@
 """KeyDictionary: the running dictionary of one non-numeric column (value -> int32 code) and the device tables derived from it,
-one entry per dictionary id: LIKE matches, translations into and joint ranks with another dictionary, upper() / lower() maps.
+one entry per dictionary id: LIKE matches, translations into and joint ranks with another dictionary, upper() / lower() maps,
+concat() with literals; and the pair tables of concat() over two columns.
 Importable without the shared library, like vinum_lib (which re-exports KeyDictionary and device_value_type)."""
 import ctypes
 from dataclasses import dataclass
@@ -72,6 +73,64 @@ class _CaseMap:                   # KeyDictionary._mapped["upper" | "lower"]
     mine: int = -1                # own value count when the table last advanced
 
 
+@dataclass
+class _Affix:                     # KeyDictionary._affixed[(prefix, suffix)]
+    derived: "KeyDictionary"
+    table: _IdTable               # int32: code here -> code in `derived`, -2 for an id never handed out
+    null_code: int = -2           # `derived`'s code of prefix + "None" + suffix, what a NULL row gets
+    mine: int = -1                # own value count when the table last advanced
+
+
+class PairTable:
+    """The device pair table (vnm_strpair) of concat(a, sep, b) over two dictionaries and the dictionary derived from them:
+    (code_a, code_b) -> code in `derived`, alive across batches so a pair keeps its code.  `pair_launches`, `pairs_concatenated`
+    (= the distinct pairs seen: string bytes are touched once per pair, never per row), `rehashes`, `slots`, `occupied` and
+    `half_written` (occupied slots without a code: 0 after every call) are read from the device object (stats())."""
+
+    def __init__(self, prefix: bytes, sep: bytes, suffix: bytes):
+        self.prefix, self.sep, self.suffix = prefix, sep, suffix
+        self.derived = KeyDictionary(pa.string())
+        self.ref = None           # weak reference to the right operand's dictionary (KeyDictionary._paired)
+        self._h = L.lib().vnm_strpair_create(prefix, len(prefix), suffix, len(suffix))
+        if not self._h:
+            raise RuntimeError(L.last_error())
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                L.lib().vnm_strpair_destroy(h)
+            except Exception:
+                pass
+
+    def stats(self) -> dict:
+        out = (ctypes.c_int64 * 6)()
+        L.check(L.lib().vnm_strpair_stats(self._h, out, None))
+        return dict(zip(("pair_launches", "pairs_concatenated", "rehashes", "slots", "occupied", "half_written"), (int(v) for v in out)))
+
+    pair_launches = property(lambda self: self.stats()["pair_launches"])
+    pairs_concatenated = property(lambda self: self.stats()["pairs_concatenated"])
+    rehashes = property(lambda self: self.stats()["rehashes"])
+
+    def column(self, da, db, col_a, col_b):
+        """the codes of prefix + a + sep + b + suffix per row: an int32 DeviceColumn WITHOUT validity (concat() is never NULL), its
+        `.dictionary` the derived dictionary"""
+        from .device import DeviceBuffer, DeviceColumn
+        n = col_a.length
+        if col_b.length != n:
+            raise ValueError(f"concat(): operands of {n} and {col_b.length} rows")
+        out = DeviceBuffer(max(n, 1) * 4)
+        a, b = col_a.dcol(), col_b.dcol()
+        rc = L.lib().vnm_strpair_concat(self._h, da.handle(), db.handle(), self.derived.handle(), self.sep, len(self.sep), ctypes.byref(a),
+                                        ctypes.byref(b), n, out.ptr, None)
+        message = L.last_error() if rc != 0 else None
+        if self.derived._h is not None and n:
+            self.derived.absorb_new()
+        if rc != 0:
+            raise L.VinumHipError(message)
+        return DeviceColumn(out, None, 0, n, pa.int32(), keep=(self,), dictionary=self.derived)
+
+
 class KeyDictionary:
     """Running dictionary of one non-numeric group-by column: value -> int32 code.
 
@@ -116,6 +175,9 @@ class KeyDictionary:
         self._mapped = {}          # "upper" | "lower" -> _CaseMap
         self.map_launches = self.map_ids_mapped = 0          # vnm_strdict_map_codepoints calls and the ids they mapped, over both functions
         self.translate_builds = self.joint_rank_builds = 0   # vnm_strdict_translate / vnm_strdict_ranks_joint calls this dictionary made
+        self._affixed = {}         # (prefix, suffix) -> _Affix
+        self.affix_launches = self.affix_ids_mapped = 0      # vnm_strdict_concat_affix calls and the ids they covered, over every (prefix, suffix)
+        self._paired = {}          # (id(other dictionary), prefix, sep, suffix) -> PairTable
 
     @property
     def on_device(self) -> bool:
@@ -356,10 +418,10 @@ class KeyDictionary:
                                       "dictionaries are the string and binary types")
 
     @staticmethod
-    def _pair_ref(cache, other):
+    def _pair_ref(cache, other, key=None):
         """A weak reference to `other` that drops `other`'s entry (and its device tables) from `cache` when `other` dies."""
         import weakref
-        key = id(other)
+        key = id(other) if key is None else key
 
         def drop(ref):
             entry = cache.get(key)
@@ -455,6 +517,76 @@ class KeyDictionary:
         row (NULL stays NULL), with `.dictionary` the derived dictionary, so every operator takes it as the string column it is."""
         derived, table = self.mapped(fn)
         return self._gather(codes_col, table.values_ptr, table, dictionary=derived)
+
+    def _concat_check(self):
+        if not self._device:
+            raise NotImplementedError(f"no GPU lowering for concat() over a {self.type} column: only string columns keep their dictionaries on the device")
+        t = self.value_type
+        if not (pa.types.is_string(t) or pa.types.is_large_string(t)):
+            raise TypeError(f"concat() needs a string column, not {self.type}")
+
+    def affixed(self, prefix: bytes, suffix: bytes):
+        """concat(prefix, c, suffix) of this dictionary (ConcatFunction, functions.py:250-276; either literal may be empty): (the
+        DERIVED dictionary, an int32 DeviceColumn `code here -> code there`, the derived code a NULL row gets).  A function of the
+        value alone, so each distinct value is written ONCE on the device -- prefix + the value without trailing NULs + suffix,
+        vnm_strdict_concat_affix -- and found or inserted in the derived dictionary; NULL is the value "None".  One derived
+        dictionary per (dictionary, prefix, suffix), the same object for the life of this one, extended only when this one gained
+        a value (`affix_launches`, `affix_ids_mapped`).  Refusals as mapped(): binary TypeError, host route NotImplementedError."""
+        self._concat_check()
+        top = self._id_count()
+        entry = self._affixed.get((prefix, suffix))
+        if entry is None:
+            entry = self._affixed[(prefix, suffix)] = _Affix(KeyDictionary(pa.string()), _IdTable(top, 4))
+        derived, table = entry.derived, entry.table
+        if entry.null_code < 0 or (top > table.covered and entry.mine != self._n_values):
+            table.reserve(top)
+            null_code = ctypes.c_int32(-2)
+            rc = L.lib().vnm_strdict_concat_affix(self.handle(), derived.handle(), prefix, len(prefix), suffix, len(suffix), table.covered,
+                                                  table.buf.ptr, ctypes.byref(null_code), None)
+            self.affix_launches += 1
+            self.affix_ids_mapped += top - table.covered
+            message = L.last_error() if rc != 0 else None
+            if derived._h is not None:
+                derived.absorb_new()
+            if rc != 0:
+                raise L.VinumHipError(message)
+            table.covered, entry.mine, entry.null_code = top, self._n_values, int(null_code.value)
+        return derived, table.column(pa.int32()), entry.null_code
+
+    def affixed_column(self, prefix: bytes, suffix: bytes, codes_col):
+        """concat(prefix, column, suffix) over a column of THIS dictionary's codes: table[code] per row, the NULL image's code where
+        the row is NULL (by validity bit or code -1); no validity -- concat() is never NULL -- and `.dictionary` the derived one."""
+        from .device import DeviceBuffer, DeviceColumn
+        derived, table, null_code = self.affixed(prefix, suffix)
+        n = codes_col.length
+        out = DeviceBuffer(max(n, 1) * 4)
+        if n:
+            L.check(L.lib().vnm_strdict_gather_codes(codes_col.values_ptr + codes_col.offset * 4, codes_col.validity_ptr, codes_col.offset,
+                                                     table.values_ptr, table.length, n, null_code, out.ptr, None))
+        return DeviceColumn(out, None, 0, n, pa.int32(), keep=(table, codes_col), dictionary=derived)
+
+    def paired(self, other, prefix: bytes, sep: bytes, suffix: bytes) -> PairTable:
+        """The pair table of concat(prefix, a, sep, b, suffix) with this dictionary on the left and `other` on the right (which may
+        be this one): one per (pair of dictionaries, literals), kept here as long as both live."""
+        self._concat_check()
+        if not isinstance(other, KeyDictionary):
+            raise NotImplementedError(f"no GPU lowering for concat() with a {type(other).__name__} dictionary")
+        other._concat_check()
+        key = (id(other), prefix, sep, suffix)
+        entry = self._paired.get(key)
+        if entry is None or entry.ref() is not other:
+            entry = self._paired[key] = PairTable(prefix, sep, suffix)
+            entry.ref = self._pair_ref(self._paired, other, key)
+        return entry
+
+    def pair_column(self, other, prefix: bytes, sep: bytes, suffix: bytes, col_a, col_b):
+        """concat(prefix, a, sep, b, suffix) per row over columns of this dictionary's and `other`'s codes (PairTable.column)"""
+        return self.paired(other, prefix, sep, suffix).column(self, other, col_a, col_b)
+
+    @property
+    def pair_tables(self):
+        """the PairTables with this dictionary on the left (their counters: pair_launches, pairs_concatenated, rehashes)"""
+        return list(self._paired.values())
 
     def values_by_code(self) -> pa.Array:
         """The dictionary as an array indexed by CODE (a code the device never handed out: NULL) -- what the ranks exchange to build

@@ -12,7 +12,8 @@ A query is a dict (see tests/golden/planner_cases.py):
     expr := the prefix tuples of vinum_amd.expr (the one definition of the node forms), with ("fn", name, arg...) for the
             aggregate functions count_star / count / sum / avg / min / max and the numeric built-in scalar functions
             (SCALAR_FN_NAMES: abs, sqrt, sin, ..., to_int, pi, e and their np. spellings) and upper / lower of a string
-            column, which are per-row expressions wherever they appear, like any operator; LIKE / NOT LIKE against a utf8 / large_utf8 column (planner.py:189-193)
+            column, which are per-row expressions; concat is the operator node ("concat", x, ...) or ("||", a, b) over string
+            columns, such nodes, upper / lower and literals (("lit", s), numbers), and they are per-row expressions wherever they appear, like any operator; LIKE / NOT LIKE against a utf8 / large_utf8 column (planner.py:189-193)
             may stand in WHERE, HAVING, the SELECT list (a uint8 mask) and aggregate arguments alike.
 
 What the planner does with the aggregate part mirrors planner.py:380-469:
@@ -45,12 +46,16 @@ SCALAR_FN_NAMES.update({"upper": "upper", "lower": "lower"})
 
 def _t(e):
     """JSON lists -> tuples (hashable, and what ops.compile_expr takes); IN value lists stay lists.  A built-in scalar
-    function ("fn", "sqrt", x) becomes the operator node ("sqrt", x); aggregate and unknown names stay "fn" nodes."""
+    function ("fn", "sqrt", x) becomes the operator node ("sqrt", x); aggregate and unknown names stay "fn" nodes.  concat is written
+    as the operator node it is -- ("concat", a, ("lit", "-"), 7, b) or ("||", a, b), literals as they are --; the "fn" spelling of
+    that name stays the unknown function it has always been to this planner."""
     if isinstance(e, (list, tuple)) and e and isinstance(e[0], str):
         if e[0] in E.IN_OPS:
             return (e[0], _t(e[1]), tuple(e[2]))
         if e[0] == "fn" and len(e) > 1 and isinstance(e[1], str) and e[1].lower() in SCALAR_FN_NAMES:
             return tuple([SCALAR_FN_NAMES[e[1].lower()]] + [_t(x) for x in e[2:]])
+        if e[0] == "||":                                      # SQLExpression.CONCAT: the same function as concat()
+            return tuple(["concat"] + [_t(x) for x in e[1:]])
         return tuple([e[0]] + [_t(x) for x in e[1:]])
     return e
 
@@ -65,6 +70,13 @@ def _case_by_type(e, schema):
             t = schema.field(n[1]).type
             if pa.types.is_integer(t) or pa.types.is_floating(t) or pa.types.is_temporal(t):
                 raise ValueError(f"unknown aggregate function {n[0]!r}: upper() / lower() take a string column, {n[1]!r} is {t}")
+        # concat(x, ...): a numeric or temporal column would need to_str on the device, which does not exist -- refused here, by name
+        if isinstance(n, tuple) and n and n[0] == "concat":
+            for x in n[1:]:
+                if isinstance(x, str) and x in schema.names:
+                    t = schema.field(x).type
+                    if pa.types.is_integer(t) or pa.types.is_floating(t) or pa.types.is_temporal(t) or pa.types.is_boolean(t) or pa.types.is_decimal(t):
+                        raise TypeError(f"concat() needs string columns and literals, {x!r} is {t} (no to_str on the device)")
 
 
 def _is_fn(e) -> bool:
