@@ -602,6 +602,40 @@ void vnm_strpair_destroy(vnm_strpair* h);
 int vnm_strpair_concat(vnm_strpair* h, vnm_strdict* a, vnm_strdict* b, vnm_strdict* dst, const uint8_t* sep, int64_t sep_len, const vnm_dcol* codes_a,
                        const vnm_dcol* codes_b, int64_t length, int32_t* out_codes, void* stream);
 int vnm_strpair_stats(vnm_strpair* h, int64_t* out6, void* stream);
+/* to_str() (StringCastFunction, vinum/core/functions.py:189-193, an AbstractCastFunction, functions.py:148-193: np.array(column,
+ * dtype='str'), NumPy's text of the value) over an integer, date32 or timestamp column: the table of vnm_strpair keyed by the VALUE.
+ * A fixed-width value widened to 64 bits (by sign; by zero extension for the unsigned types) is itself the key, so the same find /
+ * rehash / store-codes / gather passes serve, a formatter runs ONCE per distinct value (vnm_tostr.hpp: ts_room, then ts_write with
+ * every store held against that room; the longest image is 29 bytes) and the spans go through dst's encode.  No string is built per
+ * row: a row costs one load of its value, one probe and one 4-byte gather.
+ *   VNM_TOSTR_INT / VNM_TOSTR_UINT   decimal digits, '-' in front of a negative one; the width and signedness are the column's vnm_type
+ *                                    (VNM_I8 .. VNM_I64 for INT, VNM_U8 .. VNM_U64 for UINT)
+ *   VNM_TOSTR_DATE32                 a VNM_I32 column of days: datetime64[D] text, YYYY-MM-DD, the year as C's %04d with the sign inside
+ *                                    the width (0000-01-01, -001-12-31, 10000-01-01, -5877641-06-23)
+ *   VNM_TOSTR_TIMESTAMP_S .. _NS     a VNM_I64 column: YYYY-MM-DDTHH:MM:SS and .fff / .ffffff / .fffffffff at full width; division floors
+ *                                    (-1 ns is 1969-12-31T23:59:59.999999999); years of unit s reach 12 digits; INT64_MIN prints NaT.
+ *                                    A zone-aware column prints its UTC instant (the stored value), as the reference does
+ * A NULL row -- a cleared validity bit -- gives the four bytes "None", for every kind, and no validity comes out: the rule concat()
+ * has for its operands.  This DEPARTS from the reference for integers (with a NULL in the batch it converts the column to float64
+ * first and prints "1.0" / "nan", so one column prints differently from batch to batch) and for dates (it prints "NaT").
+ * The empty marker of the table is the all-ones key, which is the value -1 / UINT64_MAX: that value and NULL live in two side slots
+ * outside the probed range (slot indices `slots` and `slots + 1`), each claimed by one CAS on a flag word; both survive a rehash.
+ * vnm_strval_to_str(h, dst, values, length, out_codes, stream): `values` is a DEVICE column of `length` rows (values, validity or
+ * NULL, Arrow offset); out_codes[i] (DEVICE, `length` int32s) = dst's code of the text of row i.  4 rows per lane, one 4 / 8 / 16 /
+ * 32-byte access where row 0's address is a multiple of 4 widths and out_codes of 16 bytes, scalar loads otherwise.  A column type
+ * that does not fit the kind (a float column; a date kind over a VNM_I64 column) is refused, so is a type other than the first
+ * call's.  Returns when out_codes is written; vnm_strdict_last_new / _fetch_new on dst return the values the call added.  dst may
+ * hold values from other sources: a text it already has keeps its code.  Every call with rows leaves the route note
+ * "to_str:value_table".  The initial slot count is $VNM_STRPAIR_SLOTS, as for vnm_strpair.
+ * vnm_strval_stats: as vnm_strpair_stats: out6 = {calls with length > 0, values formatted (= distinct values seen, NULL and the
+ * all-ones value included), rehashes, slots, occupied slots (the side slots included), occupied slots WITHOUT a code}. */
+enum vnm_tostr_kind { VNM_TOSTR_INT = 0, VNM_TOSTR_UINT, VNM_TOSTR_DATE32, VNM_TOSTR_TIMESTAMP_S, VNM_TOSTR_TIMESTAMP_MS, VNM_TOSTR_TIMESTAMP_US,
+                      VNM_TOSTR_TIMESTAMP_NS };
+typedef struct vnm_strval vnm_strval;
+vnm_strval* vnm_strval_create(int kind);
+void vnm_strval_destroy(vnm_strval* h);
+int vnm_strval_to_str(vnm_strval* h, vnm_strdict* dst, const vnm_dcol* values, int64_t length, int32_t* out_codes, void* stream);
+int vnm_strval_stats(vnm_strval* h, int64_t* out6, void* stream);
 /* A dictionary-typed Arrow column (dictionary<intN, utf8 | large_utf8 | binary | large_binary>): the batch dictionary's indices ->
  * codes of the running dictionary.  The caller runs the batch dictionary's VALUES through vnm_strdict_encode and uploads the result
  * as code_of_index (n_values int32s on the DEVICE; -1 = a NULL value), so only n_values strings are hashed, not one per row.

@@ -139,6 +139,10 @@ PROTOTYPES = {
     "vnm_strpair_destroy": (None, [c_void]),
     "vnm_strpair_concat": (c_int, [c_void, c_void, c_void, c_void, c_void, c_i64, c_void, c_void, c_i64, c_void, c_void]),
     "vnm_strpair_stats": (c_int, [c_void, c_void, c_void]),
+    "vnm_strval_create": (c_void, [c_int]),
+    "vnm_strval_destroy": (None, [c_void]),
+    "vnm_strval_to_str": (c_int, [c_void, c_void, c_void, c_i64, c_void, c_void]),
+    "vnm_strval_stats": (c_int, [c_void, c_void, c_void]),
     "vnm_strdict_remap_indices": (c_int, [c_void, c_void, c_i64, c_void, c_void, c_void, c_void]),
     "vnm_dict_take_compact": (c_int, [c_void, c_void, c_i64, c_i64, c_int, c_void, c_void, c_void, c_void, c_void, c_void]),
     "vnm_like_compile": (c_int, [c_void, c_i64, c_void, c_void]),

@@ -161,7 +161,13 @@ class IntCastFunction(AbstractCastFunction):
     type = "int"
 
 
-_CAST_SPEC = {"bool": "to_bool", "float": "to_float", "int": "to_int"}
+class StringCastFunction(AbstractCastFunction):
+    """functions.py:189-193: np.array(x, dtype='str'), NumPy's text of the value."""
+    type = "str"
+
+
+_CAST_SPEC = {"bool": "to_bool", "float": "to_float", "int": "to_int", "str": "to_str"}
+_CAST_CLASSES = ("BoolCastFunction", "FloatCastFunction", "IntCastFunction", "StringCastFunction")
 
 
 class LikeFunction(VectorizedExpression):
@@ -201,8 +207,8 @@ _CASE_SPEC = {"UpperStringFunction": "upper", "LowerStringFunction": "lower"}
 _STRING_FN_NAMES = ("upper", "lower", "concat")       # their "fn" spelling builds what it always built; the operator node builds the class
 EXPRESSION_FUNCTIONS[SQLExpression.CONCAT] = (ConcatFunction, FunctionType.CLASS)       # expressions.py:51
 
-# the numeric part of _default_functions_registry, with the same callables (math constants: the lambdas themselves), and the three
-# string functions that run on the device
+# the numeric part of _default_functions_registry, with the same callables (math constants: the lambdas themselves), the three
+# string functions and the four casts that run on the device
 FUNCTIONS_REGISTRY = {
     "upper": (UpperStringFunction, FunctionType.CLASS),
     "lower": (LowerStringFunction, FunctionType.CLASS),
@@ -210,6 +216,7 @@ FUNCTIONS_REGISTRY = {
     "to_bool": (BoolCastFunction, FunctionType.CLASS),
     "to_float": (FloatCastFunction, FunctionType.CLASS),
     "to_int": (IntCastFunction, FunctionType.CLASS),
+    "to_str": (StringCastFunction, FunctionType.CLASS),
     "abs": (np.absolute, FunctionType.NUMPY),
     "sqrt": (np.sqrt, FunctionType.NUMPY),
     "cos": (np.cos, FunctionType.NUMPY),
@@ -326,7 +333,7 @@ def lower(node, index: Optional[Dict[int, str]] = None):
             if like is not None:
                 return like
         cast = getattr(type(node), "type", None)
-        if fn is None and cast in _CAST_SPEC and type(node).__name__ in ("BoolCastFunction", "FloatCastFunction", "IntCastFunction"):
+        if fn is None and cast in _CAST_SPEC and type(node).__name__ in _CAST_CLASSES:
             args = [lower(a, index) for a in node.arguments]   # AbstractCastFunction (functions.py:148-162)
             return (_CAST_SPEC[cast],) + tuple(args)
         # UpperStringFunction / LowerStringFunction (functions.py:279-298), by QUALIFIED name: the class the reference (or this
@@ -343,8 +350,8 @@ def lower(node, index: Optional[Dict[int, str]] = None):
         if fn is None or id(fn) not in index:
             raise NotImplementedError(f"no GPU lowering for {fn if fn is not None else type(node).__name__!r}: the numeric "
                                       "operators and the built-ins abs, sqrt, sin, cos, tan, log, log2, log10, power, pi, e, "
-                                      "to_int, to_float, to_bool, upper / lower / concat of string columns and LIKE / NOT LIKE "
-                                      "against a string literal run on the GPU; UDFs, to_str, the datetime functions and other "
+                                      "to_int, to_float, to_bool, to_str, upper / lower / concat of string columns and LIKE / NOT "
+                                      "LIKE against a string literal run on the GPU; UDFs, the datetime functions and other "
                                       "np.* functions do not")
         sql = index[id(fn)]
         args = [lower(a, index) for a in node.arguments]

@@ -29,6 +29,8 @@ class DeviceRecordBatch:
                 cols[n] = DeviceColumn.from_arrow(arr, dictionary=dictionaries[n])
             else:
                 cols[n] = DeviceColumn.from_arrow(arr)
+                if dictionaries is not None:      # (where the scan's to_str(n) table lives: keydict.ValueTable.of)
+                    cols[n].value_tables = dictionaries.setdefault(("to_str", n), {})
         return DeviceRecordBatch(cols, batch.num_rows)
 
     @property

@@ -4,6 +4,7 @@ path on which the operators evaluate lowered expressions (project_lowered, used_
 DeviceColumn; every rewrite returns (expression, extra), `extra` holding the tables, rank and mask columns the result reads by name."""
 from .. import expr as E
 from .. import ops
+from ..keydict import ValueTable, to_str_kind
 
 
 def _is_dict(x, columns) -> bool:
@@ -15,8 +16,13 @@ def value_type_of(dictionary):
     return getattr(dictionary, "value_type", dictionary.type)
 
 
+def pa_is_string(t) -> bool:
+    import pyarrow as pa
+    return pa.types.is_string(t) or pa.types.is_large_string(t)
+
+
 CASE_FNS = ("upper", "lower")
-STRING_FNS = CASE_FNS + ("concat",)
+STRING_FNS = CASE_FNS + ("concat", "to_str")
 
 
 def with_derived(columns, extra):
@@ -50,9 +56,14 @@ def lower_case_functions(expr, columns, extra=None):
         table, the bytes written once per distinct pair); three or more fold left as the reference does, the first step's derived
         dictionary being the second step's left one, the literal in front of the first column and the one behind the last going
         into the first / last step's byte writer.  The result has no validity: a NULL operand is "None".
-    A numeric or temporal column raises TypeError naming it (the reference would print the numbers as text: not restated), a
+      * to_str(x) (StringCastFunction, functions.py:189-193: np.array(x, dtype='str')): over an integer, date32 or timestamp
+        column a function of the row's VALUE (keydict.ValueTable.column: a persistent device value table hanging in the scan's
+        per-name registry, each distinct value formatted once, a row one probe; a NULL row is "None", no validity); over a string
+        column or another such node the value without trailing NULs, which is the empty affix (affixed_column(b"", b"", col)).
+    A BARE numeric or temporal column under upper / lower / concat raises TypeError naming it (write to_str(v)), a
     concat() of literals alone and any other operand expression NotImplementedError; a binary column TypeError and a host-route
-    dictionary NotImplementedError (KeyDictionary.mapped / affixed / paired)."""
+    dictionary NotImplementedError (KeyDictionary.mapped / affixed / paired).  to_str() of a float, decimal, date64, time, duration,
+    boolean or binary column raises TypeError naming the column and its type, of an expression or a literal NotImplementedError."""
     extra = {} if extra is None else extra
 
     def operand(fn, x):
@@ -118,11 +129,39 @@ def lower_case_functions(expr, columns, extra=None):
             name, col = out, extra[out]
         return name
 
+    def to_str(e):
+        if len(e) != 2:
+            raise NotImplementedError(f"no GPU lowering for to_str() with {len(e) - 1} operand(s)")
+        x = e[1]
+        if isinstance(x, tuple) and x and x[0] in STRING_FNS:
+            x = f(x)
+        cols = with_derived(columns, extra)
+        if not isinstance(x, str) or x not in cols:
+            raise NotImplementedError(f"no GPU lowering for to_str() over {x!r}: the operand must be a column or upper() / lower() / concat() / "
+                                      "to_str() of one")
+        c = cols[x]
+        name = f"__to_str_{x}"
+        if name in extra:
+            return name
+        if c.dictionary is None:
+            to_str_kind(c.arrow_type, x)                  # (TypeError for a float, decimal, time ... column, naming it)
+            extra[name] = ValueTable.of(c, x).column(c)
+            return name
+        affixed_column = getattr(c.dictionary, "affixed_column", None)
+        if affixed_column is None:         # (a dictionary object that cannot concatenate: refused where the node is compiled)
+            return e
+        if not getattr(c.dictionary, "on_device", True) or not (pa_is_string(value_type_of(c.dictionary))):
+            raise TypeError(f"to_str() takes an integer, date32, timestamp or string column, {x!r} is {value_type_of(c.dictionary)}")
+        extra[name] = affixed_column(b"", b"", c)
+        return name
+
     def f(e):
         if e[0] in CASE_FNS:
             return case_fn(e)
         if e[0] == "concat":
             return concat(e)
+        if e[0] == "to_str":
+            return to_str(e)
         return None
     return E.rewrite(expr, f), extra
 

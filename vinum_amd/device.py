@@ -107,10 +107,15 @@ class DeviceColumn:
         self.vnm_type, self.flags = (L.OUT_F16, 0) if pa.types.is_float16(arrow_type) else physical_type(arrow_type)
         self._keep = keep  # anything that must outlive the raw pointers (torch tensors)
         self.dictionary = dictionary
+        # a numeric / temporal column of a scan: the scan's per-name registry entry its to_str() table hangs in (keydict.ValueTable.of),
+        # so a value keeps its code from batch to batch; None for a column built by hand, which gets a table per call
+        self.value_tables = None
 
     def like(self, values, validity, offset, length) -> "DeviceColumn":
         """A column of the same logical type over other buffers (filter / take / slice outputs keep the dictionary)."""
-        return DeviceColumn(values, validity, offset, length, self.arrow_type, dictionary=self.dictionary)
+        out = DeviceColumn(values, validity, offset, length, self.arrow_type, dictionary=self.dictionary)
+        out.value_tables = self.value_tables
+        return out
 
     # -- constructors -------------------------------------------------------------------------------
     @staticmethod
@@ -201,8 +206,10 @@ class DeviceColumn:
         """View of rows [offset, offset + length): same HBM buffers, Arrow offset moved (no copy)."""
         offset = max(0, min(int(offset), self.length))
         length = max(0, min(int(length), self.length - offset))
-        return DeviceColumn(self._values, self._validity, self.offset + offset, length, self.arrow_type, keep=(self, self._keep),
-                            dictionary=self.dictionary)
+        out = DeviceColumn(self._values, self._validity, self.offset + offset, length, self.arrow_type, keep=(self, self._keep),
+                           dictionary=self.dictionary)
+        out.value_tables = self.value_tables
+        return out
 
     def to_numpy(self) -> np.ndarray:
         w = _WIDTH[self.vnm_type]

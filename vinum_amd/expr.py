@@ -17,6 +17,8 @@ table of where a form keeps its sub-expressions: operands(), with_operands() and
     ("upper" | "lower", string column or another such node)  core.lowering turns it into a derived dictionary-coded column
     ("concat", x, ...)              x: string columns, such nodes, upper / lower nodes, ("lit", s) and numbers; core.lowering turns
                                     it into a derived dictionary-coded column (never NULL: a NULL operand is "None")
+    ("to_str", column)              an integer, date32, timestamp or string column, or another string-function node; core.lowering
+                                    turns it into a derived dictionary-coded column (never NULL: a NULL row is "None")
     ("fn", name, arg...)            a function by name (planner: the aggregates); name is no operand
 
 "lit" and "strong" nodes are leaves.  Pass-through nodes keep the spelling they came with (`(">", "v", "w")` stays that):

@@ -204,6 +204,7 @@ class GpuCsvReader:
                     col.dictionary = self._dictionary(n)
                 else:
                     col = _OwnedColumn(out[i], self.schema.field(n).type)
+                    col.value_tables = self._dicts.setdefault(("to_str", n), {})
                 owned.append(col)
             if fb[k] or fb[k + 1]:          # a newline inside a quoted value / ragged or empty rows: the whole block goes through pyarrow (which raises on ragged rows)
                 whole_block_on_host = True
@@ -290,6 +291,7 @@ class _ArrowBatchSource:
             arr = b.column(b.schema.names.index(n))
             if is_supported(arr.type):
                 cols[n] = _stage_arrow_column(arr, arr.type)
+                cols[n].value_tables = self._dicts.setdefault(("to_str", n), {})
             else:
                 from .keydict import KeyDictionary
                 if n not in self._dicts:

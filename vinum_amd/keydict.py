@@ -1,6 +1,7 @@
 """KeyDictionary: the running dictionary of one non-numeric column (value -> int32 code) and the device tables derived from it,
 one entry per dictionary id: LIKE matches, translations into and joint ranks with another dictionary, upper() / lower() maps,
-concat() with literals; and the pair tables of concat() over two columns.
+concat() with literals; the pair tables of concat() over two columns; and the value tables of to_str() over a numeric or temporal
+column (ValueTable: no KeyDictionary of its own, the column's VALUE is the key).
 Importable without the shared library, like vinum_lib (which re-exports KeyDictionary and device_value_type)."""
 import ctypes
 from dataclasses import dataclass
@@ -129,6 +130,85 @@ class PairTable:
         if rc != 0:
             raise L.VinumHipError(message)
         return DeviceColumn(out, None, 0, n, pa.int32(), keep=(self,), dictionary=self.derived)
+
+
+TOSTR_INT, TOSTR_UINT, TOSTR_DATE32, TOSTR_TIMESTAMP_S, TOSTR_TIMESTAMP_MS, TOSTR_TIMESTAMP_US, TOSTR_TIMESTAMP_NS = range(7)     # enum vnm_tostr_kind
+
+
+def to_str_kind(t, name=None):
+    """The vnm_tostr_kind of a column of Arrow type `t` under to_str() (StringCastFunction, functions.py:189-193): the integers,
+    date32 and the four timestamp units (a zone-aware one prints its UTC instant, the stored value, as the reference does).
+    Everything else raises TypeError naming the column and its type: floats (shortest round-trip digits are a piece of work of
+    their own), decimal, date64, time32 / time64, duration, boolean and binary."""
+    T = pa.types
+    if T.is_signed_integer(t):
+        return TOSTR_INT
+    if T.is_unsigned_integer(t):
+        return TOSTR_UINT
+    if T.is_date32(t):
+        return TOSTR_DATE32
+    if T.is_timestamp(t):
+        return {"s": TOSTR_TIMESTAMP_S, "ms": TOSTR_TIMESTAMP_MS, "us": TOSTR_TIMESTAMP_US, "ns": TOSTR_TIMESTAMP_NS}[t.unit]
+    raise TypeError(f"to_str() takes an integer, date32, timestamp or string column, {name!r} is {t}" if name is not None else
+                    f"to_str() takes an integer, date32, timestamp or string column, not {t}")
+
+
+class ValueTable:
+    """The device value table (vnm_strval) of to_str(v) over an integer, date32 or timestamp column and the dictionary derived from
+    it: value -> code in `derived`, alive across batches so a value keeps its code and is formatted once.  `launches`,
+    `values_formatted` (= the distinct values seen, NULL and the all-ones value included: string bytes are written once per value,
+    never per row), `rehashes`, `slots`, `occupied` and `half_written` (occupied slots without a code: 0 after every call) are read
+    from the device object (stats())."""
+
+    def __init__(self, kind: int):
+        self.kind = kind
+        self.derived = KeyDictionary(pa.string())
+        self._h = L.lib().vnm_strval_create(kind)
+        if not self._h:
+            raise RuntimeError(L.last_error())
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                L.lib().vnm_strval_destroy(h)
+            except Exception:
+                pass
+
+    @staticmethod
+    def of(col, name=None) -> "ValueTable":
+        """the table of column `col`: the one hanging in its scan's per-name registry (DeviceColumn.value_tables), made on first
+        use; a column built by hand gets a table for this call only"""
+        kind = to_str_kind(col.arrow_type, name)
+        tables = col.value_tables if col.value_tables is not None else {}
+        key = (kind, col.vnm_type)
+        if key not in tables:
+            tables[key] = ValueTable(kind)
+        return tables[key]
+
+    def stats(self) -> dict:
+        out = (ctypes.c_int64 * 6)()
+        L.check(L.lib().vnm_strval_stats(self._h, out, None))
+        return dict(zip(("launches", "values_formatted", "rehashes", "slots", "occupied", "half_written"), (int(v) for v in out)))
+
+    launches = property(lambda self: self.stats()["launches"])
+    values_formatted = property(lambda self: self.stats()["values_formatted"])
+    rehashes = property(lambda self: self.stats()["rehashes"])
+
+    def column(self, col):
+        """the codes of to_str(col) per row: an int32 DeviceColumn WITHOUT validity (a NULL row is "None"), its `.dictionary` the
+        derived dictionary"""
+        from .device import DeviceBuffer, DeviceColumn
+        n = col.length
+        out = DeviceBuffer(max(n, 1) * 4)
+        v = col.dcol()
+        rc = L.lib().vnm_strval_to_str(self._h, self.derived.handle(), ctypes.byref(v), n, out.ptr, None)
+        message = L.last_error() if rc != 0 else None
+        if self.derived._h is not None and n:
+            self.derived.absorb_new()
+        if rc != 0:
+            raise L.VinumHipError(message)
+        return DeviceColumn(out, None, 0, n, pa.int32(), keep=(self, col), dictionary=self.derived)
 
 
 class KeyDictionary:

@@ -11,8 +11,8 @@ A query is a dict (see tests/golden/planner_cases.py):
     order_by   [expr]            sort_order ["ASC" | "DESC"]   limit int | None   offset int
     expr := the prefix tuples of vinum_amd.expr (the one definition of the node forms), with ("fn", name, arg...) for the
             aggregate functions count_star / count / sum / avg / min / max and the numeric built-in scalar functions
-            (SCALAR_FN_NAMES: abs, sqrt, sin, ..., to_int, pi, e and their np. spellings) and upper / lower of a string
-            column, which are per-row expressions; concat is the operator node ("concat", x, ...) or ("||", a, b) over string
+            (SCALAR_FN_NAMES: abs, sqrt, sin, ..., to_int, pi, e and their np. spellings), upper / lower of a string
+            column and to_str of an integer, date32, timestamp or string column, which are per-row expressions; concat is the operator node ("concat", x, ...) or ("||", a, b) over string
             columns, such nodes, upper / lower and literals (("lit", s), numbers), and they are per-row expressions wherever they appear, like any operator; LIKE / NOT LIKE against a utf8 / large_utf8 column (planner.py:189-193)
             may stand in WHERE, HAVING, the SELECT list (a uint8 mask) and aggregate arguments alike.
 
@@ -32,6 +32,7 @@ from .core import (AggregateFunction, AggregateOperator, FileReaderOperator, Fil
                    ProjectOperator, SliceOperator, SortOperator, TableReaderOperator)
 from . import expr as E
 from .expr import columns_of
+from .keydict import device_value_type, to_str_kind
 
 AGG_FUNCS = ("count_star", "count", "sum", "avg", "min", "max")     # vinum/core/functions.py:389-396
 # numeric part of _default_functions_registry (vinum/core/functions.py:353-387) and the `np.` spellings lookup_udf resolves
@@ -42,6 +43,8 @@ SCALAR_FN_NAMES.update({"np." + n: n for n in ("sqrt", "cos", "sin", "tan", "pow
 SCALAR_FN_NAMES["np.absolute"] = "abs"
 # the string built-ins that run on the device: a function of the column's dictionary (core.lowering.lower_case_functions)
 SCALAR_FN_NAMES.update({"upper": "upper", "lower": "lower"})
+# to_str (StringCastFunction, functions.py:189-193, 'to_str' at :358): a function of the column's VALUE (keydict.ValueTable)
+SCALAR_FN_NAMES["to_str"] = "to_str"
 
 
 def _t(e):
@@ -70,13 +73,20 @@ def _case_by_type(e, schema):
             t = schema.field(n[1]).type
             if pa.types.is_integer(t) or pa.types.is_floating(t) or pa.types.is_temporal(t):
                 raise ValueError(f"unknown aggregate function {n[0]!r}: upper() / lower() take a string column, {n[1]!r} is {t}")
-        # concat(x, ...): a numeric or temporal column would need to_str on the device, which does not exist -- refused here, by name
+        # to_str(x): the types without a formatter on the device (floats, decimal, date64, time, duration, boolean, binary) are refused
+        # here, naming the column (keydict.to_str_kind); an operand that is no column is refused by the lowering
+        if isinstance(n, tuple) and n and n[0] == "to_str" and len(n) == 2 and isinstance(n[1], str) and n[1] in schema.names:
+            t = schema.field(n[1]).type
+            dt = device_value_type(t)
+            if dt is None or pa.types.is_binary(dt) or pa.types.is_large_binary(dt):
+                to_str_kind(t, n[1])
+        # concat(x, ...): a BARE numeric or temporal column stays refused here, by name -- the explicit spelling is concat(to_str(x), ...)
         if isinstance(n, tuple) and n and n[0] == "concat":
             for x in n[1:]:
                 if isinstance(x, str) and x in schema.names:
                     t = schema.field(x).type
                     if pa.types.is_integer(t) or pa.types.is_floating(t) or pa.types.is_temporal(t) or pa.types.is_boolean(t) or pa.types.is_decimal(t):
-                        raise TypeError(f"concat() needs string columns and literals, {x!r} is {t} (no to_str on the device)")
+                        raise TypeError(f"concat() needs string columns and literals, {x!r} is {t} (write to_str({x}) for its text)")
 
 
 def _is_fn(e) -> bool:
