@@ -636,6 +636,40 @@ vnm_strval* vnm_strval_create(int kind);
 void vnm_strval_destroy(vnm_strval* h);
 int vnm_strval_to_str(vnm_strval* h, vnm_strdict* dst, const vnm_dcol* values, int64_t length, int32_t* out_codes, void* stream);
 int vnm_strval_stats(vnm_strval* h, int64_t* out6, void* stream);
+/* date() / datetime() / from_timestamp() (DateFunction / DatetimeFunction / TimestampFunction, vinum/core/functions.py:25-137:
+ * np.array(column, dtype='datetime64[unit]'), NumPy's ISO 8601 parser) -- the inverse of to_str().  Over a STRING column the function
+ * depends on the value alone: each distinct value is parsed ONCE on the device into a per-id table (vnm_dtparse.hpp has the grammar,
+ * the value rule and what is refused though NumPy takes it), and a row costs one code load and one 8-byte gather.
+ * vnm_strdict_parse_datetime: for every id in [id_begin, vnm_strdict_ids(h)) out_value_of_id[id] = the int64 value (days for
+ * VNM_UNIT_D, unit counts since 1970-01-01 otherwise; 0 unless the status is 0) and out_status_of_id[id] = 0 a value, 1 NULL (the
+ * empty string, "NaT" in any letter case: NumPy's NaT), 2 refused; an id never handed out gets status 2.  Both are DEVICE arrays of
+ * vnm_strdict_ids(h) entries and only that range is written, so a table kept across batches is extended with id_begin = the id count
+ * it covers.  One lane per value over the dictionary's heap; h is only read.  *out_first_refused_id (host; may be NULL) = the lowest
+ * id in the range that was HANDED OUT and refused, or -1: refused strings are data, the call itself succeeds, and whether a ROW
+ * holds such a value is the row pass's to say (a dictionary derived by concat() always holds the image of NULL, "None...", which
+ * no row may hold).  It reads that id back, so it returns when the tables are written.
+ * vnm_strdict_gather_temporal: the row pass.  out_values[i] = value_of_id[codes[i]] as int32 for out_width == 4 (date32) and as
+ * int64 for out_width == 8; row i is NULL in out_validity_bitmap (a DEVICE bitmap at bit offset 0, (n + 7) / 8 bytes, required) and
+ * its value 0 when its validity bit is clear (bit validity_offset + i; validity may be NULL), its code is negative, its code is at or
+ * past n_ids -- never an address -- or its id's status is 1.  A non-NULL row whose id's status is 2 keeps the table's 0 as a value
+ * and is reported: *out_first_refused_id (host; may be NULL) = the lowest such id, or -1 -- the caller raises naming the value.  codes points at row 0.  A lane takes 8 rows and writes ONE whole byte of the bitmap, which no other lane
+ * touches; the bits past n in the last byte and the bytes past (n + 7) / 8 are left as they were.  16-byte accesses where row 0 of
+ * codes / out_values is 16-byte aligned, scalar ones otherwise.  out_null_count (host; may be NULL): the NULL rows.  With either
+ * host pointer the call synchronises, without both it is one kernel on `stream`, launched asynchronously.
+ * vnm_temporal_rescale: date(ts_col) / datetime(col, unit) over a date32 (VNM_I32) or timestamp (VNM_I64) column: a change of unit.
+ * One of mul / div is 1.  div > 1 (to a coarser unit): the FLOOR of the division (-1 s is day -1), by NumPy's formula (v - (div - 1))
+ * / div for a negative v, whose subtraction wraps within div - 1 of INT64_MIN as NumPy's does.  mul > 1 (to a finer unit): the
+ * product, wrapping as NumPy's cast does (computed unsigned).  INT64_MIN in a VNM_I64 column with out_width 8 is NumPy's NaT and
+ * stays INT64_MIN.  With mul == div == 1 it is from_timestamp() over an integer column narrower than VNM_U64: the values widened
+ * to 64 bits (VNM_I8 .. VNM_U32 are taken; VNM_U64 and the float types are refused).  Rows [col->offset, col->offset + length) -> out_values[0 .. length) as int32 (out_width 4) or int64 (8); the
+ * caller passes the validity through.  One kernel on `stream`, launched asynchronously. */
+enum vnm_temporal_unit { VNM_UNIT_D = 0, VNM_UNIT_S, VNM_UNIT_MS, VNM_UNIT_US, VNM_UNIT_NS };
+int vnm_strdict_parse_datetime(vnm_strdict* h, int unit, int64_t id_begin, int64_t* out_value_of_id, uint8_t* out_status_of_id,
+                               int64_t* out_first_refused_id, void* stream);
+int vnm_strdict_gather_temporal(const int32_t* codes, const uint8_t* validity, int64_t validity_offset, const int64_t* value_of_id,
+                                const uint8_t* status_of_id, int64_t n_ids, int64_t n, int out_width, void* out_values, uint8_t* out_validity_bitmap,
+                                int64_t* out_null_count, int64_t* out_first_refused_id, void* stream);
+int vnm_temporal_rescale(const vnm_dcol* col, int64_t mul, int64_t div, int64_t length, int out_width, void* out_values, void* stream);
 /* A dictionary-typed Arrow column (dictionary<intN, utf8 | large_utf8 | binary | large_binary>): the batch dictionary's indices ->
  * codes of the running dictionary.  The caller runs the batch dictionary's VALUES through vnm_strdict_encode and uploads the result
  * as code_of_index (n_values int32s on the DEVICE; -1 = a NULL value), so only n_values strings are hashed, not one per row.

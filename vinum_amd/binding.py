@@ -203,7 +203,24 @@ class ConcatFunction(AbstractStringFunction):
         VectorizedExpression.__init__(self, arguments, function=np.char.add, is_numpy_func=True, is_binary_func=True)
 
 
+class DatetimeFunction(VectorizedExpression):
+    """Shape of functions.py:25-119: built as Cls(arguments) -- (x) or (x, Literal(unit)) --, `_function` is None, the work
+    (np.array(x, dtype='datetime64[unit]')) lives in `_expr_kernel`."""
+
+    def __init__(self, arguments: Iterable, shared_id: Optional[str] = None):
+        super().__init__(arguments)
+
+
+class DateFunction(DatetimeFunction):
+    """functions.py:122-128: unit D only."""
+
+
+class TimestampFunction(DatetimeFunction):
+    """functions.py:131-137: from_timestamp, units s / ms / us / ns, default s."""
+
+
 _CASE_SPEC = {"UpperStringFunction": "upper", "LowerStringFunction": "lower"}
+_TEMPORAL_SPEC = {"DateFunction": "date", "DatetimeFunction": "datetime", "TimestampFunction": "from_timestamp"}
 _STRING_FN_NAMES = ("upper", "lower", "concat")       # their "fn" spelling builds what it always built; the operator node builds the class
 EXPRESSION_FUNCTIONS[SQLExpression.CONCAT] = (ConcatFunction, FunctionType.CLASS)       # expressions.py:51
 
@@ -217,6 +234,9 @@ FUNCTIONS_REGISTRY = {
     "to_float": (FloatCastFunction, FunctionType.CLASS),
     "to_int": (IntCastFunction, FunctionType.CLASS),
     "to_str": (StringCastFunction, FunctionType.CLASS),
+    "date": (DateFunction, FunctionType.CLASS),
+    "datetime": (DatetimeFunction, FunctionType.CLASS),
+    "from_timestamp": (TimestampFunction, FunctionType.CLASS),
     "abs": (np.absolute, FunctionType.NUMPY),
     "sqrt": (np.sqrt, FunctionType.NUMPY),
     "cos": (np.cos, FunctionType.NUMPY),
@@ -340,6 +360,9 @@ def lower(node, index: Optional[Dict[int, str]] = None):
         # module) defines under that name at module level -- some other class whose __name__ was set to it is not that function
         if fn is None and type(node).__qualname__ in _CASE_SPEC and len(tuple(node.arguments)) == 1:
             return (_CASE_SPEC[type(node).__qualname__], lower(tuple(node.arguments)[0], index))
+        # DateFunction / DatetimeFunction / TimestampFunction (functions.py:25-137), by qualified name as above: (x) or (x, Literal(unit))
+        if fn is None and type(node).__qualname__ in _TEMPORAL_SPEC and 1 <= len(tuple(node.arguments)) <= 2:
+            return (_TEMPORAL_SPEC[type(node).__qualname__],) + tuple(lower(a, index) for a in node.arguments)
         # ConcatFunction (functions.py:250-276; `concat(...)` and `a || b` both build it), by qualified name AND by its shape: it
         # carries a callable (np.char.add) and folds as a binary function.  A VectorizedExpression that merely holds np.char.add is
         # not that function.
@@ -350,9 +373,9 @@ def lower(node, index: Optional[Dict[int, str]] = None):
         if fn is None or id(fn) not in index:
             raise NotImplementedError(f"no GPU lowering for {fn if fn is not None else type(node).__name__!r}: the numeric "
                                       "operators and the built-ins abs, sqrt, sin, cos, tan, log, log2, log10, power, pi, e, "
-                                      "to_int, to_float, to_bool, to_str, upper / lower / concat of string columns and LIKE / NOT "
-                                      "LIKE against a string literal run on the GPU; UDFs, the datetime functions and other "
-                                      "np.* functions do not")
+                                      "to_int, to_float, to_bool, to_str, upper / lower / concat of string columns, date / datetime / "
+                                      "from_timestamp and LIKE / NOT LIKE against a string literal run on the GPU; UDFs, now, "
+                                      "timedelta, is_busday and other np.* functions do not")
         sql = index[id(fn)]
         args = [lower(a, index) for a in node.arguments]
         if sql.startswith("fn:"):

@@ -4,6 +4,7 @@ path on which the operators evaluate lowered expressions (project_lowered, used_
 DeviceColumn; every rewrite returns (expression, extra), `extra` holding the tables, rank and mask columns the result reads by name."""
 from .. import expr as E
 from .. import ops
+from .. import keydict as K
 from ..keydict import ValueTable, to_str_kind
 
 
@@ -23,11 +24,14 @@ def pa_is_string(t) -> bool:
 
 CASE_FNS = ("upper", "lower")
 STRING_FNS = CASE_FNS + ("concat", "to_str")
+TEMPORAL_FNS = tuple(E.TEMPORAL_FNS)                # date, datetime, from_timestamp
+_DERIVED_TEMPORAL = "__temporal_"                   # the name prefix of the date32 / timestamp columns they derive
 
 
 def with_derived(columns, extra):
-    """`columns` plus the dictionary-coded columns a lowering has put into `extra` (lower_case_functions: upper(city) is a column)"""
-    derived = {n: c for n, c in extra.items() if getattr(c, "dictionary", None) is not None}
+    """`columns` plus the columns a lowering has put into `extra` that stand for a node (lower_case_functions: upper(city) is a
+    dictionary-coded column, date(d) a date32 column)"""
+    derived = {n: c for n, c in extra.items() if getattr(c, "dictionary", None) is not None or n.startswith(_DERIVED_TEMPORAL)}
     return {**columns, **derived} if derived else columns
 
 
@@ -63,7 +67,18 @@ def lower_case_functions(expr, columns, extra=None):
     A BARE numeric or temporal column under upper / lower / concat raises TypeError naming it (write to_str(v)), a
     concat() of literals alone and any other operand expression NotImplementedError; a binary column TypeError and a host-route
     dictionary NotImplementedError (KeyDictionary.mapped / affixed / paired).  to_str() of a float, decimal, date64, time, duration,
-    boolean or binary column raises TypeError naming the column and its type, of an expression or a literal NotImplementedError."""
+    boolean or binary column raises TypeError naming the column and its type, of an expression or a literal NotImplementedError.
+      * date(x) / datetime(x[, unit]) / from_timestamp(x[, unit]) (DateFunction / DatetimeFunction / TimestampFunction,
+        functions.py:25-137: np.array(x, dtype='datetime64[unit]')) become the name of a derived date32 / timestamp[unit] column
+        WITH validity and without a dictionary.  Over a string column or a string-function node it is a function of the VALUE
+        (KeyDictionary.parsed_column: each distinct value parsed once on the device, a row one lookup; '' and NaT are NULL; a value
+        the parser refuses raises ValueError naming it).  Over a date32 / timestamp column it is a change of unit
+        (keydict.rescaled_column; the column itself when the unit is its own), over an integer column under from_timestamp the
+        same values retyped (keydict.timestamp_column).  datetime(x) without a unit over a column is timestamp[s] -- the reference
+        lets NumPy pick the unit batch by batch.  Over a LITERAL the node folds into a ("temporal", value, unit) constant with
+        NumPy itself (expr.fold_temporal).  A comparison (BETWEEN too) with such a constant, or of two temporal operands of
+        different units, is aligned to the finer unit as NumPy does: the coarser side is multiplied by the factor.  A temporal
+        constant anywhere else -- alone in SELECT, under arithmetic -- raises NotImplementedError."""
     extra = {} if extra is None else extra
 
     def operand(fn, x):
@@ -133,7 +148,7 @@ def lower_case_functions(expr, columns, extra=None):
         if len(e) != 2:
             raise NotImplementedError(f"no GPU lowering for to_str() with {len(e) - 1} operand(s)")
         x = e[1]
-        if isinstance(x, tuple) and x and x[0] in STRING_FNS:
+        if isinstance(x, tuple) and x and x[0] in STRING_FNS + TEMPORAL_FNS:
             x = f(x)
         cols = with_derived(columns, extra)
         if not isinstance(x, str) or x not in cols:
@@ -155,6 +170,83 @@ def lower_case_functions(expr, columns, extra=None):
         extra[name] = affixed_column(b"", b"", c)
         return name
 
+    def temporal(e):
+        fn = e[0]
+        unit = E.temporal_unit_arg(e)                     # (ValueError for a unit the function does not list)
+        const = E.fold_temporal(e)
+        if const is not None:
+            return const
+        unit = unit or "s"
+        x = e[1]
+        if isinstance(x, tuple) and x and x[0] in STRING_FNS + TEMPORAL_FNS:
+            x = f(x)
+        cols = with_derived(columns, extra)
+        if not isinstance(x, str) or x not in cols:
+            raise NotImplementedError(f"no GPU lowering for {fn}() over {x!r}: the operand must be a column, upper() / lower() / concat() / to_str() "
+                                      "of one, or a literal")
+        c = cols[x]
+        name = f"{_DERIVED_TEMPORAL}{fn}_{unit}_{x}"
+        if name in extra:
+            return name
+        if c.dictionary is not None:
+            parsed_column = getattr(c.dictionary, "parsed_column", None)
+            if parsed_column is None:          # (a dictionary object that cannot parse: refused where the node is compiled)
+                return e
+            extra[name] = parsed_column(unit, c)
+            return name
+        kind = K.temporal_operand_kind(fn, c.arrow_type, x)        # (TypeError for a float, uint64, decimal ... column, naming it)
+        col = K.rescaled_column(c, unit) if kind == "rescale" else K.timestamp_column(c, unit)
+        if col is c:
+            return x
+        extra[name] = col
+        return name
+
+    def is_const(x):
+        return isinstance(x, tuple) and len(x) == 3 and x[0] == "temporal"
+
+    def unit_of(x):
+        """the unit of a temporal constant or of a date32 / timestamp column (derived ones included); None for anything else"""
+        if is_const(x):
+            return x[2]
+        cols = with_derived(columns, extra)
+        if isinstance(x, str) and x in cols and cols[x].dictionary is None:
+            return K.temporal_unit(cols[x].arrow_type)
+        return None
+
+    def in_unit(x, have, want):
+        k = K.UNITS_PER_DAY[want] // K.UNITS_PER_DAY[have]
+        if is_const(x):
+            v = x[1] * k
+            if not -2**63 <= v < 2**63:
+                raise OverflowError(f"the temporal constant {x[1]} [{have}] does not fit int64 in the unit {want!r} of the other operand")
+            return ("strong", v)
+        return x if k == 1 else ("mul", x, ("strong", k))
+
+    def lowered_operands(e):
+        return [E.rewrite(x, f) if isinstance(x, tuple) else x for x in e[1:]]
+
+    def compare(e):
+        a, b = lowered_operands(e)
+        ua, ub = unit_of(a), unit_of(b)
+        if not (is_const(a) or is_const(b)) and (ua is None or ub is None or ua == ub):
+            return E.with_operands(e, [a, b])
+        if is_const(a) and is_const(b):
+            raise NotImplementedError(f"no GPU lowering for the comparison of two temporal constants ({a!r}, {b!r}): there is no per-row work")
+        for x, u, const in ((a, ua, b), (b, ub, a)):
+            if u is None:
+                raise TypeError(f"cannot compare the temporal constant {const[1]} [{const[2]}] with {x!r}: only a date32 / timestamp column or "
+                                "date() / datetime() / from_timestamp() of a column")
+        want = max(ua, ub, key=K.TEMPORAL_UNITS.index)
+        return (e[0], in_unit(a, ua, want), in_unit(b, ub, want))
+
+    def between(e):
+        xs = lowered_operands(e)
+        units = [unit_of(x) for x in xs]
+        if any(is_const(x) for x in xs) or (all(units) and len(set(units)) > 1):
+            x, lo, hi = xs
+            return E.rewrite(("and", ("ge", x, lo), ("le", x, hi)) if e[0] == "between" else ("or", ("lt", x, lo), ("gt", x, hi)), f)
+        return E.with_operands(e, xs)
+
     def f(e):
         if e[0] in CASE_FNS:
             return case_fn(e)
@@ -162,8 +254,19 @@ def lower_case_functions(expr, columns, extra=None):
             return concat(e)
         if e[0] == "to_str":
             return to_str(e)
+        if e[0] in TEMPORAL_FNS:
+            return temporal(e)
+        if E.cmp_name(e[0]) and len(e) == 3:
+            return compare(e)
+        if e[0] in ("between", "not_between") and len(e) == 4:
+            return between(e)
         return None
-    return E.rewrite(expr, f), extra
+    out = E.rewrite(expr, f)
+    for n in E.nodes(out):
+        if is_const(n):
+            raise NotImplementedError(f"no GPU lowering for the temporal constant {n[1]} [{n[2]}] outside a comparison with a temporal column: "
+                                      "there is no per-row work (alone in SELECT), and arithmetic on temporal values is not built")
+    return out, extra
 
 
 def lower_like(expr, columns, extra=None):
@@ -300,7 +403,8 @@ def lower_literal_compares(expr, columns, extra=None):
 
 
 def lower_dictionary(expr, columns, extra=None):
-    """The four lowerings in their order: upper() / lower() / concat() -- whose results are string columns to the other three --, LIKE, then
+    """The four lowerings in their order: upper() / lower() / concat() / to_str() -- whose results are string columns to the other three -- and
+    date() / datetime() / from_timestamp() -- whose results are temporal columns --, LIKE, then
     the column pairs -- which refuse a numeric operand, so they run before the literals turn into codes and ranks -- then the
     literals; the last two only act where a dictionary-coded column is read at all."""
     expr, extra = lower_case_functions(expr, columns, extra)
@@ -319,10 +423,13 @@ def used_columns(exprs, columns, extra):
 
 def project_lowered(exprs, columns, length, scalar_length=None):
     """ops.project_many of `exprs` lowered into one shared `extra`; scalar_length: the length when none of them reads a column.
-    An expression that lowers to a column of `extra` -- upper(city): the derived column -- is that column, no program runs."""
+    An expression that lowers to a column -- upper(city): the derived column of `extra`; datetime(ts, 'ms') over a timestamp[ms] column:
+    the input column itself -- is that column, no program runs."""
     extra = {}
     exprs = [lower_dictionary(e, columns, extra)[0] for e in exprs]
-    computed = [e for e in exprs if not (isinstance(e, str) and e in extra)]
+    column_of = lambda e: extra[e] if e in extra else columns[e]
+    is_column = lambda e: isinstance(e, str) and (e in extra or e in columns)
+    computed = [e for e in exprs if not is_column(e)]
     used = used_columns(computed, columns, extra)
     res = iter(ops.project_many(computed, used, length=length if used or scalar_length is None else scalar_length) if computed else [])
-    return [extra[e] if (isinstance(e, str) and e in extra) else next(res) for e in exprs]
+    return [column_of(e) if is_column(e) else next(res) for e in exprs]

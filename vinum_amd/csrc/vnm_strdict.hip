@@ -1380,3 +1380,4 @@ int vnm_strdict_remap_indices(const vnm_dcol* indices, const int32_t* code_of_in
 }  // extern "C"
 
 #include "vnm_strconcat.inc"
+#include "vnm_datetime.inc"

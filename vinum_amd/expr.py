@@ -19,9 +19,17 @@ table of where a form keeps its sub-expressions: operands(), with_operands() and
                                     it into a derived dictionary-coded column (never NULL: a NULL operand is "None")
     ("to_str", column)              an integer, date32, timestamp or string column, or another string-function node; core.lowering
                                     turns it into a derived dictionary-coded column (never NULL: a NULL row is "None")
+    ("date", x)                     x: a string column or string-function node (parsed once per distinct value), a date32 / timestamp
+    ("datetime", x[, ("lit", unit)])  column (a change of unit), for from_timestamp an integer column (its values as timestamps), or a
+    ("from_timestamp", x[, ("lit", unit)])  literal.  core.lowering turns the node into a derived date32 / timestamp[unit] column WITH
+                                    validity ('' and NaT are NULL); units: date D; datetime D s ms us ns (default s over a column);
+                                    from_timestamp s ms us ns (default s).  The unit is no operand.  Over a literal the node folds
+                                    into a ("temporal", ...) constant (fold_temporal)
+    ("temporal", value, unit)       a date / timestamp constant: `value` days (unit D) or unit counts since 1970-01-01.  A leaf.  It
+                                    may only stand in a comparison (or BETWEEN) with a temporal operand: core.lowering aligns units
     ("fn", name, arg...)            a function by name (planner: the aggregates); name is no operand
 
-"lit" and "strong" nodes are leaves.  Pass-through nodes keep the spelling they came with (`(">", "v", "w")` stays that):
+"lit", "strong" and "temporal" nodes are leaves.  Pass-through nodes keep the spelling they came with (`(">", "v", "w")` stays that):
 an operator is canonicalised with cmp_name() only where it is matched.  A new operator is added to ops._EX (and to
 core.lowering._ARITHMETIC when it takes numbers); a new node FORM is a line above and, unless its operands are e[1:], in _OPERANDS.
 No ctypes, no library, no device: this module imports without them.
@@ -35,7 +43,8 @@ CMP_FLIP = {"eq": "eq", "ne": "ne", "lt": "gt", "le": "ge", "gt": "lt", "ge": "l
 IN_OPS = ("in", "not_in")
 # where the operands stand, by a node's first slot (the walkers slice with it themselves: operands() is a call more per node)
 _REST, _NONE = slice(1, None), slice(0, 0)
-_OPERANDS = {"lit": _NONE, "strong": _NONE, "in": slice(1, 2), "not_in": slice(1, 2), "fn": slice(2, None)}
+_OPERANDS = {"lit": _NONE, "strong": _NONE, "temporal": _NONE, "in": slice(1, 2), "not_in": slice(1, 2), "fn": slice(2, None),
+             "date": slice(1, 2), "datetime": slice(1, 2), "from_timestamp": slice(1, 2)}
 
 
 def cmp_name(op):
@@ -166,3 +175,48 @@ def fold(e):
             return ("strong", int(v))
         raise TypeError(f"a constant of type {v.dtype} is not supported")
     return transform(e, f)
+
+
+# The datetime built-ins (vinum/core/functions.py:25-137, registered at :376-379): name -> (the reference's class name, its UNITS in
+# increasing resolution, its default unit -- None: NumPy picks one from the text)
+TEMPORAL_FNS = {"date": ("DateFunction", ("D",), "D"), "datetime": ("DatetimeFunction", ("D", "s", "ms", "us", "ns"), None),
+                "from_timestamp": ("TimestampFunction", ("s", "ms", "us", "ns"), "s")}
+_NUMPY_UNITS = ("Y", "M", "W", "D", "h", "m", "s", "ms", "us", "ns")
+
+
+def temporal_unit_arg(e):
+    """The unit a date / datetime / from_timestamp node asks for: its ("lit", unit) argument checked against the function's list
+    (DatetimeFunction._ensure_ts_unit's message, as ValueError), else the function's default (None: datetime() without one)."""
+    cls, units, default = TEMPORAL_FNS[e[0]]
+    if len(e) < 2 or len(e) > 3:
+        raise NotImplementedError(f"no GPU lowering for {e[0]}() with {len(e) - 1} operand(s)")
+    if len(e) == 2:
+        return default
+    unit = e[2][1] if is_str_lit(e[2]) else e[2]
+    if not (is_str_lit(e[2]) and isinstance(unit, str) and unit in units):
+        raise ValueError(f"Unsupported {cls} unit: '{unit}'. Supported units are: [{', '.join(units)}]")
+    return unit
+
+
+def fold_temporal(e):
+    """A date / datetime / from_timestamp node over a LITERAL -> ("temporal", value, unit), computed by NumPy itself with the
+    reference's unit rules (DatetimeFunction._expr_kernel + _ensure_unit_correctness: a unit NumPy picked that the function does not
+    list -- Y, M, h, m -- is raised to the next finer one it lists).  None when the operand is no literal."""
+    x = e[1] if len(e) > 1 else None
+    if not (is_str_lit(x) or (isinstance(x, (int, np.integer)) and not isinstance(x, bool))):
+        return None
+    _, units, _ = TEMPORAL_FNS[e[0]]
+    unit = temporal_unit_arg(e)
+    v = x[1] if is_str_lit(x) else int(x)
+    if isinstance(v, bytes):
+        v = v.decode("utf-8")
+    arr = np.array(v, dtype=f"datetime64[{unit}]" if unit else "datetime64")
+    name = arr.dtype.name
+    got = name[name.index("[") + 1:name.index("]")] if "[" in name else ""
+    if got not in units:
+        finer = [u for u in _NUMPY_UNITS[_NUMPY_UNITS.index(got) + 1:] if u in units] if got in _NUMPY_UNITS else []
+        got = finer[0] if finer else units[-1]
+        arr = arr.astype(f"datetime64[{got}]")
+    if np.isnat(arr):
+        raise NotImplementedError(f"no GPU lowering for the constant {e[0]}({v!r}): it is NaT, which compares False with everything")
+    return ("temporal", int(arr.astype(np.int64)), got)

@@ -1,7 +1,7 @@
 """KeyDictionary: the running dictionary of one non-numeric column (value -> int32 code) and the device tables derived from it,
 one entry per dictionary id: LIKE matches, translations into and joint ranks with another dictionary, upper() / lower() maps,
-concat() with literals; the pair tables of concat() over two columns; and the value tables of to_str() over a numeric or temporal
-column (ValueTable: no KeyDictionary of its own, the column's VALUE is the key).
+concat() with literals, the parsed values of date() / datetime(); the pair tables of concat() over two columns; and the value tables
+of to_str() over a numeric or temporal column (ValueTable: no KeyDictionary of its own, the column's VALUE is the key).
 Importable without the shared library, like vinum_lib (which re-exports KeyDictionary and device_value_type)."""
 import ctypes
 from dataclasses import dataclass
@@ -80,6 +80,88 @@ class _Affix:                     # KeyDictionary._affixed[(prefix, suffix)]
     table: _IdTable               # int32: code here -> code in `derived`, -2 for an id never handed out
     null_code: int = -2           # `derived`'s code of prefix + "None" + suffix, what a NULL row gets
     mine: int = -1                # own value count when the table last advanced
+
+
+@dataclass
+class _Parsed:                    # KeyDictionary._parsed[unit]
+    values: _IdTable              # int64: code here -> days / unit counts since 1970-01-01
+    status: _IdTable              # uint8: 0 a value, 1 NULL ('' / NaT), 2 refused or an id never handed out
+    mine: int = -1                # own value count when the tables last advanced
+    any_refused: bool = False     # a value handed out was refused: the row pass looks for rows that hold one (and reads that back)
+    value_tables: dict = None     # where to_str(date(c))'s table lives from batch to batch (DeviceColumn.value_tables)
+
+
+TEMPORAL_UNITS = ("D", "s", "ms", "us", "ns")             # enum vnm_temporal_unit, in its order
+UNITS_PER_DAY = {"D": 1, "s": 86_400, "ms": 86_400_000, "us": 86_400_000_000, "ns": 86_400_000_000_000}
+
+
+def temporal_type(unit: str):
+    """the Arrow type of a date() / datetime() / from_timestamp() result in `unit`: date32 for D, timestamp[unit] otherwise"""
+    return pa.date32() if unit == "D" else pa.timestamp(unit)
+
+
+def temporal_unit(t):
+    """the unit of a date32 / timestamp type (a zone-aware one too: the stored value is the UTC instant); None for any other type"""
+    if pa.types.is_date32(t):
+        return "D"
+    return t.unit if pa.types.is_timestamp(t) else None
+
+
+def rescaled_column(col, unit: str):
+    """date(ts) / datetime(temporal column, unit): `col` -- date32 or timestamp -- in `unit` (vnm_temporal_rescale: to a coarser
+    unit the FLOOR of the division, to a finer one the wrapping product NumPy's cast gives), with `col`'s validity; `col` itself
+    when the unit is its own"""
+    from .device import DeviceBuffer, DeviceColumn
+    have = temporal_unit(col.arrow_type)
+    if have is None:
+        raise TypeError(f"not a date32 / timestamp column: {col.arrow_type}")
+    if have == unit and not (pa.types.is_timestamp(col.arrow_type) and col.arrow_type.tz):
+        return col
+    a, b = UNITS_PER_DAY[have], UNITS_PER_DAY[unit]
+    mul, div = (b // a, 1) if b >= a else (1, a // b)
+    n, width = col.length, 4 if unit == "D" else 8
+    off = col.offset if col._validity is not None else 0          # (one Arrow offset serves values and bitmap)
+    out = DeviceBuffer(max(off + n, 1) * width)
+    if n:
+        d = col.dcol()
+        L.check(L.lib().vnm_temporal_rescale(ctypes.byref(d), mul, div, n, width, out.ptr + off * width, None))
+    return DeviceColumn(out, col._validity, off, n, temporal_type(unit), keep=(col,))
+
+
+def timestamp_column(col, unit: str):
+    """from_timestamp(integer column[, unit]) (TimestampFunction, functions.py:131-137): the same values as timestamp[unit], exact,
+    with `col`'s validity -- an int64 column retyped over its own buffers, a narrower one widened (vnm_temporal_rescale, 1 / 1)"""
+    from .device import DeviceBuffer, DeviceColumn
+    t = pa.timestamp(unit)
+    if pa.types.is_int64(col.arrow_type):
+        return DeviceColumn(col._values, col._validity, col.offset, col.length, t, keep=(col,))
+    n = col.length
+    off = col.offset if col._validity is not None else 0
+    out = DeviceBuffer(max(off + n, 1) * 8)
+    if n:
+        d = col.dcol()
+        L.check(L.lib().vnm_temporal_rescale(ctypes.byref(d), 1, 1, n, 8, out.ptr + off * 8, None))
+    return DeviceColumn(out, col._validity, off, n, t, keep=(col,))
+
+
+def temporal_operand_kind(fn: str, t, name) -> str:
+    """How date() / datetime() / from_timestamp() (`fn`) takes a column `name` of Arrow type `t`: "parse" (a string column, through
+    its dictionary), "rescale" (date32 / timestamp: a change of unit) or "retype" (an integer column under from_timestamp).  A
+    binary, float, uint64, decimal ... column raises TypeError naming it, a column whose dictionary stays on the host (bool,
+    date64, a dictionary type over numbers) NotImplementedError -- the texts upper() / to_str() use."""
+    takes = "a string, date32, timestamp or integer column" if fn == "from_timestamp" else "a string, date32 or timestamp column"
+    dt = device_value_type(t)
+    if dt is not None:
+        if pa.types.is_binary(dt) or pa.types.is_large_binary(dt):
+            raise TypeError(f"{fn}() takes {takes}, {name!r} is {t}")
+        return "parse"
+    if temporal_unit(t) is not None:
+        return "rescale"
+    if fn == "from_timestamp" and pa.types.is_integer(t) and not pa.types.is_uint64(t):
+        return "retype"
+    if pa.types.is_integer(t) or pa.types.is_floating(t) or pa.types.is_decimal(t) or pa.types.is_temporal(t):
+        raise TypeError(f"{fn}() takes {takes}, {name!r} is {t}")
+    raise NotImplementedError(f"no GPU lowering for {fn}() over the {t} column {name!r}: only string columns keep their dictionaries on the device")
 
 
 class PairTable:
@@ -258,6 +340,8 @@ class KeyDictionary:
         self._affixed = {}         # (prefix, suffix) -> _Affix
         self.affix_launches = self.affix_ids_mapped = 0      # vnm_strdict_concat_affix calls and the ids they covered, over every (prefix, suffix)
         self._paired = {}          # (id(other dictionary), prefix, sep, suffix) -> PairTable
+        self._parsed = {}          # unit -> _Parsed
+        self.parse_launches = self.parse_ids_parsed = 0      # vnm_strdict_parse_datetime calls and the ids they covered, over every unit
 
     @property
     def on_device(self) -> bool:
@@ -644,6 +728,65 @@ class KeyDictionary:
             L.check(L.lib().vnm_strdict_gather_codes(codes_col.values_ptr + codes_col.offset * 4, codes_col.validity_ptr, codes_col.offset,
                                                      table.values_ptr, table.length, n, null_code, out.ptr, None))
         return DeviceColumn(out, None, 0, n, pa.int32(), keep=(table, codes_col), dictionary=derived)
+
+    def parsed(self, unit: str):
+        """date() / datetime() of this dictionary in `unit` (DateFunction / DatetimeFunction, functions.py:25-128: np.array(x,
+        dtype='datetime64[unit]')): (an int64 DeviceColumn `code here -> days / unit counts since 1970-01-01`, a uint8 DeviceColumn
+        `code here -> 0 a value | 1 NULL | 2 refused or never handed out`), one entry per id covered.  A function of the value
+        alone, so each distinct value is parsed ONCE on the device (vnm_strdict_parse_datetime, the grammar in csrc/vnm_dtparse.hpp);
+        a row then costs one lookup of its code (parsed_column).  Cached per unit and extended only when this dictionary gained a
+        value (`parse_launches`, `parse_ids_parsed`).  A value the parser refuses is DATA here -- status 2 --: whether a row holds it
+        is parsed_column's to say (a dictionary derived by concat() always holds the image of NULL, "None...", and a batch
+        dictionary may hold values no row uses).  Refusals as mapped(): binary TypeError, host route NotImplementedError."""
+        if unit not in TEMPORAL_UNITS:
+            raise ValueError(f"no temporal unit {unit!r}: one of {TEMPORAL_UNITS}")
+        if not self._device:
+            raise NotImplementedError(f"no GPU lowering for date() / datetime() over a {self.type} column: only string columns keep their dictionaries on the device")
+        t = self.value_type
+        if not (pa.types.is_string(t) or pa.types.is_large_string(t)):
+            raise TypeError(f"date() / datetime() need a string column, not {self.type}")
+        top = self._id_count()
+        entry = self._parsed.get(unit)
+        if entry is None:
+            entry = self._parsed[unit] = _Parsed(_IdTable(top, 8), _IdTable(top, 1))
+        values, status = entry.values, entry.status
+        if top > values.covered and entry.mine != self._n_values:       # (by values, as mapped(): only a new value is work)
+            values.reserve(top)
+            status.reserve(top)
+            refused = ctypes.c_int64(-1)
+            L.check(L.lib().vnm_strdict_parse_datetime(self.handle(), TEMPORAL_UNITS.index(unit), values.covered, values.buf.ptr, status.buf.ptr,
+                                                       ctypes.byref(refused), None))
+            self.parse_launches += 1
+            self.parse_ids_parsed += top - values.covered
+            entry.any_refused = entry.any_refused or refused.value >= 0
+            values.covered = status.covered = top
+            entry.mine = self._n_values
+        return values.column(pa.int64()), status.column(pa.uint8())
+
+    def parsed_column(self, unit: str, codes_col):
+        """date(column) / datetime(column, unit) over a column of THIS dictionary's codes: a date32 / timestamp[unit] DeviceColumn
+        WITH validity and without a dictionary -- table[code] per row (vnm_strdict_gather_temporal), NULL where the row is NULL or
+        its value is '' / NaT.  A non-NULL row that holds a value the parser refuses raises ValueError('Error parsing datetime string
+        "<value>"') -- NumPy's words -- naming the value of the lowest such id, when its batch comes through here: a predicate over
+        the node sees every row, the ones it would reject included; a row an EARLIER filter removed never gets here, as in the
+        reference.  Only a dictionary that holds a refused value pays the read-back for it."""
+        from .device import DeviceBuffer, DeviceColumn
+        values, status = self.parsed(unit)
+        refused = ctypes.c_int64(-1) if self._parsed[unit].any_refused else None
+        n, width = codes_col.length, 4 if unit == "D" else 8
+        out, bitmap = DeviceBuffer(max(n, 1) * width), DeviceBuffer(max((n + 7) >> 3, 1))
+        if n:
+            L.check(L.lib().vnm_strdict_gather_temporal(codes_col.values_ptr + codes_col.offset * 4, codes_col.validity_ptr, codes_col.offset,
+                                                        values.values_ptr, status.values_ptr, values.length, n, width, out.ptr, bitmap.ptr, None,
+                                                        ctypes.byref(refused) if refused is not None else None, None))
+        if refused is not None and refused.value >= 0:
+            raise ValueError(f'Error parsing datetime string "{self.values_by_code()[refused.value].as_py()}"')
+        col = DeviceColumn(out, bitmap, 0, n, temporal_type(unit), keep=(values, status, codes_col))
+        entry = self._parsed[unit]
+        if entry.value_tables is None:
+            entry.value_tables = {}
+        col.value_tables = entry.value_tables
+        return col
 
     def paired(self, other, prefix: bytes, sep: bytes, suffix: bytes) -> PairTable:
         """The pair table of concat(prefix, a, sep, b, suffix) with this dictionary on the left and `other` on the right (which may

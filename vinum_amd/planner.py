@@ -12,7 +12,8 @@ A query is a dict (see tests/golden/planner_cases.py):
     expr := the prefix tuples of vinum_amd.expr (the one definition of the node forms), with ("fn", name, arg...) for the
             aggregate functions count_star / count / sum / avg / min / max and the numeric built-in scalar functions
             (SCALAR_FN_NAMES: abs, sqrt, sin, ..., to_int, pi, e and their np. spellings), upper / lower of a string
-            column and to_str of an integer, date32, timestamp or string column, which are per-row expressions; concat is the operator node ("concat", x, ...) or ("||", a, b) over string
+            column, to_str of an integer, date32, timestamp or string column and date / datetime / from_timestamp (the unit a
+            ("lit", unit) argument) of a string, date32 / timestamp or -- from_timestamp -- integer column, which are per-row expressions; concat is the operator node ("concat", x, ...) or ("||", a, b) over string
             columns, such nodes, upper / lower and literals (("lit", s), numbers), and they are per-row expressions wherever they appear, like any operator; LIKE / NOT LIKE against a utf8 / large_utf8 column (planner.py:189-193)
             may stand in WHERE, HAVING, the SELECT list (a uint8 mask) and aggregate arguments alike.
 
@@ -32,7 +33,7 @@ from .core import (AggregateFunction, AggregateOperator, FileReaderOperator, Fil
                    ProjectOperator, SliceOperator, SortOperator, TableReaderOperator)
 from . import expr as E
 from .expr import columns_of
-from .keydict import device_value_type, to_str_kind
+from .keydict import device_value_type, temporal_operand_kind, to_str_kind
 
 AGG_FUNCS = ("count_star", "count", "sum", "avg", "min", "max")     # vinum/core/functions.py:389-396
 # numeric part of _default_functions_registry (vinum/core/functions.py:353-387) and the `np.` spellings lookup_udf resolves
@@ -45,6 +46,9 @@ SCALAR_FN_NAMES["np.absolute"] = "abs"
 SCALAR_FN_NAMES.update({"upper": "upper", "lower": "lower"})
 # to_str (StringCastFunction, functions.py:189-193, 'to_str' at :358): a function of the column's VALUE (keydict.ValueTable)
 SCALAR_FN_NAMES["to_str"] = "to_str"
+# the datetime built-ins (functions.py:25-137, registered at :376-379): over a string column a function of the dictionary's values
+# (KeyDictionary.parsed_column), over a temporal column a change of unit, over literals a constant folded by NumPy
+SCALAR_FN_NAMES.update({n: n for n in E.TEMPORAL_FNS})
 
 
 def _t(e):
@@ -80,6 +84,12 @@ def _case_by_type(e, schema):
             dt = device_value_type(t)
             if dt is None or pa.types.is_binary(dt) or pa.types.is_large_binary(dt):
                 to_str_kind(t, n[1])
+        # date(x) / datetime(x[, unit]) / from_timestamp(x[, unit]): the unit against the function's list (ValueError, the reference's
+        # message), a literal operand folded once to surface NumPy's parse error, a column's type against what the function takes
+        if isinstance(n, tuple) and n and n[0] in E.TEMPORAL_FNS:
+            E.temporal_unit_arg(n)
+            if E.fold_temporal(n) is None and isinstance(n[1], str) and n[1] in schema.names:
+                temporal_operand_kind(n[0], schema.field(n[1]).type, n[1])
         # concat(x, ...): a BARE numeric or temporal column stays refused here, by name -- the explicit spelling is concat(to_str(x), ...)
         if isinstance(n, tuple) and n and n[0] == "concat":
             for x in n[1:]:
