@@ -670,6 +670,32 @@ int vnm_strdict_gather_temporal(const int32_t* codes, const uint8_t* validity, i
                                 const uint8_t* status_of_id, int64_t n_ids, int64_t n, int out_width, void* out_values, uint8_t* out_validity_bitmap,
                                 int64_t* out_null_count, int64_t* out_first_refused_id, void* stream);
 int vnm_temporal_rescale(const vnm_dcol* col, int64_t mul, int64_t div, int64_t length, int out_width, void* out_values, void* stream);
+/* Arithmetic on temporal values: typed, exact int64 with validity, what NumPy's datetime64 / timedelta64
+ * arithmetic computes.
+ * vnm_temporal_affine: out_values[i] = a[i] * ka + b[i] * kb + c over rows [offset, offset + length) of one or two columns (b may
+ * be NULL, a may not), each 4 bytes (date32, VNM_I32) or 8 bytes (timestamp / duration, VNM_I64) wide with its own validity and
+ * Arrow offset; any other type is refused.  Products and sums wrap (computed unsigned) as NumPy's do.  Unit alignment is in the
+ * factors (ka = 86400 for a date against seconds), subtraction is kb = -k, negation ka = -1, a constant operand c.  out_width 4
+ * writes the low 32 bits of the result as int32, 8 the int64.  Row i is NULL in out_validity_bitmap (a DEVICE bitmap at bit offset
+ * 0, (length + 7) / 8 bytes, required) and its value 0 when either input row is NULL, an 8-byte input holds INT64_MIN (NaT) or the
+ * 64-bit result is INT64_MIN (whatever out_width is: NumPy computes dates in int64 too).  A lane takes 8 rows and writes ONE whole byte of the bitmap, which no other lane touches; the bits
+ * past length in the last byte and the bytes past (length + 7) / 8 are left as they were.  16-byte accesses where row 0 of a
+ * buffer is 16-byte aligned, scalar ones otherwise.  out_null_count (host; may be NULL): the NULL rows; with it the call
+ * synchronises, without it it is one kernel on `stream`, launched asynchronously.
+ * vnm_temporal_busday: np.is_busday over a date32 (VNM_I32) column as a byte mask (0 / 1, what a predicate program writes):
+ * out_mask[i] = bit ((day + 3) floor-mod 7) of weekmask (bit 0 Monday; 1970-01-01 is a Thursday) AND day is not among `holidays`,
+ * a sorted, distinct DEVICE array of n_holidays <= 8192 days (32 KB of LDS; more is refused with "ValueError: ...") that is staged
+ * into LDS and probed with a branch-free binary search.  A NULL row gives 0.  One kernel on `stream`, launched asynchronously. */
+int vnm_temporal_affine(const vnm_dcol* a, int64_t ka, const vnm_dcol* b, int64_t kb, int64_t c, int64_t length, int out_width,
+                        void* out_values, uint8_t* out_validity_bitmap, int64_t* out_null_count, void* stream);
+/* vnm_temporal_floordiv: duration // duration (np.floor_divide over timedelta64) -> int64: out_values[i] = floor(x / y), x = a[i] * ka
+ * and y = b[i] * kb with the unit factors in ka / kb (wrapping); a NULL column pointer makes that side the constant ka / kb itself
+ * (one side at least is a column).  Operands, validity, bitmap, lane shape and out_null_count as vnm_temporal_affine.  A NULL or NaT
+ * (8-byte INT64_MIN) input row is NULL with value 0 (NumPy gives 0 there); a zero divisor gives 0, as NumPy does. */
+int vnm_temporal_floordiv(const vnm_dcol* a, int64_t ka, const vnm_dcol* b, int64_t kb, int64_t length, int64_t* out_values,
+                          uint8_t* out_validity_bitmap, int64_t* out_null_count, void* stream);
+int vnm_temporal_busday(const vnm_dcol* days, int64_t length, int weekmask, const int32_t* holidays, int64_t n_holidays, uint8_t* out_mask,
+                        void* stream);
 /* A dictionary-typed Arrow column (dictionary<intN, utf8 | large_utf8 | binary | large_binary>): the batch dictionary's indices ->
  * codes of the running dictionary.  The caller runs the batch dictionary's VALUES through vnm_strdict_encode and uploads the result
  * as code_of_index (n_values int32s on the DEVICE; -1 = a NULL value), so only n_values strings are hashed, not one per row.

@@ -146,6 +146,9 @@ PROTOTYPES = {
     "vnm_strdict_parse_datetime": (c_int, [c_void, c_int, c_i64, c_void, c_void, c_void, c_void]),
     "vnm_strdict_gather_temporal": (c_int, [c_void, c_void, c_i64, c_void, c_void, c_i64, c_i64, c_int, c_void, c_void, c_void, c_void, c_void]),
     "vnm_temporal_rescale": (c_int, [c_void, c_i64, c_i64, c_i64, c_int, c_void, c_void]),
+    "vnm_temporal_affine": (c_int, [c_void, c_i64, c_void, c_i64, c_i64, c_i64, c_int, c_void, c_void, c_void, c_void]),
+    "vnm_temporal_floordiv": (c_int, [c_void, c_i64, c_void, c_i64, c_i64, c_void, c_void, c_void, c_void]),
+    "vnm_temporal_busday": (c_int, [c_void, c_i64, c_int, c_void, c_i64, c_void, c_void]),
     "vnm_strdict_remap_indices": (c_int, [c_void, c_void, c_i64, c_void, c_void, c_void, c_void]),
     "vnm_dict_take_compact": (c_int, [c_void, c_void, c_i64, c_i64, c_int, c_void, c_void, c_void, c_void, c_void, c_void]),
     "vnm_like_compile": (c_int, [c_void, c_i64, c_void, c_void]),

@@ -35,6 +35,7 @@ import numpy as np
 import pyarrow as pa
 import pyarrow.compute as pc
 
+from . import expr as E
 from . import ops
 from .core.base import DeviceRecordBatch, Operator
 
@@ -219,6 +220,10 @@ class TimestampFunction(DatetimeFunction):
     """functions.py:131-137: from_timestamp, units s / ms / us / ns, default s."""
 
 
+class NowFunction(DatetimeFunction):
+    """functions.py:140-145: np.array(['now'], dtype='datetime64'), evaluated per batch there -- here folded once per query."""
+
+
 _CASE_SPEC = {"UpperStringFunction": "upper", "LowerStringFunction": "lower"}
 _TEMPORAL_SPEC = {"DateFunction": "date", "DatetimeFunction": "datetime", "TimestampFunction": "from_timestamp"}
 _STRING_FN_NAMES = ("upper", "lower", "concat")       # their "fn" spelling builds what it always built; the operator node builds the class
@@ -237,6 +242,9 @@ FUNCTIONS_REGISTRY = {
     "date": (DateFunction, FunctionType.CLASS),
     "datetime": (DatetimeFunction, FunctionType.CLASS),
     "from_timestamp": (TimestampFunction, FunctionType.CLASS),
+    "now": (NowFunction, FunctionType.CLASS),
+    "timedelta": (np.timedelta64, FunctionType.NUMPY),
+    "is_busday": (np.is_busday, FunctionType.NUMPY),
     "abs": (np.absolute, FunctionType.NUMPY),
     "sqrt": (np.sqrt, FunctionType.NUMPY),
     "cos": (np.cos, FunctionType.NUMPY),
@@ -252,6 +260,8 @@ FUNCTIONS_REGISTRY = {
 _NUMERIC_FNS = tuple(FUNCTIONS_REGISTRY)
 # ufuncs are recognised by identity, whatever spelling reached them (`np.sin`, `np.abs` is np.absolute)
 _UFUNC_SPEC = {id(fn): name for name, (fn, ft) in FUNCTIONS_REGISTRY.items() if isinstance(fn, np.ufunc)}
+# timedelta and is_busday are NumPy's own callables (functions.py:380-381), recognised by identity like the ufuncs
+_UFUNC_SPEC.update({id(np.timedelta64): "timedelta", id(np.is_busday): "is_busday"})
 
 _SPEC_TO_SQL = {"add": "ADDITION", "sub": "SUBTRACTION", "mul": "MULTIPLICATION", "div": "DIVISION", "mod": "MODULUS",
                 "neg": "NEGATION", "bnot": "BINARY_NOT", "band": "BINARY_AND", "bor": "BINARY_OR", "bxor": "BINARY_XOR",
@@ -307,7 +317,10 @@ def vectorize(expr, registry=None, classes=None, functions=None, like_cls=None):
                 fn, ftype = getattr(np, name[3:]), FT.NUMPY                 # lookup_udf: eval("np.<name>")
             else:
                 fn, ftype = (functions or FUNCTIONS_REGISTRY)[name]
-            built = [build(a) for a in fargs]
+            if name == "is_busday" and len(fargs) > 2:                      # the holidays: ONE Literal holding the list, like IN's
+                built = [build(a) for a in fargs[:2]] + [Lt([h[1] if isinstance(h, tuple) else h for h in fargs[2]])]
+            else:
+                built = [build(a) for a in fargs]
             if ftype == FT.CLASS:
                 return fn(built)                                            # planner.py:129-131: Cls(arguments)
             return VE(built, function=fn, is_numpy_func=(ftype == FT.NUMPY), is_binary_func=False)
@@ -336,7 +349,17 @@ _DEFAULT_INDEX = registry_index(EXPRESSION_FUNCTIONS, FUNCTIONS_REGISTRY)
 
 
 def lower(node, index: Optional[Dict[int, str]] = None):
-    """VectorizedExpression-shaped tree -> prefix expression (str | number | tuple) for vinum_amd.ops."""
+    """VectorizedExpression-shaped tree -> prefix expression (str | number | tuple) for vinum_amd.ops.  now() folds here, ONCE for
+    the whole tree (expr.fold_now): every occurrence is the same instant, and so is every batch."""
+    return lower_all([node], index)[0]
+
+
+def lower_all(nodes, index: Optional[Dict[int, str]] = None) -> list:
+    """lower() of several trees of one operator (a SELECT list) under ONE now()"""
+    return E.fold_now([_lower_tree(n, index) for n in nodes])
+
+
+def _lower_tree(node, index: Optional[Dict[int, str]] = None):
     index = index or _DEFAULT_INDEX
     if node is None:
         return None
@@ -354,22 +377,25 @@ def lower(node, index: Optional[Dict[int, str]] = None):
                 return like
         cast = getattr(type(node), "type", None)
         if fn is None and cast in _CAST_SPEC and type(node).__name__ in _CAST_CLASSES:
-            args = [lower(a, index) for a in node.arguments]   # AbstractCastFunction (functions.py:148-162)
+            args = [_lower_tree(a, index) for a in node.arguments]   # AbstractCastFunction (functions.py:148-162)
             return (_CAST_SPEC[cast],) + tuple(args)
         # UpperStringFunction / LowerStringFunction (functions.py:279-298), by QUALIFIED name: the class the reference (or this
         # module) defines under that name at module level -- some other class whose __name__ was set to it is not that function
         if fn is None and type(node).__qualname__ in _CASE_SPEC and len(tuple(node.arguments)) == 1:
-            return (_CASE_SPEC[type(node).__qualname__], lower(tuple(node.arguments)[0], index))
+            return (_CASE_SPEC[type(node).__qualname__], _lower_tree(tuple(node.arguments)[0], index))
+        # NowFunction (functions.py:140-145), by qualified name: the ("now",) leaf lower() folds
+        if fn is None and type(node).__qualname__ == "NowFunction" and len(tuple(node.arguments)) == 0:
+            return ("now",)
         # DateFunction / DatetimeFunction / TimestampFunction (functions.py:25-137), by qualified name as above: (x) or (x, Literal(unit))
         if fn is None and type(node).__qualname__ in _TEMPORAL_SPEC and 1 <= len(tuple(node.arguments)) <= 2:
-            return (_TEMPORAL_SPEC[type(node).__qualname__],) + tuple(lower(a, index) for a in node.arguments)
+            return (_TEMPORAL_SPEC[type(node).__qualname__],) + tuple(_lower_tree(a, index) for a in node.arguments)
         # ConcatFunction (functions.py:250-276; `concat(...)` and `a || b` both build it), by qualified name AND by its shape: it
         # carries a callable (np.char.add) and folds as a binary function.  A VectorizedExpression that merely holds np.char.add is
         # not that function.
         if type(node).__qualname__ == "ConcatFunction" and fn is not None and getattr(node, "_is_binary_func", False) and len(tuple(node.arguments)) >= 1:
-            return ("concat",) + tuple(lower(a, index) for a in node.arguments)
+            return ("concat",) + tuple(_lower_tree(a, index) for a in node.arguments)
         if fn is not None and id(fn) not in index and id(fn) in _UFUNC_SPEC:
-            return (_UFUNC_SPEC[id(fn)],) + tuple(lower(a, index) for a in node.arguments)
+            return (_UFUNC_SPEC[id(fn)],) + tuple(_lower_tree(a, index) for a in node.arguments)
         if fn is None or id(fn) not in index:
             raise NotImplementedError(f"no GPU lowering for {fn if fn is not None else type(node).__name__!r}: the numeric "
                                       "operators and the built-ins abs, sqrt, sin, cos, tan, log, log2, log10, power, pi, e, "
@@ -377,7 +403,7 @@ def lower(node, index: Optional[Dict[int, str]] = None):
                                       "from_timestamp and LIKE / NOT LIKE against a string literal run on the GPU; UDFs, now, "
                                       "timedelta, is_busday and other np.* functions do not")
         sql = index[id(fn)]
-        args = [lower(a, index) for a in node.arguments]
+        args = [_lower_tree(a, index) for a in node.arguments]
         if sql.startswith("fn:"):
             return (sql[3:],) + tuple(args)
         op = _SQL_TO_SPEC[sql]
@@ -407,7 +433,7 @@ def _lower_like(node, index):
     lit = args[1]
     if type(lit).__name__ != "Literal" or not hasattr(lit, "value") or not isinstance(lit.value, str):
         return None
-    return ("not_like" if invert else "like", lower(args[0], index), ("lit", lit.value))
+    return ("not_like" if invert else "like", _lower_tree(args[0], index), ("lit", lit.value))
 
 
 def device_filter(batch: DeviceRecordBatch, predicate) -> DeviceRecordBatch:
@@ -442,7 +468,7 @@ class GpuProjectOperator(Operator):
         super().__init__(parent_operator)
         from .core.algebra import ProjectOperator
         args = list(arguments)
-        exprs = [lower(a, index) for a in args]
+        exprs = lower_all(args, index)
         if col_names is None:                                   # algebra.py:66-75: the arguments name their columns
             col_names = [a.get_column_name() if hasattr(a, "get_column_name") else f"expr_{i}" for i, a in enumerate(args)]
         self._inner = ProjectOperator(exprs, None, col_names=list(col_names), keep_input_table=keep_input_table)

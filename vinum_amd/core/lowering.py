@@ -2,6 +2,11 @@
 expression over it is a numeric program: four rewrites of vinum_amd.expr trees (lower_dictionary runs them in order) and the one
 path on which the operators evaluate lowered expressions (project_lowered, used_columns).  `columns` is a batch's name ->
 DeviceColumn; every rewrite returns (expression, extra), `extra` holding the tables, rank and mask columns the result reads by name."""
+import hashlib
+
+import numpy as np
+import pyarrow as pa
+
 from .. import expr as E
 from .. import ops
 from .. import keydict as K
@@ -77,8 +82,11 @@ def lower_case_functions(expr, columns, extra=None):
         same values retyped (keydict.timestamp_column).  datetime(x) without a unit over a column is timestamp[s] -- the reference
         lets NumPy pick the unit batch by batch.  Over a LITERAL the node folds into a ("temporal", value, unit) constant with
         NumPy itself (expr.fold_temporal).  A comparison (BETWEEN too) with such a constant, or of two temporal operands of
-        different units, is aligned to the finer unit as NumPy does: the coarser side is multiplied by the factor.  A temporal
-        constant anywhere else -- alone in SELECT, under arithmetic -- raises NotImplementedError."""
+        different units, is aligned to the finer unit as NumPy does: the coarser side is multiplied by the factor; durations
+        compare with durations the same way.
+      * timedelta(n[, unit]) folds into a ("duration", ...) constant (expr.fold_timedelta); add / sub / mul / div / neg over temporal
+        and duration operands, is_busday() and IN lists of temporal constants are the stage TemporalArithmetic below.  A temporal
+        or duration constant left alone -- in SELECT -- raises NotImplementedError; so does a now() that was not folded at plan time."""
     extra = {} if extra is None else extra
 
     def operand(fn, x):
@@ -148,8 +156,8 @@ def lower_case_functions(expr, columns, extra=None):
         if len(e) != 2:
             raise NotImplementedError(f"no GPU lowering for to_str() with {len(e) - 1} operand(s)")
         x = e[1]
-        if isinstance(x, tuple) and x and x[0] in STRING_FNS + TEMPORAL_FNS:
-            x = f(x)
+        if isinstance(x, tuple) and x and (x[0] in STRING_FNS + TEMPORAL_FNS or x[0] in E.TEMPORAL_ARITH):
+            x = lower(x)
         cols = with_derived(columns, extra)
         if not isinstance(x, str) or x not in cols:
             raise NotImplementedError(f"no GPU lowering for to_str() over {x!r}: the operand must be a column or upper() / lower() / concat() / "
@@ -178,8 +186,8 @@ def lower_case_functions(expr, columns, extra=None):
             return const
         unit = unit or "s"
         x = e[1]
-        if isinstance(x, tuple) and x and x[0] in STRING_FNS + TEMPORAL_FNS:
-            x = f(x)
+        if isinstance(x, tuple) and x and (x[0] in STRING_FNS + TEMPORAL_FNS or x[0] in E.TEMPORAL_ARITH):
+            x = lower(x)
         cols = with_derived(columns, extra)
         if not isinstance(x, str) or x not in cols:
             raise NotImplementedError(f"no GPU lowering for {fn}() over {x!r}: the operand must be a column, upper() / lower() / concat() / to_str() "
@@ -201,17 +209,10 @@ def lower_case_functions(expr, columns, extra=None):
         extra[name] = col
         return name
 
-    def is_const(x):
-        return isinstance(x, tuple) and len(x) == 3 and x[0] == "temporal"
-
-    def unit_of(x):
-        """the unit of a temporal constant or of a date32 / timestamp column (derived ones included); None for anything else"""
-        if is_const(x):
-            return x[2]
-        cols = with_derived(columns, extra)
-        if isinstance(x, str) and x in cols and cols[x].dictionary is None:
-            return K.temporal_unit(cols[x].arrow_type)
-        return None
+    is_const = is_temporal_const
+    lower = lambda x: E.rewrite(x, f) if isinstance(x, tuple) else x
+    rules = TemporalArithmetic(columns, extra, lower)
+    kind_of = rules.kind_of
 
     def in_unit(x, have, want):
         k = K.UNITS_PER_DAY[want] // K.UNITS_PER_DAY[have]
@@ -223,11 +224,18 @@ def lower_case_functions(expr, columns, extra=None):
         return x if k == 1 else ("mul", x, ("strong", k))
 
     def lowered_operands(e):
-        return [E.rewrite(x, f) if isinstance(x, tuple) else x for x in e[1:]]
+        return [lower(x) for x in e[1:]]
 
     def compare(e):
         a, b = lowered_operands(e)
-        ua, ub = unit_of(a), unit_of(b)
+        (ka, ua), (kb, ub) = kind_of(a) or (None, None), kind_of(b) or (None, None)
+        if ka and kb and ka != kb:
+            raise TypeError(f"cannot compare {rules.describe(a)} with {rules.describe(b)}: a date / timestamp and a duration")
+        # a generic duration constant -- timedelta(n) -- takes the unit of the duration it meets
+        if kb == "duration" and is_const(a) and ua is None:
+            ua = ub
+        if ka == "duration" and is_const(b) and ub is None:
+            ub = ua
         if not (is_const(a) or is_const(b)) and (ua is None or ub is None or ua == ub):
             return E.with_operands(e, [a, b])
         if is_const(a) and is_const(b):
@@ -235,13 +243,13 @@ def lower_case_functions(expr, columns, extra=None):
         for x, u, const in ((a, ua, b), (b, ub, a)):
             if u is None:
                 raise TypeError(f"cannot compare the temporal constant {const[1]} [{const[2]}] with {x!r}: only a date32 / timestamp column or "
-                                "date() / datetime() / from_timestamp() of a column")
+                                "date() / datetime() / from_timestamp() of a column" + (", or a duration" if const[0] == "duration" else ""))
         want = max(ua, ub, key=K.TEMPORAL_UNITS.index)
         return (e[0], in_unit(a, ua, want), in_unit(b, ub, want))
 
     def between(e):
         xs = lowered_operands(e)
-        units = [unit_of(x) for x in xs]
+        units = [(kind_of(x) or (None, None))[1] for x in xs]
         if any(is_const(x) for x in xs) or (all(units) and len(set(units)) > 1):
             x, lo, hi = xs
             return E.rewrite(("and", ("ge", x, lo), ("le", x, hi)) if e[0] == "between" else ("or", ("lt", x, lo), ("gt", x, hi)), f)
@@ -260,13 +268,301 @@ def lower_case_functions(expr, columns, extra=None):
             return compare(e)
         if e[0] in ("between", "not_between") and len(e) == 4:
             return between(e)
+        if e[0] == "timedelta":
+            return E.fold_timedelta(e)
+        if e[0] in E.TEMPORAL_ARITH:
+            return rules.arithmetic(e)
+        if e[0] == "is_busday":
+            return rules.is_busday(e)
+        if e[0] in E.IN_OPS and len(e) == 3:
+            return rules.in_list(e, temporal)
         return None
     out = E.rewrite(expr, f)
     for n in E.nodes(out):
         if is_const(n):
-            raise NotImplementedError(f"no GPU lowering for the temporal constant {n[1]} [{n[2]}] outside a comparison with a temporal column: "
-                                      "there is no per-row work (alone in SELECT), and arithmetic on temporal values is not built")
+            raise NotImplementedError(f"no GPU lowering for the temporal constant {n[1]} [{n[2]}] outside a comparison or arithmetic with a "
+                                      "temporal column: there is no per-row work (alone in SELECT)")
+        if isinstance(n, tuple) and n and n[0] == "now":
+            raise NotImplementedError("now() reached the per-batch lowering: it folds once per query, at plan time (expr.fold_now)")
     return out, extra
+
+
+def is_temporal_const(x) -> bool:
+    """a ("temporal", value, unit) or ("duration", value, unit) leaf"""
+    return isinstance(x, tuple) and len(x) == 3 and x[0] in ("temporal", "duration")
+
+
+def _is_int(x) -> bool:
+    return (isinstance(x, int) and not isinstance(x, bool)) or (isinstance(x, tuple) and len(x) == 2 and x[0] == "strong" and isinstance(x[1], int))
+
+
+class TemporalArithmetic:
+    """The stage of lower_case_functions that types arithmetic over temporal values the way NumPy's datetime64 / timedelta64 do
+     and lowers it onto vnm_temporal_affine (keydict.affine_column): out = a * ka + b * kb + c, exact in int64,
+    with validity.  The kinds: "temporal" [D s ms us ns] -- a date32 / timestamp column, a derived one, a ("temporal", ...) constant --
+    and "duration" [s ms us ns; a constant also D, or None: NumPy's generic timedelta, which an integer literal is too].
+      * T +- duration, duration + T -> T[finer unit] (date +- whole days stays date32); T - T -> duration[finer] (D - D: seconds, Arrow
+        has no duration in days); duration +- duration, -duration -> duration[finer]; duration * integer literal -> duration;
+        T +- integer literal -> T (the literal in T's own unit);
+      * duration / duration -> ("div", a, b) over both sides aligned to the finer unit: float64 in the interpreter, NaT reads as NaN;
+        duration // duration -> an int64 column with validity (keydict.floordiv_column: vnm_temporal_floordiv, the factors inside);
+      * an int32 / int64 COLUMN under + / - is a generic timedelta too (NumPy casts the integer array to the other operand's unit);
+      * constants among themselves fold with NumPy itself; a column against a constant uses c, two columns both factors; a constant
+        that does not fit int64 in the unit it is aligned to raises OverflowError;
+      * T + T, T * x, T / x, -T, n - T, duration - T, duration * float, duration / number, duration // number, anything with a float
+        or a string column, an integer column outside + -: TypeError naming the operator and the operand types; duration % duration:
+        NotImplementedError.
+    The result is a derived column in `extra` named __temporal_affine..., cached by (operands, factors), or a constant.
+    `lower` lowers an operand (the caller's own recursion); an arithmetic node without a temporal operand passes through.
+      * is_busday(x[, weekmask[, holidays]]) -> ("ne", mask column, 0) (keydict.busday_mask); x a date32 column or a node that lowers
+        to one; a timestamp or string column raises TypeError advising is_busday(date(x));
+      * an IN list of temporal constants: column and members aligned to the finest unit among them, the members plain integers."""
+
+    def __init__(self, columns, extra, lower, types_only=False):
+        """types_only: plan time (check_temporal) -- the columns are known by their types alone, a result is a column of its type
+        and no kernel runs"""
+        self.columns, self.extra, self.lower, self.types_only = columns, extra, lower, types_only
+
+    def kind_of(self, x):
+        """("temporal" | "duration", unit) of a constant or of a date32 / timestamp / duration column (derived ones included); None for
+        anything else"""
+        if is_temporal_const(x):
+            return x[0], x[2]
+        cols = with_derived(self.columns, self.extra)
+        if isinstance(x, str) and x in cols and cols[x].dictionary is None:
+            t = cols[x].arrow_type
+            if K.temporal_unit(t) is not None:
+                return "temporal", K.temporal_unit(t)
+            if K.duration_unit(t) is not None:
+                return "duration", K.duration_unit(t)
+        return None
+
+    def describe(self, x) -> str:
+        k = self.kind_of(x)
+        if k is not None:
+            name = "datetime64" if k[0] == "temporal" else "timedelta64"
+            return f"{name}[{k[1]}]" if k[1] else name
+        cols = with_derived(self.columns, self.extra)
+        if isinstance(x, str) and x in cols:
+            c = cols[x]
+            return f"the {value_type_of(c.dictionary) if c.dictionary is not None else c.arrow_type} column {x!r}"
+        if isinstance(x, (int, float)) or (isinstance(x, tuple) and x and x[0] == "strong"):
+            v = x[1] if isinstance(x, tuple) else x
+            return type(v).__name__
+        return f"the expression {x!r}"
+
+    def _column(self, a, ka, b, kb, c, t):
+        """the derived column a * ka + b * kb + c of type t (b may be None); a column times 1 of its own type is itself"""
+        cols = with_derived(self.columns, self.extra)
+        if b is None and ka == 1 and c == 0 and cols[a].arrow_type == t:
+            return a
+        name = f"{_DERIVED_TEMPORAL}affine({a}*{ka}" + (f"+{b}*{kb}" if b is not None else "") + f"+{c})[{t}]"
+        if name not in self.extra:
+            self.extra[name] = _Typed(t) if self.types_only else K.affine_column(cols[a], ka, cols[b] if b is not None else None, kb, c, t)
+        return name
+
+    def _is_int_column(self, x) -> bool:
+        """an int32 / int64 column: the widths vnm_temporal_affine reads"""
+        cols = with_derived(self.columns, self.extra)
+        return isinstance(x, str) and x in cols and cols[x].dictionary is None and (pa.types.is_int32(cols[x].arrow_type) or pa.types.is_int64(cols[x].arrow_type))
+
+    @staticmethod
+    def _scaled(x, have, want):
+        v = x[1] * (K.UNITS_PER_DAY[want] // K.UNITS_PER_DAY[have or want])
+        if not -2**63 <= v < 2**63:
+            raise OverflowError(f"the temporal constant {x[1]} [{have}] does not fit int64 in the unit {want!r} of the other operand")
+        return v
+
+    def _binary(self, op, a, b):
+        bad = TypeError(f"{op}() cannot use operands with types {self.describe(a)} and {self.describe(b)}")
+        ka, kb = self.kind_of(a), self.kind_of(b)
+        if ka is None and kb is None:
+            return (op, a, b)
+        if op == "mul":
+            x, n = (a, b) if ka else (b, a)
+            if not (self.kind_of(x)[0] == "duration" and _is_int(n)):
+                raise bad
+            n = n[1] if isinstance(n, tuple) else n
+            if is_temporal_const(x):
+                return E.temporal_const(E.temporal_scalar(x) * np.int64(n))
+            return self._column(x, n, None, 0, 0, pa.duration(self.kind_of(x)[1]))
+        if op in ("add", "sub"):
+            # an integer literal is NumPy's generic timedelta: it takes the unit of the operand it meets
+            if ka is None and _is_int(a):
+                a, ka = ("duration", a[1] if isinstance(a, tuple) else a, None), ("duration", None)
+            if kb is None and _is_int(b):
+                b, kb = ("duration", b[1] if isinstance(b, tuple) else b, None), ("duration", None)
+            # ... and so is an int32 / int64 COLUMN (NumPy casts the integer array to timedelta64 of the other operand's unit)
+            if ka is None and self._is_int_column(a) and kb[1] is not None:
+                ka = ("duration", None)
+            if kb is None and self._is_int_column(b) and ka is not None and ka[1] is not None:
+                kb = ("duration", None)
+        if ka is None or kb is None:
+            raise bad
+        kinds = (ka[0], kb[0])
+        if op == "floordiv":
+            if kinds != ("duration", "duration"):
+                raise bad
+            if is_temporal_const(a) and is_temporal_const(b):
+                return ("strong", int(np.floor_divide(E.temporal_scalar(a), E.temporal_scalar(b))))
+            want = max((u for u in (ka[1], kb[1]) if u is not None), key=K.TEMPORAL_UNITS.index)
+            if want == "D":
+                want = "s"
+            fa, fb = (K.UNITS_PER_DAY[want] // K.UNITS_PER_DAY[u or want] for u in (ka[1], kb[1]))
+            ca, cb = (None, self._scaled(a, ka[1], want)) if is_temporal_const(a) else (a, fa), (None, self._scaled(b, kb[1], want)) if is_temporal_const(b) else (b, fb)
+            name = f"{_DERIVED_TEMPORAL}floordiv({ca[0]}*{ca[1]},{cb[0]}*{cb[1]})"
+            if name not in self.extra:
+                cols = with_derived(self.columns, self.extra)
+                self.extra[name] = _Typed(pa.int64()) if self.types_only else \
+                    K.floordiv_column(cols[ca[0]] if ca[0] is not None else None, ca[1], cols[cb[0]] if cb[0] is not None else None, cb[1])
+            return name
+        if op == "div":
+            if kinds != ("duration", "duration"):
+                raise bad
+            out_kind = None
+        elif op == "add":
+            if kinds == ("temporal", "temporal"):
+                raise bad
+            out_kind = "temporal" if "temporal" in kinds else "duration"
+        elif op == "sub":
+            if kinds == ("duration", "temporal"):
+                raise bad
+            out_kind = "duration" if kinds[0] == kinds[1] else "temporal"
+        elif op == "mod" and kinds == ("duration", "duration"):
+            raise NotImplementedError("no GPU lowering for duration % duration")
+        else:
+            raise bad
+        if is_temporal_const(a) and is_temporal_const(b):
+            v = {"add": np.add, "sub": np.subtract, "div": np.divide}[op](E.temporal_scalar(a), E.temporal_scalar(b))
+            return ("strong", float(v)) if op == "div" else E.temporal_const(v)
+        units = [u for u in (ka[1], kb[1]) if u is not None]
+        want = max(units, key=K.TEMPORAL_UNITS.index)
+        if want == "D" and out_kind != "temporal":
+            want = "s"                       # (a difference of dates: Arrow has no duration in days)
+        fa, fb = (K.UNITS_PER_DAY[want] // K.UNITS_PER_DAY[u or want] for u in (ka[1], kb[1]))
+        if op == "div":
+            side = lambda x, k, fk: ("strong", self._scaled(x, k[1], want)) if is_temporal_const(x) else self._column(x, fk, None, 0, 0, pa.duration(want))
+            return ("div", side(a, ka, fa), side(b, kb, fb))
+        t = K.temporal_type(want) if out_kind == "temporal" else pa.duration(want)
+        sign = -1 if op == "sub" else 1
+        if is_temporal_const(b):
+            return self._column(a, fa, None, 0, sign * self._scaled(b, kb[1], want), t)
+        if is_temporal_const(a):
+            return self._column(b, sign * fb, None, 0, self._scaled(a, ka[1], want), t)
+        return self._column(a, fa, b, sign * fb, 0, t)
+
+    def arithmetic(self, e):
+        op = E.TEMPORAL_ARITH[e[0]]
+        xs = [self.lower(x) for x in e[1:]]
+        if not any(self.kind_of(x) for x in xs):
+            return E.with_operands(e, xs)
+        if op == "neg":
+            (x,), k = xs, self.kind_of(xs[0])
+            if k[0] != "duration":
+                raise TypeError(f"neg() cannot use an operand with type {self.describe(x)}")
+            if is_temporal_const(x):
+                return E.temporal_const(-E.temporal_scalar(x))
+            return self._column(x, -1, None, 0, 0, pa.duration(k[1]))
+        acc = xs[0]
+        for y in xs[1:]:                   # an n-ary chain folds left, as every operator does
+            acc = self._binary(op, acc, y)
+        return acc
+
+    def is_busday(self, e):
+        if not 2 <= len(e) <= 4:
+            raise NotImplementedError(f"no GPU lowering for is_busday() with {len(e) - 1} operand(s)")
+        x = self.lower(e[1])
+        cols = with_derived(self.columns, self.extra)
+        if not isinstance(x, str) or x not in cols:
+            raise NotImplementedError(f"no GPU lowering for is_busday() over {x!r}: the operand must be a date32 column or date() of a column")
+        c = cols[x]
+        if c.dictionary is not None or not pa.types.is_date32(c.arrow_type):
+            raise TypeError(f"is_busday() takes a date32 column, {x!r} is {value_type_of(c.dictionary) if c.dictionary is not None else c.arrow_type}: "
+                            f"write is_busday(date({x}))")
+        weekmask, holidays = busday_arguments(e)
+        # keyed on the NORMALISED calendar, as keydict's cache is (ValueError for a spelling NumPy refuses or a list too long)
+        bits, days = K.busday_key(weekmask, holidays)
+        name = f"__busday({x},{bits:07b},{len(days) // 4}:{hashlib.sha256(days).hexdigest()})"
+        if name not in self.extra:
+            self.extra[name] =_Typed(pa.uint8()) if self.types_only else K.busday_mask(c, weekmask, holidays)
+        return ("ne", name, 0)
+
+    def in_list(self, e, rescale):
+        """rescale: the caller's lowering of a ("datetime", column, ("lit", unit)) node"""
+        x = self.lower(e[1])
+        members = [E.fold_temporal(m) if isinstance(m, tuple) and m and m[0] in TEMPORAL_FNS else m for m in e[2]]
+        k = self.kind_of(x)
+        if not any(is_temporal_const(m) for m in members):       # a list of plain numbers: the storage integers, as it has always been
+            return None if x is e[1] else (e[0], x, e[2])
+        what = e[0].upper().replace("_", " ")
+        if k is None or k[0] != "temporal":
+            raise TypeError(f"{what} with temporal constants over {self.describe(x)}: only a date32 / timestamp column or date() / datetime() / "
+                            "from_timestamp() of a column")
+        for m in members:
+            if not (is_temporal_const(m) and m[0] == "temporal"):
+                raise TypeError(f"{what} over {self.describe(x)} needs date() / datetime() / from_timestamp() constants, got {m!r}")
+        want = max([k[1]] + [m[2] for m in members], key=K.TEMPORAL_UNITS.index)
+        if want != k[1]:
+            x = rescale(("datetime", x, ("lit", want)))
+        return (e[0], x, tuple(self._scaled(m, m[2], want) for m in members))
+
+
+def busday_arguments(e):
+    """(weekmask, holidays) of an is_busday node as keydict.busday_calendar takes them: the weekmask string or None, the holidays a
+    tuple of date strings.  Anything but a string literal / a list of them raises TypeError."""
+    text = lambda v: v.decode("utf-8") if isinstance(v, bytes) else v
+    weekmask = None
+    if len(e) > 2:
+        if not E.is_str_lit(e[2]):
+            raise TypeError(f"is_busday(): the weekmask must be a string literal ('1111100' or 'Mon Tue ...'), not {e[2]!r}")
+        weekmask = text(e[2][1])
+    holidays = ()
+    if len(e) > 3:
+        if not isinstance(e[3], (list, tuple)) or E.is_str_lit(e[3]) or not all(isinstance(h, (str, bytes)) or E.is_str_lit(h) for h in e[3]):
+            raise TypeError(f"is_busday(): the holidays must be a list literal of date strings, not {e[3]!r}")
+        holidays = tuple(text(h[1] if E.is_str_lit(h) else h) for h in e[3])
+    return weekmask, holidays
+
+
+class _Typed:
+    """a column known by its Arrow type alone (plan time); `dictionary` is set for a string / binary column"""
+
+    def __init__(self, t, coded=False):
+        self.arrow_type = self.type = t
+        self.dictionary = _Typed(t) if coded else None
+
+
+def check_temporal(expr, types):
+    """Plan time: TemporalArithmetic's rules over a schema (types: column name -> Arrow type), no device.  Raises what the lowering
+    would raise per batch -- TypeError for operands NumPy refuses, ValueError for a timedelta unit or a holiday list, OverflowError,
+    NotImplementedError -- and returns the type-only form of `expr`; what it does not know passes through."""
+    columns = {n: _Typed(t, coded=K.device_value_type(t) is not None) for n, t in types.items()}
+    extra = {}
+    lower = lambda x: E.rewrite(x, f) if isinstance(x, tuple) else x
+
+    def derived(e):
+        const = E.fold_temporal(e)
+        if const is not None:
+            return const
+        unit, x = E.temporal_unit_arg(e) or "s", lower(e[1])
+        name = f"{_DERIVED_TEMPORAL}{e[0]}_{unit}_{x}"
+        extra[name] = _Typed(K.temporal_type(unit))
+        return name
+    rules = TemporalArithmetic(columns, extra, lower, types_only=True)
+
+    def f(e):
+        if e[0] in TEMPORAL_FNS:
+            return derived(e)
+        if e[0] == "timedelta":
+            return E.fold_timedelta(e)
+        if e[0] in E.TEMPORAL_ARITH:
+            return rules.arithmetic(e)
+        if e[0] == "is_busday":
+            return rules.is_busday(e)
+        if e[0] in E.IN_OPS and len(e) == 3:
+            return rules.in_list(e, derived)
+        return None
+    return lower(expr)
 
 
 def lower_like(expr, columns, extra=None):

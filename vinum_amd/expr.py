@@ -27,9 +27,18 @@ table of where a form keeps its sub-expressions: operands(), with_operands() and
                                     into a ("temporal", ...) constant (fold_temporal)
     ("temporal", value, unit)       a date / timestamp constant: `value` days (unit D) or unit counts since 1970-01-01.  A leaf.  It
                                     may only stand in a comparison (or BETWEEN) with a temporal operand: core.lowering aligns units
+    ("timedelta", n[, ("lit", unit)])  n an integer literal; folds into a ("duration", ...) constant (fold_timedelta)
+    ("duration", value, unit)       a timedelta constant: `value` counts of `unit` -- D s ms us ns, or None (NumPy's generic
+                                    timedelta, which takes the unit of the operand it meets).  A leaf
+    ("now",)                        the instant of planning: fold_now replaces it ONCE per query with ("temporal", seconds, "s")
+    ("is_busday", x[, ("lit", weekmask)[, (date string, ...)]])  x: a date32 column or a date() node; core.lowering turns it into
+                                    a predicate over a mask column (np.is_busday; a NULL row is False)
+    ("floordiv" | "//", x, y)       duration // duration -> an int64 column with validity (vnm_temporal_floordiv); no other operands
+    add / sub / mul / div / neg     over temporal and duration operands follow NumPy's datetime64 / timedelta64 rules
+                                    (core.lowering): the node becomes a derived column or a constant
     ("fn", name, arg...)            a function by name (planner: the aggregates); name is no operand
 
-"lit", "strong" and "temporal" nodes are leaves.  Pass-through nodes keep the spelling they came with (`(">", "v", "w")` stays that):
+"lit", "strong", "temporal", "duration" and "now" nodes are leaves.  Pass-through nodes keep the spelling they came with (`(">", "v", "w")` stays that):
 an operator is canonicalised with cmp_name() only where it is matched.  A new operator is added to ops._EX (and to
 core.lowering._ARITHMETIC when it takes numbers); a new node FORM is a line above and, unless its operands are e[1:], in _OPERANDS.
 No ctypes, no library, no device: this module imports without them.
@@ -43,8 +52,9 @@ CMP_FLIP = {"eq": "eq", "ne": "ne", "lt": "gt", "le": "ge", "gt": "lt", "ge": "l
 IN_OPS = ("in", "not_in")
 # where the operands stand, by a node's first slot (the walkers slice with it themselves: operands() is a call more per node)
 _REST, _NONE = slice(1, None), slice(0, 0)
-_OPERANDS = {"lit": _NONE, "strong": _NONE, "temporal": _NONE, "in": slice(1, 2), "not_in": slice(1, 2), "fn": slice(2, None),
-             "date": slice(1, 2), "datetime": slice(1, 2), "from_timestamp": slice(1, 2)}
+_OPERANDS = {"lit": _NONE, "strong": _NONE, "temporal": _NONE, "duration": _NONE, "now": _NONE, "in": slice(1, 2), "not_in": slice(1, 2),
+             "fn": slice(2, None), "date": slice(1, 2), "datetime": slice(1, 2), "from_timestamp": slice(1, 2), "timedelta": slice(1, 2),
+             "is_busday": slice(1, 2)}
 
 
 def cmp_name(op):
@@ -220,3 +230,69 @@ def fold_temporal(e):
     if np.isnat(arr):
         raise NotImplementedError(f"no GPU lowering for the constant {e[0]}({v!r}): it is NaT, which compares False with everything")
     return ("temporal", int(arr.astype(np.int64)), got)
+
+
+# timedelta(n[, unit]) (np.timedelta64, functions.py:380): the units a constant may carry.  Arrow has no duration unit coarser than the
+# second and NumPy cannot add months or years to days, so W becomes 7 D, h and m become s, Y and M are refused
+_TIMEDELTA_UNITS = {"W": ("D", 7), "D": ("D", 1), "h": ("s", 3600), "m": ("s", 60), "s": ("s", 1), "ms": ("ms", 1), "us": ("us", 1), "ns": ("ns", 1)}
+TEMPORAL_ARITH = {"add": "add", "+": "add", "sub": "sub", "-": "sub", "mul": "mul", "*": "mul", "div": "div", "/": "div", "mod": "mod",
+                  "%": "mod", "neg": "neg", "floordiv": "floordiv", "//": "floordiv"}
+
+
+def fold_timedelta(e):
+    """A timedelta node -> ("duration", value, unit): unit D / s / ms / us / ns, or None without one (NumPy's generic timedelta).
+    n must be an integer literal: a column operand raises NotImplementedError, a float or string TypeError as np.timedelta64 does."""
+    if len(e) < 2 or len(e) > 3:
+        raise NotImplementedError(f"no GPU lowering for timedelta() with {len(e) - 1} operand(s)")
+    n = e[1][1] if isinstance(e[1], tuple) and len(e[1]) == 2 and e[1][0] == "strong" else e[1]
+    if isinstance(n, (str, tuple)) and not is_str_lit(n):
+        raise NotImplementedError(f"no GPU lowering for timedelta() over {n!r}: the count must be an integer literal, not a column or an expression")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+        raise TypeError(f"timedelta() takes an integer count, not {n!r}")
+    if len(e) == 2:
+        return ("duration", int(n), None)
+    unit = e[2][1] if is_str_lit(e[2]) else e[2]
+    if isinstance(unit, bytes):
+        unit = unit.decode("utf-8")
+    if unit in ("Y", "M"):
+        raise ValueError(f"timedelta() with the unit {unit!r}: years and months have no fixed length, NumPy cannot add them to days either")
+    if not (isinstance(unit, str) and unit in _TIMEDELTA_UNITS):
+        raise ValueError(f"Unsupported timedelta unit: '{unit}'. Supported units are: [{', '.join(_TIMEDELTA_UNITS)}]")
+    to, k = _TIMEDELTA_UNITS[unit]
+    v = int(n) * k
+    if not -2**63 < v < 2**63:
+        raise OverflowError(f"timedelta({n}, {unit!r}) does not fit int64 in the unit {to!r}")
+    return ("duration", v, to)
+
+
+def now_seconds() -> int:
+    """what now() folds to: np.datetime64('now'), whole seconds since 1970-01-01"""
+    import time
+    return int(time.time())
+
+
+def fold_now(exprs):
+    """The expressions of ONE query (None entries pass) with every ("now",) node replaced by the same ("temporal", seconds, "s")
+    constant: a query sees a single instant (the reference evaluates np.datetime64('now') once per batch).  The clock is read once,
+    and only when a now() occurs."""
+    is_now = lambda n: isinstance(n, tuple) and len(n) == 1 and n[0] == "now"
+    if not any(is_now(n) for e in exprs if e is not None for n in nodes(e)):
+        return list(exprs)
+    const = ("temporal", now_seconds(), "s")
+    return [e if e is None else transform(e, lambda n: const if is_now(n) else n) for e in exprs]
+
+
+def temporal_scalar(x):
+    """a ("temporal", ...) / ("duration", ...) constant as the NumPy scalar it stands for (a generic duration: np.timedelta64(n))"""
+    if x[0] == "temporal":
+        return np.datetime64(x[1], x[2])
+    return np.timedelta64(x[1], x[2]) if x[2] else np.timedelta64(x[1])
+
+
+def temporal_const(v):
+    """the NumPy datetime64 / timedelta64 scalar `v` as a constant node; its unit is one of D s ms us ns (or generic)"""
+    name = np.dtype(v.dtype).name
+    unit = name[name.index("[") + 1:name.index("]")] if "[" in name else None
+    if np.isnat(v):
+        raise NotImplementedError("no GPU lowering for a temporal constant expression that is NaT")
+    return ("temporal" if v.dtype.kind == "M" else "duration", int(v.astype(np.int64)), unit)

@@ -3,6 +3,7 @@ one entry per dictionary id: LIKE matches, translations into and joint ranks wit
 concat() with literals, the parsed values of date() / datetime(); the pair tables of concat() over two columns; and the value tables
 of to_str() over a numeric or temporal column (ValueTable: no KeyDictionary of its own, the column's VALUE is the key).
 Importable without the shared library, like vinum_lib (which re-exports KeyDictionary and device_value_type)."""
+import collections
 import ctypes
 from dataclasses import dataclass
 
@@ -142,6 +143,104 @@ def timestamp_column(col, unit: str):
         d = col.dcol()
         L.check(L.lib().vnm_temporal_rescale(ctypes.byref(d), 1, 1, n, 8, out.ptr + off * 8, None))
     return DeviceColumn(out, col._validity, off, n, t, keep=(col,))
+
+
+def duration_unit(t):
+    """the unit of a duration type; None for any other type"""
+    return t.unit if pa.types.is_duration(t) else None
+
+
+def affine_column(a, ka: int, b, kb: int, c: int, arrow_type):
+    """Arithmetic on temporal values (vnm_temporal_affine): a * ka + b * kb + c per row, exact and wrapping in int64, as a column of
+    `arrow_type` -- date32 (4 bytes), timestamp[u] or duration[u] (8) -- WITH the kernel's validity: NULL where an operand is NULL
+    or NaT, or the result is NaT.  `a` (and `b`, which may be None) are date32 / timestamp / duration columns."""
+    from .device import DeviceBuffer, DeviceColumn
+    n = a.length
+    if b is not None and b.length != n:
+        raise ValueError(f"temporal arithmetic over operands of {n} and {b.length} rows")
+    for k in (ka, kb, c):
+        if not -2**63 <= k < 2**63:
+            raise OverflowError(f"the factor or constant {k} of a temporal expression does not fit int64")
+    width = 4 if pa.types.is_date32(arrow_type) else 8
+    out, bitmap = DeviceBuffer(max(n, 1) * width), DeviceBuffer((n + 7) // 8 or 1)
+    if n:
+        da, db = a.dcol(), b.dcol() if b is not None else None
+        L.check(L.lib().vnm_temporal_affine(ctypes.byref(da), ka, ctypes.byref(db) if db is not None else None, kb, c, n, width, out.ptr,
+                                            bitmap.ptr, None, None))
+    return DeviceColumn(out, bitmap, 0, n, arrow_type, keep=(a, b))
+
+
+MAX_HOLIDAYS = 8192                      # what fits 32 KB of LDS (vnm_temporal_busday)
+_DEFAULT_WEEKMASK = "1111100"
+_CALENDAR_CACHE_SIZE = 32
+_calendars = collections.OrderedDict()   # the NORMALISED calendar (bits, the days' bytes) -> (bits, days, device buffer or None), least recently used first
+_spellings = {}                          # (weekmask, holidays) as written -> the normalised key: no np.busdaycalendar per batch
+
+
+def busday_calendar(weekmask=None, holidays=()):
+    """is_busday()'s weekmask (either of NumPy's spellings) and holidays (date strings) normalised by np.busdaycalendar itself: (the 7
+    bits as an int, bit 0 Monday; the holidays as a sorted, distinct int32 array of days without NaT and non-business days).  More
+    than MAX_HOLIDAYS of them raise ValueError."""
+    cal = np.busdaycalendar(_DEFAULT_WEEKMASK if weekmask is None else weekmask, list(holidays))
+    bits = sum(1 << k for k, on in enumerate(cal.weekmask) if on)
+    days = cal.holidays.astype("datetime64[D]").astype(np.int64).astype(np.int32)
+    if len(days) > MAX_HOLIDAYS:
+        raise ValueError(f"is_busday() takes at most {MAX_HOLIDAYS} holidays (32 KB of LDS), not {len(days)}")
+    return bits, days
+
+
+def busday_key(weekmask=None, holidays=()):
+    """the normalised calendar as a hashable key, (bits, the sorted days' bytes): two spellings of one calendar share it, two
+    calendars never do"""
+    spelt = (weekmask, tuple(holidays))
+    if spelt not in _spellings:
+        bits, days = busday_calendar(weekmask, holidays)
+        if len(_spellings) >= 8 * _CALENDAR_CACHE_SIZE:
+            _spellings.clear()
+        _spellings[spelt] = (bits, days.tobytes())
+    return _spellings[spelt]
+
+
+def busday_mask(col, weekmask=None, holidays=()):
+    """np.is_busday(col, weekmask, holidays) over a date32 column as a uint8 mask column (vnm_temporal_busday): 0 for a NULL row.  The
+    holiday list is uploaded once per normalised calendar and kept in a small LRU (an evicted list goes back to the pool once the
+    masks that hold it are gone)."""
+    from .device import DeviceBuffer, DeviceColumn
+    if not pa.types.is_date32(col.arrow_type):
+        raise TypeError(f"is_busday() takes a date32 column, not {col.arrow_type}: write is_busday(date(x))")
+    key = busday_key(weekmask, holidays)
+    if key in _calendars:
+        _calendars.move_to_end(key)
+    else:
+        days = np.frombuffer(key[1], np.int32)
+        _calendars[key] = (key[0], days, DeviceBuffer.from_host(days) if len(days) else None)
+        while len(_calendars) > _CALENDAR_CACHE_SIZE:
+            _calendars.popitem(last=False)
+    bits, days, dev = _calendars[key]
+    n = col.length
+    out = DeviceBuffer(max(n, 1))
+    if n:
+        d = col.dcol()
+        L.check(L.lib().vnm_temporal_busday(ctypes.byref(d), n, bits, dev.ptr if dev is not None else None, len(days), out.ptr, None))
+    return DeviceColumn(out, None, 0, n, pa.uint8(), keep=(col, dev))
+
+
+def floordiv_column(a, ka: int, b, kb: int):
+    """duration // duration (vnm_temporal_floordiv): floor((a * ka) / (b * kb)) per row as an int64 column WITH validity -- NULL where
+    an operand is NULL or NaT; a zero divisor gives 0 as in NumPy.  a or b may be None: that side is the constant ka / kb itself."""
+    from .device import DeviceBuffer, DeviceColumn
+    n = (a if a is not None else b).length
+    if a is not None and b is not None and b.length != n:
+        raise ValueError(f"temporal arithmetic over operands of {n} and {b.length} rows")
+    for k in (ka, kb):
+        if not -2**63 <= k < 2**63:
+            raise OverflowError(f"the factor or constant {k} of a temporal expression does not fit int64")
+    out, bitmap = DeviceBuffer(max(n, 1) * 8), DeviceBuffer((n + 7) // 8 or 1)
+    if n:
+        da, db = a.dcol() if a is not None else None, b.dcol() if b is not None else None
+        L.check(L.lib().vnm_temporal_floordiv(ctypes.byref(da) if da is not None else None, ka, ctypes.byref(db) if db is not None else None, kb, n,
+                                              out.ptr, bitmap.ptr, None, None))
+    return DeviceColumn(out, bitmap, 0, n, pa.int64(), keep=(a, b))
 
 
 def temporal_operand_kind(fn: str, t, name) -> str:

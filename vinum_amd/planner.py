@@ -33,6 +33,7 @@ from .core import (AggregateFunction, AggregateOperator, FileReaderOperator, Fil
                    ProjectOperator, SliceOperator, SortOperator, TableReaderOperator)
 from . import expr as E
 from .expr import columns_of
+from .core.lowering import check_temporal
 from .keydict import device_value_type, temporal_operand_kind, to_str_kind
 
 AGG_FUNCS = ("count_star", "count", "sum", "avg", "min", "max")     # vinum/core/functions.py:389-396
@@ -49,6 +50,9 @@ SCALAR_FN_NAMES["to_str"] = "to_str"
 # the datetime built-ins (functions.py:25-137, registered at :376-379): over a string column a function of the dictionary's values
 # (KeyDictionary.parsed_column), over a temporal column a change of unit, over literals a constant folded by NumPy
 SCALAR_FN_NAMES.update({n: n for n in E.TEMPORAL_FNS})
+# the rest of the datetime family (functions.py:380-381, :375): timedelta folds into a constant, now() folds ONCE per query (plan_query),
+# is_busday is a mask kernel; arithmetic over temporal values is typed by core.lowering.TemporalArithmetic
+SCALAR_FN_NAMES.update({"timedelta": "timedelta", "is_busday": "is_busday", "now": "now"})
 
 
 def _t(e):
@@ -57,10 +61,14 @@ def _t(e):
     as the operator node it is -- ("concat", a, ("lit", "-"), 7, b) or ("||", a, b), literals as they are --; the "fn" spelling of
     that name stays the unknown function it has always been to this planner."""
     if isinstance(e, (list, tuple)) and e and isinstance(e[0], str):
-        if e[0] in E.IN_OPS:
-            return (e[0], _t(e[1]), tuple(e[2]))
+        if e[0] in E.IN_OPS:                                  # (a member may be a date() / datetime() node: a temporal constant)
+            return (e[0], _t(e[1]), tuple(_t(v) if isinstance(v, (list, tuple)) else v for v in e[2]))
         if e[0] == "fn" and len(e) > 1 and isinstance(e[1], str) and e[1].lower() in SCALAR_FN_NAMES:
-            return tuple([SCALAR_FN_NAMES[e[1].lower()]] + [_t(x) for x in e[2:]])
+            e = [SCALAR_FN_NAMES[e[1].lower()]] + list(e[2:])
+        if e[0] == "is_busday" and len(e) > 3 and isinstance(e[3], (list, tuple)) and not E.is_str_lit(tuple(e[3])):
+            # the holidays are a list literal of date strings, no operand: kept as a tuple of plain strings
+            days = tuple(h[1] if isinstance(h, (list, tuple)) and len(h) == 2 and h[0] == "lit" else h for h in e[3])
+            return tuple([e[0]] + [_t(x) for x in e[1:3]]) + (days,) + tuple(_t(x) for x in e[4:])
         if e[0] == "||":                                      # SQLExpression.CONCAT: the same function as concat()
             return tuple(["concat"] + [_t(x) for x in e[1:]])
         return tuple([e[0]] + [_t(x) for x in e[1:]])
@@ -72,6 +80,11 @@ def _case_by_type(e, schema):
     known at plan time -- the name is no function of this planner, and the query is refused as one with any unknown function is
     ("unknown aggregate function 'upper'"; the reference would print the numbers as text, which is not restated).  Without a schema
     (a file source, the adapter) the lowering raises TypeError for such an operand when the batch arrives (core.lowering)."""
+    # arithmetic over temporal values, timedelta(), is_busday() and IN lists of temporal constants: the lowering's own type rules over
+    # the schema (core.lowering.check_temporal) accept what runs and refuse here what a batch would be refused for
+    if e is not None and any(isinstance(n, tuple) and n and (n[0] in ("timedelta", "is_busday") or n[0] in E.TEMPORAL_ARITH or n[0] in E.IN_OPS)
+                             for n in E.nodes(e)):
+        check_temporal(e, {f.name: f.type for f in schema})
     for n in E.nodes(e) if e is not None else ():
         if isinstance(n, tuple) and n and n[0] in ("upper", "lower") and len(n) == 2 and isinstance(n[1], str) and n[1] in schema.names:
             t = schema.field(n[1]).type
@@ -151,6 +164,11 @@ def plan_query(query: Dict, source, expected_groups: int = 0) -> Plan:
     limit, offset = query.get("limit"), query.get("offset") or 0
     distinct = bool(query.get("distinct"))
     steps = []
+    # now() folds ONCE per query: every occurrence, in every clause, is the same instant (expr.fold_now)
+    n_sel, n_grp = len(select), len(group_by)
+    folded = E.fold_now(select + group_by + order_by + [where, having])
+    select, group_by, order_by = folded[:n_sel], folded[n_sel:n_sel + n_grp], folded[n_sel + n_grp:-2]
+    where, having = folded[-2:]
     if isinstance(source, pa.Table):
         for e in select + group_by + order_by + [where, having]:
             _case_by_type(e, source.schema)
